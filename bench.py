@@ -11,9 +11,14 @@ A = I + s Q2, right-hand side = standardised rotation angle.
 
 One "step" = one complete CG solve of A x = y to a relative residual of 1e-6 on device-resident
 inputs.  `value` = algorithmic SpMV bytes streamed by the solves / wall time (whole job, GB/s);
-`ms_per_step` = CG-solve wall time.  `roofline` times the dominant kernel (the fused C=1 SpMV)
-back to back with HIP events on the launch stream; `cpu_baseline` times the reference-style torch
-CPU operator (oracle/ref_torch.py, kind "port") on the host cores in the same run.
+`ms_per_step` = CG-solve wall time.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times exactly K steps and prints the line.
+`--dump-outputs DIR` writes what the last timed step computed (the solution x, float32) to DIR/solution.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.  Everything else is behind
+`--full`: `roofline` times the dominant kernel (the fused C=1 SpMV) back to back with HIP events on the launch stream;
+`cpu_baseline` times the reference-style torch CPU operator (oracle/ref_torch.py, kind "port") on the host cores in the
+same run; the residual re-check, the alternating right-hand side and the cg_multi_rhs / roofline_hbm / stages blocks.
 
 N>1 (launched by torch.distributed.run, one rank per GPU): STRONG scaling by default -- the same 60 000-node graph
 (the metric's configuration), rows and vectors partitioned across ranks, partitioned pipelined CG with one grouped
@@ -60,6 +65,23 @@ def source_hash():
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: every array as <dirname>/<name>.npy, float32 (float64 stays float64).  An array above its share of the
+    64 MB budget is written as a fixed sample of its rows (seed 0, sorted): the same rows on every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > budget:
+            rows = budget // max(1, a[:1].nbytes)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def build_workload(args, dev, rank, world, shard_knn=False, scale_nodes=True):
@@ -350,10 +372,15 @@ def _main(quiet):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3", choices=["c3", "s5"])
     ap.add_argument("--nodes", type=int, default=0, help="override nodes per GPU (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cg_multi_rhs / roofline_hbm / stages blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline (roofline, residual re-check, alternating "
+                         "right-hand side, extra blocks, CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's solution to DIR/solution.npy (single-GPU path)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cg_multi_rhs / roofline_hbm / stages blocks")
     ap.add_argument("--force-extras", action="store_true",
-                    help="with --nodes: run the extra blocks all the same, at reduced sizes (tests of the line's contract)")
+                    help="with --full --nodes: run the extra blocks all the same, at reduced sizes (tests of the line's contract)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = the SAME graph on every world size (the metric's N = 60k), weak = N x nodes")
     ap.add_argument("--tol", type=float, default=1e-6)
@@ -380,9 +407,12 @@ def _main(quiet):
 
     if world > 1 or os.environ.get("MGP_FORCE_DIST") == "1":
         from manifold_gp_amd import parallel
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is implemented for the single-GPU path only")
+        args.no_extras = args.no_extras or not args.full        # (cg_multi_rhs_sharded)
         try:
             return parallel.bench_distributed(args, dev, rank, world, build_workload, spmm_bytes, HBM_PEAK_GBS, quiet.emit,
-                                              cpu_baseline=None if args.no_cpu_baseline else cpu_baseline)
+                                              cpu_baseline=cpu_baseline if args.full and not args.no_cpu_baseline else None)
         except BaseException as e:      # a failed or timed-out collective (MGP_ERR_TIMEOUT) must end THIS process with a
             # non-zero code at once -- no communicator teardown (it can hang on a dead peer), never a re-exec
             import traceback
@@ -437,9 +467,30 @@ def _main(quiet):
     value = B * spmvs_per_solve * args.steps / dt / 1e9
     B = spmm_bytes(g.n, g.M)
     resid = max(plan.resid)
+    line = dict(metric="CG-solve wall-time + SpMV HBM GB/s, N=60k RMNIST graph", value=round(value, 2),
+                unit="GB/s (algorithmic SpMV bytes inside the CG solve)", n_gpus=1, steps=args.steps,
+                warmup=args.warmup, preheat_solves=preheat, ms_per_step=round(dt / args.steps * 1e3, 4), higher_is_better=True,
+                scaling=args.scaling, vs_baseline=None, dtype="f32", data="synthetic",
+                config=dict(workload=wl["name"], nodes=g.n, edges=g.M, nnz_padded=g.nnz, rhs_columns=1,
+                            system="A = I + noise*outputscale*Q, Q=(2nu/kappa^2 I + L)^nu x D",
+                            solver=("COCG on the complex factor I + i sigma B (A = I + c B^2): one 4-column SpMM per iteration"
+                                    if plan.complex_shift else "CG on A (Chronopoulos-Gear, one hipGraph per solve)"),
+                            cg_tol=args.tol, cg_iters=its, cg_rel_residual=resid,
+                            spmv_per_solve=spmvs_per_solve, eps=wl["eps"], knn_graph_build_s=round(wl["t_graph"], 3)),
+                cg_solve_ms=round(dt / args.steps * 1e3, 4))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solution=out)      # the last timed solve's x [n, 1], caller order
+    if not args.full:
+        gc.enable()
+        plan.close()
+        quiet.emit(json.dumps(line))
+        return
+
+    # ---- --full: everything beside the headline
     # residual re-check with one explicit operator apply
     r = wl["desc"].apply(out) - y
     true_res = float(r.norm() / y.norm())
+    line["config"]["cg_true_residual_fp32_apply"] = true_res
 
     # the same K steps with the right-hand side alternating between two buffers: every solve re-points the graph's root
     # node (hipGraphExecKernelNodeSetParams), which the loop above -- one buffer -- never pays
@@ -520,18 +571,8 @@ def _main(quiet):
                                      % (prof_file, prof_hash == tree_hash)
         except Exception:
             pass
-    line = dict(metric="CG-solve wall-time + SpMV HBM GB/s, N=60k RMNIST graph", value=round(value, 2),
-                unit="GB/s (algorithmic SpMV bytes inside the CG solve)", n_gpus=1, steps=args.steps,
-                warmup=args.warmup, preheat_solves=preheat, ms_per_step=round(dt / args.steps * 1e3, 4),
-                ms_per_step_alternating_rhs=round(dt_alt / args.steps * 1e3, 4), higher_is_better=True,
-                scaling=args.scaling, vs_baseline=None, dtype="f32", data="synthetic",
-                config=dict(workload=wl["name"], nodes=g.n, edges=g.M, nnz_padded=g.nnz, rhs_columns=1,
-                            system="A = I + noise*outputscale*Q, Q=(2nu/kappa^2 I + L)^nu x D",
-                            solver=("COCG on the complex factor I + i sigma B (A = I + c B^2): one 4-column SpMM per iteration"
-                                    if plan.complex_shift else "CG on A (Chronopoulos-Gear, one hipGraph per solve)"),
-                            cg_tol=args.tol, cg_iters=its, cg_rel_residual=resid, cg_true_residual_fp32_apply=true_res,
-                            spmv_per_solve=spmvs_per_solve, eps=wl["eps"], knn_graph_build_s=round(wl["t_graph"], 3)),
-                cg_solve_ms=round(dt / args.steps * 1e3, 4), roofline=roof)
+    line["ms_per_step_alternating_rhs"] = round(dt_alt / args.steps * 1e3, 4)
+    line["roofline"] = roof
     if args.workload == "c3" and not args.no_extras and (not args.nodes or args.force_extras):
         small = 100000 if args.nodes else 0          # (--force-extras: the blocks at sizes a test can afford)
         line["cg_multi_rhs"] = multi_rhs_solve(wl)

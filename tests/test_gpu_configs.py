@@ -681,14 +681,14 @@ def test_c5_swiss_roll_1m_pipeline(mgp, dev):
 
 @pytest.mark.gpu
 def test_bench_line_contract(dev):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline and cpu_baseline objects and a solution that
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline and cpu_baseline objects and a solution that
     matches the CPU baseline's (a reduced node count keeps the CPU leg to a second; the full-size line is the driver's)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--nodes", "8000"],
-                       capture_output=True, text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--nodes", "8000",
+                        "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -743,7 +743,7 @@ def test_bench_line_stages_contract(dev):
     (`reference_bench`, `cpu_baseline.reference_shape`; benchmark/bench_sparse_laplacian.py:15-34), the S5 k-NN
     (`roofline_hbm.knn`) and the conditioned 60k-shape workload (`manifold_784`).  Reduced sizes here (--nodes 8000
     --force-extras); the full-size line is the driver's."""
-    line = _run_bench(["--steps", "3", "--warmup", "1", "--nodes", "8000", "--force-extras"])
+    line = _run_bench(["--steps", "3", "--warmup", "1", "--nodes", "8000", "--full", "--force-extras"])
     st = line["stages"]
     for key in ("knn", "graph_symmetrise_csr_tiles", "laplacian_build", "eigensolve", "spmm_wide_C128", "spmm_wide_C100",
                 "features_insample", "features_oos", "kernel_block", "train_epoch_supervised", "train_epoch_semisupervised"):
@@ -778,6 +778,29 @@ def test_bench_line_stages_contract(dev):
     assert m7["posterior_test_rmse"] < 0.5 and m7["precision_cg"]["rel_residual"] <= 1e-6 and m7["eval_eigensolve_ms"] > 0
 
 
+def test_bench_plain_line_and_dumped_solution(dev, tmp_path):
+    """A plain run (no --full) times the steps and prints the headline only; --dump-outputs writes the last timed solve's
+    solution, which solves the workload's system: the same seeded workload rebuilt here, one fp32 operator apply."""
+    import argparse
+    import bench
+    out_dir = tmp_path / "dump"
+    line = _run_bench(["--steps", "5", "--warmup", "2", "--nodes", "8000", "--dump-outputs", str(out_dir)])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in line, key
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["dtype"] == "f32" and line["higher_is_better"] is True and line["config"]["cg_iters"] > 0
+    for key in ("roofline", "cpu_baseline", "ms_per_step_alternating_rhs", "cg_multi_rhs", "roofline_hbm", "stages"):
+        assert key not in line, key
+    x = np.load(str(out_dir / "solution.npy"))
+    n = line["config"]["nodes"]
+    assert x.dtype == np.float32 and x.shape == (n, 1) and np.isfinite(x).all()
+    wl = bench.build_workload(argparse.Namespace(workload="c3", nodes=8000, s5_order="morton"), dev, 0, 1)
+    assert wl["graph"].n == n and abs(wl["eps"] - line["config"]["eps"]) <= 1e-6 * line["config"]["eps"]
+    y = wl["y"].view(-1, 1).contiguous()
+    r = wl["desc"].apply(T(x, dev)) - y
+    assert float(r.norm() / y.norm()) < 1e-5
+
+
 @pytest.mark.parametrize("workload", ["c3", "s5"])
 def test_bench_distributed_world1_line_contract(dev, workload):
     """What `bench.py --gpus N` runs for N > 1 (parallel.bench_distributed: graph padding, row partition, RCCL communicator,
@@ -785,7 +808,7 @@ def test_bench_distributed_world1_line_contract(dev, workload):
     cannot fail on plumbing: the N > 1 line's contract -- driver keys, `roofline`, `cpu_baseline`, `rccl_ranks.consistent`,
     `cg_multi_rhs_sharded` (C3), the single-GPU plan's time in the same process -- and a converged solve.  c3: the pipelined
     recurrence in chunks of 4; s5: Chronopoulos-Gear + refinement on the true residual."""
-    args = ["--steps", "3", "--warmup", "1", "--workload", workload, "--nodes", "8000" if workload == "c3" else "200000"]
+    args = ["--steps", "3", "--warmup", "1", "--workload", workload, "--nodes", "8000" if workload == "c3" else "200000", "--full"]
     line = _run_bench(args, env_extra={"MGP_FORCE_DIST": "1"})
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "rccl_ranks", "ms_per_step_single_gpu_plan"):

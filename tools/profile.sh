@@ -14,7 +14,7 @@ failed=0
 run() {   # name, steps, warmup, profiler flags...
   local name="$1" steps="$2" warm="$3"; shift 3
   if ! timeout -k 10 400 rocprofv3 "$@" --output-format csv -d "$out/$name" -- python3 bench.py --steps "$steps" --warmup "$warm" \
-        --no-cpu-baseline --no-extras "${BENCH_ARGS[@]}" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"; then
+        --full --no-cpu-baseline --no-extras "${BENCH_ARGS[@]}" > "$out/bench_${name}.json" 2> "$out/bench_${name}.err"; then
     echo "pass $name FAILED (rc $?)"; tail -5 "$out/bench_${name}.err"; failed=1
   fi
 }

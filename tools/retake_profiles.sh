@@ -55,8 +55,9 @@ fi
 [ $fail = 0 ] && { bash tools/pmc_knn.sh > "$out/${tag}_pmc_knn_mfma_raw.txt" 2>&1 || fail=1; }
 [ $fail = 0 ] && { bash tools/pmc_select.sh > "$out/${tag}_pmc_knn_select_raw.txt" 2>&1 || fail=1; }
 if [ $fail = 0 ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_s5cx -- python3 bench.py --workload s5 --steps 20 --warmup 3 --no-cpu-baseline --no-extras > gpurun_out/prof_s5cx.json 2> gpurun_out/prof_s5cx.err || fail=1
-  f=$(ls -t gpurun_out/prof_s5cx/*/*_kernel_stats.csv | head -1)
+  s5cx="${out%/*}/prof_s5cx"          # raw trace beside the summaries' folder, removed below
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$s5cx" -- python3 bench.py --workload s5 --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras > "$s5cx.json" 2> "$s5cx.err" || fail=1
+  f=$(ls -t "$s5cx"/*/*_kernel_stats.csv | head -1)
   python3 - "$f" "$out/${tag}_s5_complex_shift_kernel_stats.csv" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
@@ -65,7 +66,7 @@ with open(sys.argv[2], "w") as f:
     for r in rows[:16]:
         w.writerow([r["Name"][:150], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"]])
 PY
-  cp gpurun_out/prof_s5cx.json "$out/${tag}_s5_complex_shift_bench.json"
+  cp "$s5cx.json" "$out/${tag}_s5_complex_shift_bench.json"
 fi
 [ $fail = 0 ] && { bash tools/profile_training.sh "$tag" > "$out/${tag}_training_log.txt" 2>&1 || fail=1; }
 rm -rf gpurun_out/pmc_kbres gpurun_out/trace_kbres gpurun_out/prof_knn gpurun_out/pmc_knn gpurun_out/pmc_select gpurun_out/prof_s5cx
