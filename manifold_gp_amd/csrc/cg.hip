@@ -25,6 +25,7 @@
 #include <new>
 #include <vector>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include "mgp_common.h"
 #include "mgp_internal.h"
@@ -978,10 +979,15 @@ __global__ void cg_marker_kernel(int* state, int* host_state) {
 //     four real sums of u . B u = (d0 - d1) + i (d2 + d3); w = M u = u + i sigma B u is formed in the update;
 //   * single-reduction (Chronopoulos-Gear) form as cg_update_kernel: gamma = r . r, delta = u . M u = gamma + i sigma u . B u
 //     (u = r: no preconditioner), beta = gamma / gamma_old, alpha = gamma / (delta - beta gamma / alpha_old), all complex;
-//   * stop: ||r||_2 <= tol ||b||_2 on the COMPLEX residual (an upper bound for the residual of the real system's solution
-//     Re z up to the factor |I - i sigma B|; callers that need a certified true residual use the refinement rounds, which
-//     evaluate b - A x in fp64 on the original operator);
-//   * state words, host flags, skip / tick and the chunked hipGraph replay are those of the real solver.
+//   * stop: on the REAL system's residual, ||e||_2 <= tol ||b||_2 with e = b - A Re z = r_re + sigma B r_im.  The complex
+//     residual r alone is no bound for it: e can be up to |I - i sigma B| ~ sqrt(cond A) times larger (dumbbell fixture,
+//     tol 1e-2: complex residual 9.6e-3, real residual 2.5e-1).  The update already holds u = r_{k-1} and B u for every
+//     row, so e_{k-1} costs no extra pass: it is summed into the fourth word of the gamma partials and the NEXT launch
+//     decides on it, one step behind.  The solution therefore lags by one step too: the update of step k writes
+//     x = Re z_{k-1}, so that a stop decided on e_{k-1} returns exactly the x it was decided on and `resid` is its
+//     real relative residual.  `iters` reports the COCG steps of that x (the launch count less one: cg_plan_solve_body),
+//     and the max_iter exit waits one launch longer, so that it returns x = Re z_{max_iter} with iters = max_iter;
+////   * state words, host flags, skip / tick and the chunked hipGraph replay are those of the real solver.
 constexpr int kCxDeltaSlots = 16;    // nbs4 <= 4096
 
 struct CxArgs {
@@ -991,7 +997,7 @@ struct CxArgs {
   const float* pd4;          // [nbs4][4] partials of w4 . y4 per column
   int nbs4;
   float sigma;
-  float* pd_g;               // [2][nbv][4]: gamma_re, gamma_im, ||r||^2, 0
+  float* pd_g;               // [2][nbv][4]: gamma_re, gamma_im, ||r||^2 of r_k, ||e||^2 of the previous step (see above)
   float* sc;                 // [2][4] {gamma_old re, im, alpha_old re, im} per parity, then [8] = ||b||^2
 };
 
@@ -1028,13 +1034,13 @@ __global__ __launch_bounds__(kBlock) void cx_init_kernel(CgArgs a, CxArgs c, con
   if (tid == 0) {
     const float t = (sh_o[0] + sh_o[1]) + (sh_o[2] + sh_o[3]);
     float* dst = c.pd_g + 4 * (int64_t)lb;            // parity slot 0 = "previous" of iteration 1
-    dst[0] = t; dst[1] = 0.f; dst[2] = t; dst[3] = 0.f;
+    dst[0] = t; dst[1] = 0.f; dst[2] = t; dst[3] = t;     // e_0 = b
   }
 }
 
 __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
-  __shared__ float sh_w[kBlock / 64][7];
-  __shared__ float sh_o[kBlock / 64][3];
+  __shared__ float sh_w[kBlock / 64][8];
+  __shared__ float sh_o[kBlock / 64][4];
   __shared__ int sh_state[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int st_it = a.state[0], st_done = a.state[1];
@@ -1043,7 +1049,7 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   int64_t r1 = r0 + a.rows_per_block;
   if (r1 > a.n) r1 = a.n;
   // ---- one round trip: the partials of both parities, the four-column partials of u . B u, the scalars
-  float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // gamma re/im, rr (parity 0), gamma re/im, rr (parity 1) -> selected below
+  float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // gamma re/im, rr of the previous parity, u . B u (4), ee
   mgp_cg_v4f gv[2][kC1GammaSlots];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -1064,12 +1070,12 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   const float go_r0 = c.sc[0], go_i0 = c.sc[1], ao_r0 = c.sc[2], ao_i0 = c.sc[3];
   const float go_r1 = c.sc[4], go_i1 = c.sc[5], ao_r1 = c.sc[6], ao_i1 = c.sc[7];
   const float bb_old = c.sc[8];
-  float g0[3] = {0.f, 0.f, 0.f}, g1[3] = {0.f, 0.f, 0.f}, d4[4] = {0.f, 0.f, 0.f, 0.f};
+  float g0[4] = {0.f, 0.f, 0.f, 0.f}, g1[4] = {0.f, 0.f, 0.f, 0.f}, d4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < kC1GammaSlots; ++q) {
     const bool on = tid + q * kBlock < a.nbv;
-    g0[0] += on ? gv[0][q].x : 0.f; g0[1] += on ? gv[0][q].y : 0.f; g0[2] += on ? gv[0][q].z : 0.f;
-    g1[0] += on ? gv[1][q].x : 0.f; g1[1] += on ? gv[1][q].y : 0.f; g1[2] += on ? gv[1][q].z : 0.f;
+    g0[0] += on ? gv[0][q].x : 0.f; g0[1] += on ? gv[0][q].y : 0.f; g0[2] += on ? gv[0][q].z : 0.f; g0[3] += on ? gv[0][q].w : 0.f;
+    g1[0] += on ? gv[1][q].x : 0.f; g1[1] += on ? gv[1][q].y : 0.f; g1[2] += on ? gv[1][q].z : 0.f; g1[3] += on ? gv[1][q].w : 0.f;
   }
 #pragma unroll
   for (int q = 0; q < kCxDeltaSlots; ++q) {
@@ -1083,21 +1089,22 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   const int par = it & 1, prev = par ^ 1;
   t[0] = prev ? g1[0] : g0[0]; t[1] = prev ? g1[1] : g0[1]; t[2] = prev ? g1[2] : g0[2];
   t[3] = d4[0]; t[4] = d4[1]; t[5] = d4[2]; t[6] = d4[3];
+  t[7] = prev ? g1[3] : g0[3];
 #pragma unroll
-  for (int k = 0; k < 7; ++k) t[k] = mgp_wave_sum(t[k]);
+  for (int k = 0; k < 8; ++k) t[k] = mgp_wave_sum(t[k]);
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 7; ++k) sh_w[wave][k] = t[k];
+    for (int k = 0; k < 8; ++k) sh_w[wave][k] = t[k];
   }
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < 7; ++k) t[k] = (sh_w[0][k] + sh_w[1][k]) + (sh_w[2][k] + sh_w[3][k]);
+  for (int k = 0; k < 8; ++k) t[k] = (sh_w[0][k] + sh_w[1][k]) + (sh_w[2][k] + sh_w[3][k]);
   const float2 gamma = make_float2(t[0], t[1]);
-  const float rr2 = t[2];
+  const float rr2 = t[2], ee = t[7];
   const float2 uBu = make_float2(t[3] - t[4], t[5] + t[6]);
   const float2 delta = make_float2(gamma.x - c.sigma * uBu.y, gamma.y + c.sigma * uBu.x);     // u . (u + i sigma B u)
   const float bb = (it == 1) ? rr2 : bb_old;
-  const float rel = (bb > 0.f) ? sqrtf(rr2 / bb) : 0.f;
+  const float rel = (bb > 0.f) ? sqrtf(ee / bb) : 0.f;     // the real system's residual of x = Re z_{it-2}
   float2 alpha = make_float2(0.f, 0.f), beta = make_float2(0.f, 0.f);
   if (rel > a.tol) {
     if (it == 1) {
@@ -1116,7 +1123,7 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   int done = 0, status = 0;
   if (rel <= a.tol) { done = 1; status = 1; }
   if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it > a.max_iter) { done = 1; status = 2; }
+  if (!done && it > a.max_iter + 1) { done = 1; status = 2; }   // (decided on e_{it-2}: x = Re z_{max_iter})
   if (blockIdx.x == 0 && tid == 0) {
     c.sc[4 * par + 0] = gamma.x; c.sc[4 * par + 1] = gamma.y;
     c.sc[4 * par + 2] = alpha.x; c.sc[4 * par + 3] = alpha.y;
@@ -1132,7 +1139,7 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   }
   if (done) return;
   // ---- vector update over this workgroup's rows, four rows per lane in flight
-  float ngr = 0.f, ngi = 0.f, nrr = 0.f;
+  float ngr = 0.f, ngi = 0.f, nrr = 0.f, nee = 0.f;
   constexpr int U = 4;
   const int64_t rf = r0 + tid;
   for (int64_t rb = rf; rb < r1; rb += (int64_t)U * kBlock) {
@@ -1150,6 +1157,7 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
       if (r < r1) {
         const float2 u = uo[k];
         const float2 w = make_float2(u.x - c.sigma * yo[k].y, u.y + c.sigma * yo[k].x);       // M u = u + i sigma B u
+        const float e = u.x + c.sigma * yo[k].y;                   // b - A Re z_{it-1} = r_re + sigma B r_im
         const float2 bp = cx_mul(beta, po[k]), bs = cx_mul(beta, so[k]);
         const float2 pn = make_float2(u.x + bp.x, u.y + bp.y);
         const float2 sn = make_float2(w.x + bs.x, w.y + bs.y);
@@ -1157,24 +1165,25 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
         const float2 zn = make_float2(zo[k].x + ap.x, zo[k].y + ap.y);
         const float2 rn = make_float2(u.x - as.x, u.y - as.y);
         c.p[r] = pn; c.s[r] = sn; c.z[r] = zn; c.r[r] = rn;
-        a.x[r] = zn.x;                                             // the real system's solution: Re z
+        a.x[r] = zo[k].x;                                          // Re z_{it-1}: the x that e belongs to
         c.u4[r] = mgp_cg_v4f{rn.x, rn.y, rn.x, rn.y};
         c.w4[r] = mgp_cg_v4f{rn.x, rn.y, rn.y, rn.x};
         ngr += rn.x * rn.x - rn.y * rn.y;
         ngi += 2.f * rn.x * rn.y;
         nrr += rn.x * rn.x + rn.y * rn.y;
+        nee = fmaf(e, e, nee);
       }
     }
   }
-  ngr = mgp_wave_sum(ngr); ngi = mgp_wave_sum(ngi); nrr = mgp_wave_sum(nrr);
-  if (lane == 0) { sh_o[wave][0] = ngr; sh_o[wave][1] = ngi; sh_o[wave][2] = nrr; }
+  ngr = mgp_wave_sum(ngr); ngi = mgp_wave_sum(ngi); nrr = mgp_wave_sum(nrr); nee = mgp_wave_sum(nee);
+  if (lane == 0) { sh_o[wave][0] = ngr; sh_o[wave][1] = ngi; sh_o[wave][2] = nrr; sh_o[wave][3] = nee; }
   __syncthreads();
   if (tid == 0) {
     float* dst = c.pd_g + 4 * ((int64_t)par * a.nbv + lb);
     dst[0] = (sh_o[0][0] + sh_o[1][0]) + (sh_o[2][0] + sh_o[3][0]);
     dst[1] = (sh_o[0][1] + sh_o[1][1]) + (sh_o[2][1] + sh_o[3][1]);
     dst[2] = (sh_o[0][2] + sh_o[1][2]) + (sh_o[2][2] + sh_o[3][2]);
-    dst[3] = 0.f;
+    dst[3] = (sh_o[0][3] + sh_o[1][3]) + (sh_o[2][3] + sh_o[3][3]);
   }
 }
 
@@ -1984,9 +1993,11 @@ static int cg_plan_solve_body(void* plan, const float* B, float* X, int32_t* ite
   hipStream_t st = pl->stream;
   const size_t nc = (size_t)pl->args.n * pl->C;
   const int max_refine = (pl->prm.stop_mode == 1) ? pl->prm.max_refine : 0;
+  // COCG decides one step behind (cx_update_kernel): its x has one step fewer than the launches that ran
+  const int lag = pl->cx ? 1 : 0;
   if (max_refine <= 0) {
     MGP_TRY(run_cg(pl, B, X));
-    if (iters) *iters = pl->host_state[0] - 1;
+    if (iters) *iters = std::max(pl->host_state[0] - 1 - lag, 0);
     if (status) *status = pl->host_state[2];
     if (resid) memcpy(resid, pl->host_resid, (size_t)pl->C * sizeof(float));
     return MGP_OK;
@@ -1998,7 +2009,7 @@ static int cg_plan_solve_body(void* plan, const float* B, float* X, int32_t* ite
   const int rgrid = 256;
   for (int ref = 0; ref <= max_refine; ++ref) {
     MGP_TRY(run_cg(pl, rhs, nullptr));
-    total_iters += pl->host_state[0] - 1;
+    total_iters += std::max(pl->host_state[0] - 1 - lag, 0);
     last_status = pl->host_state[2];
     if (f64) {
       hipLaunchKernelGGL(refine_accumulate64_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->xacc64, pl->args.x, (int64_t)nc,

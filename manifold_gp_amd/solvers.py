@@ -355,7 +355,7 @@ def _factorised_solve(desc, B, kw):
 def cg_solve(desc, rhs, **kw):
     """Solve A X = rhs with the HIP CG.  Returns (X, iterations, relative residuals).  A form-0 chain with nu >= 2 is
     solved factor by factor (_factorised_solve); iterations then counts all factors' iterations (one SpMM each) and the
-    residuals are those of the last factor."""
+    residuals are the true relative residuals ||rhs - A X|| / ||rhs|| of the whole system (one fp32 apply of A)."""
     squeeze = rhs.dim() == 1
     B = _lib.f32c(rhs.unsqueeze(-1) if squeeze else rhs)
     kw = dict(kw)
