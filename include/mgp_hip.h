@@ -311,6 +311,16 @@ int mgp_spmm_repeat(const mgp_csr_t* L, const float* X, int C, float* Y, int rep
 int mgp_laplacian_matmul(const mgp_csr_t* L, const float* dsqrt, const float* dinvsqrt, int mode,
                          const float* X, int C, float* Y, float* work_nc, void* stream);
 
+/* GMRF noise for exact sampling (csrc/sampling.hip, docs/kernels/sampling.md): tau I + L_sym = G G^T with
+ * G = [sqrt(tau) I | E], E[a, e] = +sqrt(S_ab dsqrt_b / dsqrt_a), E[b, e] = -sqrt(S_ab dsqrt_a / dsqrt_b) for the
+ * undirected edge e = (a < b).  Writes Y [n, S] row-major = node_coef w_tag (+ E w_edge when with_edges), the noise of
+ * global sample index sample_offset + j in column j: Philox4x32-10 keyed on seed, node counter (i, 0, s >> 2, tag), edge
+ * counter (a, b, s >> 2, 1), Box-Muller on the output words.  L: the natural-order CSR of mgp_laplacian_build (row and
+ * column ids are the noise keys; entries with col == row or S_ij == 0 are skipped); tiles are not read.  Deterministic,
+ * no atomics.  MGP_ERR_ARG for S < 1, null pointers, n >= 2^31, tag < 0, sample_offset < 0. */
+int mgp_gmrf_noise(const mgp_csr_t* L, const float* dsqrt, float node_coef, int tag, int with_edges,
+                   uint64_t seed, int64_t sample_offset, int S, float* Y, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Precision-side operator family, applied matrix-free as a chain of fused SpMMs:
  *   Q2  = scale * diag(post) (tau I + L_sym)^nu diag(pre)          tau = 2 nu / kappa^2

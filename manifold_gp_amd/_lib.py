@@ -133,6 +133,7 @@ SIGNATURES = {
                                     c_float, _P, _P, _P]),
     "mgp_spmm_repeat": (c_int, [POINTER(CsrT), _P, c_int, _P, c_int, POINTER(c_float), _P]),
     "mgp_laplacian_matmul": (c_int, [POINTER(CsrT), _P, _P, c_int, _P, c_int, _P, _P, _P]),
+    "mgp_gmrf_noise": (c_int, [POINTER(CsrT), _P, c_float, c_int, c_int, c_uint64, c_int64, c_int, _P, _P]),
     "mgp_operator_workspace_bytes": (c_size_t, [POINTER(OperatorT), c_int]),
     "mgp_operator_apply": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, c_size_t, _P]),
     "mgp_operator_apply_dot": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, _P, _P, c_size_t, _P]),

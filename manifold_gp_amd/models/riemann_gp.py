@@ -105,6 +105,33 @@ class RiemannGP(torch.nn.Module):
             opt = NoiseWrapperOperator(opt, self.likelihood.noise)
         return opt
 
+    # ------------------------------------------------------------------ exact samples at the graph nodes (precision form)
+    def _sampling_args(self):
+        """(descriptor of precision(noise=False), likelihood noise, train_targets); semi-supervised models are not sampled."""
+        if self.labeled is not None:
+            raise NotImplementedError("sampling of semi-supervised (Schur-complement) models is not supported")
+        desc = getattr(self.precision(noise=False), "_descriptor", lambda: None)()
+        return desc, self._scale_noise()[1], self.train_targets
+
+    def sample_prior(self, num_samples, seed=None, tol=1e-5):
+        """f ~ N(0, Q^-1) at every graph node: [num_samples, N] float32 (sampling.prior_samples)."""
+        from ..sampling import prior_samples
+        desc, _, _ = self._sampling_args()
+        return prior_samples(desc, num_samples, seed, tol=tol)
+
+    def sample_posterior(self, num_samples, seed=None, noisy=False, tol=1e-5):
+        """f | y at every graph node by perturb-and-MAP: [num_samples, N] float32 with mean precision_posterior_mean() and
+        covariance (Q + I / noise)^-1; noisy=True adds the likelihood noise (sampling.posterior_samples)."""
+        from ..sampling import posterior_samples
+        desc, noise, y = self._sampling_args()
+        return posterior_samples(desc, y, noise, num_samples, seed, noisy=noisy, tol=tol)
+
+    def precision_posterior_mean(self, tol=1e-5):
+        """(I + noise Q)^-1 y at every graph node: [N] float32 (sampling.posterior_mean)."""
+        from ..sampling import posterior_mean
+        desc, noise, y = self._sampling_args()
+        return posterior_mean(desc, y, noise, tol=tol)
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)

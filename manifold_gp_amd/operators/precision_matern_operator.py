@@ -58,6 +58,12 @@ class PrecisionMaternOperator(LinearOperator):
         from ..solvers import cg_solve
         return cg_solve(self._descriptor(), rhs)[0]
 
+    def zero_mean_mvn_samples(self, num_samples, seed=None):
+        """Samples of N(0, Q) (linear_operator's meaning: this operator is the covariance), [num_samples, N], drawn exactly
+        through the sparse factor of tau I + L (sampling.precision_samples)."""
+        from ..sampling import precision_samples
+        return precision_samples(self._descriptor(), num_samples, seed)
+
     def _average_variance(self, num_rand_vec=100):
         """precision_matern_operator.py:45-53: mean_i (Q^-1)_ii over random one-hot columns
         (indices drawn from [0, d-2] with replacement, as the reference does)."""

@@ -48,3 +48,9 @@ class ScaleWrapperOperator(LinearOperator):
             from ..solvers import cg_solve
             return cg_solve(d, rhs)[0]
         return self.operator._solve(rhs) / self._factor()
+
+    def zero_mean_mvn_samples(self, num_samples, seed=None):
+        """Samples of N(0, s Q), [num_samples, N] (sampling.precision_samples); NotImplementedError unless the wrapped operator
+        is a Matern precision without masks."""
+        from ..sampling import precision_samples
+        return precision_samples(self._descriptor(), num_samples, seed)

@@ -1,0 +1,196 @@
+"""Exact samples of the Matern graph GP in precision form (docs/kernels/sampling.md).
+
+With A = tau I + L_sym (tau = 2 nu / kappa^2) the precision of a form-0 descriptor is Q2 = scale P A^nu P, P = I
+(symmetric normalisation) or D^1/2 (random walk: pre = post = sqrt(D)).  A has the sparse factor
+G = [sqrt(tau) I | E] (A = G G^T, one entry of E per edge and endpoint), so with w node noise and g = G w_full:
+
+    z ~ N(0, Q2)                   odd nu: sqrt(scale) P A^((nu-1)/2) g        even nu: sqrt(scale) P A^(nu/2) w
+    f ~ N(0, Q2^-1)                odd nu: scale^-1/2 P^-1 A^-((nu+1)/2) g    even nu: scale^-1/2 P^-1 A^-(nu/2) w
+    f | y, noise s (perturb-and-MAP):  x = (I + s Q2)^-1 (y + s z + sqrt(s) w2)   [+ sqrt(s) w3 with noisy=True]
+
+g and w come from mgp_gmrf_noise (one row-parallel pass over the CSR, noise regenerated from a counter-based generator);
+the applies and solves are the library's own (Descriptor.apply, cg_solve).  Column j of a call is the sample of global
+index offset + j whatever the batch size: every sample is a function of (seed, its index) alone.  Streams: tag 0 node
+noise w, tag 1 edge noise (inside g), tag 2 w2, tag 3 w3.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr, stream
+
+CHUNK = 256          # columns per noise launch / solve (the operator and CG paths take at most 256)
+NODE_TAGS = (0, 2, 3)
+
+
+def draw_seed():
+    """A 63-bit seed from torch's default CPU generator (torch.manual_seed governs it)."""
+    return int(torch.randint(0, 2 ** 63 - 1, (), dtype=torch.int64))
+
+
+def _seed(seed):
+    if seed is None:
+        return draw_seed()
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be an int in [0, 2^64) or None, got %r" % (seed,))
+    return seed
+
+
+def _count(S, name="S"):
+    if isinstance(S, bool) or not isinstance(S, int) or S < 1:
+        raise ValueError("%s must be a positive int, got %r" % (name, S))
+    return S
+
+
+def gmrf_noise(data, S, seed, offset=0, node_coef=1.0, tag=0, edges=False):
+    """node_coef w_tag (+ E w_edge with edges=True) as [n, S] float32 on the graph's device: column j holds global sample
+    index offset + j.  data: graph.LaplacianData (the natural-order CSR and sqrt(D))."""
+    S = _count(S)
+    seed = _seed(seed)
+    if isinstance(offset, bool) or not isinstance(offset, int) or offset < 0:
+        raise ValueError("offset must be a non-negative int, got %r" % (offset,))
+    if tag not in NODE_TAGS:
+        raise ValueError("tag must be one of %s (tag 1 is the edge stream), got %r" % (NODE_TAGS, tag))
+    g = data.graph
+    csr = _lib.csr_struct(g.n, g.rowptr, g.col, data.vals, data.diag)
+    Y = torch.empty(g.n, S, dtype=torch.float32, device=g.device)
+    check(lib().mgp_gmrf_noise(ctypes.byref(csr), ptr(data.dsqrt), float(node_coef), int(tag), int(bool(edges)),
+                               ctypes.c_uint64(seed), int(offset), S, ptr(Y), stream()), "mgp_gmrf_noise")
+    return Y
+
+
+def _check_desc(desc):
+    """Form-0 precision descriptors without masks: pre = post = None (symmetric) or both sqrt(D) (random walk)."""
+    if desc is None or int(desc.form) != 0 or getattr(desc, "noise", 0.0):
+        raise NotImplementedError("sampling needs a form-0 precision descriptor (no noise wrapper)")
+    if int(desc.nu) < 1:
+        raise NotImplementedError("sampling needs an integer nu >= 1")
+    if desc.pre is None and desc.post is None:
+        return None
+    sq = getattr(desc.data, "dsqrt", None)
+    if (sq is None or desc.pre is None or desc.post is None or desc.pre.data_ptr() != sq.data_ptr()
+            or desc.post.data_ptr() != sq.data_ptr()):
+        raise NotImplementedError("sampling of masked (Schur-complement) descriptors is not supported")
+    return sq
+
+
+def _tau(desc):
+    return 2.0 * int(desc.nu) / (float(desc.kappa) ** 2)
+
+
+def _power(desc, k, post=None, scale=1.0):
+    """Descriptor of scale diag(post) A^k: nu = k at the length scale that keeps tau = 2 nu / kappa^2."""
+    return desc.with_(nu=int(k), kappa=float(desc.kappa) * math.sqrt(k / int(desc.nu)), scale=float(scale), pre=None,
+                      post=post, form=0, noise=0.0)
+
+
+def _base_noise(desc, C, seed, offset):
+    """(noise, k): g = G w_full for odd nu (k = (nu - 1) / 2), w for even nu (k = nu / 2); z = sqrt(scale) P A^k noise."""
+    nu = int(desc.nu)
+    if nu % 2:
+        return gmrf_noise(desc.data, C, seed, offset, node_coef=math.sqrt(_tau(desc)), tag=0, edges=True), (nu - 1) // 2
+    return gmrf_noise(desc.data, C, seed, offset, node_coef=1.0, tag=0, edges=False), nu // 2
+
+
+def _precision_chunk(desc, P, C, seed, offset):
+    noise, k = _base_noise(desc, C, seed, offset)
+    rs = math.sqrt(float(desc.scale))
+    if k == 0:
+        return noise * (rs if P is None else rs * P.view(-1, 1))
+    return _power(desc, k, post=P, scale=rs).apply(noise)
+
+
+def _solve_kw(tol, refine, max_iter):
+    kw = dict(tol=float(tol), stop_mode=1, max_iter=int(max_iter))
+    if refine:
+        kw["refine"] = int(refine)
+    return kw
+
+
+def precision_samples(desc, S, seed=None):
+    """z ~ N(0, Q2): [S, n] float32."""
+    P = _check_desc(desc)
+    S, seed = _count(S), _seed(seed)
+    out = torch.empty(S, desc.n, dtype=torch.float32, device=desc.data.graph.device)
+    with torch.no_grad():
+        for c0 in range(0, S, CHUNK):
+            C = min(CHUNK, S - c0)
+            out[c0:c0 + C] = _precision_chunk(desc, P, C, seed, c0).t()
+    return out
+
+
+def prior_samples(desc, S, seed=None, tol=1e-5, refine=0, max_iter=5000):
+    """f ~ N(0, Q2^-1): [S, n] float32 (CG solves with A^k to `tol`, true relative residual per column)."""
+    from .solvers import cg_solve
+    P = _check_desc(desc)
+    S, seed = _count(S), _seed(seed)
+    nu = int(desc.nu)
+    k = (nu + 1) // 2 if nu % 2 else nu // 2
+    dk = _power(desc, k)
+    coef = 1.0 / math.sqrt(float(desc.scale))
+    pinv = None if P is None else desc.data.dinvsqrt.view(-1, 1)
+    kw = _solve_kw(tol, refine, max_iter)
+    out = torch.empty(S, desc.n, dtype=torch.float32, device=desc.data.graph.device)
+    with torch.no_grad():
+        for c0 in range(0, S, CHUNK):
+            C = min(CHUNK, S - c0)
+            noise, _ = _base_noise(desc, C, seed, c0)
+            X = cg_solve(dk, noise, **kw)[0]
+            X = X * coef if pinv is None else X * (pinv * coef)
+            out[c0:c0 + C] = X.t()
+    return out
+
+
+def _targets(desc, y):
+    _lib.require_device(y)
+    y = y.reshape(-1)
+    if y.shape[0] != desc.n:
+        raise ValueError("y has %d entries, the graph %d nodes" % (y.shape[0], desc.n))
+    return _lib.f32c(y).view(-1, 1)
+
+
+def posterior_rhs(desc, y, noise, C, seed, offset=0):
+    """y + s z + sqrt(s) w2 for the columns offset .. offset + C - 1 (the perturbed right-hand side of posterior_samples)."""
+    P = _check_desc(desc)
+    s = float(noise)
+    z = _precision_chunk(desc, P, C, seed, offset)
+    rhs = gmrf_noise(desc.data, C, seed, offset, node_coef=math.sqrt(s), tag=2)
+    rhs += s * z
+    rhs += _targets(desc, y)
+    return rhs
+
+
+def posterior_samples(desc, y, noise, S, seed=None, noisy=False, tol=1e-5, refine=0, max_iter=5000):
+    """f | y ~ N((I + s Q2)^-1 y, (Q2 + I/s)^-1) by perturb-and-MAP, s = noise: [S, n] float32.  noisy=True: samples of
+    y* = f + eps (adds sqrt(s) w3)."""
+    from .solvers import cg_solve
+    _check_desc(desc)
+    S, seed = _count(S), _seed(seed)
+    s = float(noise)
+    if not s > 0.0:
+        raise ValueError("noise must be positive, got %r" % (noise,))
+    d2 = desc.with_(form=2, noise=s)
+    kw = _solve_kw(tol, refine, max_iter)
+    out = torch.empty(S, desc.n, dtype=torch.float32, device=desc.data.graph.device)
+    with torch.no_grad():
+        yv = _targets(desc, y)
+        for c0 in range(0, S, CHUNK):
+            C = min(CHUNK, S - c0)
+            X = cg_solve(d2, posterior_rhs(desc, yv, s, C, seed, c0), **kw)[0]
+            if noisy:
+                X = X + gmrf_noise(desc.data, C, seed, c0, node_coef=math.sqrt(s), tag=3)
+            out[c0:c0 + C] = X.t()
+    return out
+
+
+def posterior_mean(desc, y, noise, tol=1e-5, refine=0, max_iter=5000):
+    """(I + s Q2)^-1 y: [n] float32 (the precision-form posterior mean at the graph nodes)."""
+    from .solvers import cg_solve
+    _check_desc(desc)
+    s = float(noise)
+    if not s > 0.0:
+        raise ValueError("noise must be positive, got %r" % (noise,))
+    with torch.no_grad():
+        return cg_solve(desc.with_(form=2, noise=s), _targets(desc, y), **_solve_kw(tol, refine, max_iter))[0].view(-1)
