@@ -101,7 +101,7 @@ class SchurComplementOperator(LinearOperator):
         _lib.require_device(rhs)
         squeeze = rhs.dim() == 1
         v = _lib.f32c(rhs.unsqueeze(-1) if squeeze else rhs)
-        hyper = self._hyper_tensors()
+        hyper = [h for h in self._hyper_tensors() if torch.is_tensor(h)]      # (a hyper-parameter may be a python float)
         if needs_grad(rhs, *hyper):
             res = _SchurMatmul.apply(v, self, *hyper)
         else:

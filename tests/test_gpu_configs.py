@@ -551,6 +551,83 @@ def test_c4_semisupervised_60k_schur(mgp, dev, rmnist60k):
     assert losses[-1] < losses[0]
 
 
+def test_c3c4_surrogate_gradients_60k_vs_float64(mgp, dev, rmnist60k):
+    """The training gradient at size: the stochastic branch's surrogate of solvers.inv_quad_logdet, <S, Q3 Z> with Z the 32
+    Rademacher probes of seed 4321 and S = Q3^-1 Z the library's own solves (detached), on the C3 / C4 graph (60k nodes, k = 50,
+    random walk, nu = 2, Noise(Scale(Precision(L)))).  Its gradients wrt eps, lengthscale, outputscale and noise against
+    oracle/grad_ref.py in float64 on the same S and Z (the Monte-Carlo and solve errors cancel): |got - ref| <= 2e-4 sum_i
+    |S_i| |(dQ3/d theta Z)_i|, and <= 2e-3 |ref| where |ref| is a tenth of that or more.  Measured worst ratio: 4.9e-5."""
+    from manifold_gp_amd.slq import rademacher_probes
+    from oracle.grad_ref import bilinear_grads_f64
+    w = rmnist60k
+    kern, hp, eps = w["kern"], w["hp"], w["eps"]
+    graph = kern.knn.knn_graph
+    n = graph.n
+    assert n == 60000
+    O = mgp.operators
+    theta = [float(eps), hp["lengthscale"], hp["outputscale"], hp["noise"]]
+    th = [torch.tensor(v, device=dev, requires_grad=True) for v in theta]
+    lap = O.GraphLaplacianOperator(graph.edge_value, graph.edge_index, n, th[0].view(1, 1), "randomwalk", True, graph=graph)
+    Q3 = O.NoiseWrapperOperator(O.ScaleWrapperOperator(O.PrecisionMaternOperator(lap, 2, th[1]), th[2]), th[3])
+    Z = rademacher_probes(n, 32, 4321, dev)
+    with torch.no_grad(), mgp.settings.cg_tolerance(1e-4):
+        S = Q3.solve(Z)
+    got = np.array([float(x) for x in torch.autograd.grad((S * Q3.matmul(Z)).sum(), th)])
+    th32 = [float(np.float32(v)) for v in theta]
+    ref, scale = bilinear_grads_f64(graph.edge_value.double().cpu(), graph.edge_index.cpu(), n, th32, 2, "randomwalk", True,
+                                    Z.double().cpu(), S.double().cpu(), chunk=8)
+    worst = 0.0
+    for nm, x, r, s in zip(["eps", "lengthscale", "outputscale", "noise"], got, ref, scale):
+        assert abs(x - r) <= 2e-4 * s, (nm, x, r, s)
+        if abs(r) >= 0.1 * s:
+            assert abs(x - r) <= 2e-3 * abs(r), (nm, x, r)
+        worst = max(worst, abs(x - r) / (2e-4 * s))
+    print("C3/C4 surrogate gradients: HIP", got, "float64", ref, "worst ratio %.2e" % worst)
+
+
+def test_c4_wrapped_schur_gradients_60k_vs_float64(mgp, dev, rmnist60k):
+    """C4's loss operator Noise(Scale(Schur(Q))) on the 60k graph, 10 % labelled, inner CG at 1e-7: the gradients of
+    <v, Noise(Scale(S)) v> wrt outputscale and noise against the closed form with converged float64 Schur matvecs
+    (oracle/grad_ref.py::wrapped_schur_quadform_f64), wrt eps against a float64 central difference of that oracle.  Bound 2e-3
+    relative; measured worst: 1.9e-7 (eps).  The length scale is a python float: the regression test of
+    SchurComplementOperator passing only tensor hyper-parameters to _SchurMatmul."""
+    from oracle.grad_ref import wrapped_schur_quadform_f64
+    from oracle.sparse import SparsePrecision
+    w = rmnist60k
+    kern, hp, eps = w["kern"], w["hp"], w["eps"]
+    graph = kern.knn.knn_graph
+    n = graph.n
+    torch.manual_seed(1337)
+    labeled = torch.zeros(n, dtype=torch.bool, device=dev)
+    labeled[torch.randperm(n, device=dev)[: n // 10]] = True
+    mask = labeled.cpu().numpy()
+    O = mgp.operators
+    v = w["y"][labeled].contiguous()
+    e_t = torch.tensor([[float(eps)]], device=dev, requires_grad=True)
+    s_t = torch.tensor(hp["outputscale"], device=dev, requires_grad=True)
+    z_t = torch.tensor(hp["noise"], device=dev, requires_grad=True)
+    lap = O.GraphLaplacianOperator(graph.edge_value, graph.edge_index, n, e_t, "randomwalk", True, graph=graph)
+    P = O.NoiseWrapperOperator(O.ScaleWrapperOperator(O.SchurComplementOperator(O.PrecisionMaternOperator(lap, 2, hp["lengthscale"]),
+                                                                               labeled), s_t), z_t)
+    with mgp.settings.cg_tolerance(1e-7), mgp.settings.cg_stop_mode(1), mgp.settings.max_cg_iterations(20000):
+        loss = torch.dot(v, P.matmul(v))
+    loss.backward()
+    eps32 = float(np.float32(eps))
+    v64 = v.double().cpu().numpy()
+
+    def oracle(e):
+        sp_ = SparsePrecision(_oracle_lap(graph, e, "randomwalk"), 2, float(np.float32(hp["lengthscale"])))
+        return wrapped_schur_quadform_f64(sp_, v64, mask, float(np.float32(hp["outputscale"])), float(np.float32(hp["noise"])))
+    f64, d_scale, d_noise = oracle(eps32)
+    h = 1e-4 * eps32
+    d_eps = (oracle(eps32 + h)[0] - oracle(eps32 - h)[0]) / (2 * h)
+    assert abs(float(loss) - f64) <= 1e-4 * abs(f64), (float(loss), f64)
+    for name, t, want in (("scale", s_t, d_scale), ("noise", z_t, d_noise), ("eps", e_t, d_eps)):
+        err = abs(float(t.grad) - want) / abs(want)
+        print("C4 wrapped Schur gradient %s: HIP %.8g float64 %.8g rel err %.1e" % (name, float(t.grad), want, err))
+        assert err <= 2e-3, (name, float(t.grad), want)
+
+
 @pytest.mark.parametrize("recurrence", ["pipelined", "chronopoulos-gear"])
 def test_c4_partition_60k_eight_virtual_ranks(mgp, dev, rmnist60k, recurrence):
     """Config C4's partition at its size (rows AND vectors of the 60k graph over the 8 GPUs of a node)

@@ -2135,6 +2135,26 @@ def test_schur_matmul_gradients(mgp, golden, dev):
         loss = torch.dot(v, P.matmul(v))
     loss.backward()
     assert all(torch.isfinite(t.grad).all() and float(t.grad.abs().max()) > 0 for t in (eps2, noise, scale))
+    # ... and their values: the scale and noise gradients from the closed form of <v, Noise(Scale(S)) v> with converged float64
+    # Schur matvecs (oracle/grad_ref.py::wrapped_schur_quadform_f64), the eps gradient from a float64 central difference of the
+    # same oracle.  Bound 2e-3 relative (inner CG at 1e-7; measured worst: 1.0e-7)
+    from oracle.grad_ref import wrapped_schur_quadform_f64
+    from oracle.laplacian import LaplacianOracle
+    from oracle.sparse import SparsePrecision
+    mk, v64 = g["symmetric_schur_mask"].astype(bool), v.double().cpu().numpy()
+    eps32, ls32 = float(np.float32(eps0)), float(np.float32(ls0))
+
+    def oracle(e):
+        lo = LaplacianOracle(g["edge_value"], g["edge_index"], n, e, "symmetric", bool(g["self_loops"]), dtype=np.float64)
+        return wrapped_schur_quadform_f64(SparsePrecision(lo, 1, ls32), v64, mk, float(np.float32(0.8)), float(np.float32(1e-3)))
+    f64, d_scale, d_noise = oracle(eps32)
+    h = 1e-4 * eps32
+    d_eps = (oracle(eps32 + h)[0] - oracle(eps32 - h)[0]) / (2 * h)
+    assert abs(float(loss) - f64) <= 1e-4 * abs(f64), (float(loss), f64)
+    for name, t, want in (("scale", scale, d_scale), ("noise", noise, d_noise), ("eps", eps2, d_eps)):
+        err = abs(float(t.grad) - want) / abs(want)
+        print("wrapped Schur gradient %s: HIP %.8g float64 %.8g rel err %.1e" % (name, float(t.grad), want, err))
+        assert err <= 2e-3, (name, float(t.grad), want)
 
 
 @pytest.mark.parametrize("max_cholesky", [4000, 50])
