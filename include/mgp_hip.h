@@ -337,7 +337,18 @@ int mgp_gmrf_noise(const mgp_csr_t* L, const float* dsqrt, float node_coef, int 
  *         form 1: Q2 - s Q2^2 + s^2 Q2^3   (NoiseWrapperOperator, noise_wrapper_operator.py:22,
  *                                           evaluated as Q2(v - s Q2(v - s Q2 v)))
  *         form 2: I + s Q2                 ((K + s I) in precision form with K = Q2^-1:
- *                                           K (K + s I)^-1 y = (I + s Q2)^-1 y) */
+ *                                           K (K + s I)^-1 y = (I + s Q2)^-1 y)
+ *         form 3: diag(w) + s Q2           w = obs_w >= 0: observation precisions relative to the reference noise s
+ *                                           (w_i = s / sigma_i^2 on observed nodes, 0 elsewhere).  The GMRF posterior
+ *                                           on a subset of nodes / with per-node noise: precision P = Q2 + W / s,
+ *                                           mean (W + s Q2)^-1 W y; form 2 is w = 1 (docs/kernels/sampling.md).
+ *                                           Evaluated in the epilogue of the chain's last SpMM (w_i X_i + s Q2 X).
+ * obs_w is read ONLY when form == 3 (a caller built against the struct without it never has it read); form 3 with
+ * obs_w == NULL is MGP_ERR_ARG.  The weights live on the device and are not validated (the Python layer does).
+ * Form 3 is supported by: mgp_operator_apply / _apply_dot / _jacobi, the single-GPU CG (mgp_cg_solve, mgp_cg_plan_*
+ * incl. refinement and rebind; never the complex-shift or init-free starts), the Lanczos tridiagonalisations
+ * (mgp_lanczos_tridiag, mgp_lanczos_tridiag_block: A is SPD).  MGP_ERR_UNSUPPORTED from the row-partitioned and
+ * distributed paths: mgp_operator_apply_part, mgp_cg_plan_create_dist, mgp_pcg_plan_create. */
 typedef struct {
   mgp_csr_t L;
   const float* pre;   /* nullable [n] */
@@ -345,8 +356,9 @@ typedef struct {
   int32_t nu;
   float kappa;        /* lengthscale */
   float scale;        /* 1 = none */
-  int32_t form;       /* 0, 1, 2 above */
+  int32_t form;       /* 0, 1, 2, 3 above */
   float noise;        /* s */
+  const float* obs_w; /* form 3 only: [n] non-negative observation weights w (device); not read for forms 0-2 */
 } mgp_operator_t;
 
 size_t mgp_operator_workspace_bytes(const mgp_operator_t* op, int C);

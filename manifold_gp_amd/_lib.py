@@ -45,7 +45,8 @@ class CsrT(Structure):
 
 class OperatorT(Structure):
     _fields_ = [("L", CsrT), ("pre", c_void_p), ("post", c_void_p), ("nu", c_int32),
-                ("kappa", c_float), ("scale", c_float), ("form", c_int32), ("noise", c_float)]
+                ("kappa", c_float), ("scale", c_float), ("form", c_int32), ("noise", c_float),
+                ("obs_w", c_void_p)]
 
 
 class CgParamsT(Structure):

@@ -1641,11 +1641,12 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
   const int world = dist ? dist->world : 1;
   if (dist && (dist->n_loc != op->L.n || dist->world < 1 || dist->rank < 0 || dist->rank >= dist->world))
     return MGP_ERR_ARG;
+  if (dist && op->form == 3) return MGP_ERR_UNSUPPORTED;       // form 3: single-GPU plans only
   if (work_bytes < cg_bytes(op, C, world)) return MGP_ERR_WORKSPACE;
   CgPlan* pl = new (std::nothrow) CgPlan();
   if (!pl) return MGP_ERR_ARG;
   memset(pl, 0, sizeof(*pl));
-  pl->op = *op;
+  pl->op = mgp_operator_copy(op);
   pl->is_dist = dist != nullptr;
   if (dist) pl->dist = *dist;
   pl->C = C;
@@ -1740,7 +1741,7 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
     const float cc = op->noise * op->scale;
     if (g_cg_complex_shift && !minv && op->form == 2 && op->nu == 2 && !op->pre && !op->post && cc > 0.f && ar.ok() &&
         a.nbv <= kC1GammaSlots * kBlock && pl->prm.stop_mode == 1) {
-      pl->opB = *op;
+      pl->opB = mgp_operator_copy(op);
       pl->opB.nu = 1;
       pl->opB.kappa = op->kappa / sqrtf(2.0f);       // tau_B = 2 / kappa_B^2 = 2 nu / kappa^2
       pl->opB.scale = 1.0f; pl->opB.form = 0; pl->opB.noise = 0.f;
@@ -1832,7 +1833,9 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
   if (pl->poisoned || pl->is_dist) return MGP_ERR_UNSUPPORTED;
   const mgp_operator_t& o = pl->op;
   // the same STRUCTURE: everything that chose kernels, grids and buffer sizes at creation
+  // (form 3: obs_w is read for that form only -- present on both sides, as the form is the same)
   const bool same = op->L.n == o.L.n && op->L.ncols == o.L.ncols && op->nu == o.nu && op->form == o.form &&
+                    (op->form != 3 || ((op->obs_w != nullptr) == (o.obs_w != nullptr))) &&
                     (op->pre != nullptr) == (o.pre != nullptr) && (op->post != nullptr) == (o.post != nullptr) &&
                     (minv != nullptr) == (pl->args.minv != nullptr) &&
                     (op->L.tile_ptr != nullptr) == (o.L.tile_ptr != nullptr) && op->L.tile_rows == o.L.tile_rows &&
@@ -1846,14 +1849,14 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
   if (pl->cx) {
     const float cc = op->noise * op->scale;
     if (!(cc > 0.f)) return MGP_ERR_UNSUPPORTED;
-    pl->opB = *op;
+    pl->opB = mgp_operator_copy(op);
     pl->opB.nu = 1;
     pl->opB.kappa = op->kappa / sqrtf(2.0f);
     pl->opB.scale = 1.0f; pl->opB.form = 0; pl->opB.noise = 0.f;
     if (mgp_spmm_dot_blocks_for(&pl->opB.L, 4) != pl->nb4) return MGP_ERR_UNSUPPORTED;
     pl->cxa.sigma = sqrtf(cc);
   }
-  pl->op = *op;
+  pl->op = mgp_operator_copy(op);
   pl->args.minv = minv;
   pl->args.pre = op->pre;
   pl->rebound = true;

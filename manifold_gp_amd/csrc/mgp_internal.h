@@ -1,7 +1,18 @@
 // Internal (non-exported) entry points shared between the translation units of libmgp_hip.
 #pragma once
+#include <stddef.h>
+#include <string.h>
 #include <vector>
 #include "mgp_hip.h"
+
+// A copy of the caller's operator that touches obs_w only for form 3: a caller built against the struct without that
+// trailing field passes fewer bytes (include/mgp_hip.h).
+inline mgp_operator_t mgp_operator_copy(const mgp_operator_t* op) {
+  mgp_operator_t o;
+  memcpy(&o, op, offsetof(mgp_operator_t, obs_w));
+  o.obs_w = op->form == 3 ? op->obs_w : nullptr;
+  return o;
+}
 
 // mgp_spmm_fused plus: `skip` (device flag: the launch is a no-op when non-zero) and `tick`
 // (device counter incremented once per non-skipped launch) -- used by the CG iteration graph.
@@ -30,6 +41,12 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
                          const float* pre, const float* post, const float* base, float cb, float co,
                          const float* dotw, float* dot_partials, const int* skip, int* tick,
                          const MgpFirst* first, void* stream);
+// the same with a per-row coefficient of base: Y = cbv[i] * base + co * t (cbv nullable: cb as above; indexed like post,
+// i.e. by global row).  Operator form 3 (diag(w) X + s Q2 X) passes its observation weights here.
+int mgp_spmm_fused_cbv(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
+                       const float* pre, const float* post, const float* base, float cb, const float* cbv, float co,
+                       const float* dotw, float* dot_partials, const int* skip, int* tick, const MgpFirst* first,
+                       void* stream);
 int mgp_spmm_patch_node(void* exec, void* node, const void* record, const float* old_ptr, const float* new_ptr);
 // first apply of an init-free solve: launch 0 reads `rhs` (pre-scaled in the kernel by op->pre) and copies it to
 // r_copy; later launches take r_copy as base / dot weight; partials of r . A r and ||r||^2; state reset

@@ -5,6 +5,8 @@
 //   form 0: A = Q2
 //   form 1: A = Q2 (I - s Q2 (I - s Q2))                     noise_wrapper_operator.py:22
 //   form 2: A = I + s Q2                                     (K + s I) system, K = Q2^-1
+//   form 3: A = diag(w) + s Q2                               w = obs_w: observation weights (GMRF posterior on a subset
+//                                                            of nodes / per-node noise; form 2 is w = 1)
 //
 // The reference runs nu x (2 spmm + ~5 elementwise) launches per Q application and allocates a
 // fresh [N,C] tensor for each; here one Q application is nu launches that ping-pong between two
@@ -43,8 +45,10 @@ namespace {
 // Y = cb * base + co * Q2 X   (base nullable).  t0/t1: [n*C] scratch, distinct from X and Y.
 // Xs (nullable): diag(pre) X already formed by the producer of X (saves the second gather per entry)
 // d (nullable): row partition -- each launch computes the local rows, then the slices are gathered
+// cbv (nullable): per-row cb (form 3: Y = diag(w) base + co Q2 X), read by the last launch only
 int q2_chain(const mgp_operator_t* op, const MgpDist* d, int nb_loc, const float* X, const float* Xs, int C,
-             float* Y, const float* base, float cb, float co, float* t0, float* t1, const Hooks* hk, void* stream) {
+             float* Y, const float* base, float cb, float co, float* t0, float* t1, const Hooks* hk, void* stream,
+             const float* cbv = nullptr) {
   const float tau = 2.0f * (float)op->nu / (op->kappa * op->kappa);
   const float* in = Xs ? Xs : X;
   for (int s = 0; s < op->nu; ++s) {
@@ -56,11 +60,11 @@ int q2_chain(const mgp_operator_t* op, const MgpDist* d, int nb_loc, const float
     MgpFirst fst{(first && hk) ? hk->copy_x : nullptr, (last && hk) ? hk->dot2_partials : nullptr,
                  (last && hk) ? hk->tick_reset : 0, (first && hk) ? hk->record : nullptr};
     const bool use_fst = fst.copy_x || fst.dot2_partials || fst.tick_reset || fst.record;
-    MGP_TRY(mgp_spmm_fused_first(&op->L, d ? d->row_offset : 0, in, C, out, tau, 1.0f,
-                                 (first && !Xs) ? op->pre : nullptr, last ? op->post : nullptr,
-                                 last ? base : nullptr, cb, last ? co * op->scale : 1.0f,
-                                 (last && hk) ? hk->dotw : nullptr, dp, hk ? hk->skip : nullptr,
-                                 (last && hk) ? hk->tick : nullptr, use_fst ? &fst : nullptr, stream));
+    MGP_TRY(mgp_spmm_fused_cbv(&op->L, d ? d->row_offset : 0, in, C, out, tau, 1.0f,
+                               (first && !Xs) ? op->pre : nullptr, last ? op->post : nullptr,
+                               last ? base : nullptr, cb, last ? cbv : nullptr, last ? co * op->scale : 1.0f,
+                               (last && hk) ? hk->dotw : nullptr, dp, hk ? hk->skip : nullptr,
+                               (last && hk) ? hk->tick : nullptr, use_fst ? &fst : nullptr, stream));
     if (d) {
       // the collectives run unconditionally (also after convergence) so that every rank issues
       // the same sequence; a skipped launch leaves stale but finite data behind them
@@ -87,7 +91,8 @@ int q2_chain(const mgp_operator_t* op, const MgpDist* d, int nb_loc, const float
 int check_op(const mgp_operator_t* op) {
   if (!op || !op->L.rowptr || !op->L.col || !op->L.vals || !op->L.diag) return MGP_ERR_ARG;
   if (op->L.n <= 0 || op->nu < 1 || op->nu > 16 || !(op->kappa > 0.f)) return MGP_ERR_ARG;
-  if (op->form < 0 || op->form > 2) return MGP_ERR_ARG;
+  if (op->form < 0 || op->form > 3) return MGP_ERR_ARG;
+  if (op->form == 3 && !op->obs_w) return MGP_ERR_ARG;     // obs_w is read for form 3 only
   return MGP_OK;
 }
 
@@ -117,6 +122,7 @@ int mgp_operator_apply_dist(const mgp_operator_t* op, const MgpDist* d, const fl
                             void* work, size_t work_bytes, void* stream) {
   MGP_TRY(check_op(op));
   if (!X || !Y || X == Y || C <= 0) return MGP_ERR_ARG;
+  if (d && op->form == 3) return MGP_ERR_UNSUPPORTED;       // form 3 is single-GPU only
   const int64_t nrows = d ? d->n_loc * d->world : op->L.n;
   if (!work || work_bytes < 4 * mgp_align((size_t)nrows * C * sizeof(float))) return MGP_ERR_WORKSPACE;
   MgpArena ar(work, work_bytes);
@@ -133,6 +139,8 @@ int mgp_operator_apply_dist(const mgp_operator_t* op, const MgpDist* d, const fl
       return q2_chain(op, d, nb_loc, X, Xs, C, Y, nullptr, 0.f, 1.f, t0, t1, &hk, stream);
     case 2:
       return q2_chain(op, d, nb_loc, X, Xs, C, Y, X, 1.f, op->noise, t0, t1, &hk, stream);
+    case 3:
+      return q2_chain(op, d, nb_loc, X, Xs, C, Y, X, 1.f, op->noise, t0, t1, &hk, stream, op->obs_w);
     case 1:
       // Q(v - s Q(v - s Q v))
       MGP_TRY(q2_chain(op, d, nb_loc, X, Xs, C, ua, X, 1.f, -op->noise, t0, t1, &hk_mid, stream));
@@ -176,7 +184,7 @@ __global__ void spmm_f64_kernel(int64_t n, const int32_t* __restrict__ rowptr, c
                                 const float* __restrict__ vals, const float* __restrict__ diag,
                                 const double* __restrict__ X, double* __restrict__ Y, int C, double a, double b,
                                 const float* __restrict__ pre, const float* __restrict__ post,
-                                const double* __restrict__ base, double cb, double co) {
+                                const double* __restrict__ base, double cb, double co, const float* __restrict__ cbv) {
   const int64_t total = n * C;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / C;
@@ -192,7 +200,7 @@ __global__ void spmm_f64_kernel(int64_t n, const int32_t* __restrict__ rowptr, c
     if (pre) xs *= (double)pre[r];
     double t = a * xs + b * ((double)diag[r] * xs - acc);
     if (post) t *= (double)post[r];
-    Y[i] = (base ? cb * base[i] : 0.0) + co * t;
+    Y[i] = (base ? (cbv ? (double)cbv[r] : cb) * base[i] : 0.0) + co * t;
   }
 }
 
@@ -205,7 +213,8 @@ __global__ __launch_bounds__(256) void spmv_f64_kernel(int64_t n, const int32_t*
                                                        const float* __restrict__ diag, const double* __restrict__ X,
                                                        double* __restrict__ Y, double a, double b,
                                                        const float* __restrict__ pre, const float* __restrict__ post,
-                                                       const double* __restrict__ base, double cb, double co) {
+                                                       const double* __restrict__ base, double cb, double co,
+                                                       const float* __restrict__ cbv) {
   const int lane = threadIdx.x & (G - 1);
   const int64_t rows_per_pass = (int64_t)gridDim.x * (256 / G);
   for (int64_t r = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G; r < n; r += rows_per_pass) {
@@ -224,13 +233,13 @@ __global__ __launch_bounds__(256) void spmv_f64_kernel(int64_t n, const int32_t*
       if (pre) xs *= (double)pre[r];
       double t = a * xs + b * ((double)diag[r] * xs - acc);
       if (post) t *= (double)post[r];
-      Y[r] = (base ? cb * base[r] : 0.0) + co * t;
+      Y[r] = (base ? (cbv ? (double)cbv[r] : cb) * base[r] : 0.0) + co * t;
     }
   }
 }
 
 int q2_chain_f64(const mgp_operator_t* op, const double* X, int C, double* Y, const double* base, double cb, double co,
-                 double* t0, double* t1, hipStream_t st) {
+                 double* t0, double* t1, hipStream_t st, const float* cbv = nullptr) {
   const double tau = 2.0 * (double)op->nu / ((double)op->kappa * (double)op->kappa);
   const int64_t n = op->L.n;
   int64_t grid = mgp_cdiv(n * C, 256);
@@ -244,11 +253,11 @@ int q2_chain_f64(const mgp_operator_t* op, const double* X, int C, double* Y, co
       if (g1 > 65535 * 4) g1 = 65535 * 4;
       hipLaunchKernelGGL((spmv_f64_kernel<16>), dim3((unsigned)g1), dim3(256), 0, st, n, op->L.rowptr, op->L.col,
                          op->L.vals, op->L.diag, in, out, tau, 1.0, first ? op->pre : nullptr, last ? op->post : nullptr,
-                         last ? base : nullptr, cb, last ? co * (double)op->scale : 1.0);
+                         last ? base : nullptr, cb, last ? co * (double)op->scale : 1.0, last ? cbv : nullptr);
     } else {
       hipLaunchKernelGGL(spmm_f64_kernel, dim3((unsigned)grid), dim3(256), 0, st, n, op->L.rowptr, op->L.col, op->L.vals,
                          op->L.diag, in, out, C, tau, 1.0, first ? op->pre : nullptr, last ? op->post : nullptr,
-                         last ? base : nullptr, cb, last ? co * (double)op->scale : 1.0);
+                         last ? base : nullptr, cb, last ? co * (double)op->scale : 1.0, last ? cbv : nullptr);
     }
     MGP_LAUNCH_CHECK();
     in = out;
@@ -269,6 +278,7 @@ int mgp_operator_apply_f64(const mgp_operator_t* op, const double* X, int C, dou
   switch (op->form) {
     case 0: return q2_chain_f64(op, X, C, Y, nullptr, 0.0, 1.0, t0, t1, st);
     case 2: return q2_chain_f64(op, X, C, Y, X, 1.0, noise, t0, t1, st);
+    case 3: return q2_chain_f64(op, X, C, Y, X, 1.0, noise, t0, t1, st, op->obs_w);
     case 1:
       MGP_TRY(q2_chain_f64(op, X, C, ua, X, 1.0, -noise, t0, t1, st));
       MGP_TRY(q2_chain_f64(op, ua, C, ub, X, 1.0, -noise, t0, t1, st));
@@ -294,7 +304,7 @@ extern "C" int mgp_operator_apply_dot(const mgp_operator_t* op, const float* X, 
 __global__ void jacobi_kernel(int64_t n, const int32_t* __restrict__ rowptr, const float* __restrict__ vals,
                               const float* __restrict__ diag, const float* __restrict__ pre,
                               const float* __restrict__ post, int nu, float tau, float scale, int form,
-                              float noise, float* __restrict__ minv) {
+                              float noise, const float* __restrict__ obs_w, float* __restrict__ minv) {
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n;
        r += (int64_t)gridDim.x * blockDim.x) {
     const float b = tau + diag[r];
@@ -314,6 +324,7 @@ __global__ void jacobi_kernel(int64_t n, const int32_t* __restrict__ rowptr, con
     float a;
     if (form == 0) a = q;
     else if (form == 2) a = 1.0f + noise * q;
+    else if (form == 3) a = obs_w[r] + noise * q;
     else a = q * (1.0f - noise * q * (1.0f - noise * q));
     minv[r] = (a > 0.f && isfinite(a)) ? 1.0f / a : 1.0f;
   }
@@ -327,7 +338,7 @@ extern "C" int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* 
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(jacobi_kernel, dim3((int)grid), dim3(256), 0, mgp_stream(stream), op->L.n, op->L.rowptr,
                      op->L.vals, op->L.diag, op->pre, op->post, op->nu, tau, op->scale, op->form, op->noise,
-                     minv);
+                     op->form == 3 ? op->obs_w : nullptr, minv);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

@@ -760,7 +760,7 @@ extern "C" int mgp_pcg_plan_create(const mgp_operator_t* op, const int64_t* laun
   PcgPlan* pl = new (std::nothrow) PcgPlan();
   if (!pl) return MGP_ERR_ARG;
   memset(pl, 0, sizeof(*pl));
-  pl->op = *op;
+  pl->op = mgp_operator_copy(op);
   pl->recurrence = recurrence;
   memcpy(pl->launch_rows, launch_rows, sizeof(int64_t) * op->nu);
   pl->comm = static_cast<ncclComm_t>(comm);

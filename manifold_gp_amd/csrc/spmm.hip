@@ -3,7 +3,8 @@
 //   xs_j = pre ? pre[j] * X[j,:] : X[j,:]
 //   lx_i = diag[i] * xs_i - sum_j vals[ij] * xs_j
 //   t_i  = (post ? post[i] : 1) * (a * xs_i + b * lx_i)
-//   Y[i,:] = (base ? cb * base[i,:] : 0) + co * t_i ;  partial sums of dotw[i,:] * Y[i,:]
+//   Y[i,:] = (base ? cb_i * base[i,:] : 0) + co * t_i ;  partial sums of dotw[i,:] * Y[i,:]
+//   cb_i = cbv ? cbv[i] : cb   (cbv: internal, the observation weights of operator form 3)
 //
 // Replaces GraphLaplacianOperator._matmul (manifold_gp/operators/graph_laplacian_operator.py:
 // 108-124), i.e. 2 x torch_sparse.spmm (index_select + mul + atomic scatter_add) + ~5
@@ -58,6 +59,7 @@ struct SpmmArgs {
   float* copy_x;          // nullable: the epilogue stores the row's raw input x[row] here (r = b)
   float* dot2_partials;   // nullable: per-workgroup partials of sum dotw[row]^2 (||b||^2)
   int tick_reset;         // tick != NULL: write {1, 0, 0} (iteration 1, not done, no status) instead of adding 1
+  const float* cbv;       // nullable [rows]: per-row coefficient of base (cbv[row] instead of cb; indexed like post)
 #ifdef MGP_STAMP
   // lab build only: the stamps go BEHIND the skip / tick words, space that only cg.hip's CgPlan reserves (its state block
   // + 1024 + 8192 floats).  Other callers of the tile kernel with skip / tick (pcg.hip's 16-float state, the Lanczos and
@@ -80,13 +82,14 @@ __device__ __forceinline__ float4 load_val4(const float* base, int idx) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
+template <bool CBV>
 __device__ __forceinline__ float epilogue(const SpmmArgs& p, int64_t r, int c, float xs, float acc) {
   const int64_t gr = r + p.goff;
   float lx = p.diag[r] * xs - acc;
   float t = p.a * xs + p.b * lx;
   if (p.post) t *= p.post[gr];
   float y = p.co * t;
-  if (p.base) y += p.cb * p.base[gr * p.C + c];
+  if (p.base) y += (CBV ? p.cbv[gr] : p.cb) * p.base[gr * p.C + c];
   return y;
 }
 
@@ -96,7 +99,7 @@ __device__ __forceinline__ float epilogue(const SpmmArgs& p, int64_t r, int c, f
 // then R shuffle reductions.  Three dependent memory phases per group instead of 3R: at N = 60k
 // the kernel is latency-bound (the matrix is cache resident), so bytes in flight per lane is
 // what sets the rate.  Rows longer than 4G entries take the (rare) remainder loop.
-template <int G, int R, bool PRE>
+template <int G, int R, bool PRE, bool CBV>
 __global__ __launch_bounds__(kBlock) void spmv_kernel(SpmmArgs p) {
   constexpr int BS = kBlock;
   if (p.skip && *p.skip) return;
@@ -130,6 +133,7 @@ __global__ __launch_bounds__(kBlock) void spmv_kernel(SpmmArgs p) {
     const float e_diag = p.diag[er];
     const float e_post = p.post ? p.post[ger] : 1.f;
     const float e_base = p.base ? p.base[ger] : 0.f;
+    const float e_cb = CBV ? p.cbv[ger] : p.cb;
     const float e_dotw = p.dotw ? p.dotw[ger] : 0.f;
     int4 c[R];
     float4 v[R];
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void spmv_kernel(SpmmArgs p) {
     if (mine) {
       const float lx = e_diag * e_x - my_acc;
       const float tt = (p.a * e_x + p.b * lx) * e_post;
-      const float y = p.co * tt + p.cb * e_base;
+      const float y = p.co * tt + e_cb * e_base;
       p.Y[myr + p.goff] = y;
       dsum = fmaf(e_dotw, y, dsum);
     }
@@ -234,7 +238,7 @@ struct TileArgs {
 
 typedef unsigned short mgp_v4h __attribute__((ext_vector_type(4)));
 
-template <bool PRE, int BS>
+template <bool PRE, int BS, bool CBV>
 __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
   // the CG graph's skip flag / iteration tick: loaded here, consumed only after the first tile's
@@ -339,6 +343,7 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
     const float e_post = p.post ? l_post : 1.f;
     const float e_base = p.base ? l_base : 0.f;
     const float e_dotw = p.dotw ? l_dotw : 0.f;
+    const float e_cb = CBV ? p.cbv[grr] : p.cb;
     __builtin_amdgcn_sched_barrier(0);
     if (p.skip && skipl) return;          // CG converged: every load above went to a valid address, nothing is written
 #pragma unroll
@@ -390,7 +395,7 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
     if (valid && sub == 0) {
       const float lx = e_diag * e_x - acc;
       const float tt = (p.a * e_x + p.b * lx) * e_post;
-      const float y = p.co * tt + p.cb * e_base;
+      const float y = p.co * tt + e_cb * e_base;
       p.Y[grr] = y;
       dsum = fmaf(e_dotw, y, dsum);
       dsum2 = fmaf(e_dotw, e_dotw, dsum2);
@@ -427,7 +432,7 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
 
 // ---------------------------------------------------------------- C > 1
 // G lanes per row laid over columns; NACC column accumulators per lane (columns lane + a*G).
-template <int G, int NACC, bool PRE>
+template <int G, int NACC, bool PRE, bool CBV>
 __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs p) {
   if (p.skip && *p.skip) return;
   if (p.tick && blockIdx.x == 0 && threadIdx.x == 0) *p.tick += 1;
@@ -495,7 +500,7 @@ __global__ __launch_bounds__(kBlock) void spmm_kernel(SpmmArgs p) {
       const int c = lane + a * G;
       if (c < C) {
         const float xs = p.X[gr * C + c] * prer;
-        const float y = epilogue(p, r, c, xs, acc[a]);
+        const float y = epilogue<CBV>(p, r, c, xs, acc[a]);
         p.Y[gr * C + c] = y;
         if (p.dotw) dsum[a] = fmaf(p.dotw[gr * C + c], y, dsum[a]);
       }
@@ -557,7 +562,7 @@ __device__ __forceinline__ mgp_v4f quad_products(mgp_v4f vv, mgp_v4f a0, mgp_v4f
 // 16 bytes of each of the four X rows that are its own; two quads = eight X pieces per lane are in flight while the
 // next quads' ids are fetched.  Per entry and 4 columns: a quarter of a 16-byte id load, one 64-bit address, one
 // 16-byte load, two packed fmas.
-template <int LPR, bool PRE>
+template <int LPR, bool PRE, bool CBV>
 __global__ __launch_bounds__(kBlock) void spmm_v4_kernel(SpmmArgs p) {
   if (p.skip && *p.skip) return;
   if (p.tick && blockIdx.x == 0 && threadIdx.x == 0) *p.tick += 1;
@@ -614,10 +619,11 @@ __global__ __launch_bounds__(kBlock) void spmm_v4_kernel(SpmmArgs p) {
     if (lon) {
       const float xs0 = e_x.x * e_pre, xs1 = e_x.y * e_pre, xs2 = e_x.z * e_pre, xs3 = e_x.w * e_pre;
       mgp_v4f y;
-      y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? p.cb * l_base.x : 0.f);
-      y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? p.cb * l_base.y : 0.f);
-      y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? p.cb * l_base.z : 0.f);
-      y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? p.cb * l_base.w : 0.f);
+      const float l_cb = CBV ? p.cbv[gr] : p.cb;
+      y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? l_cb * l_base.x : 0.f);
+      y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? l_cb * l_base.y : 0.f);
+      y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? l_cb * l_base.z : 0.f);
+      y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? l_cb * l_base.w : 0.f);
       *reinterpret_cast<mgp_v4f*>(p.Y + gr * C + 4 * l) = y;
       if (p.dotw) {
         dsum.x = fmaf(l_dotw.x, y.x, dsum.x); dsum.y = fmaf(l_dotw.y, y.y, dsum.y);
@@ -661,7 +667,7 @@ __device__ __forceinline__ float row16_class_sum(float v) {   // sum over lanes 
   return v;
 }
 
-template <int C4, bool PRE>
+template <int C4, bool PRE, bool CBV>
 __global__ __launch_bounds__(kBlock) void spmm_row16_kernel(SpmmArgs p) {
   if (p.skip && *p.skip) return;
   if (p.tick && blockIdx.x == 0 && threadIdx.x == 0) *p.tick += 1;
@@ -714,8 +720,8 @@ __global__ __launch_bounds__(kBlock) void spmm_row16_kernel(SpmmArgs p) {
       const float prer = PRE ? p.pre[gr] : 1.f;
       const mgp_v4f xin = X4[gr * C4 + q];
       mgp_v4f y;
-      y.x = epilogue(p, r, 4 * q + 0, xin.x * prer, acc.x); y.y = epilogue(p, r, 4 * q + 1, xin.y * prer, acc.y);
-      y.z = epilogue(p, r, 4 * q + 2, xin.z * prer, acc.z); y.w = epilogue(p, r, 4 * q + 3, xin.w * prer, acc.w);
+      y.x = epilogue<CBV>(p, r, 4 * q + 0, xin.x * prer, acc.x); y.y = epilogue<CBV>(p, r, 4 * q + 1, xin.y * prer, acc.y);
+      y.z = epilogue<CBV>(p, r, 4 * q + 2, xin.z * prer, acc.z); y.w = epilogue<CBV>(p, r, 4 * q + 3, xin.w * prer, acc.w);
       *reinterpret_cast<mgp_v4f*>(p.Y + gr * C + 4 * q) = y;
       if (p.dotw) {
         const float* dw = p.dotw + gr * C + 4 * q;
@@ -754,7 +760,7 @@ __global__ __launch_bounds__(kBlock) void spmm_row16_kernel(SpmmArgs p) {
 // overlapped with it.  Counters (tools/pmc_kernel.sh, C = 12): LDS array busy 12 k cycles per CU (51 % of them bank
 // conflicts of the random gathers), 3.2 M L1 accesses, 2.1 M VALU wave-instructions, waves 42 % waiting on a
 // counter and 20 % issuing: no unit is saturated, the phases between the three barriers of a pass do not overlap.
-template <int C4, bool PRE>
+template <int C4, bool PRE, bool CBV>
 __global__ __launch_bounds__(256, 4) void spmm_tile_q_kernel(SpmmArgs p, TileArgs t) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
   constexpr int BS = 256, TR = 64, NQ = 4, C = 4 * C4;
@@ -899,10 +905,11 @@ __global__ __launch_bounds__(256, 4) void spmm_tile_q_kernel(SpmmArgs p, TileArg
       if (valid && sub == u) {
         const float xs0 = e_x.x * e_pre, xs1 = e_x.y * e_pre, xs2 = e_x.z * e_pre, xs3 = e_x.w * e_pre;
         mgp_v4f y;
-        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? p.cb * l_base.x : 0.f);
-        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? p.cb * l_base.y : 0.f);
-        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? p.cb * l_base.z : 0.f);
-        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? p.cb * l_base.w : 0.f);
+        const float l_cb = CBV ? p.cbv[grr] : p.cb;
+        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? l_cb * l_base.x : 0.f);
+        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? l_cb * l_base.y : 0.f);
+        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? l_cb * l_base.z : 0.f);
+        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? l_cb * l_base.w : 0.f);
         *reinterpret_cast<mgp_v4f*>(p.Y + grr * C + 4 * u) = y;
         if (p.dotw) {
           dsum.x = fmaf(l_dotw.x, y.x, dsum.x); dsum.y = fmaf(l_dotw.y, y.y, dsum.y);
@@ -947,7 +954,7 @@ __global__ __launch_bounds__(256, 4) void spmm_tile_q_kernel(SpmmArgs p, TileArg
 constexpr int kWideCap = 1024;     // dictionary columns staged per slice (64 bytes each)
 constexpr int kWideRQ = 16;        // quads of a row held in registers for all chunks of a tile
 
-template <bool PRE>
+template <bool PRE, bool CBV>
 __global__ __launch_bounds__(256, 2) void spmm_tile_wide_kernel(SpmmArgs p, TileArgs t, int dict_cap) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
   constexpr int BS = 256, TR = 64;
@@ -1070,10 +1077,11 @@ __global__ __launch_bounds__(256, 2) void spmm_tile_wide_kernel(SpmmArgs p, Tile
       mgp_v4f y = mgp_v4f{0.f, 0.f, 0.f, 0.f};
       if (valid && fon) {
         const float xs0 = e_x.x * e_pre, xs1 = e_x.y * e_pre, xs2 = e_x.z * e_pre, xs3 = e_x.w * e_pre;
-        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? p.cb * l_base.x : 0.f);
-        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? p.cb * l_base.y : 0.f);
-        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? p.cb * l_base.z : 0.f);
-        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? p.cb * l_base.w : 0.f);
+        const float l_cb = CBV ? p.cbv[grr] : p.cb;
+        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc.x)) * l_post) + (p.base ? l_cb * l_base.x : 0.f);
+        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc.y)) * l_post) + (p.base ? l_cb * l_base.y : 0.f);
+        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc.z)) * l_post) + (p.base ? l_cb * l_base.z : 0.f);
+        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc.w)) * l_post) + (p.base ? l_cb * l_base.w : 0.f);
         *reinterpret_cast<mgp_v4f*>(p.Y + grr * C + 4 * f) = y;
       }
       if (p.dot_partials) {
@@ -1137,7 +1145,7 @@ __device__ __forceinline__ void quad_fma(mgp_v4f& acc, mgp_v4f vv, mgp_v4f a0, m
   acc = mgp_v4f{lo.x, lo.y, hi.x, hi.y};
 }
 
-template <int NV, bool PRE>
+template <int NV, bool PRE, bool CBV>
 __global__ __launch_bounds__(kDictThreads) void spmm_dict_kernel(SpmmArgs p, TileArgs t, int S, int stream_cap) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
   constexpr int TR = 64, SLOT4 = 16 * NV;            // float4 per dictionary slot
@@ -1297,10 +1305,11 @@ __global__ __launch_bounds__(kDictThreads) void spmm_dict_kernel(SpmmArgs p, Til
         const mgp_v4f ld4 = *reinterpret_cast<const mgp_v4f*>((p.dotw ? p.dotw : p.X) + grr * C + 4 * f);
         const float xs0 = ex.x * e_pre, xs1 = ex.y * e_pre, xs2 = ex.z * e_pre, xs3 = ex.w * e_pre;
         mgp_v4f y;
-        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc[v].x)) * l_post) + (p.base ? p.cb * lb4.x : 0.f);
-        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc[v].y)) * l_post) + (p.base ? p.cb * lb4.y : 0.f);
-        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc[v].z)) * l_post) + (p.base ? p.cb * lb4.z : 0.f);
-        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc[v].w)) * l_post) + (p.base ? p.cb * lb4.w : 0.f);
+        const float l_cb = CBV ? p.cbv[grr] : p.cb;
+        y.x = p.co * ((p.a * xs0 + p.b * (e_diag * xs0 - acc[v].x)) * l_post) + (p.base ? l_cb * lb4.x : 0.f);
+        y.y = p.co * ((p.a * xs1 + p.b * (e_diag * xs1 - acc[v].y)) * l_post) + (p.base ? l_cb * lb4.y : 0.f);
+        y.z = p.co * ((p.a * xs2 + p.b * (e_diag * xs2 - acc[v].z)) * l_post) + (p.base ? l_cb * lb4.z : 0.f);
+        y.w = p.co * ((p.a * xs3 + p.b * (e_diag * xs3 - acc[v].w)) * l_post) + (p.base ? l_cb * lb4.w : 0.f);
         *reinterpret_cast<mgp_v4f*>(p.Y + grr * C + 4 * f) = y;
         if (p.dotw) {
           dsum[v].x = fmaf(ld4.x, y.x, dsum[v].x); dsum[v].y = fmaf(ld4.y, y.y, dsum[v].y);
@@ -1449,174 +1458,16 @@ __device__ __forceinline__ void mt_mfma(const MtBuf<PRE>& cb, mgp_v4f (&acc)[4])
 // tile order no longer share X rows in L2.  The hardware's dispatch of one wave per tile balances and co-locates better.
 template <bool PRE>
 __global__ __launch_bounds__(kBlock) void spmm_mt_kernel(SpmmArgs p, MtArgs m) {
-  constexpr int LR = PRE ? 12 : 8;      // loads per block request
-  if (p.skip && *p.skip) return;
-  if (p.tick && blockIdx.x == 0 && threadIdx.x == 0) *p.tick += 1;
-  const int lane = threadIdx.x & 63, j = lane & 15, kq = lane >> 4;
-  const int lb = mgp_xcd_block(blockIdx.x, gridDim.x);
-  const int w = __builtin_amdgcn_readfirstlane(lb * (kBlock / 64) + (int)(threadIdx.x >> 6));
-  const int t = w / m.NCB, cb = w % m.NCB;           // the column blocks of a tile side by side: they share its image
-  const int C = p.C;
-  if (t >= m.T && !p.dot_partials) return;           // (with dot partials every wave of the workgroup meets at the barrier below)
-  mgp_v4f ds = {0.f, 0.f, 0.f, 0.f};                 // this lane's share of sum_rows dotw * y for columns c0 .. c0 + 3
-  MT_STAMP(0);
-  if (t < m.T) {
-  const int blk0 = __builtin_amdgcn_readfirstlane(m.sptr[t]) >> 2, blk1 = __builtin_amdgcn_readfirstlane(m.sptr[t + 1]) >> 2;
-  const int64_t nx = p.n + p.goff;                   // rows of X the columns can name (host side: goff == 0)
-#if defined(MGP_MT_LAB) && (MGP_MT_LAB & 2)     // lab (tools/lab/mt_bounds.sh): every X request out of range -> zeros, no memory traffic
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X), (short)0, 0, 0x00020000);
-#else
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.X), (short)0, (int)(nx * C * 4), 0x00020000);
-#endif
-  const __amdgpu_buffer_rsrc_t rimg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(m.img), (short)0, m.img_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdic = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(m.dcol), (short)0, m.dic_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rpre = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(PRE ? p.pre : p.X), (short)0, (int)(nx * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdiag = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.diag), (short)0, (int)(p.n * 4), 0x00020000);
-#if defined(MGP_MT_LAB) && (MGP_MT_LAB & 4)     // lab: every X request goes to row 0 (always cached)
-  const int lane4 = lane * 4, rowbytes = 0, joff = cb * 256 + j * 16;
-#else
-  const int lane4 = lane * 4, rowbytes = C * 4, joff = cb * 256 + j * 16;
-#endif
-  const int c0 = 64 * cb + 4 * j;                    // acc[e][r]: row 16 t + 4 kq + r, column c0 + e
-  mgp_v4f acc[4], ex[4];
-  float ed[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { acc[e] = mgp_v4f{0.f, 0.f, 0.f, 0.f}; ex[e] = mgp_v4f{0.f, 0.f, 0.f, 0.f}; ed[e] = 0.f; }
-  MtBuf<PRE> buf0, buf1, buf2, buf3;
-  int dq0, dq1, dq2;          // column-list batches of the body in hand, of the next one, and the one in flight
-  const int dic0 = blk0 * 64, img0 = blk0 * 1024;      // byte offsets of the tile's first block
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(dq0) : "v"(lane4), "s"(rdic), "s"(dic0));
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:256" : "=v"(dq1) : "v"(lane4), "s"(rdic), "s"(dic0));
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(dq0), "+v"(dq1));
-  mt_request<PRE>(buf0, dq0, 0, kq, joff, rowbytes, img0, rimg, rx, rpre, lane4);
-  mt_request<PRE>(buf1, dq0, 4, kq, joff, rowbytes, img0 + 1024, rimg, rx, rpre, lane4);
-  mt_request<PRE>(buf2, dq0, 8, kq, joff, rowbytes, img0 + 2048, rimg, rx, rpre, lane4);
-  {
-    // the epilogue's operands: the X block of the tile's own rows (16 bytes per lane and row) and the diagonal
-    int offx[4], offd[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * t + 4 * kq + r;
-      // (rows past n / columns past C: in range of the descriptor or answered with 0; 24-bit multiply as in mt_request)
-      offx[r] = (int)__umul24((unsigned)row, (unsigned)(C * 4)) + c0 * 4;
-      offd[r] = row * 4;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(ex[r]) : "v"(offx[r]), "s"(rx));
-      asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "+v"(ed[r]) : "v"(offd[r]), "s"(rdiag));
-    }
-    asm volatile("" :: "v"(offx[0]), "v"(offx[1]), "v"(offx[2]), "v"(offx[3]), "v"(offd[0]), "v"(offd[1]), "v"(offd[2]), "v"(offd[3]));
-  }
-  MT_STAMP(1);
-  for (int k = blk0; k < blk1 - 4; k += 4) {
-    const int so = k * 1024, sd = k * 64;
-    asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:512" : "=v"(dq2) : "v"(lane4), "s"(rdic), "s"(sd));
-    mt_wait<2 * LR + 1, PRE>(buf0);
-    mt_request<PRE>(buf3, dq0, 12, kq, joff, rowbytes, so + 3 * 1024, rimg, rx, rpre, lane4);
-    __builtin_amdgcn_sched_barrier(0);      // requests stay in front of the block's MFMAs (left alone, the scheduler sinks them)
-    mt_mfma<PRE>(buf0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<2 * LR + 1, PRE>(buf1);
-    mt_request<PRE>(buf0, dq1, 0, kq, joff, rowbytes, so + 4 * 1024, rimg, rx, rpre, lane4);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_mfma<PRE>(buf1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<2 * LR + 1, PRE>(buf2);
-    mt_request<PRE>(buf1, dq1, 4, kq, joff, rowbytes, so + 5 * 1024, rimg, rx, rpre, lane4);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_mfma<PRE>(buf2, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<2 * LR, PRE>(buf3);
-    mt_request<PRE>(buf2, dq1, 8, kq, joff, rowbytes, so + 6 * 1024, rimg, rx, rpre, lane4);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_mfma<PRE>(buf3, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    dq0 = dq1;
-    // the batch requested at the top of this body is older than R(k+3), which wait(k+3) has seen land: 3 LR = R(k+4..k+6)
-    // waits for nothing new, it only tells the compiler where dq2 becomes readable
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(dq2) : "n"(3 * LR));
-    dq1 = dq2;
-  }
-  // ---- the tile's LAST body, peeled: in flight at the top R(k) R(k+1) R(k+2); behind the one request left, R(k+1) R(k+2) R(k+3)
-  {
-    const int so = (blk1 - 4) * 1024;
-    mt_wait<2 * LR, PRE>(buf0);
-    mt_request<PRE>(buf3, dq0, 12, kq, joff, rowbytes, so + 3 * 1024, rimg, rx, rpre, lane4);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_mfma<PRE>(buf0, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<2 * LR, PRE>(buf1);
-    mt_mfma<PRE>(buf1, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<LR, PRE>(buf2);
-    mt_mfma<PRE>(buf2, acc);
-    __builtin_amdgcn_sched_barrier(0);
-    mt_wait<0, PRE>(buf3);
-    mt_mfma<PRE>(buf3, acc);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(dq0), "+v"(dq1));
-  mt_wait<0, PRE>(buf0); mt_wait<0, PRE>(buf1); mt_wait<0, PRE>(buf2);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(ex[r]), "+v"(ed[r]));
-  MT_STAMP(2);
-#ifdef MGP_MT_STAMP
-  if (m.stamps && lane == 0) {
-    m.stamps[(size_t)w * 8 + 4] = (unsigned long long)(blk1 - blk0);
-    m.stamps[(size_t)w * 8 + 5] = (unsigned long long)__builtin_amdgcn_s_getreg(63492);     // HW_REG_HW_ID
-    m.stamps[(size_t)w * 8 + 6] = (unsigned long long)__builtin_amdgcn_s_getreg(63508);     // HW_REG_XCC_ID
-  }
-#endif
-  if (c0 < C) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = (int64_t)16 * t + 4 * kq + r;
-      if (row < p.n) {
-        const int64_t gr = row + p.goff;
-        mgp_v4f xs = ex[r];
-        if (PRE) xs *= p.pre[gr];
-        const mgp_v4f av = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
-        const mgp_v4f lx = ed[r] * xs - av;
-        mgp_v4f tt = p.a * xs + p.b * lx;
-        if (p.post) tt *= p.post[gr];
-        mgp_v4f y = p.co * tt;
-        if (p.base) y += p.cb * *reinterpret_cast<const mgp_v4f*>(p.base + gr * C + c0);
-        *reinterpret_cast<mgp_v4f*>(p.Y + gr * C + c0) = y;
-        if (p.dot_partials) {
-          const mgp_v4f dw = (p.dotw == p.X) ? ex[r] : *reinterpret_cast<const mgp_v4f*>(p.dotw + gr * C + c0);
-          ds += dw * y;
-        }
-      }
-    }
-  }
-#ifdef MGP_MT_STAMP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  MT_STAMP(3);
-  }   // t < m.T
-  if (p.dot_partials) {
-    // per workgroup and column: lanes kq = 1..3 onto kq = 0 (fixed order), then the workgroup's waves of the column's block in
-    // wave order.  Any four consecutive waves hold every column block (NCB <= 4), except past the last tile: zeros there.
-    __shared__ float red[kBlock / 64][64];
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float v = ds[e];
-      v += __shfl_down(v, 16, 64);
-      v += __shfl_down(v, 32, 64);
-      if (kq == 0) red[wave][4 * j + e] = v;
-    }
-    __syncthreads();
-    const int w0 = lb * (kBlock / 64);
-    for (int c = threadIdx.x; c < C; c += kBlock) {
-      float tsum = 0.f;
-#pragma unroll
-      for (int wv = 0; wv < kBlock / 64; ++wv)
-        if ((w0 + wv) % m.NCB == c / 64 && (w0 + wv) / m.NCB < m.T) tsum += red[wv][c & 63];
-      p.dot_partials[(int64_t)lb * C + c] = tsum;
-    }
-  }
+  constexpr bool CBV = false;
+#include "spmm_mt_body.inc"
+}
+
+// operator form 3 (per-row coefficient of base, SpmmArgs::cbv): the same body as a kernel of its own, so that
+// spmm_mt_kernel's code (and the name tools/check_kblock_isa.py reads its instruction stream by) stays as it was
+template <bool PRE>
+__global__ __launch_bounds__(kBlock) void spmm_mt_cbv_kernel(SpmmArgs p, MtArgs m) {
+  constexpr bool CBV = true;
+#include "spmm_mt_body.inc"
 }
 
 // the image and the padded column list of the tiles: one thread per row scatters its entries
@@ -1967,25 +1818,25 @@ extern "C" int mgp_spmm_dot_blocks(int64_t n, int C) {
   return make_plan(n, spmm_rows_per_pass(C)).grid;
 }
 
-template <int G, int R, bool PRE>
+template <int G, int R, bool PRE, bool CBV>
 static void launch_spmv(const SpmmArgs& a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((spmv_kernel<G, R, PRE>), dim3(grid), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((spmv_kernel<G, R, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a);
 }
 
-template <int G, bool PRE>
+template <int G, bool PRE, bool CBV>
 static int launch_spmv_r(const SpmmArgs& a, int R, int grid, hipStream_t st) {
   switch (R) {
-    case 1: launch_spmv<G, 1, PRE>(a, grid, st); return MGP_OK;
-    case 2: launch_spmv<G, 2, PRE>(a, grid, st); return MGP_OK;
-    case 4: launch_spmv<G, 4, PRE>(a, grid, st); return MGP_OK;
-    case 8: if (G >= 8) { launch_spmv<G, (G >= 8 ? 8 : 4), PRE>(a, grid, st); return MGP_OK; }
+    case 1: launch_spmv<G, 1, PRE, CBV>(a, grid, st); return MGP_OK;
+    case 2: launch_spmv<G, 2, PRE, CBV>(a, grid, st); return MGP_OK;
+    case 4: launch_spmv<G, 4, PRE, CBV>(a, grid, st); return MGP_OK;
+    case 8: if (G >= 8) { launch_spmv<G, (G >= 8 ? 8 : 4), PRE, CBV>(a, grid, st); return MGP_OK; }
   }
   return MGP_ERR_ARG;
 }
 
-template <int G, int NACC, bool PRE>
+template <int G, int NACC, bool PRE, bool CBV>
 static void launch_spmm(const SpmmArgs& a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((spmm_kernel<G, NACC, PRE>), dim3(grid), dim3(kBlock), 0, st, a);
+  hipLaunchKernelGGL((spmm_kernel<G, NACC, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a);
 }
 
 extern "C" int mgp_spmm_fused(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
@@ -2037,26 +1888,13 @@ int mgp_spmm_patch_node(void* exec, void* node, const void* record, const float*
   return MGP_OK;
 }
 
-int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                         const float* pre, const float* post, const float* base, float cb, float co,
-                         const float* dotw, float* dot_partials, const int* skip, int* tick,
-                         const MgpFirst* first, void* stream) {
-  if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !X || !Y) return MGP_ERR_ARG;
-  if (L->n <= 0 || C <= 0 || C > 256) return C > 256 ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
-  if (X == Y) return MGP_ERR_ARG;  // rows gather other rows of X: never in place
-  knobs_snap();
-  hipStream_t st = mgp_stream(stream);
-  SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, X, Y, C, a, b, pre, post, base, cb, co,
-             dotw, dotw ? dot_partials : nullptr, 0, skip, tick, row_offset, nullptr, nullptr, 0};
-#ifdef MGP_STAMP
-  p.stamp_on = g_stamp_enable;
-#endif
-  if (first) {
-    if (!use_tiles(L, C)) return MGP_ERR_UNSUPPORTED;
-    p.copy_x = first->copy_x;
-    p.dot2_partials = (dotw && dot_partials) ? first->dot2_partials : nullptr;
-    p.tick_reset = first->tick_reset;
-  }
+namespace {
+// the kernel choice of mgp_spmm_fused_cbv; CB: p.cbv is set (every kernel family has a CBV instantiation of its own,
+// so the code of the cbv == NULL calls is what it was before the per-row coefficient existed)
+template <bool CB>
+int spmm_launch(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, const float* pre,
+                const float* base, const float* dotw, float* dot_partials, const MgpFirst* first, SpmmArgs& p,
+                hipStream_t st) {
   if (use_tiles(L, C)) {
     TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
                 L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, 0};
@@ -2072,8 +1910,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
   } while (0)
 #define MGP_TILE_LAUNCH(BS)                                                                              \
   do {                                                                                                   \
-    if (pre) MGP_TILE_LAUNCH_K((spmv_tile_kernel<true, BS>), BS);                                        \
-    else MGP_TILE_LAUNCH_K((spmv_tile_kernel<false, BS>), BS);                                           \
+    if (pre) MGP_TILE_LAUNCH_K((spmv_tile_kernel<true, BS, CB>), BS);                                    \
+    else MGP_TILE_LAUNCH_K((spmv_tile_kernel<false, BS, CB>), BS);                                       \
   } while (0)
     if (first && first->record) {
       TileLaunchRecord rec{p, ta};
@@ -2094,8 +1932,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     const size_t lds = tile_small_lds_bytes(L, C);
 #define MGP_TILE_SMALL_LAUNCH(C4)                                                                                 \
   do {                                                                                                            \
-    if (pre) hipLaunchKernelGGL((spmm_tile_q_kernel<C4, true>), dim3(grid), dim3(256), lds, st, p, ta);        \
-    else hipLaunchKernelGGL((spmm_tile_q_kernel<C4, false>), dim3(grid), dim3(256), lds, st, p, ta);           \
+    if (pre) hipLaunchKernelGGL((spmm_tile_q_kernel<C4, true, CB>), dim3(grid), dim3(256), lds, st, p, ta);    \
+    else hipLaunchKernelGGL((spmm_tile_q_kernel<C4, false, CB>), dim3(grid), dim3(256), lds, st, p, ta);       \
   } while (0)
     if (C == 4) MGP_TILE_SMALL_LAUNCH(1);
     else if (C == 8) MGP_TILE_SMALL_LAUNCH(2);
@@ -2117,8 +1955,13 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
 #ifdef MGP_MT_STAMP
     ma.stamps = g_mt_stamps;
 #endif
-    if (pre) hipLaunchKernelGGL((spmm_mt_kernel<true>), dim3(grid), dim3(kBlock), 0, st, p, ma);
-    else hipLaunchKernelGGL((spmm_mt_kernel<false>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+    if constexpr (CB) {
+      if (pre) hipLaunchKernelGGL((spmm_mt_cbv_kernel<true>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+      else hipLaunchKernelGGL((spmm_mt_cbv_kernel<false>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+    } else {
+      if (pre) hipLaunchKernelGGL((spmm_mt_kernel<true>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+      else hipLaunchKernelGGL((spmm_mt_kernel<false>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+    }
   } else if (dict_shape_ok(L, C)) {
     if (!aligned16(X, Y, base, dotw)) return MGP_ERR_ARG;   // (the plan counted this kernel's dot-partial blocks)
     TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
@@ -2131,13 +1974,13 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     /* the attribute is per DEVICE and the call is cheap next to a launch: set every time (a process that drives a  \
        second GPU, or two host threads, must not depend on a process-wide flag) */                                  \
     if (pre) {                                                                                                      \
-      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, true>),                   \
+      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, true, CB>),               \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kDictLdsBudget));                 \
-      hipLaunchKernelGGL((spmm_dict_kernel<NV, true>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap);     \
+      hipLaunchKernelGGL((spmm_dict_kernel<NV, true, CB>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap); \
     } else {                                                                                                        \
-      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, false>),                  \
+      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, false, CB>),              \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kDictLdsBudget));                 \
-      hipLaunchKernelGGL((spmm_dict_kernel<NV, false>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap);    \
+      hipLaunchKernelGGL((spmm_dict_kernel<NV, false, CB>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap);    \
     }                                                                                                               \
   } while (0)
     switch (dict_nv(C)) {
@@ -2154,8 +1997,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     const int grid = tile_grid(L, &ta.tiles_per_block);
     const size_t lds = tile_wide_lds_bytes(L);
     const int cap = tile_wide_cap(L);
-    if (pre) hipLaunchKernelGGL((spmm_tile_wide_kernel<true>), dim3(grid), dim3(256), lds, st, p, ta, cap);
-    else hipLaunchKernelGGL((spmm_tile_wide_kernel<false>), dim3(grid), dim3(256), lds, st, p, ta, cap);
+    if (pre) hipLaunchKernelGGL((spmm_tile_wide_kernel<true, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
+    else hipLaunchKernelGGL((spmm_tile_wide_kernel<false, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
   } else if (C == 1) {
     const int G = tl_knobs.hint;
     const int R = spmv_rows_in_flight();
@@ -2164,7 +2007,7 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     int rc = MGP_OK;
 #define MGP_SPMV_CASE(GG)                                                                     \
   case GG:                                                                                    \
-    rc = pre ? launch_spmv_r<GG, true>(p, R, pl.grid, st) : launch_spmv_r<GG, false>(p, R, pl.grid, st); \
+    rc = pre ? launch_spmv_r<GG, true, CB>(p, R, pl.grid, st) : launch_spmv_r<GG, false, CB>(p, R, pl.grid, st); \
     break;
     switch (G) {
       MGP_SPMV_CASE(4)
@@ -2181,8 +2024,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     p.rows_per_block = pl.rows_per_block;
 #define MGP_ROW16_LAUNCH(C4)                                                                                   \
   do {                                                                                                         \
-    if (pre) hipLaunchKernelGGL((spmm_row16_kernel<C4, true>), dim3(pl.grid), dim3(kBlock), 0, st, p);          \
-    else hipLaunchKernelGGL((spmm_row16_kernel<C4, false>), dim3(pl.grid), dim3(kBlock), 0, st, p);             \
+    if (pre) hipLaunchKernelGGL((spmm_row16_kernel<C4, true, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);      \
+    else hipLaunchKernelGGL((spmm_row16_kernel<C4, false, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);         \
   } while (0)
     if (C == 4) MGP_ROW16_LAUNCH(1);
     else if (C == 8) MGP_ROW16_LAUNCH(2);
@@ -2203,8 +2046,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     p.rows_per_block = pl.rows_per_block;
 #define MGP_V4_LAUNCH(LPR)                                                                          \
   do {                                                                                              \
-    if (pre) hipLaunchKernelGGL((spmm_v4_kernel<LPR, true>), dim3(pl.grid), dim3(kBlock), 0, st, p);  \
-    else hipLaunchKernelGGL((spmm_v4_kernel<LPR, false>), dim3(pl.grid), dim3(kBlock), 0, st, p);     \
+    if (pre) hipLaunchKernelGGL((spmm_v4_kernel<LPR, true, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);  \
+    else hipLaunchKernelGGL((spmm_v4_kernel<LPR, false, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p); \
   } while (0)
     if (C <= 32) MGP_V4_LAUNCH(8);
     else if (C <= 64) MGP_V4_LAUNCH(16);
@@ -2218,8 +2061,8 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
     p.rows_per_block = pl.rows_per_block;
 #define MGP_SPMM_LAUNCH(GG, NA)                                    \
   do {                                                             \
-    if (pre) launch_spmm<GG, NA, true>(p, pl.grid, st);            \
-    else launch_spmm<GG, NA, false>(p, pl.grid, st);               \
+    if (pre) launch_spmm<GG, NA, true, CB>(p, pl.grid, st);        \
+    else launch_spmm<GG, NA, false, CB>(p, pl.grid, st);           \
   } while (0)
     if (G == 4) MGP_SPMM_LAUNCH(4, 1);
     else if (G == 8) MGP_SPMM_LAUNCH(8, 1);
@@ -2232,6 +2075,39 @@ int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X,
   }
   MGP_LAUNCH_CHECK();
   return MGP_OK;
+}
+}  // namespace
+
+int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
+                         const float* pre, const float* post, const float* base, float cb, float co,
+                         const float* dotw, float* dot_partials, const int* skip, int* tick,
+                         const MgpFirst* first, void* stream) {
+  return mgp_spmm_fused_cbv(L, row_offset, X, C, Y, a, b, pre, post, base, cb, nullptr, co, dotw, dot_partials, skip, tick,
+                            first, stream);
+}
+
+int mgp_spmm_fused_cbv(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
+                       const float* pre, const float* post, const float* base, float cb, const float* cbv, float co,
+                       const float* dotw, float* dot_partials, const int* skip, int* tick, const MgpFirst* first,
+                       void* stream) {
+  if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !X || !Y) return MGP_ERR_ARG;
+  if (L->n <= 0 || C <= 0 || C > 256) return C > 256 ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
+  if (X == Y) return MGP_ERR_ARG;  // rows gather other rows of X: never in place
+  knobs_snap();
+  hipStream_t st = mgp_stream(stream);
+  SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, X, Y, C, a, b, pre, post, base, cb, co,
+             dotw, dotw ? dot_partials : nullptr, 0, skip, tick, row_offset, nullptr, nullptr, 0, cbv};
+#ifdef MGP_STAMP
+  p.stamp_on = g_stamp_enable;
+#endif
+  if (first) {
+    if (!use_tiles(L, C)) return MGP_ERR_UNSUPPORTED;
+    p.copy_x = first->copy_x;
+    p.dot2_partials = (dotw && dot_partials) ? first->dot2_partials : nullptr;
+    p.tick_reset = first->tick_reset;
+  }
+  return cbv ? spmm_launch<true>(L, row_offset, X, C, Y, pre, base, dotw, dot_partials, first, p, st)
+             : spmm_launch<false>(L, row_offset, X, C, Y, pre, base, dotw, dot_partials, first, p, st);
 }
 
 // elementwise y = s[i] * x[i,:]

@@ -119,18 +119,20 @@ class RiemannGP(torch.nn.Module):
         desc, _, _ = self._sampling_args()
         return prior_samples(desc, num_samples, seed, tol=tol)
 
-    def sample_posterior(self, num_samples, seed=None, noisy=False, tol=1e-5):
+    def sample_posterior(self, num_samples, seed=None, noisy=False, tol=1e-5, observed=None):
         """f | y at every graph node by perturb-and-MAP: [num_samples, N] float32 with mean precision_posterior_mean() and
-        covariance (Q + I / noise)^-1; noisy=True adds the likelihood noise (sampling.posterior_samples)."""
+        covariance (Q + I / noise)^-1; noisy=True adds the likelihood noise (sampling.posterior_samples).  observed (bool [N]):
+        condition on train_targets[observed] only -- the transductive posterior at the other nodes (operator form 3)."""
         from ..sampling import posterior_samples
         desc, noise, y = self._sampling_args()
-        return posterior_samples(desc, y, noise, num_samples, seed, noisy=noisy, tol=tol)
+        return posterior_samples(desc, y, noise, num_samples, seed, noisy=noisy, tol=tol, observed=observed)
 
-    def precision_posterior_mean(self, tol=1e-5):
-        """(I + noise Q)^-1 y at every graph node: [N] float32 (sampling.posterior_mean)."""
+    def precision_posterior_mean(self, tol=1e-5, observed=None):
+        """(I + noise Q)^-1 y at every graph node: [N] float32 (sampling.posterior_mean).  observed (bool [N]): the mean
+        conditioned on train_targets[observed] only, at every node."""
         from ..sampling import posterior_mean
         desc, noise, y = self._sampling_args()
-        return posterior_mean(desc, y, noise, tol=tol)
+        return posterior_mean(desc, y, noise, tol=tol, observed=observed)
 
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
@@ -141,7 +143,11 @@ class RiemannGP(torch.nn.Module):
     # ------------------------------------------------------------------ the ExactGP prediction, spelled out
     def _scale_noise(self):
         s = float(self.covar_module.outputscale.detach()) if hasattr(self.covar_module, "outputscale") else 1.0
-        return s, float(self.likelihood.noise.detach().reshape(-1)[0])
+        nz = self.likelihood.noise.detach().reshape(-1)
+        if nz.numel() != 1:
+            # per-node noise is the precision-form sampler's (sampling.posterior_mean / posterior_samples with noise [n])
+            raise NotImplementedError("per-node likelihood noise is not supported by the spectral posterior or training")
+        return s, float(nz[0])
 
     def _train_cache(self):
         if self._cache is None:

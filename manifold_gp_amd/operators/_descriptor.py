@@ -18,8 +18,9 @@ class Descriptor:
     pre: Optional[torch.Tensor] = None
     post: Optional[torch.Tensor] = None
     scale: float = 1.0
-    form: int = 0                      # 0: Q2, 1: Q2 - s Q2^2 + s^2 Q2^3, 2: I + s Q2
+    form: int = 0                      # 0: Q2, 1: Q2 - s Q2^2 + s^2 Q2^3, 2: I + s Q2, 3: diag(obs_w) + s Q2
     noise: float = 0.0
+    obs_w: Optional[torch.Tensor] = None   # form 3: [n] float32 observation weights on the device (read for form 3 only)
 
     @property
     def n(self):
@@ -50,7 +51,8 @@ class Descriptor:
         rel = getattr(self.data, name, getattr(self.data, "relabelled", lambda: None))()
         if rel is None:
             return None, None
-        return replace(self, data=rel, pre=rel.permuted(self.pre), post=rel.permuted(self.post)), rel.graph
+        return (replace(self, data=rel, pre=rel.permuted(self.pre), post=rel.permuted(self.post), obs_w=rel.permuted(self.obs_w)),
+                rel.graph)
 
     def struct(self, wide=False):
         d = self.data
@@ -65,6 +67,7 @@ class Descriptor:
         op.scale = float(self.scale)
         op.form = int(self.form)
         op.noise = float(self.noise)
+        op.obs_w = self.obs_w.data_ptr() if (self.form == 3 and self.obs_w is not None) else None
         return op
 
     def apply(self, X):

@@ -8,6 +8,11 @@ G = [sqrt(tau) I | E] (A = G G^T, one entry of E per edge and endpoint), so with
     f ~ N(0, Q2^-1)                odd nu: scale^-1/2 P^-1 A^-((nu+1)/2) g    even nu: scale^-1/2 P^-1 A^-(nu/2) w
     f | y, noise s (perturb-and-MAP):  x = (I + s Q2)^-1 (y + s z + sqrt(s) w2)   [+ sqrt(s) w3 with noisy=True]
 
+Observed subsets / per-node noise (observed=, noise [n]): W = diag(w), w_i = s_ref / sigma_i^2 on observed nodes and 0
+elsewhere, s_ref = min over observed sigma_i^2.  Posterior precision Q2 + W / s_ref, system A3 = W + s_ref Q2 (operator form 3):
+
+    mean  x = A3^-1 W y          sample  x = A3^-1 (W y + s_ref z + sqrt(s_ref) W^1/2 w2)   [+ sigma w3 with noisy=True]
+
 g and w come from mgp_gmrf_noise (one row-parallel pass over the CSR, noise regenerated from a counter-based generator);
 the applies and solves are the library's own (Descriptor.apply, cg_solve).  Column j of a call is the sample of global
 index offset + j whatever the batch size: every sample is a function of (seed, its index) alone.  Streams: tag 0 node
@@ -23,6 +28,10 @@ from ._lib import check, lib, ptr, stream
 
 CHUNK = 256          # columns per noise launch / solve (the operator and CG paths take at most 256)
 NODE_TAGS = (0, 2, 3)
+# Form-3 solves run Jacobi-preconditioned CG: on the 60k manifold_784 graph (nu = 2, noise 1e-2, one column, tol 1e-5) it
+# takes 20 -> 9 iterations at 50 % observed and 49 -> 23 at 10 % (0.34 -> 0.19 ms, 0.75 -> 0.39 ms), and nothing at 100 %
+# (3 iterations either way; docs/kernels/sampling.md).  The form-2 path keeps the library default.
+OBSERVED_JACOBI = [True]
 
 
 def draw_seed():
@@ -151,9 +160,77 @@ def _targets(desc, y):
     return _lib.f32c(y).view(-1, 1)
 
 
-def posterior_rhs(desc, y, noise, C, seed, offset=0):
-    """y + s z + sqrt(s) w2 for the columns offset .. offset + C - 1 (the perturbed right-hand side of posterior_samples)."""
+class _Observation:
+    """Form-3 conditioning (docs/kernels/sampling.md): s_ref, w [n, 1] and the noise standard deviation sigma [n, 1], all on
+    the graph's device; obs [n, 1] bool."""
+
+    def __init__(self, s_ref, w, sigma, obs):
+        self.s_ref, self.w, self.sigma, self.obs = s_ref, w, sigma, obs
+
+    def descriptor(self, desc):
+        return desc.with_(form=3, noise=self.s_ref, obs_w=self.w.view(-1))
+
+    def weighted_targets(self, y):
+        """W y with the entries of unobserved nodes (which may be NaN) never read into the product."""
+        return torch.where(self.obs, y, torch.zeros((), dtype=y.dtype, device=y.device)) * self.w
+
+
+def _observation(desc, noise, observed):
+    """None when the call is today's form-2 system (a python-float noise, every node observed); else the _Observation of
+    form 3.  Raises ValueError for wrong lengths, non-positive / non-finite noise and an empty observed set."""
+    n = desc.n
+    dev = desc.data.graph.device
+    if observed is not None:
+        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
+            raise ValueError("observed must be a bool tensor [n]")
+        if observed.dim() != 1 or observed.shape[0] != n:
+            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
+        observed = observed.to(dev)
+        if not bool(observed.any()):
+            raise ValueError("observed selects no node")
+    if torch.is_tensor(noise) and noise.numel() != 1:
+        if noise.dim() != 1 or noise.shape[0] != n:
+            raise ValueError("noise has shape %s: a float or a tensor [n] of per-node variances (n = %d)"
+                             % (tuple(noise.shape), n))
+        var = noise.to(device=dev, dtype=torch.float64)
+        if not bool((torch.isfinite(var) & (var > 0)).all()):
+            raise ValueError("per-node noise variances must be finite and positive at every node")
+    else:
+        # one noise (a float, or a tensor of one element such as likelihood.noise): with every node observed, today's path
+        # and its checks exactly
+        s = float(noise)
+        if not s > 0.0:
+            raise ValueError("noise must be positive, got %r" % (noise,))
+        if observed is None or bool(observed.all()):
+            return None
+        if not math.isfinite(s):
+            raise ValueError("noise must be finite when conditioning on a subset of nodes, got %r" % (noise,))
+        var = torch.full((n,), s, dtype=torch.float64, device=dev)
+    obs = torch.ones(n, dtype=torch.bool, device=dev) if observed is None else observed
+    s_ref = float(var[obs].min())
+    w = torch.where(obs, s_ref / var, torch.zeros((), dtype=torch.float64, device=dev))
+    return _Observation(s_ref, w.float().view(-1, 1).contiguous(), var.sqrt().float().view(-1, 1), obs.view(-1, 1))
+
+
+def _observed_rhs(desc, P, ob, yv, C, seed, offset):
+    """W y + s_ref z + sqrt(s_ref) W^1/2 w2 (columns offset .. offset + C - 1)."""
+    s = ob.s_ref
+    z = _precision_chunk(desc, P, C, seed, offset)
+    rhs = gmrf_noise(desc.data, C, seed, offset, node_coef=1.0, tag=2)
+    rhs *= (s * ob.w).sqrt()
+    rhs += s * z
+    rhs += ob.weighted_targets(yv)
+    return rhs
+
+
+def posterior_rhs(desc, y, noise, C, seed, offset=0, observed=None):
+    """y + s z + sqrt(s) w2 for the columns offset .. offset + C - 1 (the perturbed right-hand side of posterior_samples).
+    With observed= or a per-node noise [n]: W y + s_ref z + sqrt(s_ref) W^1/2 w2, the right-hand side of form 3."""
     P = _check_desc(desc)
+    one = observed is None and not (torch.is_tensor(noise) and noise.numel() != 1)
+    ob = None if one else _observation(desc, noise, observed)         # (one noise, every node: unchecked, as before)
+    if ob is not None:
+        return _observed_rhs(desc, P, ob, _targets(desc, y), C, seed, offset)
     s = float(noise)
     z = _precision_chunk(desc, P, C, seed, offset)
     rhs = gmrf_noise(desc.data, C, seed, offset, node_coef=math.sqrt(s), tag=2)
@@ -162,18 +239,31 @@ def posterior_rhs(desc, y, noise, C, seed, offset=0):
     return rhs
 
 
-def posterior_samples(desc, y, noise, S, seed=None, noisy=False, tol=1e-5, refine=0, max_iter=5000):
+def posterior_samples(desc, y, noise, S, seed=None, noisy=False, tol=1e-5, refine=0, max_iter=5000, observed=None):
     """f | y ~ N((I + s Q2)^-1 y, (Q2 + I/s)^-1) by perturb-and-MAP, s = noise: [S, n] float32.  noisy=True: samples of
-    y* = f + eps (adds sqrt(s) w3)."""
+    y* = f + eps (adds sqrt(s) w3).
+    observed (bool [n]) and / or noise as a tensor [n] of per-node variances: f | y_observed ~ N(A3^-1 W y, (Q2 + W / s_ref)^-1)
+    at every node (form 3); targets at unobserved nodes are not read (NaN allowed); noisy=True adds sigma_i w3 at every node."""
     from .solvers import cg_solve
-    _check_desc(desc)
+    P = _check_desc(desc)
     S, seed = _count(S), _seed(seed)
-    s = float(noise)
-    if not s > 0.0:
-        raise ValueError("noise must be positive, got %r" % (noise,))
-    d2 = desc.with_(form=2, noise=s)
+    ob = _observation(desc, noise, observed)
     kw = _solve_kw(tol, refine, max_iter)
     out = torch.empty(S, desc.n, dtype=torch.float32, device=desc.data.graph.device)
+    if ob is not None:
+        kw["jacobi"] = OBSERVED_JACOBI[0]
+        d3 = ob.descriptor(desc)
+        with torch.no_grad():
+            yv = _targets(desc, y)
+            for c0 in range(0, S, CHUNK):
+                C = min(CHUNK, S - c0)
+                X = cg_solve(d3, _observed_rhs(desc, P, ob, yv, C, seed, c0), **kw)[0]
+                if noisy:
+                    X = X + gmrf_noise(desc.data, C, seed, c0, node_coef=1.0, tag=3) * ob.sigma
+                out[c0:c0 + C] = X.t()
+        return out
+    s = float(noise)
+    d2 = desc.with_(form=2, noise=s)
     with torch.no_grad():
         yv = _targets(desc, y)
         for c0 in range(0, S, CHUNK):
@@ -185,12 +275,15 @@ def posterior_samples(desc, y, noise, S, seed=None, noisy=False, tol=1e-5, refin
     return out
 
 
-def posterior_mean(desc, y, noise, tol=1e-5, refine=0, max_iter=5000):
-    """(I + s Q2)^-1 y: [n] float32 (the precision-form posterior mean at the graph nodes)."""
+def posterior_mean(desc, y, noise, tol=1e-5, refine=0, max_iter=5000, observed=None):
+    """(I + s Q2)^-1 y: [n] float32 (the precision-form posterior mean at the graph nodes).  observed (bool [n]) and / or
+    noise as a tensor [n] of per-node variances: (W + s_ref Q2)^-1 W y (form 3), targets at unobserved nodes not read."""
     from .solvers import cg_solve
     _check_desc(desc)
-    s = float(noise)
-    if not s > 0.0:
-        raise ValueError("noise must be positive, got %r" % (noise,))
+    ob = _observation(desc, noise, observed)
     with torch.no_grad():
+        if ob is not None:
+            rhs = ob.weighted_targets(_targets(desc, y))
+            return cg_solve(ob.descriptor(desc), rhs, jacobi=OBSERVED_JACOBI[0], **_solve_kw(tol, refine, max_iter))[0].view(-1)
+        s = float(noise)
         return cg_solve(desc.with_(form=2, noise=s), _targets(desc, y), **_solve_kw(tol, refine, max_iter))[0].view(-1)

@@ -230,27 +230,31 @@ REBIND_PLANS = [True]          # lab / test switch: False = a new plan for every
 
 def _cached_plan(desc, C, kw):
     """Plans own a workspace, host-mapped flags and captured hipGraphs (~0.9 ms of host time over a plan's life): they are
-    kept per operator STRUCTURE -- graph, nu, form, which of pre / post are present, column count, solver settings, stream --
-    and pointed at the current operator VALUES (bandwidth, length scale, scale, noise, the pre / post vectors) when those
+    kept per operator STRUCTURE -- graph, nu, form, which of pre / post / obs_w are present, column count, solver settings,
+    stream -- and pointed at the current operator VALUES (bandwidth, length scale, scale, noise, the pre / post / obs_w vectors) when those
     changed since the plan's last use (CgPlan.rebind): the nested CG of a Schur-complement matvec and `_average_variance` reuse
     one plan within an epoch, and the next epoch -- new hyper-parameters, same graph -- reuses it again."""
     # a plan is bound to the stream that was current when it was created (its launches, its graph replays and the
     # copy of X are ordered there only): a solve issued under another torch.cuda.stream gets its own plan.
-    # (graph / data uids are assigned monotonically -- an id() could be reused by a new object once the old one is gone; the
-    # pre / post pointers in the value key are safe because a plan keeps its descriptor, hence those tensors, alive)
+    # (graph / data uids are assigned monotonically -- an id() could be reused by a new object once the old one is gone.  The
+    # value key names the pre / post / obs_w tensors by address: the plan holds those very tensors (`_keep`), so that no new
+    # tensor can take a key's address while the plan remembers it.  Its descriptor alone does not hold them: on a relabelled
+    # graph it carries permuted copies, and form 3's weights are a fresh tensor per call.)
     g = getattr(desc.data, "graph", None)
-    skey = (getattr(g, "uid", None) or id(g), desc.nu, desc.form, desc.pre is not None, desc.post is not None,
+    obs_w = desc.obs_w if desc.form == 3 else None
+    skey = (getattr(g, "uid", None) or id(g), desc.nu, desc.form, desc.pre is not None, desc.post is not None, obs_w is not None,
             int(C), settings.cg_tolerance.value(), settings.max_cg_iterations.value(), settings.cg_stop_mode.value(),
             settings.cg_jacobi_preconditioner.value(), tuple(sorted(kw.items())),
             int(torch.cuda.current_stream(desc.data.graph.device).cuda_stream))
     vkey = (getattr(desc.data, "uid", None) or id(desc.data), desc.kappa, desc.scale, desc.noise,
-            desc.pre.data_ptr() if desc.pre is not None else 0, desc.post.data_ptr() if desc.post is not None else 0)
+            desc.pre.data_ptr() if desc.pre is not None else 0, desc.post.data_ptr() if desc.post is not None else 0,
+            obs_w.data_ptr() if obs_w is not None else 0)
     if not REBIND_PLANS[0]:
         skey = skey + vkey
     plan = _PLAN_CACHE.get(skey)
     if plan is not None and plan._vkey != vkey:
         if plan.rebind(desc):
-            plan._vkey = vkey
+            plan._vkey, plan._keep = vkey, (desc.pre, desc.post, obs_w)
         else:
             _PLAN_CACHE.pop(skey).close()
             plan = None
@@ -258,7 +262,7 @@ def _cached_plan(desc, C, kw):
         if len(_PLAN_CACHE) >= _PLAN_CACHE_MAX:
             _PLAN_CACHE.pop(next(iter(_PLAN_CACHE))).close()
         plan = CgPlan(desc, C, **kw)
-        plan._vkey = vkey
+        plan._vkey, plan._keep = vkey, (desc.pre, desc.post, obs_w)
         _PLAN_CACHE[skey] = plan
     return plan
 
