@@ -228,7 +228,8 @@ typedef struct {
   int32_t tile_rows;
   int32_t tile_max_cols;     /* max over tiles of the list length (LDS floats per workgroup) */
   int32_t tile_max_entries;  /* max over tiles of the padded entry count */
-  int32_t tile_reserved;
+  int32_t spmv_lanes;        /* C == 1 row-group kernel: lanes per row for THIS matrix, one of 4, 8, 16, 32, 64; 0 = the process
+                                default (mgp_spmm_set_group_hint, initially 16).  Any other value: MGP_ERR_ARG */
   /* tiles over a row ORDER (mgp_graph_tiles with row_order): all NULL = tile t is rows 64 t .. 64 t + 63 */
   const int32_t* tile_rowptr;  /* [n+1] entry offsets in tile order */
   const float* tile_vals;      /* [nnz] vals gathered through emap */
@@ -246,21 +247,21 @@ int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C);
 int mgp_spmm_set_tile_mode(int on);          /* C == 1: use the tile dictionaries when present (default 1) */
 int mgp_spmm_set_tile_small_mode(int on);    /* C in {4,8,12,16}: LDS-dictionary multi-column kernel on 64-row tiles
                                                 (default 1; 0 = the per-entry gather kernel) */
-/* 16 < C <= 256 with C % 4 == 0 on 64-row tiles: LDS-dictionary kernel in 16-column chunks where it wins (C <= 32, or
- * an X block of 96 MB and more: default 1); 0 = always the per-entry X-row gather kernel; 2 = always the dictionary
- * kernel (tests, A/B runs). */
+/* 16 < C <= 256 with C % 4 == 0 on 64-row tiles: LDS-dictionary kernel in 16-column chunks where it wins (an X block of
+ * 96 MB and more: default 1); 0 = never; 2 = whenever the shape allows (tests, A/B runs). */
 int mgp_spmm_set_tile_wide_mode(int on);
 /* 16 < C <= 256 with C % 4 == 0 on 64-row tiles (round 3): the dictionary kernel with LANES OVER COLUMNS
  * (csrc/spmm.hip spmm_dict_kernel) -- a tile's distinct X rows cross the vector memory path once per tile, staged in
  * double-buffered slices of 256-byte-aligned LDS slots that every entry then reads conflict-free.  Default 1: taken
- * wherever the shape allows (it takes precedence over the two kernels above); 0 = never.  Requires what the graph
+ * where it was measured to win (from 64 columns up, an X block of 96 MB and more); 0 = never; 2 = wherever the shape allows.
+ * Requires what the graph
  * builders guarantee: within a row the entries' columns ascend (padding entries, value 0, at the row's end).
  * Replaces torch_sparse.spmm at manifold_gp/operators/graph_laplacian_operator.py:118-119 for the [N, 100] right-hand
  * sides of precision_matern_operator.py:50-53 and the eigensolver's blocks. */
 int mgp_spmm_set_dict_mode(int on);
 /* 48 <= C <= 256 with C % 4 == 0 (round 4): the SpMM on the fp32 MATRIX CORES over 16-row tiles stored dense in their own distinct
  * columns (csrc/spmm.hip spmm_mt_kernel): a tile's distinct X rows cross the vector memory path once per tile and 64-column
- * block, straight into the MFMA operand layout; no LDS, no barrier.  Taken (before every other wide kernel) when the CSR
+ * block, straight into the MFMA operand layout; no LDS, no barrier.  Taken when the CSR
  * carries mt_* and the call has no row offset (weighted dot-product partials included: one row of partials per workgroup of four
  * (tile, block) waves, mgp_spmm_dot_blocks_csr counts them); a row's sum is taken in ascending column order.
  * N = 60k, C = 128: 60 us against 94 for the gather kernel.  mgp_spmm_set_mt_mode(0) = never; returns the previous setting.
@@ -270,11 +271,21 @@ int mgp_spmm_set_dict_mode(int on);
  * Replaces torch_sparse.spmm at manifold_gp/operators/graph_laplacian_operator.py:118-119 for the eigensolver's blocks and
  * the [N, 100] right-hand sides of precision_matern_operator.py:50-53. */
 int mgp_spmm_set_mt_mode(int on);
-/* which kernel mgp_spmm_fused would launch for this CSR / width (tests, docs): 0 = gather, 1 = C == 1 tile kernel, 2 = small-C
- * tile kernel, 3 = matrix-core tiles, 5 = lanes-over-columns dictionary, 6 = chunked dictionary (4 was a round-4 kernel, removed) */
-/* A CSR that carries the matrix-core image, called with a row offset: the other kernels run (the image is ignored) -- except
- * with dot partials, whose count mgp_spmm_dot_blocks_csr sized for the matrix-core kernel: MGP_ERR_UNSUPPORTED from this
- * function and from mgp_spmm_fused_rows alike (strip mt_* from the struct for such a call). */
+/* which kernel mgp_spmm_fused would launch for this CSR / width (tests, docs).  The precedence order, the one of spmm_plan in
+ * csrc/spmm.hip rule for rule; the first rule that matches decides, and the returned number is the one in brackets
+ * (4 was a round-4 kernel, removed):
+ *   1. [1] C == 1, tile dictionaries of 32 / 64 / 128 rows that fit the LDS (tile mode 1): the C == 1 tile kernel
+ *   2. [2] C in {4, 8, 12, 16}, 64-row tiles within the LDS budget (tile mode 1, tile-small mode 1): the small-C tile kernel
+ *   3. [3] 48 <= C <= 256, C % 4 == 0, the CSR carries mt_* (mt mode 1), no row offset: matrix-core tiles.  With a row offset
+ *          the image is ignored and rules 4-7 apply -- except with dot partials, whose count mgp_spmm_dot_blocks_csr sized for
+ *          the matrix-core kernel: MGP_ERR_UNSUPPORTED from this function and from mgp_spmm_fused_rows alike (strip mt_* from
+ *          the struct for such a call)
+ *   4. [5] 16 < C <= 256, C % 4 == 0, 64-row tiles, C >= 64, X block >= 96 MB (dict mode 1; 2: any size): lanes-over-columns dictionary
+ *   5. [6] the same shapes, X block >= 96 MB (tile-wide mode 1; 2: any size): chunked dictionary
+ *   6. [0] C == 1: row groups of spmv_lanes lanes
+ *   7. [0] C > 1: gather from memory; the member (row16, float4 lanes under v4 mode, per-column) by pointer alignment at launch --
+ *          all three write the same dot-partial blocks
+ * Rules 2-5: X / Y / base / dotw that are not 16-byte aligned are MGP_ERR_ARG at launch, never a fall-through to another kernel. */
 int mgp_spmm_kernel_choice(const mgp_csr_t* L, int C, int with_dot, int64_t row_offset);
 int mgp_spmm_mt_fill(int64_t n, const int32_t* rowptr, const float* vals, const uint16_t* lid16, const int32_t* tile_ptr16,
                      const int32_t* tile_cols16, const int32_t* sptr, int64_t steps, int32_t* dcol, float* img, void* stream);
@@ -289,7 +300,8 @@ int mgp_spmm_timing_end(float* total_ms, int* launches);
 int mgp_spmm_set_v4_mode(int on);
 
 int mgp_spmm_dot_blocks(int64_t n, int C);   /* workgroups that write dot partials */
-int mgp_spmm_set_group_hint(int lanes);      /* C == 1: lanes per row, one of 4,8,16,32,64 */
+int mgp_spmm_set_group_hint(int lanes);      /* C == 1: lanes per row, one of 4,8,16,32,64: the default for structs whose
+                                                spmv_lanes is 0 (a struct that sets the field is not affected) */
 int mgp_spmm_set_rows_in_flight(int rows);   /* C == 1 fallback kernel: rows a lane group loads at once: 1,2,4,8 */
 int mgp_spmm_fused(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
                    const float* pre, const float* post, const float* base, float cb, float co,
@@ -399,7 +411,7 @@ typedef struct {
 
 size_t mgp_cg_workspace_bytes(const mgp_operator_t* op, int C);
 /* ---- Lab-only switches (every mgp_*_set_* in this header): process-wide std::atomic<int> words for A/B measurements and tests.
- * The SpMM family copies them once per call into a thread-local snapshot that all of the call's shape tests consult; the CG
+ * The SpMM family reads them once per call, into the plan value that the call passes down; the CG
  * switches are read at plan creation; the kernel-block switch once per call; the k-NN / eigensolver switches where a call
  * branches on them.  They are not part of the path's contract and are not meant to be flipped while another thread is inside a
  * call of the same family: two calls that size and launch the same product (mgp_spmm_dot_blocks_csr, then mgp_spmm_fused; the

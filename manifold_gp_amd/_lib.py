@@ -38,7 +38,7 @@ class CsrT(Structure):
                 ("diag", c_void_p),
                 ("ncols", c_int64), ("tile_ptr", c_void_p), ("tile_cols", c_void_p), ("lid", c_void_p),
                 ("tile_rows", c_int32), ("tile_max_cols", c_int32), ("tile_max_entries", c_int32),
-                ("tile_reserved", c_int32), ("tile_rowptr", c_void_p), ("tile_vals", c_void_p),
+                ("spmv_lanes", c_int32), ("tile_rowptr", c_void_p), ("tile_vals", c_void_p),
                 ("tile_rowid", c_void_p),
                 ("mt_sptr", c_void_p), ("mt_dcol", c_void_p), ("mt_img", c_void_p), ("mt_tiles", c_int32), ("mt_steps", c_int32)]
 
@@ -304,12 +304,14 @@ def leak(*objects):
     _LEAKED.extend(objects)
 
 
-def csr_struct(n, rowptr, col, vals, diag, ncols=0, tiles=None, tile_vals=None, mt=None):
+def csr_struct(n, rowptr, col, vals, diag, ncols=0, tiles=None, tile_vals=None, mt=None, lanes=0):
     """tiles: None or the dict KnnGraph.tiles holds (tile_ptr, tile_cols, lid tensors + rows / max_cols /
     max_entries; for tiles over a row order also tile_rowptr / rowid / emap).  tile_vals: `vals` gathered
     through tiles["emap"] -- required with ordered tiles, which are otherwise left out of the struct.
-    mt: None or a graph.MtPlan built over the same rowptr / col / vals."""
+    mt: None or a graph.MtPlan built over the same rowptr / col / vals.
+    lanes: the owning graph's spmv_lanes (lanes per row of the C == 1 row-group kernel); 0 = the library's process default."""
     s = CsrT(int(n), rowptr.data_ptr(), col.data_ptr(), vals.data_ptr(), diag.data_ptr(), int(ncols))
+    s.spmv_lanes = int(lanes)
     if tiles is not None and (tiles.get("rowid") is None or tile_vals is not None):
         s.tile_ptr, s.tile_cols, s.lid = tiles["tile_ptr"].data_ptr(), tiles["tile_cols"].data_ptr(), tiles["lid"].data_ptr()
         s.tile_rows, s.tile_max_cols, s.tile_max_entries = tiles["rows"], tiles["max_cols"], tiles["max_entries"]

@@ -32,7 +32,6 @@ def needs_grad(*tensors):
 def _spmm(data, X, a, b, pre, post, base, cb, co, tangent=False):
     """Plain (non-differentiable) launch of the fused SpMM on the Laplacian or its eps-tangent."""
     g = data.graph
-    check(lib().mgp_spmm_set_group_hint(g.spmv_lanes), "mgp_spmm_set_group_hint")
     if tangent:
         t = data.tangent()
         csr = g.csr_with(t.d_vals, t.d_diag, t.d_vals_t)

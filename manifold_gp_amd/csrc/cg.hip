@@ -1552,7 +1552,7 @@ bool patch_first_rhs(CgPlan* pl, const float* rhs) {
 }  // namespace
 
 extern "C" size_t mgp_cg_workspace_bytes(const mgp_operator_t* op, int C) {
-  if (!op || C <= 0 || C > kMaxC || op->L.n <= 0) return 0;
+  if (!op || C <= 0 || C > kMaxC || op->L.n <= 0 || !mgp_spmv_lanes_ok(op->L.spmv_lanes)) return 0;
   return cg_bytes(op, C);
 }
 
@@ -1636,7 +1636,7 @@ static void capture_graphs(CgPlan* pl) {
 
 static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, const mgp_cg_params_t* params,
                             const MgpDist* dist, void* work, size_t work_bytes, void* stream, void** plan_out) {
-  if (!op || !params || !work || !plan_out) return MGP_ERR_ARG;
+  if (!op || !params || !work || !plan_out || !mgp_spmv_lanes_ok(op->L.spmv_lanes)) return MGP_ERR_ARG;
   if (C <= 0 || C > kMaxC) return C > kMaxC ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
   const int world = dist ? dist->world : 1;
   if (dist && (dist->n_loc != op->L.n || dist->world < 1 || dist->rank < 0 || dist->rank >= dist->world))
@@ -1760,8 +1760,7 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
   if (a.arrive) MGP_HIP_TRY(hipMemsetAsync(a.arrive, 0, 9 * 32 * sizeof(int), pl->stream));
   pl->init_free = false;
   if (g_cg_init_free && C == 1 && !dist && !minv && !pl->cx && (op->form == 0 || op->form == 2) &&
-      mgp_tile_plan(&op->L, 1, nullptr, nullptr, nullptr) && a.nbv <= kC1GammaSlots * kBlock &&
-      a.nbs <= kC1DeltaSlots * kBlock) {
+      mgp_tile_plan(&op->L) && a.nbv <= kC1GammaSlots * kBlock && a.nbs <= kC1DeltaSlots * kBlock) {
     pl->init_free = true;
     a.pd_bb = pl->pd_bb;
   }
@@ -1844,7 +1843,8 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
                     (op->L.tile_vals != nullptr) == (o.L.tile_vals != nullptr) &&
                     (op->L.tile_rowid != nullptr) == (o.L.tile_rowid != nullptr) &&
                     (op->L.mt_img != nullptr) == (o.L.mt_img != nullptr) && op->L.mt_tiles == o.L.mt_tiles &&
-                    op->L.mt_steps == o.L.mt_steps && mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc;
+                    op->L.mt_steps == o.L.mt_steps && op->L.spmv_lanes == o.L.spmv_lanes &&
+                    mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc;
   if (!same) return MGP_ERR_UNSUPPORTED;
   if (pl->cx) {
     const float cc = op->noise * op->scale;
@@ -1864,7 +1864,7 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
 }
 
 extern "C" size_t mgp_cg_dist_workspace_bytes(const mgp_operator_t* op_local, int C, int world) {
-  if (!op_local || C <= 0 || C > kMaxC || op_local->L.n <= 0 || world < 1) return 0;
+  if (!op_local || C <= 0 || C > kMaxC || op_local->L.n <= 0 || world < 1 || !mgp_spmv_lanes_ok(op_local->L.spmv_lanes)) return 0;
   return cg_bytes(op_local, C, world);
 }
 

@@ -855,6 +855,7 @@ static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_pa
                                  int32_t* info, float* block_evals, float* block_evecs, float* block_resid, const float* warm_block,
                                  const float* warm_evals, void* work, size_t work_bytes, void* stream) {
   if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !evals || !evecs || !work) return MGP_ERR_ARG;
+  if (!mgp_spmv_lanes_ok(L->spmv_lanes)) return MGP_ERR_ARG;
   const int64_t n = L->n;
   if (n <= 0 || m <= 0 || m > n) return MGP_ERR_ARG;
   int b = block_size_for(m, p);
@@ -915,17 +916,16 @@ static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_pa
     MGP_LAUNCH_CHECK();
     const double ce = ub / 2.0;     // centre = half width of [0, ub]
     // T_1 = (L - c) / e
-    MGP_TRY(mgp_spmm_fused_ex(L, KT, 1, KT + n, (float)(-1.0), (float)(1.0 / ce), nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
-                              nullptr, nullptr, nullptr, stream));
+    MGP_TRY(mgp_spmm_fused(L, KT, 1, KT + n, (float)(-1.0), (float)(1.0 / ce), nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
+                           nullptr, stream));
     for (int j = 2; j < kk; ++j) {
       // T_j = 2 (L - c) / e T_{j-1} - T_{j-2}, written where it stays (round 5: no column copy behind every launch)
-      MGP_TRY(mgp_spmm_fused_ex(L, KT + (int64_t)(j - 1) * n, 1, KT + (int64_t)j * n, (float)(-2.0), (float)(2.0 / ce), nullptr, nullptr,
-                                KT + (int64_t)(j - 2) * n, -1.f, 1.f, nullptr, nullptr, nullptr, nullptr, stream));
+      MGP_TRY(mgp_spmm_fused(L, KT + (int64_t)(j - 1) * n, 1, KT + (int64_t)j * n, (float)(-2.0), (float)(2.0 / ce), nullptr, nullptr,
+                             KT + (int64_t)(j - 2) * n, -1.f, 1.f, nullptr, nullptr, stream));
     }
     hipLaunchKernelGGL(vecs_to_cols_kernel, dim3((unsigned)mgp_cdiv(n, 64)), dim3(256), 0, st, KT, n, kk, K);
     MGP_LAUNCH_CHECK();
-    MGP_TRY(mgp_spmm_fused_ex(L, K, kk, LK, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, nullptr, nullptr,
-                              stream));
+    MGP_TRY(mgp_spmm_fused(L, K, kk, LK, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, stream));
     MGP_TRY(launch_gram(K, K, n, kk, w, w.G, st));
     MGP_TRY(launch_gram(K, LK, n, kk, w, w.H, st));
     std::vector<double> Gk((size_t)kk * kk), Hk((size_t)kk * kk);
@@ -1004,22 +1004,21 @@ static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_pa
     move_cols(w.buf[bV], b, nlock, ba, w.buf[iX], ba, 0);
     MGP_LAUNCH_CHECK();
     // Y = (sig/e) (L X - c X)
-    MGP_TRY(mgp_spmm_fused_ex(L, w.buf[iX], ba, w.buf[iY], (float)(-c * sig / e), (float)(sig / e), nullptr, nullptr,
-                              nullptr, 0.f, 1.f, nullptr, nullptr, nullptr, nullptr, stream));
+    MGP_TRY(mgp_spmm_fused(L, w.buf[iX], ba, w.buf[iY], (float)(-c * sig / e), (float)(sig / e), nullptr, nullptr,
+                           nullptr, 0.f, 1.f, nullptr, nullptr, stream));
     ++nspmm;
     for (int i = 2; i <= deg; ++i) {
       const double sn = 1.0 / (tau - sig);
       // Ynew = (2 sn / e) (L Y - c Y) - (sig sn) X
-      MGP_TRY(mgp_spmm_fused_ex(L, w.buf[iY], ba, w.buf[iN], (float)(-c * 2.0 * sn / e), (float)(2.0 * sn / e),
-                                nullptr, nullptr, w.buf[iX], (float)(-sig * sn), 1.f, nullptr, nullptr, nullptr,
-                                nullptr, stream));
+      MGP_TRY(mgp_spmm_fused(L, w.buf[iY], ba, w.buf[iN], (float)(-c * 2.0 * sn / e), (float)(2.0 * sn / e),
+                             nullptr, nullptr, w.buf[iX], (float)(-sig * sn), 1.f, nullptr, nullptr, stream));
       ++nspmm;
       const int t = iX; iX = iY; iY = iN; iN = t;
       sig = sn;
     }
     // filtered active block in iY; L (filtered) into iN; both back into the active columns of V / L V
-    MGP_TRY(mgp_spmm_fused_ex(L, w.buf[iY], ba, w.buf[iN], 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
-                              nullptr, nullptr, nullptr, stream));
+    MGP_TRY(mgp_spmm_fused(L, w.buf[iY], ba, w.buf[iN], 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
+                           nullptr, stream));
     ++nspmm;
     move_cols(w.buf[iY], ba, 0, ba, w.buf[bV], b, nlock);
     move_cols(w.buf[iN], ba, 0, ba, w.buf[bLV], b, nlock);

@@ -14,17 +14,11 @@ inline mgp_operator_t mgp_operator_copy(const mgp_operator_t* op) {
   return o;
 }
 
-// mgp_spmm_fused plus: `skip` (device flag: the launch is a no-op when non-zero) and `tick`
-// (device counter incremented once per non-skipped launch) -- used by the CG iteration graph.
-int mgp_spmm_fused_ex(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
-                      const float* pre, const float* post, const float* base, float cb, float co,
-                      const float* dotw, float* dot_partials, const int* skip, int* tick, void* stream);
-
-// row-partitioned form: L holds the LOCAL rows [0, L->n) of a larger operator whose vectors are
-// global; local row r is global row r + row_offset (columns in L->col are global already)
-int mgp_spmm_fused_part(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                        const float* pre, const float* post, const float* base, float cb, float co,
-                        const float* dotw, float* dot_partials, const int* skip, int* tick, void* stream);
+// spmv_lanes of an mgp_csr_t: lanes per row of the C == 1 row-group kernel, 0 = the process default (include/mgp_hip.h).
+// Every entry that takes the struct refuses another value with MGP_ERR_ARG.
+inline bool mgp_spmv_lanes_ok(int lanes) {
+  return lanes == 0 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64;
+}
 
 // Init-free CG solve (cg.hip): the FIRST operator apply of a solve reads the caller's right-hand side directly
 // (no cg_init launch).  Launch 0 of the chain stores its raw input rows to copy_x (r = b); the chain's last launch
@@ -37,25 +31,32 @@ struct MgpFirst {
   int tick_reset;
   void* record;
 };
-int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                         const float* pre, const float* post, const float* base, float cb, float co,
-                         const float* dotw, float* dot_partials, const int* skip, int* tick,
-                         const MgpFirst* first, void* stream);
-// the same with a per-row coefficient of base: Y = cbv[i] * base + co * t (cbv nullable: cb as above; indexed like post,
-// i.e. by global row).  Operator form 3 (diag(w) X + s Q2 X) passes its observation weights here.
-int mgp_spmm_fused_cbv(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                       const float* pre, const float* post, const float* base, float cb, const float* cbv, float co,
-                       const float* dotw, float* dot_partials, const int* skip, int* tick, const MgpFirst* first,
-                       void* stream);
+// What the library's own callers add to mgp_spmm_fused (all off by default).
+struct MgpSpmmOpts {
+  // row-partitioned form: L holds the LOCAL rows [0, L->n) of a larger operator whose vectors are
+  // global; local row r is global row r + row_offset (columns in L->col are global already)
+  int64_t row_offset = 0;
+  // per-row coefficient of base: Y = cbv[i] * base + co * t (nullable: cb; indexed like post, i.e. by global row).
+  // Operator form 3 (diag(w) X + s Q2 X) passes its observation weights here.
+  const float* cbv = nullptr;
+  // `skip` (device flag: the launch is a no-op when non-zero) and `tick` (device counter incremented once per
+  // non-skipped launch) -- used by the CG iteration graph.
+  const int* skip = nullptr;
+  int* tick = nullptr;
+  const MgpFirst* first = nullptr;   // MGP_ERR_UNSUPPORTED unless the C == 1 tile kernel runs
+};
+int mgp_spmm_fused_opts(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b, const float* pre,
+                        const float* post, const float* base, float cb, float co, const float* dotw, float* dot_partials,
+                        const MgpSpmmOpts& opts, void* stream);
 int mgp_spmm_patch_node(void* exec, void* node, const void* record, const float* old_ptr, const float* new_ptr);
 // first apply of an init-free solve: launch 0 reads `rhs` (pre-scaled in the kernel by op->pre) and copies it to
 // r_copy; later launches take r_copy as base / dot weight; partials of r . A r and ||r||^2; state reset
 int mgp_operator_apply_first(const mgp_operator_t* op, const float* rhs, float* r_copy, float* Y, float* dot_partials,
                              float* dot2_partials, int* state, void* record, void* work, size_t work_bytes, void* stream);
-// 1 when the C == 1 tile kernel would run on L; launch geometry of that kernel
-int mgp_tile_plan(const mgp_csr_t* L, int C, int* grid, int* tiles_per_block, size_t* lds_bytes);
+// 1 when the C == 1 tile kernel would run on L
+int mgp_tile_plan(const mgp_csr_t* L);
 
-// workgroups that write dot partials for this CSR (depends on whether the tile kernel is used)
+// workgroups that write dot partials for this CSR (the planned kernel's count; MGP_ERR_ARG for a bad spmv_lanes)
 int mgp_spmm_dot_blocks_for(const mgp_csr_t* L, int C);
 
 // operator chain with the same hooks on its LAST SpMM

@@ -60,11 +60,11 @@ int q2_chain(const mgp_operator_t* op, const MgpDist* d, int nb_loc, const float
     MgpFirst fst{(first && hk) ? hk->copy_x : nullptr, (last && hk) ? hk->dot2_partials : nullptr,
                  (last && hk) ? hk->tick_reset : 0, (first && hk) ? hk->record : nullptr};
     const bool use_fst = fst.copy_x || fst.dot2_partials || fst.tick_reset || fst.record;
-    MGP_TRY(mgp_spmm_fused_cbv(&op->L, d ? d->row_offset : 0, in, C, out, tau, 1.0f,
-                               (first && !Xs) ? op->pre : nullptr, last ? op->post : nullptr,
-                               last ? base : nullptr, cb, last ? cbv : nullptr, last ? co * op->scale : 1.0f,
-                               (last && hk) ? hk->dotw : nullptr, dp, hk ? hk->skip : nullptr,
-                               (last && hk) ? hk->tick : nullptr, use_fst ? &fst : nullptr, stream));
+    const MgpSpmmOpts o{d ? d->row_offset : 0, last ? cbv : nullptr, hk ? hk->skip : nullptr,
+                        (last && hk) ? hk->tick : nullptr, use_fst ? &fst : nullptr};      // row_offset, cbv, skip, tick, first
+    MGP_TRY(mgp_spmm_fused_opts(&op->L, in, C, out, tau, 1.0f, (first && !Xs) ? op->pre : nullptr, last ? op->post : nullptr,
+                                last ? base : nullptr, cb, last ? co * op->scale : 1.0f, (last && hk) ? hk->dotw : nullptr, dp,
+                                o, stream));
     if (d) {
       // the collectives run unconditionally (also after convergence) so that every rank issues
       // the same sequence; a skipped launch leaves stale but finite data behind them
@@ -93,6 +93,7 @@ int check_op(const mgp_operator_t* op) {
   if (op->L.n <= 0 || op->nu < 1 || op->nu > 16 || !(op->kappa > 0.f)) return MGP_ERR_ARG;
   if (op->form < 0 || op->form > 3) return MGP_ERR_ARG;
   if (op->form == 3 && !op->obs_w) return MGP_ERR_ARG;     // obs_w is read for form 3 only
+  if (!mgp_spmv_lanes_ok(op->L.spmv_lanes)) return MGP_ERR_ARG;
   return MGP_OK;
 }
 

@@ -532,8 +532,9 @@ int chain_launch(PcgPlan* pl, int s, const float* in, float* out, const float* b
     co = op.scale;
     if (op.form == 2) { bs = base; cb = 1.f; co = op.noise * op.scale; }
   }
-  return mgp_spmm_fused_first(&L, 0, in, 1, out, tau, 1.0f, first ? op.pre : nullptr, last ? op.post : nullptr, bs, cb, co,
-                              last ? dotw : nullptr, last ? dot_partials : nullptr, skip, last ? tick : nullptr, nullptr, st);
+  const MgpSpmmOpts o{0, nullptr, skip, last ? tick : nullptr};      // row_offset, cbv, skip, tick
+  return mgp_spmm_fused_opts(&L, in, 1, out, tau, 1.0f, first ? op.pre : nullptr, last ? op.post : nullptr, bs, cb, co,
+                             last ? dotw : nullptr, last ? dot_partials : nullptr, o, st);
 }
 
 // q (or w_0) = A v on this rank's rows; v gathered at the global length
@@ -738,7 +739,7 @@ extern "C" int mgp_pcg_plan_create(const mgp_operator_t* op, const int64_t* laun
                                    int64_t n_real, void* comm, int rank, int world, float* shared, int recurrence,
                                    const mgp_cg_params_t* params, void* work, size_t work_bytes, void* stream,
                                    void** plan_out) {
-  if (!op || !launch_rows || !params || !work || !plan_out) return MGP_ERR_ARG;
+  if (!op || !launch_rows || !params || !work || !plan_out || !mgp_spmv_lanes_ok(op->L.spmv_lanes)) return MGP_ERR_ARG;
   if (recurrence != 0 && recurrence != 1) return MGP_ERR_ARG;
   if (op->nu < 1 || op->nu > kMaxNu || (op->form != 0 && op->form != 2)) return MGP_ERR_UNSUPPORTED;
   if (world < 1 || rank < 0 || rank >= world || n_loc <= 0 || row0 < 0) return MGP_ERR_ARG;

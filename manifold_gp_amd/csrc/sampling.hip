@@ -18,6 +18,7 @@
 // one quad on a 16-lane group (the lap_pass form), S >= 13 a whole wave per row whose quad lanes loop over their quads.
 #include <math.h>
 #include "mgp_common.h"
+#include "mgp_internal.h"
 
 namespace {
 
@@ -155,7 +156,7 @@ int pow2_ceil(int v) {
 
 extern "C" int mgp_gmrf_noise(const mgp_csr_t* L, const float* dsqrt, float node_coef, int tag, int with_edges,
                               uint64_t seed, int64_t sample_offset, int S, float* Y, void* stream) {
-  if (!L || !L->rowptr || !L->col || !L->vals || !dsqrt || !Y) return MGP_ERR_ARG;
+  if (!L || !L->rowptr || !L->col || !L->vals || !dsqrt || !Y || !mgp_spmv_lanes_ok(L->spmv_lanes)) return MGP_ERR_ARG;
   if (S < 1 || L->n < 1 || L->n >= ((int64_t)1 << 31) || tag < 0 || sample_offset < 0) return MGP_ERR_ARG;
   if (with_edges != 0 && with_edges != 1) return MGP_ERR_ARG;
   if (((sample_offset + S) >> 2) >= ((int64_t)1 << 32)) return MGP_ERR_ARG;        // the quad index is one 32-bit word

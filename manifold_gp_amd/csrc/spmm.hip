@@ -24,6 +24,7 @@
 //     that each XCD streams one contiguous slice of rows (mgp_xcd_block).
 #include <string.h>
 #include <atomic>
+#include <type_traits>
 #include "mgp_common.h"
 #include "mgp_internal.h"
 #include <hip/hip_ext.h>
@@ -1524,24 +1525,29 @@ Plan make_plan(int64_t n, int rows_per_pass) {
   return Plan{(int)grid, rpb};
 }
 
-// C == 1 shape: lanes per row (4 entries per lane per pass) and rows in flight per lane group.
-// The host wrapper sets the lanes from the mean padded row length of the graph it built
-// (mgp_spmm_set_group_hint); measured best on the 60k and 500k graphs: 8 lanes x 1 row (tools/tune_spmv.py).
+// C == 1 row-group shape: lanes per row (4 entries per lane per pass) and rows in flight per lane group.  The lanes are a
+// property of the matrix and travel with it (mgp_csr_t.spmv_lanes: the host wrapper derives them from the mean padded row
+// length of the graph it built); g_row_group_hint is only the default for structs that leave the field 0
+// (mgp_spmm_set_group_hint).  Measured best on the 60k and 500k graphs: 8 lanes x 1 row (tools/tune_spmv.py).
 std::atomic<int> g_row_group_hint{16};
 std::atomic<int> g_rows_in_flight{1};
+// Lab switches (include/mgp_hip.h): process-wide, read ONCE per call by spmm_plan, whose answer is passed down by value --
+// the helpers of one call cannot see two settings.  (Two CALLS -- sizing the dot partials, then launching -- can still see
+// different settings: the header says the switches are not to be flipped while another thread is inside this family of calls.)
+std::atomic<int> g_tile_mode{1};
+std::atomic<int> g_tile_small_mode{1};
+std::atomic<int> g_tile_wide_mode{1};
+std::atomic<int> g_spmm_v4_mode{1};
+std::atomic<int> g_dict_mode{1};
+std::atomic<int> g_mt_mode{1};
+#ifdef MGP_STAMP
+std::atomic<int> g_stamp_enable{0};
+#endif
 
 }  // namespace
 
-// The lab switches below are process-wide atomics; a call reads them ONCE, at its entry point (knobs_snap), into a thread-local
-// snapshot that every helper of the call consults: a switch flipped by another thread in the middle of a call cannot make the
-// call's shape tests disagree with each other.  (Two CALLS -- sizing the dot partials, then launching -- can still see different
-// settings: the header says the switches are not to be flipped while another thread is inside this family of calls.)
-struct Knobs { int hint, rif, tile, tile_small, tile_wide, v4, dict, mt; };
-thread_local Knobs tl_knobs{16, 1, 1, 1, 1, 1, 1, 1};
-static void knobs_snap();
-
 extern "C" int mgp_spmm_set_group_hint(int lanes) {
-  if (lanes != 4 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64) return MGP_ERR_ARG;
+  if (!mgp_spmv_lanes_ok(lanes) || lanes == 0) return MGP_ERR_ARG;
   g_row_group_hint = lanes;
   return MGP_OK;
 }
@@ -1552,119 +1558,13 @@ extern "C" int mgp_spmm_set_rows_in_flight(int rows) {
   return MGP_OK;
 }
 
-static int spmv_rows_in_flight() {
-  int r = tl_knobs.rif;
-  if (r > tl_knobs.hint) r = tl_knobs.hint;   // lane t finishes row t: needs R <= G
-  return r;
-}
-
-static int spmm_cols_group(int C) {
-  int g = 4;
-  while (g < C && g < 64) g <<= 1;
-  return g;
-}
-
-// rows a workgroup covers per pass (the grid / dot-partial count follows from it).  C in {4,8,12,16}
-// uses 64 whichever kernel runs (the row16 kernel needs 16-byte aligned X, the generic one does not)
-static int spmm_rows_per_pass(int C) {
-  if (C == 1) return (kBlock / tl_knobs.hint) * spmv_rows_in_flight();
-  if (C <= 16 && (C & 3) == 0) return (kBlock / 16) * 4;
-  return kBlock / spmm_cols_group(C) * 4;
-}
-
 #ifdef MGP_STAMP
-std::atomic<int> g_stamp_enable{0};
 extern "C" int mgp_stamp_enable(int on) { g_stamp_enable = on ? 1 : 0; return 0; }
 #endif
-std::atomic<int> g_tile_mode{1};
 
 extern "C" int mgp_spmm_set_tile_mode(int on) {
   g_tile_mode = on ? 1 : 0;
   return MGP_OK;
-}
-
-int mgp_tile_plan(const mgp_csr_t* L, int C, int* grid, int* tiles_per_block, size_t* lds_bytes);
-
-static size_t tile_lds_bytes(const mgp_csr_t* L) {
-  return ((size_t)L->tile_max_cols + (size_t)(L->tile_max_entries >> 2)) * sizeof(float);
-}
-
-static bool use_tiles(const mgp_csr_t* L, int C) {
-  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
-  if (ord != 0 && ord != 3) return false;      // an ordered tile view is all three arrays or none
-  return C == 1 && tl_knobs.tile && L->lid && L->tile_ptr && L->tile_cols &&
-         (L->tile_rows == 32 || L->tile_rows == 64 || L->tile_rows == 128) && tile_lds_bytes(L) <= 65536 - 64;
-}
-
-static int tile_grid(const mgp_csr_t* L, int* tiles_per_block) {
-  const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
-  const int64_t tpb = mgp_cdiv(ntiles, kMaxGrid);
-  if (tiles_per_block) *tiles_per_block = (int)tpb;
-  return (int)mgp_cdiv(ntiles, tpb);
-}
-
-int mgp_tile_plan(const mgp_csr_t* L, int C, int* grid, int* tiles_per_block, size_t* lds_bytes) {
-  knobs_snap();
-  if (!L || !use_tiles(L, C)) return 0;
-  const int g = tile_grid(L, tiles_per_block);
-  if (grid) *grid = g;
-  if (lds_bytes) *lds_bytes = tile_lds_bytes(L);
-  return 1;
-}
-
-// C in {4, 8, 12, 16} on 64-row tiles whose staged data (dictionary rows + matrix stream) fits the LDS budget
-std::atomic<int> g_tile_small_mode{1};
-// quads of partial sums staged at once: what is left of a quarter of the CU's LDS (160 KB, four workgroups) behind the
-// dictionary, in steps of 256, at least 1024 (the quads a workgroup holds in registers), at most the largest tile
-static int tile_small_window(const mgp_csr_t* L) {
-  const int max_q = L->tile_max_entries >> 2;
-  const long budget = 40448 - (long)L->tile_max_cols * 16;
-  long w = budget > 0 ? budget / 16 / 256 * 256 : 0;
-  if (w < 1024) w = 1024;
-  if (w > max_q) w = (max_q + 255) / 256 * 256;
-  return (int)(w > 0 ? w : 256);
-}
-static size_t tile_small_lds_bytes(const mgp_csr_t* L, int C) {
-  const size_t max_q = (size_t)(L->tile_max_entries >> 2), w = (size_t)tile_small_window(L);
-  size_t b = ((size_t)L->tile_max_cols + (max_q < w ? max_q : w)) * 16;
-  const size_t red = (size_t)64 * C * sizeof(float);        // dot-partial staging reuses the same LDS
-  return b > red ? b : red;
-}
-static bool use_tiles_small(const mgp_csr_t* L, int C) {
-  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
-  if (ord != 0 && ord != 3) return false;
-  if (!(C == 4 || C == 8 || C == 12 || C == 16) || !tl_knobs.tile || !tl_knobs.tile_small) return false;
-  if (!L->lid || !L->tile_ptr || !L->tile_cols || L->tile_rows != 64) return false;
-  if ((L->tile_max_entries & 3) != 0) return false;
-  return tile_small_lds_bytes(L, C) <= 65536 - 64;
-}
-
-// 16 < C <= 256, C % 4 == 0 on 64-row tiles: the wide tile kernel (mgp_spmm_set_tile_wide_mode(0): spmm_kernel)
-std::atomic<int> g_tile_wide_mode{1};
-std::atomic<int> g_spmm_v4_mode{1};     // float4-lane gather kernel for 16 < C <= 256 (mgp_spmm_set_v4_mode(0): spmm_kernel)
-static int tile_wide_cap(const mgp_csr_t* L) {
-  int cap = (L->tile_max_cols + 63) / 64 * 64;
-  if (cap > kWideCap) cap = kWideCap;
-  if (cap < 64) cap = 64;
-  return cap;
-}
-static size_t tile_wide_lds_bytes(const mgp_csr_t* L) {
-  const size_t b = (size_t)tile_wide_cap(L) * 64;
-  return b > 4096 ? b : 4096;                                // (dot-partial staging: 64 x 16 floats)
-}
-static bool use_tiles_wide(const mgp_csr_t* L, int C) {
-  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
-  if (ord != 0 && ord != 3) return false;
-  if (C <= 16 || C > 256 || (C & 3) != 0 || !tl_knobs.tile || !tl_knobs.tile_wide) return false;
-  if (!L->lid || !L->tile_ptr || !L->tile_cols || L->tile_rows != 64) return false;
-  if ((L->tile_max_entries & 3) != 0) return false;
-  // measured (tools/lab/time_spmm_wide.py): on the 60k graph the per-entry gather kernel reads its X rows out of L2 and
-  // wins from 64 columns up (63 vs 84 us at C = 64, 91 vs 158 us at C = 128; 47 vs 59 us at C = 32 the other way, but see below); on
-  // the 1M graph, whose X block does not fit the caches, the dictionary kernel is 1.5-2.4x faster at every width
-  // (1.48 vs 3.04 ms at C = 128).  mode 2 forces it at any size (tests, A/B).
-  // (and up to 64 columns the float4-lane gather kernel beats both on a cache-resident X block: 33 us at C = 32)
-  if (tl_knobs.tile_wide == 2) return true;
-  return (size_t)L->n * (size_t)C * sizeof(float) >= ((size_t)96 << 20);
 }
 
 extern "C" int mgp_spmm_set_v4_mode(int on) {
@@ -1682,13 +1582,95 @@ extern "C" int mgp_spmm_set_tile_small_mode(int on) {
   return MGP_OK;
 }
 
-// 16 < C <= 256 on 64-row tiles with lanes over columns (spmm_dict_kernel): slots per slice from what the stream leaves
-// of the CU's LDS.  mgp_spmm_set_dict_mode: 0 never, 1 (default) where it was measured to win, 2 wherever the shape allows.
-// Measured (tools/lab/time_spmm_wide.py, round 3; us: this kernel | chunked dictionary kernel | float4 gather | per-column
-// gather):  60k graph  C = 64: 52 | 84 | 54 | 63   C = 128: 90 | 160 | 101 | 91   C = 256: 176 | 319 | 204 | 186
-//           1M graph   C = 64: 704 | 777 | 1020 | 1188   C = 128: 1201 | 1458 | 2084 | 3037   C = 256: 2380 | 2871 | 6515 | 6828
-// -> taken from 64 columns up when the X block (n x C floats) is 96 MB or more, i.e. does not sit in the caches.
-std::atomic<int> g_dict_mode{1};
+extern "C" int mgp_spmm_set_dict_mode(int on) {
+  g_dict_mode = on == 2 ? 2 : (on ? 1 : 0);
+  return MGP_OK;
+}
+
+extern "C" int mgp_spmm_set_mt_mode(int on) {
+  const int prev = g_mt_mode;
+  g_mt_mode = on ? 1 : 0;
+  return prev;
+}
+
+#ifdef MGP_MT_STAMP
+extern "C" int mgp_mt_set_stamp_buffer(void* buf) {
+  g_mt_stamps = static_cast<unsigned long long*>(buf);
+  return MGP_OK;
+}
+#endif
+
+extern "C" int mgp_spmm_mt_fill(int64_t n, const int32_t* rowptr, const float* vals, const uint16_t* lid16,
+                                const int32_t* tile_ptr16, const int32_t* tile_cols16, const int32_t* sptr, int64_t steps,
+                                int32_t* dcol, float* img, void* stream) {
+  if (n <= 0 || !rowptr || !vals || !lid16 || !tile_ptr16 || !tile_cols16 || !sptr || !dcol || !img || steps <= 0 || (steps & 15))
+    return MGP_ERR_ARG;
+  hipStream_t st = mgp_stream(stream);
+  MGP_HIP_TRY(hipMemsetAsync(img, 0, (size_t)(steps + 32) * 256, st));
+  MGP_HIP_TRY(hipMemsetAsync(dcol + 4 * steps, 0, 192 * sizeof(int32_t), st));
+  hipLaunchKernelGGL(spmm_mt_fill_kernel, dim3((unsigned)mgp_cdiv(n + 15, kBlock)), dim3(kBlock), 0, st, n, rowptr, vals, lid16,
+                     tile_ptr16, tile_cols16, sptr, dcol, img);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+// ---- launch geometry of the kernel families: pure functions of the CSR and the width --------------------------------------
+
+static int spmm_cols_group(int C) {
+  int g = 4;
+  while (g < C && g < 64) g <<= 1;
+  return g;
+}
+
+// rows a workgroup covers per pass (the grid / dot-partial count follows from it).  C in {4,8,12,16}
+// uses 64 whichever kernel runs (the row16 kernel needs 16-byte aligned X, the generic one does not)
+static int spmm_rows_per_pass(int C, int lanes, int rows_in_flight) {
+  if (C == 1) return (kBlock / lanes) * rows_in_flight;
+  if (C <= 16 && (C & 3) == 0) return (kBlock / 16) * 4;
+  return kBlock / spmm_cols_group(C) * 4;
+}
+
+static size_t tile_lds_bytes(const mgp_csr_t* L) {
+  return ((size_t)L->tile_max_cols + (size_t)(L->tile_max_entries >> 2)) * sizeof(float);
+}
+
+static int tile_grid(const mgp_csr_t* L, int* tiles_per_block) {
+  const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
+  const int64_t tpb = mgp_cdiv(ntiles, kMaxGrid);
+  if (tiles_per_block) *tiles_per_block = (int)tpb;
+  return (int)mgp_cdiv(ntiles, tpb);
+}
+
+// small-C tile kernel: quads of partial sums staged at once: what is left of a quarter of the CU's LDS (160 KB, four
+// workgroups) behind the dictionary, in steps of 256, at least 1024 (the quads a workgroup holds in registers), at most the
+// largest tile
+static int tile_small_window(const mgp_csr_t* L) {
+  const int max_q = L->tile_max_entries >> 2;
+  const long budget = 40448 - (long)L->tile_max_cols * 16;
+  long w = budget > 0 ? budget / 16 / 256 * 256 : 0;
+  if (w < 1024) w = 1024;
+  if (w > max_q) w = (max_q + 255) / 256 * 256;
+  return (int)(w > 0 ? w : 256);
+}
+static size_t tile_small_lds_bytes(const mgp_csr_t* L, int C) {
+  const size_t max_q = (size_t)(L->tile_max_entries >> 2), w = (size_t)tile_small_window(L);
+  size_t b = ((size_t)L->tile_max_cols + (max_q < w ? max_q : w)) * 16;
+  const size_t red = (size_t)64 * C * sizeof(float);        // dot-partial staging reuses the same LDS
+  return b > red ? b : red;
+}
+
+static int tile_wide_cap(const mgp_csr_t* L) {
+  int cap = (L->tile_max_cols + 63) / 64 * 64;
+  if (cap > kWideCap) cap = kWideCap;
+  if (cap < 64) cap = 64;
+  return cap;
+}
+static size_t tile_wide_lds_bytes(const mgp_csr_t* L) {
+  const size_t b = (size_t)tile_wide_cap(L) * 64;
+  return b > 4096 ? b : 4096;                                // (dot-partial staging: 64 x 16 floats)
+}
+
+// lanes-over-columns dictionary kernel: slots per slice from what the stream leaves of the CU's LDS
 static int dict_nv(int C) { return (C + 63) / 64; }
 static int dict_stream_cap(const mgp_csr_t* L) { return (L->tile_max_entries + 7) / 8 * 8; }
 static int dict_slots(const mgp_csr_t* L, int C) {
@@ -1712,35 +1694,11 @@ static int dict_grid(const mgp_csr_t* L) {
   const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
   return (int)(ntiles < kMaxGrid ? ntiles : kMaxGrid);
 }
-static bool dict_shape_ok(const mgp_csr_t* L, int C) {
-  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
-  if (ord != 0 && ord != 3) return false;
-  if (C <= 16 || C > 256 || (C & 3) != 0 || !tl_knobs.tile || !tl_knobs.dict) return false;
-  if (!L->lid || !L->tile_ptr || !L->tile_cols || L->tile_rows != 64) return false;
-  if ((L->tile_max_entries & 3) != 0) return false;
-  if (dict_slots(L, C) < 32) return false;
-  if (tl_knobs.dict == 2) return true;
-  return C >= 64 && (size_t)L->n * (size_t)C * sizeof(float) >= ((size_t)96 << 20);
-}
-// the kernel moves 16 bytes per lane: X, Y, base and dotw rows must be 16-byte aligned (C % 4 == 0 makes every row so
-// once the block is); the planned kernel (dot-partial blocks) and the launched one must never disagree, so a
-// misaligned operand is an argument error at launch instead of a silent fall-through to another kernel
-static bool aligned16(const void* a, const void* b, const void* c, const void* d) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
 
-// 48 <= C <= 256 on the matrix cores (spmm_mt_kernel): taken when the CSR carries the dense 16-row tile image (mgp_spmm_mt_fill;
-// the host wrapper builds it for graphs in natural row order whose tiles are at least 1/8 full) and the call has no row offset
-// (weighted dot-product partials included: one row of partials per workgroup).  mgp_spmm_set_mt_mode(0) = never (A/B runs, tests).
-std::atomic<int> g_mt_mode{1};
-static void knobs_snap() {
-  tl_knobs = Knobs{g_row_group_hint.load(), g_rows_in_flight.load(), g_tile_mode.load(), g_tile_small_mode.load(), g_tile_wide_mode.load(),
-                   g_spmm_v4_mode.load(), g_dict_mode.load(), g_mt_mode.load()};
-}
+// the CSR carries a usable dense 16-row tile image (mgp_spmm_mt_fill) for this width
 constexpr int kMtMinCols = 48;
-static bool mt_shape_ok(const mgp_csr_t* L, int C) {
-  if (!tl_knobs.mt || !L->mt_img || !L->mt_sptr || !L->mt_dcol || L->mt_tiles <= 0 || L->mt_steps <= 0) return false;
+static bool mt_image_fits(const mgp_csr_t* L, int C) {
+  if (!L->mt_img || !L->mt_sptr || !L->mt_dcol || L->mt_tiles <= 0 || L->mt_steps <= 0) return false;
   // below 48 columns most lanes of a wave's 64-column block idle: the gather kernel is faster there (C = 32: 34 us against 41)
   if (C < kMtMinCols || C > 256 || (C & 3) != 0 || L->tile_rowid) return false;
   if (L->ncols != 0 && L->ncols != L->n) return false;        // a row slice of a partitioned operator never carries an image
@@ -1749,62 +1707,161 @@ static bool mt_shape_ok(const mgp_csr_t* L, int C) {
   return L->mt_tiles == (int32_t)mgp_cdiv(L->n, 16);
 }
 
-#ifdef MGP_MT_STAMP
-extern "C" int mgp_mt_set_stamp_buffer(void* buf) {
-  g_mt_stamps = static_cast<unsigned long long*>(buf);
-  return MGP_OK;
-}
-#endif
-extern "C" int mgp_spmm_set_mt_mode(int on) {
-  const int prev = g_mt_mode;
-  g_mt_mode = on ? 1 : 0;
-  return prev;
+static TileArgs tile_args(const mgp_csr_t* L, int tiles_per_block, int part_window) {
+  return TileArgs{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), tiles_per_block, L->tile_max_cols,
+                  L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, part_window};
 }
 
-extern "C" int mgp_spmm_mt_fill(int64_t n, const int32_t* rowptr, const float* vals, const uint16_t* lid16,
-                                const int32_t* tile_ptr16, const int32_t* tile_cols16, const int32_t* sptr, int64_t steps,
-                                int32_t* dcol, float* img, void* stream) {
-  if (n <= 0 || !rowptr || !vals || !lid16 || !tile_ptr16 || !tile_cols16 || !sptr || !dcol || !img || steps <= 0 || (steps & 15))
-    return MGP_ERR_ARG;
-  hipStream_t st = mgp_stream(stream);
-  MGP_HIP_TRY(hipMemsetAsync(img, 0, (size_t)(steps + 32) * 256, st));
-  MGP_HIP_TRY(hipMemsetAsync(dcol + 4 * steps, 0, 192 * sizeof(int32_t), st));
-  hipLaunchKernelGGL(spmm_mt_fill_kernel, dim3((unsigned)mgp_cdiv(n + 15, kBlock)), dim3(kBlock), 0, st, n, rowptr, vals, lid16,
-                     tile_ptr16, tile_cols16, sptr, dcol, img);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+// ---- which kernel runs: the ONE statement of the policy -------------------------------------------------------------------
+// spmm_plan reads the switches once, applies the precedence order once and returns everything that follows from the choice.
+// The sizing call (mgp_spmm_dot_blocks_csr), the reporting call (mgp_spmm_kernel_choice) and the launch (spmm_launch) all
+// read this value: the planned kernel and the launched one cannot disagree.
+namespace {
+enum class SpmmFamily { RowGroups, Gather, TileC1, TileSmall, MatrixCore, Dict, TileWide };
+
+struct SpmmPlan {
+  int err;                  // MGP_OK; MGP_ERR_ARG (spmv_lanes); MGP_ERR_UNSUPPORTED (tile image + row offset + dot partials)
+  SpmmFamily family;
+  int grid;
+  size_t lds;               // dynamic LDS bytes
+  int dot_blocks;           // workgroups that write dot partials
+  bool align16;             // X, Y, base and dotw must be 16-byte aligned: MGP_ERR_ARG at launch otherwise
+  int64_t rows_per_block;   // RowGroups, Gather: contiguous row range of a workgroup
+  int lanes, rows_in_flight;    // RowGroups
+  bool v4_ok;               // Gather: switch and shape allow the float4 member (the launch adds the alignment test)
+  int tiles_per_block;      // TileC1, TileSmall, TileWide (Dict: 1)
+  int window;               // TileSmall: quads of partial sums staged per window
+  int slots, stream_cap;    // Dict
+  int wide_cap;             // TileWide
+};
+}  // namespace
+
+static SpmmPlan spmm_plan(const mgp_csr_t* L, int C, int64_t row_offset, bool with_dot) {
+  SpmmPlan pl{};
+  pl.tiles_per_block = 1;
+  if (!mgp_spmv_lanes_ok(L->spmv_lanes)) { pl.err = MGP_ERR_ARG; return pl; }
+  const int tile = g_tile_mode, tile_small = g_tile_small_mode, tile_wide = g_tile_wide_mode, v4 = g_spmm_v4_mode,
+            dict = g_dict_mode, mt = g_mt_mode;
+  // row-tile dictionaries present and switched on; an ordered tile view is all three arrays or none
+  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
+  const bool dicts = tile && (ord == 0 || ord == 3) && L->lid && L->tile_ptr && L->tile_cols;
+  const bool dicts64 = dicts && L->tile_rows == 64 && (L->tile_max_entries & 3) == 0;      // 64-row tiles, quad-padded rows
+  const bool wide = C > 16 && C <= 256 && (C & 3) == 0;
+  const bool big_x = (size_t)L->n * (size_t)C * sizeof(float) >= ((size_t)96 << 20);   // the X block does not sit in the caches
+
+  // 1. C == 1 on 32 / 64 / 128-row tiles: the column dictionary of a tile staged in LDS (spmv_tile_kernel)
+  if (C == 1 && dicts && (L->tile_rows == 32 || L->tile_rows == 64 || L->tile_rows == 128) && tile_lds_bytes(L) <= 65536 - 64) {
+    pl.family = SpmmFamily::TileC1;
+    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
+    pl.lds = tile_lds_bytes(L);
+    return pl;
+  }
+  // 2. C in {4, 8, 12, 16} on 64-row tiles whose staged data (dictionary rows + matrix stream) fits the LDS budget
+  //    (spmm_tile_q_kernel); [n, C] blocks with C a multiple of 4 are 16-byte aligned row by row
+  if ((C == 4 || C == 8 || C == 12 || C == 16) && tile_small && dicts64 && tile_small_lds_bytes(L, C) <= 65536 - 64) {
+    pl.family = SpmmFamily::TileSmall;
+    pl.align16 = true;
+    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
+    pl.lds = tile_small_lds_bytes(L, C);
+    pl.window = tile_small_window(L);
+    return pl;
+  }
+  // 3. 48 <= C <= 256 on the matrix cores (spmm_mt_kernel): taken when the CSR carries the dense 16-row tile image
+  //    (mgp_spmm_mt_fill; the host wrapper builds it for graphs in natural row order whose tiles are at least 1/8 full) and the
+  //    call has no row offset (weighted dot-product partials included: one row of partials per workgroup).
+  //    mgp_spmm_set_mt_mode(0) = never (A/B runs, tests).
+  if (mt && mt_image_fits(L, C)) {
+    if (row_offset == 0) {
+      pl.family = SpmmFamily::MatrixCore;
+      pl.align16 = true;
+      pl.grid = pl.dot_blocks = (int)mgp_cdiv((int64_t)L->mt_tiles * ((C + 63) / 64), kBlock / 64);
+      return pl;
+    }
+    // a CSR that carries the tile image, a row offset AND dot partials: mgp_spmm_dot_blocks_csr sized them for the matrix-core
+    // kernel, which takes no row offset -- the one combination that is refused.  Without dot partials the rules below apply.
+    if (with_dot) { pl.err = MGP_ERR_UNSUPPORTED; return pl; }
+  }
+  // 4. 16 < C <= 256 on 64-row tiles with lanes over columns (spmm_dict_kernel), at least 32 slots per slice.
+  //    mgp_spmm_set_dict_mode: 0 never, 1 (default) where it was measured to win, 2 wherever the shape allows.
+  //    Measured (tools/lab/time_spmm_wide.py, round 3; us: this kernel | chunked dictionary kernel | float4 gather | per-column
+  //    gather):  60k graph  C = 64: 52 | 84 | 54 | 63   C = 128: 90 | 160 | 101 | 91   C = 256: 176 | 319 | 204 | 186
+  //              1M graph   C = 64: 704 | 777 | 1020 | 1188   C = 128: 1201 | 1458 | 2084 | 3037   C = 256: 2380 | 2871 | 6515 | 6828
+  //    -> taken from 64 columns up when the X block (n x C floats) is 96 MB or more, i.e. does not sit in the caches.
+  if (wide && dict && dicts64 && dict_slots(L, C) >= 32 && (dict == 2 || (C >= 64 && big_x))) {
+    pl.family = SpmmFamily::Dict;
+    pl.align16 = true;       // the kernel moves 16 bytes per lane (C % 4 == 0 makes every row aligned once the block is)
+    pl.grid = pl.dot_blocks = dict_grid(L);
+    pl.lds = dict_lds_bytes(L, C);
+    pl.slots = dict_slots(L, C);
+    pl.stream_cap = dict_stream_cap(L);
+    return pl;
+  }
+  // 5. 16 < C <= 256 on 64-row tiles in 16-column chunks (spmm_tile_wide_kernel).
+  //    Measured (tools/lab/time_spmm_wide.py): on the 60k graph the per-entry gather kernel reads its X rows out of L2 and
+  //    wins from 64 columns up (63 vs 84 us at C = 64, 91 vs 158 us at C = 128; 47 vs 59 us at C = 32 the other way, but see below); on
+  //    the 1M graph, whose X block does not fit the caches, the dictionary kernel is 1.5-2.4x faster at every width
+  //    (1.48 vs 3.04 ms at C = 128).  mode 2 forces it at any size (tests, A/B).
+  //    (and up to 64 columns the float4-lane gather kernel beats both on a cache-resident X block: 33 us at C = 32)
+  if (wide && tile_wide && dicts64 && (tile_wide == 2 || big_x)) {
+    pl.family = SpmmFamily::TileWide;
+    pl.align16 = true;
+    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
+    pl.lds = tile_wide_lds_bytes(L);
+    pl.wide_cap = tile_wide_cap(L);
+    return pl;
+  }
+  // 6. C == 1 without dictionaries: a row per lane group (spmv_kernel); the lanes are the matrix's own, 0 = process default
+  if (C == 1) {
+    pl.family = SpmmFamily::RowGroups;
+    pl.lanes = L->spmv_lanes ? L->spmv_lanes : g_row_group_hint.load();
+    pl.rows_in_flight = g_rows_in_flight;
+    if (pl.rows_in_flight > pl.lanes) pl.rows_in_flight = pl.lanes;   // lane t finishes row t: needs R <= G
+    const Plan rows = make_plan(L->n, spmm_rows_per_pass(1, pl.lanes, pl.rows_in_flight));
+    pl.grid = pl.dot_blocks = rows.grid;
+    pl.rows_per_block = rows.rows_per_block;
+    return pl;
+  }
+  // 7. C > 1 gather from memory.  The plan fixes the FAMILY and its grid; the launch picks the member (row16, float4 lanes,
+  //    per-column) by pointer alignment, which a sizing call cannot know.  That is sound because all three cover the same
+  //    make_plan(n, spmm_rows_per_pass(C)) row ranges and therefore write the same dot-partial blocks.
+  //    float4 member, measured (tools/lab/time_spmm_wide.py): 33 vs 59 us at C = 32 and 54 vs 63 us at C = 64 on the 60k graph, but
+  //    101 vs 91 us at C = 128 (the X block no longer sits in L2 and the per-column kernel's whole-line pieces use
+  //    the Infinity Cache path better); on the 1M graph, when the dictionaries are not there, it wins at every width.
+  //    (quad-padded rows are what the tile builder guarantees: the CSR of a graph without dictionaries keeps the per-column kernel)
+  pl.family = SpmmFamily::Gather;
+  pl.v4_ok = v4 && wide && (v4 == 2 || C <= 64 || big_x) && (L->tile_max_entries & 3) == 0 && L->lid != nullptr;
+  const Plan rows = make_plan(L->n, spmm_rows_per_pass(C, 0, 0));
+  pl.grid = pl.dot_blocks = rows.grid;
+  pl.rows_per_block = rows.rows_per_block;
+  return pl;
 }
 
-extern "C" int mgp_spmm_set_dict_mode(int on) {
-  g_dict_mode = on == 2 ? 2 : (on ? 1 : 0);
-  return MGP_OK;
+int mgp_tile_plan(const mgp_csr_t* L) {
+  if (!L) return 0;
+  const SpmmPlan pl = spmm_plan(L, 1, 0, false);
+  return pl.err == MGP_OK && pl.family == SpmmFamily::TileC1;
 }
 
 int mgp_spmm_dot_blocks_for(const mgp_csr_t* L, int C) {
   if (!L) return MGP_ERR_ARG;
-  knobs_snap();
-  if (use_tiles(L, C) || use_tiles_small(L, C)) return tile_grid(L, nullptr);
-  if (mt_shape_ok(L, C)) return (int)mgp_cdiv((int64_t)L->mt_tiles * ((C + 63) / 64), kBlock / 64);
-  if (dict_shape_ok(L, C)) return dict_grid(L);
-  if (use_tiles_wide(L, C)) return tile_grid(L, nullptr);
-  return mgp_spmm_dot_blocks(L->n, C);
+  const SpmmPlan pl = spmm_plan(L, C, 0, false);
+  return pl.err != MGP_OK ? pl.err : pl.dot_blocks;
 }
 
-// which kernel a call of mgp_spmm_fused with this CSR / width would launch (tests, docs): 0 = gather (C == 1: row groups),
-// 1 = C == 1 tile kernel, 2 = small-C tile kernel, 3 = matrix-core tiles, 5 = lanes-over-columns dictionary, 6 = chunked
-// dictionary (4 was round 4's persistent 8-lanes-per-row dictionary kernel: measured slower, removed in round 5)
+// the public numbers of the families (include/mgp_hip.h; 4 was round 4's persistent 8-lanes-per-row dictionary kernel:
+// measured slower, removed in round 5)
 extern "C" int mgp_spmm_kernel_choice(const mgp_csr_t* L, int C, int with_dot, int64_t row_offset) {
   if (!L || L->n <= 0 || C <= 0 || C > 256) return MGP_ERR_ARG;
-  knobs_snap();
-  static const float one = 1.f;
-  if (use_tiles(L, C)) return 1;
-  if (use_tiles_small(L, C)) return 2;
-  (void)one;
-  if (mt_shape_ok(L, C) && row_offset == 0) return 3;
-  if (mt_shape_ok(L, C) && with_dot) return MGP_ERR_UNSUPPORTED;      // (as mgp_spmm_fused_rows: partials were sized for kernel 3)
-  if (dict_shape_ok(L, C)) return 5;
-  if (use_tiles_wide(L, C)) return 6;
-  return 0;
+  const SpmmPlan pl = spmm_plan(L, C, row_offset, with_dot != 0);
+  if (pl.err != MGP_OK) return pl.err;
+  switch (pl.family) {
+    case SpmmFamily::TileC1: return 1;
+    case SpmmFamily::TileSmall: return 2;
+    case SpmmFamily::MatrixCore: return 3;
+    case SpmmFamily::Dict: return 5;
+    case SpmmFamily::TileWide: return 6;
+    default: return 0;      // gather (C == 1: row groups)
+  }
 }
 
 extern "C" int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C) {
@@ -1812,51 +1869,22 @@ extern "C" int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C) {
   return mgp_spmm_dot_blocks_for(L, C);
 }
 
+// no CSR: the gather kernels' count, C == 1 with the process-default lanes
 extern "C" int mgp_spmm_dot_blocks(int64_t n, int C) {
   if (n <= 0 || C <= 0) return MGP_ERR_ARG;
-  knobs_snap();
-  return make_plan(n, spmm_rows_per_pass(C)).grid;
-}
-
-template <int G, int R, bool PRE, bool CBV>
-static void launch_spmv(const SpmmArgs& a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((spmv_kernel<G, R, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a);
+  const int lanes = g_row_group_hint, rif = g_rows_in_flight;
+  return make_plan(n, spmm_rows_per_pass(C, lanes, rif < lanes ? rif : lanes)).grid;
 }
 
 template <int G, bool PRE, bool CBV>
 static int launch_spmv_r(const SpmmArgs& a, int R, int grid, hipStream_t st) {
   switch (R) {
-    case 1: launch_spmv<G, 1, PRE, CBV>(a, grid, st); return MGP_OK;
-    case 2: launch_spmv<G, 2, PRE, CBV>(a, grid, st); return MGP_OK;
-    case 4: launch_spmv<G, 4, PRE, CBV>(a, grid, st); return MGP_OK;
-    case 8: if (G >= 8) { launch_spmv<G, (G >= 8 ? 8 : 4), PRE, CBV>(a, grid, st); return MGP_OK; }
+    case 1: hipLaunchKernelGGL((spmv_kernel<G, 1, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a); return MGP_OK;
+    case 2: hipLaunchKernelGGL((spmv_kernel<G, 2, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a); return MGP_OK;
+    case 4: hipLaunchKernelGGL((spmv_kernel<G, 4, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a); return MGP_OK;
+    case 8: if (G >= 8) { hipLaunchKernelGGL((spmv_kernel<G, (G >= 8 ? 8 : 4), PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a); return MGP_OK; }
   }
   return MGP_ERR_ARG;
-}
-
-template <int G, int NACC, bool PRE, bool CBV>
-static void launch_spmm(const SpmmArgs& a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((spmm_kernel<G, NACC, PRE, CBV>), dim3(grid), dim3(kBlock), 0, st, a);
-}
-
-extern "C" int mgp_spmm_fused(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
-                              const float* pre, const float* post, const float* base, float cb,
-                              float co, const float* dotw, float* dot_partials, void* stream) {
-  return mgp_spmm_fused_ex(L, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, nullptr, nullptr,
-                           stream);
-}
-
-int mgp_spmm_fused_ex(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
-                      const float* pre, const float* post, const float* base, float cb, float co,
-                      const float* dotw, float* dot_partials, const int* skip, int* tick, void* stream) {
-  return mgp_spmm_fused_part(L, 0, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, skip, tick, stream);
-}
-
-int mgp_spmm_fused_part(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                        const float* pre, const float* post, const float* base, float cb, float co,
-                        const float* dotw, float* dot_partials, const int* skip, int* tick, void* stream) {
-  return mgp_spmm_fused_first(L, row_offset, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, skip, tick,
-                              nullptr, stream);
 }
 
 namespace {
@@ -1889,225 +1917,179 @@ int mgp_spmm_patch_node(void* exec, void* node, const void* record, const float*
 }
 
 namespace {
-// the kernel choice of mgp_spmm_fused_cbv; CB: p.cbv is set (every kernel family has a CBV instantiation of its own,
-// so the code of the cbv == NULL calls is what it was before the per-row coefficient existed)
+// f(std::true_type / std::false_type): the PRE instantiation of a kernel by whether the call has a pre vector;
+// f(IntC<C / 4>) for C in {4, 8, 12, 16}
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> static void with_pre(bool pre, F&& f) { if (pre) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_quads(int C, F&& f) {
+  if (C == 4) f(IntC<1>{});
+  else if (C == 8) f(IntC<2>{});
+  else if (C == 12) f(IntC<3>{});
+  else f(IntC<4>{});
+}
+
+static bool aligned16(const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+// builds the arguments of the planned family and launches it: no shape test, no switch is read here.  CB: p.cbv is set
+// (every kernel family has a CBV instantiation of its own, so the code of the cbv == NULL calls is what it was before the
+// per-row coefficient existed)
 template <bool CB>
-int spmm_launch(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, const float* pre,
-                const float* base, const float* dotw, float* dot_partials, const MgpFirst* first, SpmmArgs& p,
-                hipStream_t st) {
-  if (use_tiles(L, C)) {
-    TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
-                L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, 0};
-    const int grid = tile_grid(L, &ta.tiles_per_block);
-    const size_t lds = tile_lds_bytes(L);
-#define MGP_TILE_LAUNCH_K(KERNEL, BS)                                                                   \
-  do {                                                                                                   \
-    if (g_spmv_timer.on && 2 * g_spmv_timer.used + 1 < (int)g_spmv_timer.ev.size()) {                    \
-      hipEvent_t e0 = g_spmv_timer.ev[2 * g_spmv_timer.used], e1 = g_spmv_timer.ev[2 * g_spmv_timer.used + 1]; \
-      ++g_spmv_timer.used;                                                                               \
-      hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(BS), lds, st, e0, e1, 0, p, ta);                    \
-    } else hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(BS), lds, st, p, ta);                             \
-  } while (0)
-#define MGP_TILE_LAUNCH(BS)                                                                              \
-  do {                                                                                                   \
-    if (pre) MGP_TILE_LAUNCH_K((spmv_tile_kernel<true, BS, CB>), BS);                                    \
-    else MGP_TILE_LAUNCH_K((spmv_tile_kernel<false, BS, CB>), BS);                                       \
-  } while (0)
-    if (first && first->record) {
+int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArgs& p, hipStream_t st) {
+  const int C = p.C, grid = pl.grid;
+  const size_t lds = pl.lds;
+  const bool pre = p.pre != nullptr;
+  // the planned kernel (dot-partial blocks) and the launched one must never disagree, so a misaligned operand is an argument
+  // error at launch instead of a silent fall-through to another kernel
+  if (pl.align16 && !aligned16(p.X, p.Y, p.base, p.dotw)) return MGP_ERR_ARG;
+  p.rows_per_block = pl.rows_per_block;
+  switch (pl.family) {
+  case SpmmFamily::TileC1: {
+    TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+    if (record_to) {
       TileLaunchRecord rec{p, ta};
-      memcpy(first->record, &rec, sizeof(rec));
+      memcpy(record_to, &rec, sizeof(rec));
     }
-    if (L->tile_rows == 32) MGP_TILE_LAUNCH(128);
-    else if (L->tile_rows == 64) MGP_TILE_LAUNCH(256);
-    else MGP_TILE_LAUNCH(512);
-#undef MGP_TILE_LAUNCH_K
-#undef MGP_TILE_LAUNCH
-  } else if (use_tiles_small(L, C)) {
-    if (((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(base) |
-          reinterpret_cast<uintptr_t>(dotw)) & 15) != 0)
-      return MGP_ERR_ARG;                  // [n, C] blocks with C a multiple of 4 are 16-byte aligned row by row
-    TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
-                L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, tile_small_window(L)};
-    const int grid = tile_grid(L, &ta.tiles_per_block);
-    const size_t lds = tile_small_lds_bytes(L, C);
-#define MGP_TILE_SMALL_LAUNCH(C4)                                                                                 \
-  do {                                                                                                            \
-    if (pre) hipLaunchKernelGGL((spmm_tile_q_kernel<C4, true, CB>), dim3(grid), dim3(256), lds, st, p, ta);    \
-    else hipLaunchKernelGGL((spmm_tile_q_kernel<C4, false, CB>), dim3(grid), dim3(256), lds, st, p, ta);       \
-  } while (0)
-    if (C == 4) MGP_TILE_SMALL_LAUNCH(1);
-    else if (C == 8) MGP_TILE_SMALL_LAUNCH(2);
-    else if (C == 12) MGP_TILE_SMALL_LAUNCH(3);
-    else MGP_TILE_SMALL_LAUNCH(4);
-#undef MGP_TILE_SMALL_LAUNCH
-  } else if (mt_shape_ok(L, C) && row_offset != 0 && dotw && dot_partials) {
-    // a CSR that carries the tile image, a row offset AND dot partials: mgp_spmm_dot_blocks_csr sized them for the matrix-core
-    // kernel, which takes no row offset -- the one combination that is refused (mgp_spmm_kernel_choice reports it too)
-    return MGP_ERR_UNSUPPORTED;
-  } else if (mt_shape_ok(L, C) && row_offset == 0) {
-    if (!aligned16(X, Y, base, dotw)) return MGP_ERR_ARG;
+    auto tiles = [&](auto bs) { with_pre(pre, [&](auto P) {
+      constexpr int BS = decltype(bs)::value;
+      const auto kernel = &spmv_tile_kernel<decltype(P)::value, BS, CB>;
+      if (g_spmv_timer.on && 2 * g_spmv_timer.used + 1 < (int)g_spmv_timer.ev.size()) {
+        hipEvent_t e0 = g_spmv_timer.ev[2 * g_spmv_timer.used], e1 = g_spmv_timer.ev[2 * g_spmv_timer.used + 1];
+        ++g_spmv_timer.used;
+        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BS), lds, st, e0, e1, 0, p, ta);
+      } else hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), lds, st, p, ta);
+    }); };
+    if (L->tile_rows == 32) tiles(IntC<128>{});
+    else if (L->tile_rows == 64) tiles(IntC<256>{});
+    else tiles(IntC<512>{});
+  } break;
+  case SpmmFamily::TileSmall: {
+    TileArgs ta = tile_args(L, pl.tiles_per_block, pl.window);
+    with_quads(C, [&](auto c4) { with_pre(pre, [&](auto P) {
+      hipLaunchKernelGGL((spmm_tile_q_kernel<decltype(c4)::value, decltype(P)::value, CB>), dim3(grid), dim3(256), lds, st, p, ta);
+    }); });
+  } break;
+  case SpmmFamily::MatrixCore: {
     MtArgs ma{L->mt_sptr, L->mt_dcol, L->mt_img, L->mt_tiles, (C + 63) / 64, (int)(((int64_t)L->mt_steps + 32) * 256),
               (int)(((int64_t)L->mt_steps * 4 + 192) * 4)};
-    const int grid = (int)mgp_cdiv((int64_t)ma.T * ma.NCB, kBlock / 64);
 #if defined(MGP_MT_LAB) && (MGP_MT_LAB & 1)     // lab: every image request out of range -> zeros, no memory traffic
     ma.img_bytes = 0;
 #endif
 #ifdef MGP_MT_STAMP
     ma.stamps = g_mt_stamps;
 #endif
-    if constexpr (CB) {
-      if (pre) hipLaunchKernelGGL((spmm_mt_cbv_kernel<true>), dim3(grid), dim3(kBlock), 0, st, p, ma);
-      else hipLaunchKernelGGL((spmm_mt_cbv_kernel<false>), dim3(grid), dim3(kBlock), 0, st, p, ma);
-    } else {
-      if (pre) hipLaunchKernelGGL((spmm_mt_kernel<true>), dim3(grid), dim3(kBlock), 0, st, p, ma);
-      else hipLaunchKernelGGL((spmm_mt_kernel<false>), dim3(grid), dim3(kBlock), 0, st, p, ma);
-    }
-  } else if (dict_shape_ok(L, C)) {
-    if (!aligned16(X, Y, base, dotw)) return MGP_ERR_ARG;   // (the plan counted this kernel's dot-partial blocks)
-    TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
-                L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, 0};
-    const int grid = dict_grid(L);
-    const size_t lds = dict_lds_bytes(L, C);
-    const int S = dict_slots(L, C), cap = dict_stream_cap(L);
-#define MGP_DICT_LAUNCH(NV)                                                                                         \
-  do {                                                                                                              \
-    /* the attribute is per DEVICE and the call is cheap next to a launch: set every time (a process that drives a  \
-       second GPU, or two host threads, must not depend on a process-wide flag) */                                  \
-    if (pre) {                                                                                                      \
-      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, true, CB>),               \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kDictLdsBudget));                 \
-      hipLaunchKernelGGL((spmm_dict_kernel<NV, true, CB>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap); \
-    } else {                                                                                                        \
-      MGP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_dict_kernel<NV, false, CB>),              \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kDictLdsBudget));                 \
-      hipLaunchKernelGGL((spmm_dict_kernel<NV, false, CB>), dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap);    \
-    }                                                                                                               \
-  } while (0)
+    with_pre(pre, [&](auto P) {
+      if constexpr (CB) hipLaunchKernelGGL((spmm_mt_cbv_kernel<decltype(P)::value>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+      else hipLaunchKernelGGL((spmm_mt_kernel<decltype(P)::value>), dim3(grid), dim3(kBlock), 0, st, p, ma);
+    });
+  } break;
+  case SpmmFamily::Dict: {
+    TileArgs ta = tile_args(L, 1, 0);
+    const int S = pl.slots, cap = pl.stream_cap;
+    hipError_t attr = hipSuccess;
+    auto slices = [&](auto nv) { with_pre(pre, [&](auto P) {
+      const auto kernel = &spmm_dict_kernel<decltype(nv)::value, decltype(P)::value, CB>;
+      // the attribute is per DEVICE and the call is cheap next to a launch: set every time (a process that drives a
+      // second GPU, or two host threads, must not depend on a process-wide flag)
+      attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kDictLdsBudget);
+      if (attr == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(kDictThreads), lds, st, p, ta, S, cap);
+    }); };
     switch (dict_nv(C)) {
-      case 1: MGP_DICT_LAUNCH(1); break;
-      case 2: MGP_DICT_LAUNCH(2); break;
-      case 3: MGP_DICT_LAUNCH(3); break;
-      default: MGP_DICT_LAUNCH(4); break;
+      case 1: slices(IntC<1>{}); break;
+      case 2: slices(IntC<2>{}); break;
+      case 3: slices(IntC<3>{}); break;
+      default: slices(IntC<4>{}); break;
     }
-#undef MGP_DICT_LAUNCH
-  } else if (use_tiles_wide(L, C)) {
-    if (!aligned16(X, Y, base, dotw)) return MGP_ERR_ARG;   // planned and launched kernel must not disagree
-    TileArgs ta{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), 1, L->tile_max_cols,
-                L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, 0};
-    const int grid = tile_grid(L, &ta.tiles_per_block);
-    const size_t lds = tile_wide_lds_bytes(L);
-    const int cap = tile_wide_cap(L);
-    if (pre) hipLaunchKernelGGL((spmm_tile_wide_kernel<true, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
-    else hipLaunchKernelGGL((spmm_tile_wide_kernel<false, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
-  } else if (C == 1) {
-    const int G = tl_knobs.hint;
-    const int R = spmv_rows_in_flight();
-    Plan pl = make_plan(L->n, (kBlock / G) * R);
-    p.rows_per_block = pl.rows_per_block;
+    MGP_HIP_TRY(attr);
+  } break;
+  case SpmmFamily::TileWide: {
+    TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+    const int cap = pl.wide_cap;
+    with_pre(pre, [&](auto P) {
+      hipLaunchKernelGGL((spmm_tile_wide_kernel<decltype(P)::value, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
+    });
+  } break;
+  case SpmmFamily::RowGroups: {
+    const int R = pl.rows_in_flight;
     int rc = MGP_OK;
-#define MGP_SPMV_CASE(GG)                                                                     \
-  case GG:                                                                                    \
-    rc = pre ? launch_spmv_r<GG, true, CB>(p, R, pl.grid, st) : launch_spmv_r<GG, false, CB>(p, R, pl.grid, st); \
-    break;
-    switch (G) {
-      MGP_SPMV_CASE(4)
-      MGP_SPMV_CASE(8)
-      MGP_SPMV_CASE(16)
-      MGP_SPMV_CASE(32)
-      MGP_SPMV_CASE(64)
+    auto rows = [&](auto g) { with_pre(pre, [&](auto P) {
+      rc = launch_spmv_r<decltype(g)::value, decltype(P)::value, CB>(p, R, grid, st);
+    }); };
+    switch (pl.lanes) {
+      case 4: rows(IntC<4>{}); break;
+      case 8: rows(IntC<8>{}); break;
+      case 16: rows(IntC<16>{}); break;
+      case 32: rows(IntC<32>{}); break;
+      case 64: rows(IntC<64>{}); break;
       default: return MGP_ERR_ARG;
     }
-#undef MGP_SPMV_CASE
     MGP_TRY(rc);
-  } else if (C <= 16 && (C & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0) {
-    Plan pl = make_plan(L->n, spmm_rows_per_pass(C));
-    p.rows_per_block = pl.rows_per_block;
-#define MGP_ROW16_LAUNCH(C4)                                                                                   \
-  do {                                                                                                         \
-    if (pre) hipLaunchKernelGGL((spmm_row16_kernel<C4, true, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);      \
-    else hipLaunchKernelGGL((spmm_row16_kernel<C4, false, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);         \
-  } while (0)
-    if (C == 4) MGP_ROW16_LAUNCH(1);
-    else if (C == 8) MGP_ROW16_LAUNCH(2);
-    else if (C == 12) MGP_ROW16_LAUNCH(3);
-    else MGP_ROW16_LAUNCH(4);
-#undef MGP_ROW16_LAUNCH
-  } else if (tl_knobs.v4 && C > 16 && C <= 256 && (C & 3) == 0 &&
-             // measured (tools/lab/time_spmm_wide.py): 33 vs 59 us at C = 32 and 54 vs 63 us at C = 64 on the 60k graph, but
-             // 101 vs 91 us at C = 128 (the X block no longer sits in L2 and the per-column kernel's whole-line pieces use
-             // the Infinity Cache path better); on the 1M graph, when the dictionaries are not there, it wins at every width
-             (tl_knobs.v4 == 2 || C <= 64 || (size_t)L->n * (size_t)C * sizeof(float) >= ((size_t)96 << 20)) &&
-             ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(base) |
-               reinterpret_cast<uintptr_t>(dotw) | reinterpret_cast<uintptr_t>(L->col) | reinterpret_cast<uintptr_t>(L->vals)) & 15) == 0 &&
-             (L->tile_max_entries & 3) == 0 && L->lid != nullptr) {
-    // (quad-padded rows are what the tile builder guarantees: the CSR of a graph without dictionaries keeps the
-    // per-column kernel below)
-    Plan pl = make_plan(L->n, spmm_rows_per_pass(C));        // the same row ranges / dot-partial blocks as spmm_kernel
-    p.rows_per_block = pl.rows_per_block;
-#define MGP_V4_LAUNCH(LPR)                                                                          \
-  do {                                                                                              \
-    if (pre) hipLaunchKernelGGL((spmm_v4_kernel<LPR, true, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p);  \
-    else hipLaunchKernelGGL((spmm_v4_kernel<LPR, false, CB>), dim3(pl.grid), dim3(kBlock), 0, st, p); \
-  } while (0)
-    if (C <= 32) MGP_V4_LAUNCH(8);
-    else if (C <= 64) MGP_V4_LAUNCH(16);
-    else if (C <= 128) MGP_V4_LAUNCH(32);
-    else MGP_V4_LAUNCH(64);
-#undef MGP_V4_LAUNCH
-  } else {
-    const int G = spmm_cols_group(C);
-    const int nacc = (int)mgp_cdiv(C, G);
-    Plan pl = make_plan(L->n, spmm_rows_per_pass(C));
-    p.rows_per_block = pl.rows_per_block;
-#define MGP_SPMM_LAUNCH(GG, NA)                                    \
-  do {                                                             \
-    if (pre) launch_spmm<GG, NA, true, CB>(p, pl.grid, st);        \
-    else launch_spmm<GG, NA, false, CB>(p, pl.grid, st);           \
-  } while (0)
-    if (G == 4) MGP_SPMM_LAUNCH(4, 1);
-    else if (G == 8) MGP_SPMM_LAUNCH(8, 1);
-    else if (G == 16) MGP_SPMM_LAUNCH(16, 1);
-    else if (G == 32) MGP_SPMM_LAUNCH(32, 1);
-    else if (nacc == 1) MGP_SPMM_LAUNCH(64, 1);
-    else if (nacc == 2) MGP_SPMM_LAUNCH(64, 2);
-    else MGP_SPMM_LAUNCH(64, 4);
-#undef MGP_SPMM_LAUNCH
+  } break;
+  case SpmmFamily::Gather:
+    // the member by alignment (see spmm_plan, rule 7): same row ranges, same dot-partial blocks
+    if (C <= 16 && (C & 3) == 0 && aligned16(p.X, p.Y)) {
+      with_quads(C, [&](auto c4) { with_pre(pre, [&](auto P) {
+        hipLaunchKernelGGL((spmm_row16_kernel<decltype(c4)::value, decltype(P)::value, CB>), dim3(grid), dim3(kBlock), 0, st, p);
+      }); });
+    } else if (pl.v4_ok && aligned16(p.X, p.Y, p.base, p.dotw) && aligned16(L->col, L->vals)) {
+      auto v4 = [&](auto lpr) { with_pre(pre, [&](auto P) {
+        hipLaunchKernelGGL((spmm_v4_kernel<decltype(lpr)::value, decltype(P)::value, CB>), dim3(grid), dim3(kBlock), 0, st, p);
+      }); };
+      if (C <= 32) v4(IntC<8>{});
+      else if (C <= 64) v4(IntC<16>{});
+      else if (C <= 128) v4(IntC<32>{});
+      else v4(IntC<64>{});
+    } else {
+      const int G = spmm_cols_group(C);
+      const int nacc = (int)mgp_cdiv(C, G);
+      auto cols = [&](auto g, auto na) { with_pre(pre, [&](auto P) {
+        hipLaunchKernelGGL((spmm_kernel<decltype(g)::value, decltype(na)::value, decltype(P)::value, CB>), dim3(grid), dim3(kBlock), 0, st, p);
+      }); };
+      if (G == 4) cols(IntC<4>{}, IntC<1>{});
+      else if (G == 8) cols(IntC<8>{}, IntC<1>{});
+      else if (G == 16) cols(IntC<16>{}, IntC<1>{});
+      else if (G == 32) cols(IntC<32>{}, IntC<1>{});
+      else if (nacc == 1) cols(IntC<64>{}, IntC<1>{});
+      else if (nacc == 2) cols(IntC<64>{}, IntC<2>{});
+      else cols(IntC<64>{}, IntC<4>{});
+    }
+    break;
   }
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }
 }  // namespace
 
-int mgp_spmm_fused_first(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                         const float* pre, const float* post, const float* base, float cb, float co,
-                         const float* dotw, float* dot_partials, const int* skip, int* tick,
-                         const MgpFirst* first, void* stream) {
-  return mgp_spmm_fused_cbv(L, row_offset, X, C, Y, a, b, pre, post, base, cb, nullptr, co, dotw, dot_partials, skip, tick,
-                            first, stream);
-}
-
-int mgp_spmm_fused_cbv(const mgp_csr_t* L, int64_t row_offset, const float* X, int C, float* Y, float a, float b,
-                       const float* pre, const float* post, const float* base, float cb, const float* cbv, float co,
-                       const float* dotw, float* dot_partials, const int* skip, int* tick, const MgpFirst* first,
-                       void* stream) {
+int mgp_spmm_fused_opts(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b, const float* pre,
+                        const float* post, const float* base, float cb, float co, const float* dotw, float* dot_partials,
+                        const MgpSpmmOpts& o, void* stream) {
   if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !X || !Y) return MGP_ERR_ARG;
   if (L->n <= 0 || C <= 0 || C > 256) return C > 256 ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
   if (X == Y) return MGP_ERR_ARG;  // rows gather other rows of X: never in place
-  knobs_snap();
-  hipStream_t st = mgp_stream(stream);
+  const SpmmPlan pl = spmm_plan(L, C, o.row_offset, dotw && dot_partials);
+  if (pl.err != MGP_OK) return pl.err;
   SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, X, Y, C, a, b, pre, post, base, cb, co,
-             dotw, dotw ? dot_partials : nullptr, 0, skip, tick, row_offset, nullptr, nullptr, 0, cbv};
+             dotw, dotw ? dot_partials : nullptr, 0, o.skip, o.tick, o.row_offset, nullptr, nullptr, 0, o.cbv};
 #ifdef MGP_STAMP
   p.stamp_on = g_stamp_enable;
 #endif
-  if (first) {
-    if (!use_tiles(L, C)) return MGP_ERR_UNSUPPORTED;
-    p.copy_x = first->copy_x;
-    p.dot2_partials = (dotw && dot_partials) ? first->dot2_partials : nullptr;
-    p.tick_reset = first->tick_reset;
+  if (o.first) {
+    if (pl.family != SpmmFamily::TileC1) return MGP_ERR_UNSUPPORTED;
+    p.copy_x = o.first->copy_x;
+    p.dot2_partials = (dotw && dot_partials) ? o.first->dot2_partials : nullptr;
+    p.tick_reset = o.first->tick_reset;
   }
-  return cbv ? spmm_launch<true>(L, row_offset, X, C, Y, pre, base, dotw, dot_partials, first, p, st)
-             : spmm_launch<false>(L, row_offset, X, C, Y, pre, base, dotw, dot_partials, first, p, st);
+  void* record_to = o.first ? o.first->record : nullptr;
+  hipStream_t st = mgp_stream(stream);
+  return o.cbv ? spmm_launch<true>(pl, L, record_to, p, st) : spmm_launch<false>(pl, L, record_to, p, st);
+}
+
+extern "C" int mgp_spmm_fused(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,
+                              const float* pre, const float* post, const float* base, float cb,
+                              float co, const float* dotw, float* dot_partials, void* stream) {
+  return mgp_spmm_fused_opts(L, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, MgpSpmmOpts{}, stream);
 }
 
 // elementwise y = s[i] * x[i,:]
@@ -2140,8 +2122,7 @@ extern "C" int mgp_spmm_fused_rows(const mgp_csr_t* L_local, int64_t row_offset,
                                    float a, float b, const float* pre, const float* post, const float* base,
                                    float cb, float co, const float* dotw, float* dot_partials, void* stream) {
   if (row_offset < 0) return MGP_ERR_ARG;
-  return mgp_spmm_fused_part(L_local, row_offset, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, nullptr,
-                             nullptr, stream);
+  return mgp_spmm_fused_opts(L_local, X, C, Y, a, b, pre, post, base, cb, co, dotw, dot_partials, MgpSpmmOpts{row_offset}, stream);
 }
 
 // Measurement helper (bench.py / tools): `reps` back-to-back launches of Y = L X enqueued from C as ONE
@@ -2188,8 +2169,7 @@ extern "C" int mgp_spmm_repeat(const mgp_csr_t* L, const float* X, int C, float*
   if (ok) {
     int rc = MGP_OK;
     for (int i = 0; i < reps && rc == MGP_OK; ++i)
-      rc = mgp_spmm_fused_ex(L, X, C, Y, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, nullptr,
-                             nullptr, cap);
+      rc = mgp_spmm_fused(L, X, C, Y, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, cap);
     ok = hipStreamEndCapture(cap, &graph) == hipSuccess && rc == MGP_OK && graph != nullptr;
     if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
   }
@@ -2201,8 +2181,7 @@ extern "C" int mgp_spmm_repeat(const mgp_csr_t* L, const float* X, int C, float*
     rc = (int)hipGraphLaunch(exec, mgp_stream(stream));
   } else {
     for (int i = 0; i < reps && rc == MGP_OK; ++i)
-      rc = mgp_spmm_fused_ex(L, X, C, Y, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, nullptr,
-                             nullptr, stream);
+      rc = mgp_spmm_fused(L, X, C, Y, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, stream);
   }
   if (elapsed_ms) {
     (void)hipEventRecord(e1, mgp_stream(stream));

@@ -176,7 +176,8 @@ class KnnGraph:
     def csr_with(self, vals, diag, tile_vals=None, mt=None):
         """mgp_csr_t over this graph's structure with the given entry values / diagonal (tile_vals: the
         values in tile order when the tiles follow a row order, see tile_values)."""
-        return _lib.csr_struct(self.n, self.rowptr, self.col, vals, diag, tiles=self.tiles, tile_vals=tile_vals, mt=mt)
+        return _lib.csr_struct(self.n, self.rowptr, self.col, vals, diag, tiles=self.tiles, tile_vals=tile_vals, mt=mt,
+                               lanes=self.spmv_lanes)
 
     def tile_values(self, vals):
         """`vals` gathered into tile order (None when the tiles are in row order)."""
@@ -353,7 +354,8 @@ class RelabelledData:
         """wide: the caller is about to multiply 48 columns or more -- build the matrix-core tile image if there is none
         yet (once built it rides in every struct)."""
         g = self.graph
-        return _lib.csr_struct(g.n, g.rowptr, g.col, self.vals, self.diag, tiles=g.tiles, mt=self.mt_plan(wide))
+        return _lib.csr_struct(g.n, g.rowptr, g.col, self.vals, self.diag, tiles=g.tiles, mt=self.mt_plan(wide),
+                               lanes=g.spmv_lanes)
 
     def mt_plan(self, build=True):
         """MtPlan of this CSR (built at the first call with build=True; None when it does not pay)."""

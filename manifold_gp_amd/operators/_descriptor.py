@@ -56,8 +56,6 @@ class Descriptor:
 
     def struct(self, wide=False):
         d = self.data
-        g = d.graph
-        check(lib().mgp_spmm_set_group_hint(g.spmv_lanes), "mgp_spmm_set_group_hint")
         op = OperatorT()
         op.L = d.csr(wide) if wide else d.csr()
         op.pre = self.pre.data_ptr() if self.pre is not None else None

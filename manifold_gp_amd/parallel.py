@@ -104,8 +104,9 @@ def local_operator_struct(desc, part, rank):
     """mgp_operator_t for the local rows of a Descriptor built on the padded graph."""
     loc = local_csr(desc.data, part, rank)
     op = desc.struct()
+    # (the padded graph's lanes: a slice and the full matrix must sum a row in the same order)
     op.L = _lib.csr_struct(loc["n_loc"], loc["rowptr"], loc["col"], loc["vals"], loc["diag"], loc["ncols"],
-                           tiles=loc["tiles"])
+                           tiles=loc["tiles"], lanes=desc.data.graph.spmv_lanes)
     return op, loc
 
 
@@ -266,7 +267,8 @@ class PartitionedOperator:
             # launch s produces its output on own rows + (nu - 1 - s) ghost layers
             self.launch_rows = [min(g.n, -(-sizes[nu - 1 - s] // tr) * tr) for s in range(nu)]
         self.op = desc.struct()
-        self.op.L = _lib.csr_struct(g.n, g.rowptr, g.col, d.vals, d.diag, tiles=self.tiles, tile_vals=self.vals_t)
+        self.op.L = _lib.csr_struct(g.n, g.rowptr, g.col, d.vals, d.diag, tiles=self.tiles, tile_vals=self.vals_t,
+                                    lanes=g.spmv_lanes)
         self.ghost_rows = sum(int(gl.numel()) for gl in self.ghosts)
 
 

@@ -63,7 +63,7 @@ def gmrf_noise(data, S, seed, offset=0, node_coef=1.0, tag=0, edges=False):
     if tag not in NODE_TAGS:
         raise ValueError("tag must be one of %s (tag 1 is the edge stream), got %r" % (NODE_TAGS, tag))
     g = data.graph
-    csr = _lib.csr_struct(g.n, g.rowptr, g.col, data.vals, data.diag)
+    csr = _lib.csr_struct(g.n, g.rowptr, g.col, data.vals, data.diag, lanes=g.spmv_lanes)
     Y = torch.empty(g.n, S, dtype=torch.float32, device=g.device)
     check(lib().mgp_gmrf_noise(ctypes.byref(csr), ptr(data.dsqrt), float(node_coef), int(tag), int(bool(edges)),
                                ctypes.c_uint64(seed), int(offset), S, ptr(Y), stream()), "mgp_gmrf_noise")

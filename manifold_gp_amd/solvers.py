@@ -535,7 +535,6 @@ def lanczos_smallest(lap_data, m, tol=1e-5, max_basis=0, degree=0, max_restarts=
     from that block instead of a random one (mgp_lanczos_smallest_warm).  keep_warm=True leaves this call's block there."""
     g = lap_data.graph
     dev = g.device
-    check(lib().mgp_spmm_set_group_hint(g.spmv_lanes), "mgp_spmm_set_group_hint")
     # A graph whose nodes arrive without locality carries tiles over a locality order (graph.build_tiles_auto).
     # The block iteration gathers an X row per entry: on the CSR as given those rows are scattered over a
     # block of n x b floats (HBM-bound, 4.3 ms per 84-column SpMM at N = 1M); on the SAME matrix relabelled

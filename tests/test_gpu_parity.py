@@ -312,6 +312,43 @@ def test_cg_plan_poisoned_after_timeout_leaks_instead_of_waiting(mgp, golden, de
     plan2.close()
 
 
+def test_eager_cg_plan_keeps_its_lane_width_across_another_graph(mgp, golden, dev):
+    """The lanes per row of the C == 1 row-group kernel travel with the matrix (mgp_csr_t.spmv_lanes), not with the process:
+    an eager plan on graph A (16 lanes) launches the kernel and grid it sized its dot partials for also after a product on
+    graph B (8 lanes) in between.  Neither graph has tile dictionaries, so C == 1 takes the row-group kernel and nothing is
+    relabelled; form 0, so the plan runs plain CG on single-column products."""
+    import ctypes
+    from manifold_gp_amd import _lib
+    from manifold_gp_amd.graph import KnnGraph
+    from manifold_gp_amd.solvers import CgPlan
+    g = golden("dumbbell_k10_loop")
+    n = g["train_x"].shape[0]
+    idx, val = T(g["edge_index"].astype(np.int64), dev), T(g["edge_value"], dev)
+    eps = torch.tensor([[float(g["eps"])]], device=dev)
+    kappa = torch.tensor([[float(g["kappa"])]], device=dev)
+
+    def precision(graph):
+        lap = mgp.operators.GraphLaplacianOperator(val, idx, n, eps, "symmetric", bool(g["self_loops"]), graph=graph)
+        return mgp.operators.PrecisionMaternOperator(lap, 2, kappa)
+
+    ga, gb = KnnGraph.from_coo(idx, val, n, tiles=None), KnnGraph.from_coo(idx, val, n, tiles=None)
+    assert gb.spmv_lanes == 8
+    ga.spmv_lanes = 16                        # before A's LaplacianData exists (as parallel.pad_graph overrides it)
+    Qa, Qb = precision(ga), precision(gb)
+    y = T(g["train_y"], dev).view(-1, 1).contiguous()
+    lib = _lib.lib()
+    plan = CgPlan(Qa._descriptor(), 1, tol=1e-6, stop_mode=1, max_iter=5000, use_graph=False)
+    assert plan.op.L.spmv_lanes == 16 and lib.mgp_spmm_kernel_choice(ctypes.byref(plan.op.L), 1, 1, 0) == 0
+    nb = lib.mgp_spmm_dot_blocks_csr(ctypes.byref(plan.op.L), 1)
+    x1, its1, res1 = plan.solve(y).clone(), plan.iters, plan.resid
+    assert plan.status == 1
+    Qb._descriptor().apply(y)                 # a single-column product on the 8-lane graph
+    x2, its2, res2 = plan.solve(y).clone(), plan.iters, plan.resid
+    assert lib.mgp_spmm_dot_blocks_csr(ctypes.byref(plan.op.L), 1) == nb
+    assert torch.equal(x1, x2) and its1 == its2 and res1 == res2, (its1, its2, res1, res2)
+    plan.close()
+
+
 def test_cg_linear_cg_stopping_rule(mgp, golden, dev):
     """stop_mode 0 restates linear_cg: >= 10 iterations, mean relative residual < tol."""
     from oracle.laplacian import LaplacianOracle
@@ -1336,6 +1373,7 @@ def test_tile_dictionary_spmv(mgp, golden, dev, name, rows):
     pre = torch.rand(n, device=dev) + 0.5
     base = torch.randn(n, 1, device=dev)
     outs = {}
+    lib.mgp_spmm_set_group_hint(graph.spmv_lanes)     # mgp_spmm_dot_blocks (no CSR) counts with the process default: like with like
     try:
         for mode in (0, 1):
             lib.mgp_spmm_set_tile_mode(mode)

@@ -43,9 +43,9 @@ def test_struct_layouts_match_c_abi(tmp_path):
 #include <stddef.h>
 #include "mgp_hip.h"
 int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mgp_csr_t), sizeof(mgp_operator_t), sizeof(mgp_cg_params_t),
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mgp_csr_t), sizeof(mgp_operator_t), sizeof(mgp_cg_params_t),
          sizeof(mgp_lanczos_params_t), offsetof(mgp_operator_t, pre), offsetof(mgp_operator_t, nu), offsetof(mgp_csr_t, mt_sptr),
-         offsetof(mgp_csr_t, mt_tiles), offsetof(mgp_csr_t, mt_steps));
+         offsetof(mgp_csr_t, mt_tiles), offsetof(mgp_csr_t, mt_steps), offsetof(mgp_csr_t, spmv_lanes));
   return 0;
 }
 """)
@@ -54,7 +54,7 @@ int main(void) {
     c = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
     assert c == [ctypes.sizeof(_lib.CsrT), ctypes.sizeof(_lib.OperatorT), ctypes.sizeof(_lib.CgParamsT),
                  ctypes.sizeof(_lib.LanczosParamsT), _lib.OperatorT.pre.offset, _lib.OperatorT.nu.offset, _lib.CsrT.mt_sptr.offset,
-                 _lib.CsrT.mt_tiles.offset, _lib.CsrT.mt_steps.offset], c
+                 _lib.CsrT.mt_tiles.offset, _lib.CsrT.mt_steps.offset, _lib.CsrT.spmv_lanes.offset], c
     assert ctypes.sizeof(_lib.CsrT) == 144 and ctypes.sizeof(_lib.CgParamsT) == 28 and ctypes.sizeof(_lib.LanczosParamsT) == 24
 
 
@@ -72,6 +72,20 @@ def test_argument_errors_without_gpu():
     assert lib.mgp_cg_plan_destroy(None) == -1
     with pytest.raises(_lib.MgpError):
         _lib.check(-2, "x")
+    # mgp_csr_t.spmv_lanes (lanes per row of the C == 1 row-group kernel, 0 = the process default): validated before any device
+    # use, and it -- not the process default -- decides the grid of a struct that sets it (both counts are host arithmetic)
+    L = _lib.CsrT()
+    L.n, L.spmv_lanes = 8, 3
+    assert lib.mgp_spmm_dot_blocks_csr(ctypes.byref(L), 1) == -1
+    assert lib.mgp_spmm_kernel_choice(ctypes.byref(L), 1, 0, 0) == -1
+    n = 4 * 256                                  # four workgroups of 256 threads at one lane per row: the two grids differ
+    L.n, L.spmv_lanes = n, 8
+    assert lib.mgp_spmm_set_group_hint(8) == 0
+    nb8 = lib.mgp_spmm_dot_blocks_csr(ctypes.byref(L), 1)
+    assert nb8 > 0 and nb8 == lib.mgp_spmm_dot_blocks(n, 1)
+    assert lib.mgp_spmm_set_group_hint(64) == 0
+    assert lib.mgp_spmm_dot_blocks_csr(ctypes.byref(L), 1) == nb8 != lib.mgp_spmm_dot_blocks(n, 1)
+    assert lib.mgp_spmm_set_group_hint(8) == 0
 
 
 def test_knn_workspace_sizing_follows_the_filter_switch():
