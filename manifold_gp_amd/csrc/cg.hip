@@ -29,6 +29,7 @@
 #include <atomic>
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "cg_rule.h"
 
 namespace {
 
@@ -182,6 +183,41 @@ __global__ __launch_bounds__(kBlock) void cg_reduce_kernel(CgArgs a) {
   if (tid < 4 && c < a.C) a.tot[(int64_t)k * a.C + c] = (sh[0][tid] + sh[1][tid]) + (sh[2][tid] + sh[3][tid]);
 }
 
+// ---- One step of the multi-column update kernels (cg_update_kernel, cg_update_q_kernel), from "thread c < C holds the totals
+// of column c" to "sh_alpha / sh_beta hold this step's coefficients": the rule of cg_rule.h per column, gamma_old / alpha_old /
+// bb / resid written by workgroup 0, the block's stopping decision taken by thread 0 and published.  Returns true, in every
+// thread, when the solve has ended.  `go` / `ao` are the previous step's gamma / alpha (the caller selects the parity);
+// `lab`: MGP_LAB_UPD builds never converge and hold the vectors still (alpha = beta = 0); max_iter still ends them.
+__device__ __forceinline__ bool cg_columns_step(const CgArgs& a, int it, float gamma, float rr, float delta, float go, float ao,
+                                                float bb_old, bool lab, float* sh_alpha, float* sh_beta, float* sh_rel,
+                                                int* sh_done) {
+  const int tid = threadIdx.x, C = a.C, par = it & 1;
+  if (tid < C) {
+    const float bb = (it == 1) ? rr : bb_old;
+    const float rel = cg_rel(rr, bb);
+    sh_rel[tid] = rel;
+    CgCoef k = cg_coef(it == 1, cg_frozen(a.stop_mode, a.tol, rel), gamma, delta, go, ao);
+    if (lab) { k.alpha = 0.f; k.beta = 0.f; }
+    sh_alpha[tid] = k.alpha;
+    sh_beta[tid] = k.beta;
+    if (blockIdx.x == 0) {
+      a.gamma_old[par * C + tid] = gamma;
+      a.alpha_old[par * C + tid] = k.alpha;
+      if (it == 1) a.bb[tid] = bb;
+      a.resid[tid] = rel;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const CgStop st = lab ? cg_stop_rest(0, true, a.max_iter, it)
+                          : cg_stop_columns(a.stop_mode, a.min_iter, a.max_iter, a.tol, it, sh_rel, C);
+    *sh_done = st.done;
+    if (st.done && blockIdx.x == 0) cg_publish(a.state, a.host_state, a.host_resid, sh_rel, C, it, st.status);
+  }
+  __syncthreads();
+  return *sh_done != 0;
+}
+
 __global__ __launch_bounds__(kBlock) void cg_update_kernel(CgArgs a) {
   __shared__ float sh[3][kBlock];
   __shared__ float sh_alpha[kMaxC], sh_beta[kMaxC], sh_rel[kMaxC];
@@ -315,62 +351,10 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(CgArgs a) {
   const float g = prev ? g2[1] : g2[0], rr = prev ? rr2[1] : rr2[0];
   sh[0][tid] = g; sh[1][tid] = rr; sh[2][tid] = d;
   reduce_slices<3>(sh, a.TC, a.TS, sl, cc);
-  if (tid < C) {
-    const float gamma = sh[0][tid], rr2 = sh[1][tid], delta = sh[2][tid];
-    const float bb = (it == 1) ? rr2 : bb_old;
-    const float rel = (bb > 0.f) ? sqrtf(rr2 / bb) : 0.f;
-    sh_rel[tid] = rel;
-    const bool frozen = (a.stop_mode == 0) ? (rel < 1e-10f) : (rel <= a.tol);
-    float alpha = 0.f, beta = 0.f;
-    if (!frozen) {
-      if (it == 1) {
-        alpha = (delta != 0.f) ? gamma / delta : 0.f;
-      } else {
-        const float go = prev ? go2[1] : go2[0], ao = prev ? ao2[1] : ao2[0];
-        beta = (go != 0.f) ? gamma / go : 0.f;
-        const float den = delta - ((ao != 0.f) ? beta * gamma / ao : 0.f);
-        alpha = (den != 0.f) ? gamma / den : 0.f;
-      }
-      if (!isfinite(alpha) || !isfinite(beta)) { alpha = 0.f; beta = 0.f; }
-    }
-    if (MGP_LAB_UPD) { alpha = 0.f; beta = 0.f; }
-    sh_alpha[tid] = alpha;
-    sh_beta[tid] = beta;
-    if (blockIdx.x == 0) {
-      a.gamma_old[par * C + tid] = gamma;
-      a.alpha_old[par * C + tid] = alpha;
-      if (it == 1) a.bb[tid] = bb;
-      a.resid[tid] = rel;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int done = 0, status = 0;
-    if (a.stop_mode == 0) {
-      float m = 0.f;
-      for (int c = 0; c < C; ++c) m += sh_rel[c];
-      m /= (float)C;
-      if (it > a.min_iter && m < a.tol) { done = 1; status = 1; }   // >= min_iter iterations done
-    } else {
-      int all = 1;
-      for (int c = 0; c < C; ++c) all &= (sh_rel[c] <= a.tol) ? 1 : 0;
-      if (all) { done = 1; status = 1; }
-    }
-    for (int c = 0; c < C; ++c) if (!isfinite(sh_rel[c])) { done = 1; status = 3; }
-    if (MGP_LAB_UPD) { done = 0; status = 0; }
-    if (!done && it > a.max_iter) { done = 1; status = 2; }
-    sh_done = done;
-    if (done && blockIdx.x == 0) {
-      a.state[2] = status; a.state[1] = 1;
-      // zero-copy results for the host: no blit kernels behind the solve
-      for (int c = 0; c < C; ++c) a.host_resid[c] = sh_rel[c];
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
-    }
-  }
-  __syncthreads();
-  if (sh_done) return;
+  float gamma = 0.f, rrn = 0.f, delta = 0.f;
+  if (tid < C) { gamma = sh[0][tid]; rrn = sh[1][tid]; delta = sh[2][tid]; }
+  if (cg_columns_step(a, it, gamma, rrn, delta, prev ? go2[1] : go2[0], prev ? ao2[1] : ao2[0], bb_old, MGP_LAB_UPD != 0,
+                      sh_alpha, sh_beta, sh_rel, &sh_done)) return;
 
   // ---- fused vector update over this workgroup's contiguous rows
   float ng = 0.f, nrr = 0.f;
@@ -503,59 +487,8 @@ __global__ __launch_bounds__(BLOCK) void cg_update_q_kernel(CgArgs a) {
   if (sh_state[1]) return;
   const int it = sh_state[0];
   const int par = it & 1, prev = par ^ 1;
-  if (tid < C) {
-    const float gamma = tg, rrn = trr, delta = td;
-    const float bb = (it == 1) ? rrn : bb_old;
-    const float rel = (bb > 0.f) ? sqrtf(rrn / bb) : 0.f;
-    sh_rel[tid] = rel;
-    const bool frozen = (a.stop_mode == 0) ? (rel < 1e-10f) : (rel <= a.tol);
-    float alpha = 0.f, beta = 0.f;
-    if (!frozen) {
-      if (it == 1) {
-        alpha = (delta != 0.f) ? gamma / delta : 0.f;
-      } else {
-        const float go = prev ? go2[1] : go2[0], ao = prev ? ao2[1] : ao2[0];
-        beta = (go != 0.f) ? gamma / go : 0.f;
-        const float den = delta - ((ao != 0.f) ? beta * gamma / ao : 0.f);
-        alpha = (den != 0.f) ? gamma / den : 0.f;
-      }
-      if (!isfinite(alpha) || !isfinite(beta)) { alpha = 0.f; beta = 0.f; }
-    }
-    sh_alpha[tid] = alpha;
-    sh_beta[tid] = beta;
-    if (blockIdx.x == 0) {
-      a.gamma_old[par * C + tid] = gamma;
-      a.alpha_old[par * C + tid] = alpha;
-      if (it == 1) a.bb[tid] = bb;
-      a.resid[tid] = rel;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int done = 0, status = 0;
-    if (a.stop_mode == 0) {
-      float m = 0.f;
-      for (int c = 0; c < C; ++c) m += sh_rel[c];
-      m /= (float)C;
-      if (it > a.min_iter && m < a.tol) { done = 1; status = 1; }   // >= min_iter iterations done
-    } else {
-      int all = 1;
-      for (int c = 0; c < C; ++c) all &= (sh_rel[c] <= a.tol) ? 1 : 0;
-      if (all) { done = 1; status = 1; }
-    }
-    for (int c = 0; c < C; ++c) if (!isfinite(sh_rel[c])) { done = 1; status = 3; }
-    if (!done && it > a.max_iter) { done = 1; status = 2; }
-    sh_done = done;
-    if (done && blockIdx.x == 0) {
-      a.state[2] = status; a.state[1] = 1;
-      for (int c = 0; c < C; ++c) a.host_resid[c] = sh_rel[c];
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
-    }
-  }
-  __syncthreads();
-  if (sh_done) return;
+  if (cg_columns_step(a, it, tg, trr, td, prev ? go2[1] : go2[0], prev ? ao2[1] : ao2[0], bb_old, false,
+                      sh_alpha, sh_beta, sh_rel, &sh_done)) return;
 
   // ---- fused vector update: U row passes per batch, every load of a batch in flight before the first use
   mgp_cg_v4f ng = z4, nrr = z4;
@@ -636,8 +569,8 @@ constexpr int kC1GammaSlots = 2;    // nbv <= kMaxGridVec = 2 * 256
 constexpr int kC1DeltaSlots = 16;   // nbs <= 4096
 
 // DECIDE (the LAST update of a plan's first graph): the workgroup whose partials arrive last also takes the stopping decision
-// of the NEXT step -- ||r_k||^2 summed over the partials this very launch wrote, in cg_decide_c1_kernel's order, the same rule,
-// the same flags -- and leaves the end-of-graph mark.  The single-workgroup decision launch + the marker launch (4.5 + 4.0 us
+// of the NEXT step -- ||r_k||^2 summed over the partials this very launch wrote, in cg_decide_c1_kernel's order, decided by
+// cg_rule.h -- and leaves the end-of-graph mark.  The single-workgroup decision launch + the marker launch (4.5 + 4.0 us
 // and two kernel boundaries of a ~57 us solve at N = 60k) go away.  Hand-off inside the launch: lane 0 of every workgroup
 // stores its ||r||^2 partial write-through (sc1), drains its stores (s_waitcnt vmcnt(0)), makes one returning agent-scope
 // atomic add on its group's arrival counter (CgArgs::arrive); the lane that completes the count joins the workgroup barrier, then all lanes of that workgroup
@@ -740,26 +673,12 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
   const bool fresh = a.pd_bb != nullptr && it == 1;       // init-free solve, first update: r = b, p = s = x = 0
   const float gamma = fresh ? t[5] : (prev ? t[1] : t[0]), rr2 = fresh ? t[5] : (prev ? t[3] : t[2]), delta = t[4];
   const float bb = (it == 1) ? rr2 : bb_old;
-  const float rel = (bb > 0.f) ? sqrtf(rr2 / bb) : 0.f;
-  const bool frozen = (a.stop_mode == 0) ? (rel < 1e-10f) : (rel <= a.tol);
-  float alpha = 0.f, beta = 0.f;
-  if (!frozen) {
-    if (it == 1) {
-      alpha = (delta != 0.f) ? gamma / delta : 0.f;
-    } else {
-      const float go = prev ? go1 : go0, ao = prev ? ao1 : ao0;
-      beta = (go != 0.f) ? gamma / go : 0.f;
-      const float den = delta - ((ao != 0.f) ? beta * gamma / ao : 0.f);
-      alpha = (den != 0.f) ? gamma / den : 0.f;
-    }
-    if (!isfinite(alpha) || !isfinite(beta)) { alpha = 0.f; beta = 0.f; }
-  }
-  int done = 0, status = 0;
-  if (a.stop_mode == 0) {
-    if (it > a.min_iter && rel < a.tol) { done = 1; status = 1; }
-  } else if (rel <= a.tol) { done = 1; status = 1; }
-  if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it > a.max_iter) { done = 1; status = 2; }
+  // the rule of cg_rule.h, derived redundantly by every lane
+  const float rel = cg_rel(rr2, bb);
+  const CgCoef k = cg_coef(it == 1, cg_frozen(a.stop_mode, a.tol, rel), gamma, delta, prev ? go1 : go0, prev ? ao1 : ao0);
+  const float alpha = k.alpha, beta = k.beta;
+  const CgStop st = cg_stop(a.stop_mode, a.min_iter, a.max_iter, a.tol, it, rel);
+  const int done = st.done;
   if (blockIdx.x == 0 && tid == 0) {
     a.gamma_old[par] = gamma;
     a.alpha_old[par] = alpha;
@@ -767,13 +686,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
     // DECIDE and not done: the last arriver of this launch writes the residual of step it + 1 to the same word, possibly
     // through another XCD's L2 -- one writer per launch, so that the device value is defined
     if (!DECIDE || done) a.resid[0] = rel;
-    if (done) {
-      a.state[2] = status; a.state[1] = 1;
-      a.host_resid[0] = rel;
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
-    }
+    if (done) cg_publish(a.state, a.host_state, a.host_resid, &rel, 1, it, st.status);
   }
   if (done) {
     // an init-free solve that ends before its first update (b = 0): nobody has zeroed x
@@ -860,7 +773,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
   if (!DECIDE) return;
   __syncthreads();
   if (!sh_last) return;
-  // ---- the last arriver: stopping decision of step it + 1 (cg_decide_c1_kernel, same sums in the same order)
+  // ---- the last arriver: stopping decision of step it + 1 (cg_rule.h; the sums in cg_decide_c1_kernel's order)
   {
     const int itn = it + 1;
     float t2 = 0.f;
@@ -877,13 +790,8 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
     __syncthreads();
     if (tid != 0) return;
     const float rr2n = (sh_o[0][0] + sh_o[1][0]) + (sh_o[2][0] + sh_o[3][0]);
-    const float reln = (bb > 0.f) ? sqrtf(rr2n / bb) : 0.f;
-    int dn = 0, stn = 0;
-    if (a.stop_mode == 0) {
-      if (itn > a.min_iter && reln < a.tol) { dn = 1; stn = 1; }
-    } else if (reln <= a.tol) { dn = 1; stn = 1; }
-    if (!isfinite(reln)) { dn = 1; stn = 3; }
-    if (!dn && itn > a.max_iter) { dn = 1; stn = 2; }
+    const float reln = cg_rel(rr2n, bb);
+    const CgStop stn = cg_stop(a.stop_mode, a.min_iter, a.max_iter, a.tol, itn, reln);
     // The host reads nothing but host-mapped words (the solution stays in stream order).  The decision travels as ONE
     // naturally aligned 8-byte record {residual bits, step << 8 | status << 4 | 3} at host_state[8..9], written by one store
     // instruction (one PCIe write, observed whole by the host's 8-byte read): no drain between "the details" and "the
@@ -893,10 +801,10 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
     const int c = a.state[5] + 1;
     a.state[5] = c;
     a.resid[0] = reln;                        // the only writer of this word in a deciding launch that goes on (see above)
-    if (dn) {
-      a.state[2] = stn; a.state[1] = 1;
+    if (stn.done) {
+      a.state[2] = stn.status; a.state[1] = 1;
       const unsigned long long rec = (unsigned long long)__builtin_bit_cast(unsigned, reln) |
-                                     ((unsigned long long)(unsigned)((itn << 8) | (stn << 4) | 3) << 32);
+                                     ((unsigned long long)(unsigned)((itn << 8) | (stn.status << 4) | 3) << 32);
       __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.host_state + 8), rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     __hip_atomic_store(a.host_state + 4, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);       // end-of-graph mark
@@ -907,7 +815,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
 // apply k+1 has already run for nothing: at 3 iterations per solve that is 2 of 8 SpMVs + a launch, ~14 us of
 // ~76.  The first graph of a plan is captured for the step count the previous solves needed, so its last
 // (apply, update) pair -- the one that only detects -- is replaced by this single-workgroup launch: the same
-// partial sums in the same order, the same rule, the same flags as cg_update_c1_kernel would write at
+// partial sums in the same order, decided and published through cg_rule.h as cg_update_c1_kernel would at
 // it + 1.  Not converged: it writes nothing and the continuation graph carries on as before.
 __global__ __launch_bounds__(kBlock) void cg_decide_c1_kernel(CgArgs a) {
   __shared__ float sh_w[kBlock / 64];
@@ -935,21 +843,12 @@ __global__ __launch_bounds__(kBlock) void cg_decide_c1_kernel(CgArgs a) {
   if (tid != 0) return;
   const float rr2 = (sh_w[0] + sh_w[1]) + (sh_w[2] + sh_w[3]);
   const float bb = sc.bb;                   // it >= 2 here: written by the first update
-  const float rel = (bb > 0.f) ? sqrtf(rr2 / bb) : 0.f;
-  int done = 0, status = 0;
-  if (a.stop_mode == 0) {
-    if (it > a.min_iter && rel < a.tol) { done = 1; status = 1; }
-  } else if (rel <= a.tol) { done = 1; status = 1; }
-  if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it > a.max_iter) { done = 1; status = 2; }
-  if (!done) return;
+  const float rel = cg_rel(rr2, bb);
+  const CgStop st = cg_stop(a.stop_mode, a.min_iter, a.max_iter, a.tol, it, rel);
+  if (!st.done) return;
   a.resid[0] = rel;
-  a.state[2] = status; a.state[1] = 1;
-  a.host_resid[0] = rel;
-  a.host_state[0] = it; a.host_state[2] = status;
   a.host_state[3] = 1;                      // decided without running apply `it`
-  __threadfence_system();
-  a.host_state[1] = 1;
+  cg_publish(a.state, a.host_state, a.host_resid, &rel, 1, it, st.status);
 }
 
 // ---- End-of-graph marker.  The host reads the stopping flag alone while the first graph of a solve runs (a stream query
@@ -1104,7 +1003,7 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
   const float2 uBu = make_float2(t[3] - t[4], t[5] + t[6]);
   const float2 delta = make_float2(gamma.x - c.sigma * uBu.y, gamma.y + c.sigma * uBu.x);     // u . (u + i sigma B u)
   const float bb = (it == 1) ? rr2 : bb_old;
-  const float rel = (bb > 0.f) ? sqrtf(ee / bb) : 0.f;     // the real system's residual of x = Re z_{it-2}
+  const float rel = cg_rel(ee, bb);     // the real system's residual of x = Re z_{it-2}
   float2 alpha = make_float2(0.f, 0.f), beta = make_float2(0.f, 0.f);
   if (rel > a.tol) {
     if (it == 1) {
@@ -1120,22 +1019,15 @@ __global__ __launch_bounds__(kBlock) void cx_update_kernel(CgArgs a, CxArgs c) {
       alpha = make_float2(0.f, 0.f); beta = make_float2(0.f, 0.f);
     }
   }
-  int done = 0, status = 0;
-  if (rel <= a.tol) { done = 1; status = 1; }
-  if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it > a.max_iter + 1) { done = 1; status = 2; }   // (decided on e_{it-2}: x = Re z_{max_iter})
+  // stop_mode 1 only (plan_create_impl); max_iter + 1: decided on e_{it-2}, so that x = Re z_{max_iter}
+  const CgStop st = cg_stop(1, 0, a.max_iter + 1, a.tol, it, rel);
+  const int done = st.done;
   if (blockIdx.x == 0 && tid == 0) {
     c.sc[4 * par + 0] = gamma.x; c.sc[4 * par + 1] = gamma.y;
     c.sc[4 * par + 2] = alpha.x; c.sc[4 * par + 3] = alpha.y;
     if (it == 1) c.sc[8] = bb;
     a.resid[0] = rel;
-    if (done) {
-      a.state[2] = status; a.state[1] = 1;
-      a.host_resid[0] = rel;
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
-    }
+    if (done) cg_publish(a.state, a.host_state, a.host_resid, &rel, 1, it, st.status);
   }
   if (done) return;
   // ---- vector update over this workgroup's rows, four rows per lane in flight
@@ -1220,7 +1112,7 @@ __global__ void refine_finalize_kernel(const float* __restrict__ partial, int nb
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float rr = 0.f, bb = 0.f;
     for (int b = 0; b < nblk; ++b) { rr += partial[((int64_t)b * C + c) * 2]; bb += partial[((int64_t)b * C + c) * 2 + 1]; }
-    host_rel[c] = bb > 0.f ? sqrtf(rr / bb) : 0.f;
+    host_rel[c] = cg_rel(rr, bb);
   }
 }
 
@@ -1412,6 +1304,13 @@ std::atomic<int> g_cg_poll_spin{64};    // flag reads between two looks at the c
 std::atomic<int> g_cg_init_free{1};   // C == 1 plans start without a cg_init launch (mgp_cg_set_init_free(0): classic start)
 std::atomic<int> g_cg_decide_in_update{1};   // the first graph's last update decides + marks (mgp_cg_set_decide_in_update(0): separate launches)
 
+// The single-column kernel family (cg_update_c1_kernel, cg_decide_c1_kernel, cx_update_kernel) can run this plan: one column
+// whose partials fit the slots a lane of those kernels sums.  (One column on one device always does: the update grid is at most
+// kMaxGridVec and the SpMV grids at most 4096 workgroups; a row-partitioned plan has `world` times the SpMV partials.)
+bool c1_family(const CgArgs& a) {
+  return a.C == 1 && a.nbv <= kC1GammaSlots * kBlock && a.nbs <= kC1DeltaSlots * kBlock;
+}
+
 // one CG step = operator apply (w = A u, partials of u . w, ticks the iteration counter; skipped once
 // converged) followed by the fused update kernel, which also takes the stopping decision: every
 // graph therefore ends right behind a decision and a solve that needs k steps runs exactly k bodies.
@@ -1441,7 +1340,7 @@ int enqueue_body(CgPlan* pl, hipStream_t st, bool decide_last = false) {
   MGP_TRY(mgp_operator_apply_dist(&pl->op, pl->is_dist ? &pl->dist : nullptr, pl->args.u, pl->args.us, pl->C,
                                   pl->args.w, pl->args.u, pl->pd_delta, pl->nb_loc, pl->args.state + 1,
                                   pl->args.state, pl->op_work, pl->op_work_bytes, st));
-  if (pl->C == 1 && pl->args.nbv <= kC1GammaSlots * kBlock && pl->args.nbs <= kC1DeltaSlots * kBlock) {
+  if (c1_family(pl->args)) {
     launch_update_c1(pl, st, decide_last);
   } else {
     if (pl->args.tot) {
@@ -1473,8 +1372,7 @@ bool record_first(CgPlan* pl, int len, hipGraph_t* out) {
   if (hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
   int rc = MGP_OK;
   // `len` = steps until the stopping rule fires: the last of them only detects (see cg_decide_c1_kernel)
-  const bool decide = len >= 2 && !pl->is_dist && pl->C == 1 &&
-                      pl->args.nbv <= kC1GammaSlots * kBlock && pl->args.nbs <= kC1DeltaSlots * kBlock;
+  const bool decide = len >= 2 && !pl->is_dist && c1_family(pl->args);
   const int bodies = decide ? len - 1 : len;
   int done_bodies = 0;
   // decide: the graph's LAST update also takes the next step's decision and leaves the end-of-graph mark (g_cg_decide_in_update;
@@ -1740,7 +1638,7 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
     cx.pd4 = pl->pd4;
     const float cc = op->noise * op->scale;
     if (g_cg_complex_shift && !minv && op->form == 2 && op->nu == 2 && !op->pre && !op->post && cc > 0.f && ar.ok() &&
-        a.nbv <= kC1GammaSlots * kBlock && pl->prm.stop_mode == 1) {
+        c1_family(a) && pl->prm.stop_mode == 1) {
       pl->opB = mgp_operator_copy(op);
       pl->opB.nu = 1;
       pl->opB.kappa = op->kappa / sqrtf(2.0f);       // tau_B = 2 / kappa_B^2 = 2 nu / kappa^2
@@ -1759,8 +1657,8 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
   a.arrive = ar.take<int>(9 * 32);
   if (a.arrive) MGP_HIP_TRY(hipMemsetAsync(a.arrive, 0, 9 * 32 * sizeof(int), pl->stream));
   pl->init_free = false;
-  if (g_cg_init_free && C == 1 && !dist && !minv && !pl->cx && (op->form == 0 || op->form == 2) &&
-      mgp_tile_plan(&op->L) && a.nbv <= kC1GammaSlots * kBlock && a.nbs <= kC1DeltaSlots * kBlock) {
+  if (g_cg_init_free && c1_family(a) && !dist && !minv && !pl->cx && (op->form == 0 || op->form == 2) &&
+      mgp_tile_plan(&op->L)) {
     pl->init_free = true;
     a.pd_bb = pl->pd_bb;
   }

@@ -45,6 +45,7 @@
 #include <string.h>
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "cg_rule.h"
 
 namespace {
 
@@ -136,67 +137,73 @@ __global__ __launch_bounds__(kBlock) void pcg_start_kernel(PcgArgs a, const floa
   }
 }
 
-// one pipelined-CG vector update on this rank's rows (see the file header); takes the stopping decision on
-// ||r_i|| BEFORE updating, so that x is the iterate the decision was taken on
-__global__ __launch_bounds__(kBlock) void pcg_update_kernel(PcgArgs a) {
-  __shared__ float sh[kBlock / 64][2];
-  __shared__ float sh2[kBlock / 64][2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // everything another workgroup of THIS launch may rewrite is read through the parity: workgroup 0 stores
-  // gamma / alpha of iteration i in slot i & 1 while the others still read slot (i - 1) & 1; the iteration counter
-  // is ticked by the SpMV launch in front, never here; bb is written at i = 0 only and read from i = 1 on
-  __shared__ int sh_done;
+// ---- One step of the two partitioned update kernels (pcg_update_kernel, cgp_update_kernel), everything but their reductions
+// and vector passes: the scalar prologue, the decision (cg_rule.h, plus the stagnation guard), the coefficients and the
+// scal[] / publication writes of workgroup 0.
+// Everything another workgroup of THIS launch may rewrite is read through the parity: workgroup 0 stores gamma / alpha of
+// iteration i in slot i & 1 while the others still read slot (i - 1) & 1; the iteration counter is ticked by the SpMV launch
+// in front, never here; bb is written at i = 0 only and read from i = 1 on.  All of these reads, and one lane's view of the
+// done flag (so that all waves take the same branch), are issued before `reduce`, whose barrier publishes that flag.
+struct PcgStep {
+  int par;
+  float alpha, beta;
+  bool done;
+};
+
+template <class Reduce>
+__device__ __forceinline__ PcgStep pcg_step(const PcgArgs& a, int* sh_done, Reduce reduce) {
+  const int tid = threadIdx.x;
   const int it = a.state[0] - 1;
-  if (tid == 0) sh_done = a.state[1];                    // one lane's view, so that all waves take the same branch
+  if (tid == 0) *sh_done = a.state[1];
   const int par = it & 1;
   const float gamma_old = a.scal[par ^ 1], alpha_old = a.scal[2 + (par ^ 1)], bb_old = a.scal[4];
   const float tol = a.scal[6];
   const float best_old = a.scal[8 + (par ^ 1)];
   const int it_best_old = reinterpret_cast<const int*>(a.scal)[10 + (par ^ 1)];
-  const int count = a.world * a.nbu;
   float gamma, delta;
-  reduce_two(a.pd[par], a.pd[par] + count, count, sh, &gamma, &delta);
-  if (sh_done) return;                                   // (published before the barrier inside reduce_two)
+  reduce(par, &gamma, &delta);
+  PcgStep s = {par, 0.f, 0.f, true};
+  if (*sh_done) return s;
   const float bb = it == 0 ? gamma : bb_old;
-  const float rel = bb > 0.f ? sqrtf(gamma / bb) : 0.f;
-  int done = 0, status = 0;
-  if (a.stop_mode == 0) {
-    if (it >= a.min_iter && rel < tol) { done = 1; status = 1; }
-  } else if (rel <= tol) { done = 1; status = 1; }
-  if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it >= a.max_iter) { done = 1; status = 2; }
+  const float rel = cg_rel(gamma, bb);
+  // `it` counts from 0 here and cg_rule.h's step from 1: this call is the only place the two counters meet
+  CgStop st = cg_stop(a.stop_mode, a.min_iter, a.max_iter, tol, it + 1, rel);
   // stagnation: no new minimum of the residual norm for 50 + it_best / 4 iterations (file header)
   const float best = rel < best_old ? rel : best_old;
   const int it_best = rel < best_old ? it : it_best_old;
-  if (!done && it - it_best >= 50 + it_best / 4) { done = 1; status = 4; }
-  float alpha = 0.f, beta = 0.f;
-  if (!done) {
-    if (it == 0) {
-      alpha = delta != 0.f ? gamma / delta : 0.f;
-    } else {
-      beta = gamma_old != 0.f ? gamma / gamma_old : 0.f;
-      const float den = delta - (alpha_old != 0.f ? beta * gamma / alpha_old : 0.f);
-      alpha = den != 0.f ? gamma / den : 0.f;
-    }
-    if (!isfinite(alpha) || !isfinite(beta)) { alpha = 0.f; beta = 0.f; }
-  }
+  if (!st.done && it - it_best >= 50 + it_best / 4) { st.done = 1; st.status = kCgStagnated; }
+  // never frozen: a solve that goes on takes a full step
+  const CgCoef k = cg_coef(it == 0, false, gamma, delta, gamma_old, alpha_old);
   if (blockIdx.x == 0 && tid == 0) {
     a.scal[5] = rel;
     if (it == 0) a.scal[4] = bb;
-    if (done) {
+    if (st.done) {
       // (a workgroup that starts late and reads done = 1 returns at once: it would have decided the same)
-      a.state[2] = status; a.state[1] = 1;
-      a.host_resid[0] = rel;
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
+      cg_publish(a.state, a.host_state, a.host_resid, &rel, 1, it, st.status);
     } else {
-      a.scal[par] = gamma; a.scal[2 + par] = alpha;
+      a.scal[par] = gamma; a.scal[2 + par] = k.alpha;
       a.scal[8 + par] = best;
       reinterpret_cast<int*>(a.scal)[10 + par] = it_best;
     }
   }
-  if (done) return;
+  s.alpha = k.alpha; s.beta = k.beta; s.done = st.done != 0;
+  return s;
+}
+
+// one pipelined-CG vector update on this rank's rows (see the file header); takes the stopping decision on
+// ||r_i|| BEFORE updating, so that x is the iterate the decision was taken on
+__global__ __launch_bounds__(kBlock) void pcg_update_kernel(PcgArgs a) {
+  __shared__ float sh[kBlock / 64][2];
+  __shared__ float sh2[kBlock / 64][2];
+  __shared__ int sh_done;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int count = a.world * a.nbu;
+  const PcgStep st = pcg_step(a, &sh_done, [&](int par, float* gamma, float* delta) {
+    reduce_two(a.pd[par], a.pd[par] + count, count, sh, gamma, delta);
+  });
+  if (st.done) return;
+  const int par = st.par;
+  const float alpha = st.alpha, beta = st.beta;
   const float* __restrict__ wc = a.w[par];
   float* __restrict__ wn = a.w[par ^ 1];
   const int64_t rows_per = (a.n_loc + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
@@ -277,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void pcg_refine_finalize_kernel(PcgArgs a, 
   const int count = a.world * a.nbu;
   reduce_two(a.pd[0], a.pd[0] + count, count, sh, &rr, &bb);
   if (threadIdx.x == 0) {
-    const float rel = bb > 0.f ? sqrtf(rr / bb) : 0.f;
+    const float rel = cg_rel(rr, bb);
     float next = rel > 0.f ? 0.5f * a.tol / rel : a.tol;
     next = next < a.tol ? a.tol : (next > 0.1f ? 0.1f : next);
     a.scal[6] = next;
@@ -389,16 +396,8 @@ __global__ __launch_bounds__(kBlock) void cgp_update_kernel(PcgArgs a) {
   __shared__ float sh2[kBlock / 64];
   __shared__ int sh_done;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int it = a.state[0] - 1;
-  if (tid == 0) sh_done = a.state[1];
-  const int par = it & 1;
-  const float gamma_old = a.scal[par ^ 1], alpha_old = a.scal[2 + (par ^ 1)], bb_old = a.scal[4];
-  const float tol = a.scal[6];
-  const float best_old = a.scal[8 + (par ^ 1)];
-  const int it_best_old = reinterpret_cast<const int*>(a.scal)[10 + (par ^ 1)];
   // gamma from the update-kernel partials (world * nbu), delta from the SpMV partials (world * nb2)
-  float gamma, delta;
-  {
+  const PcgStep st = pcg_step(a, &sh_done, [&](int par, float* gamma, float* delta) {
     const int cg = a.world * a.nbu, cd = a.world;
     float gv[kMaxSlots], dv[kMaxSlots];
 #pragma unroll
@@ -417,48 +416,12 @@ __global__ __launch_bounds__(kBlock) void cgp_update_kernel(PcgArgs a) {
     d = mgp_wave_sum(d);
     if (lane == 0) { sh[wave][0] = g; sh[wave][1] = d; }
     __syncthreads();
-    gamma = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
-    delta = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
-  }
-  if (sh_done) return;
-  const float bb = it == 0 ? gamma : bb_old;
-  const float rel = bb > 0.f ? sqrtf(gamma / bb) : 0.f;
-  int done = 0, status = 0;
-  if (a.stop_mode == 0) {
-    if (it >= a.min_iter && rel < tol) { done = 1; status = 1; }
-  } else if (rel <= tol) { done = 1; status = 1; }
-  if (!isfinite(rel)) { done = 1; status = 3; }
-  if (!done && it >= a.max_iter) { done = 1; status = 2; }
-  const float best = rel < best_old ? rel : best_old;
-  const int it_best = rel < best_old ? it : it_best_old;
-  if (!done && it - it_best >= 50 + it_best / 4) { done = 1; status = 4; }
-  float alpha = 0.f, beta = 0.f;
-  if (!done) {
-    if (it == 0) {
-      alpha = delta != 0.f ? gamma / delta : 0.f;
-    } else {
-      beta = gamma_old != 0.f ? gamma / gamma_old : 0.f;
-      const float den = delta - (alpha_old != 0.f ? beta * gamma / alpha_old : 0.f);
-      alpha = den != 0.f ? gamma / den : 0.f;
-    }
-    if (!isfinite(alpha) || !isfinite(beta)) { alpha = 0.f; beta = 0.f; }
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    a.scal[5] = rel;
-    if (it == 0) a.scal[4] = bb;
-    if (done) {
-      a.state[2] = status; a.state[1] = 1;
-      a.host_resid[0] = rel;
-      a.host_state[0] = it; a.host_state[2] = status;
-      __threadfence_system();
-      a.host_state[1] = 1;
-    } else {
-      a.scal[par] = gamma; a.scal[2 + par] = alpha;
-      a.scal[8 + par] = best;
-      reinterpret_cast<int*>(a.scal)[10 + par] = it_best;
-    }
-  }
-  if (done) return;
+    *gamma = (sh[0][0] + sh[1][0]) + (sh[2][0] + sh[3][0]);
+    *delta = (sh[0][1] + sh[1][1]) + (sh[2][1] + sh[3][1]);
+  });
+  if (st.done) return;
+  const int par = st.par;
+  const float alpha = st.alpha, beta = st.beta;
   float* __restrict__ un = a.w[par ^ 1];
   const int64_t rows_per = (a.n_loc + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
   const int64_t l0 = (int64_t)blockIdx.x * rows_per;
