@@ -26,15 +26,12 @@
 #include <string.h>
 #include <algorithm>
 #include <vector>
-#include <thread>
-#include <mutex>
-#include <condition_variable>
-#include <functional>
-#include <chrono>
 #include <cstdio>
 #include <atomic>
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "eig_host.h"
+#include "eig_policy.h"
 
 namespace {
 
@@ -289,413 +286,6 @@ __global__ __launch_bounds__(256) void vecs_to_cols_kernel(const float* __restri
   }
 }
 
-// ---------------------------------------------------------------- host: symmetric eigensolver (fp64)
-// Householder tridiagonalisation + implicit-shift QL, restated so that every O(n^3) loop walks a ROW of a row-major
-// array and the eigenvector update runs on host threads:
-//   1. T = Q^T A Q on the lower triangle (symmetric rank-2 updates, 4/3 n^3 flops);
-//   2. Z^T = Q^T accumulated by right multiplications (4/3 n^3);
-//   3. QL on (d, e) alone -- its plane rotations are RECORDED (they do not depend on the vectors);
-//   4. the ~n^2 recorded rotations are applied to Z^T, rows i / i+1, over column slices of 32: a slice is an
-//      L1-resident private copy owned by one host thread (3 n^3 flops, the largest part, now parallel).
-// Round 3: the b = 128 Rayleigh-Ritz problem took 2.0 ms per round in the column-walking EISPACK form this replaces
-// (4 rounds = 8 of the 48 ms of the 60k eigensolve).  Dot products use four interleaved partial sums in a fixed
-// order and -ffp-contract=off holds for the host pass too, so the result does not depend on the thread count or on
-// whether the AVX2 clones run.  A [n x n] row-major symmetric; evals ascending; eigenvectors = columns of V.
-#define MGP_HOST_INLINE static inline __attribute__((always_inline))
-
-MGP_HOST_INLINE double dot4(const double* __restrict__ a, const double* __restrict__ b, int n) {
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  int i = 0;
-  for (; i + 4 <= n; i += 4) {
-    s0 += a[i] * b[i];
-    s1 += a[i + 1] * b[i + 1];
-    s2 += a[i + 2] * b[i + 2];
-    s3 += a[i + 3] * b[i + 3];
-  }
-  double s = (s0 + s2) + (s1 + s3);
-  for (; i < n; ++i) s += a[i] * b[i];
-  return s;
-}
-
-struct PlaneRot { int i; double c, s; };
-
-// T = Q^T A Q, Q = H_0 H_1 ... H_{n-3}, H_k = I - tau_k v_k v_k^T with v_k in indices k+1 .. n-1 (v_k[k+1] = 1; row k
-// of hv).  Only the LOWER triangle of W is read and written.  d = diagonal of T, e[i] = T[i+1, i].
-MGP_HOST_INLINE void householder_tridiag_impl(int n, int ld, double* W, double* d, double* e, double* hv, double* tau,
-                                              double* p, double* w) {
-  for (int k = 0; k + 2 < n; ++k) {
-    const int s = n - k - 1;
-    double* v = hv + (size_t)k * ld + (k + 1);
-    double scale = 0.0, tail = 0.0;
-    for (int j = 0; j < s; ++j) {
-      v[j] = W[(size_t)(k + 1 + j) * ld + k];
-      scale = std::max(scale, fabs(v[j]));
-      if (j) tail = std::max(tail, fabs(v[j]));
-    }
-    d[k] = W[(size_t)k * ld + k];
-    const double alpha = v[0];
-    if (tail == 0.0) { tau[k] = 0.0; e[k] = alpha; continue; }   // the column is tridiagonal already: H_k = I
-    double ss = 0.0;
-    for (int j = 0; j < s; ++j) { const double t = v[j] / scale; ss += t * t; }
-    const double nrm = scale * sqrt(ss);
-    const double beta = alpha > 0.0 ? -nrm : nrm;
-    const double tk = (beta - alpha) / beta;
-    const double inv = 1.0 / (alpha - beta);
-    v[0] = 1.0;
-    for (int j = 1; j < s; ++j) v[j] *= inv;
-    tau[k] = tk;
-    e[k] = beta;
-    double* B = W + (size_t)(k + 1) * ld + (k + 1);
-    // p = tau B v: row j of the lower triangle gives its own dot product and its share of the entries above it
-    for (int j = 0; j < s; ++j) {
-      const double* __restrict__ row = B + (size_t)j * ld;
-      const double vj = v[j];
-      const double t = dot4(row, v, j);
-      for (int i = 0; i < j; ++i) p[i] += row[i] * vj;
-      p[j] = t + row[j] * vj;
-    }
-    for (int j = 0; j < s; ++j) p[j] *= tk;
-    const double hh = 0.5 * tk * dot4(p, v, s);
-    for (int j = 0; j < s; ++j) w[j] = p[j] - hh * v[j];
-    for (int j = 0; j < s; ++j) {          // B -= v w^T + w v^T
-      double* __restrict__ row = B + (size_t)j * ld;
-      const double vj = v[j], wj = w[j];
-      for (int i = 0; i <= j; ++i) row[i] -= vj * w[i] + wj * v[i];
-    }
-  }
-  if (n >= 2) { d[n - 2] = W[(size_t)(n - 2) * ld + (n - 2)]; e[n - 2] = W[(size_t)(n - 1) * ld + (n - 2)]; }
-  d[n - 1] = W[(size_t)(n - 1) * ld + (n - 1)];
-  e[n - 1] = 0.0;
-}
-
-// Zt = Q^T = H_{n-3} ... H_0 as ((I H_{n-3}) H_{n-4}) ... H_0: M <- M - tau (M v) v^T touches rows and columns
-// k+1 .. n-1 only (the rows above are still rows of the identity).
-MGP_HOST_INLINE void householder_accumulate_impl(int n, int ld, const double* hv, const double* tau, double* Zt, int r0, int r1) {
-  // rows [r0, r1) only: a row of M runs through all the H_k on its own, so row ranges are independent jobs
-  for (int r = r0; r < r1; ++r) {
-    for (int c = 0; c < n; ++c) Zt[(size_t)r * ld + c] = 0.0;
-    Zt[(size_t)r * ld + r] = 1.0;
-  }
-  for (int k = std::min(n - 3, r1 - 2); k >= 0; --k) {
-    if (tau[k] == 0.0) continue;
-    const int s = n - k - 1;
-    const double* __restrict__ v = hv + (size_t)k * ld + (k + 1);
-    for (int r = std::max(r0, k + 1); r < r1; ++r) {
-      double* __restrict__ row = Zt + (size_t)r * ld + (k + 1);
-      const double g = tau[k] * dot4(row, v, s);
-      for (int i = 0; i < s; ++i) row[i] -= g * v[i];
-    }
-  }
-}
-
-// rows i, i+1 of Zt <- the recorded rotations, columns [k0, k1): worked on in a compact private copy (n x len: 32 KB
-// at n = 128 and 32 columns), so no cache line is shared with the neighbouring slices' threads
-MGP_HOST_INLINE void apply_rots_impl(int n, int ld, double* Zt, const std::vector<PlaneRot>& rots, int k0, int k1) {
-  const int len = k1 - k0;
-  if (len <= 0) return;
-  std::vector<double> loc((size_t)n * len);
-  for (int r = 0; r < n; ++r) memcpy(&loc[(size_t)r * len], Zt + (size_t)r * ld + k0, len * sizeof(double));
-  for (const PlaneRot& q : rots) {
-    double* __restrict__ r0 = &loc[(size_t)q.i * len];
-    double* __restrict__ r1 = r0 + len;
-    const double c = q.c, s = q.s;
-    for (int k = 0; k < len; ++k) {
-      const double h = r1[k], g = r0[k];
-      r1[k] = s * g + c * h;
-      r0[k] = c * g - s * h;
-    }
-  }
-  for (int r = 0; r < n; ++r) memcpy(Zt + (size_t)r * ld + k0, &loc[(size_t)r * len], len * sizeof(double));
-}
-
-// the same three loops compiled twice: baseline x86-64 and AVX2 (picked at run time; identical arithmetic)
-void householder_tridiag_base(int n, int ld, double* W, double* d, double* e, double* hv, double* tau, double* p, double* w) {
-  householder_tridiag_impl(n, ld, W, d, e, hv, tau, p, w);
-}
-__attribute__((target("avx2"))) void householder_tridiag_avx2(int n, int ld, double* W, double* d, double* e, double* hv,
-                                                              double* tau, double* p, double* w) {
-  householder_tridiag_impl(n, ld, W, d, e, hv, tau, p, w);
-}
-void householder_accumulate_base(int n, int ld, const double* hv, const double* tau, double* Zt, int r0, int r1) {
-  householder_accumulate_impl(n, ld, hv, tau, Zt, r0, r1);
-}
-__attribute__((target("avx2"))) void householder_accumulate_avx2(int n, int ld, const double* hv, const double* tau, double* Zt, int r0,
-                                                                 int r1) {
-  householder_accumulate_impl(n, ld, hv, tau, Zt, r0, r1);
-}
-void apply_rots_base(int n, int ld, double* Zt, const std::vector<PlaneRot>& rots, int k0, int k1) {
-  apply_rots_impl(n, ld, Zt, rots, k0, k1);
-}
-__attribute__((target("avx2"))) void apply_rots_avx2(int n, int ld, double* Zt, const std::vector<PlaneRot>& rots, int k0, int k1) {
-  apply_rots_impl(n, ld, Zt, rots, k0, k1);
-}
-
-inline double pythag(double a, double b) {
-  const double r2 = a * a + b * b;
-  if (r2 > 1e-280 && r2 < 1e280) return sqrt(r2);
-  return hypot(a, b);
-}
-
-// implicit-shift QL on the symmetric tridiagonal (d, e[i] = T[i+1, i]): eigenvalues into d (unsorted), the plane
-// rotations (acting on vector indices i, i+1) appended to `rots` in the order they have to be applied
-void tridiag_ql(int n, double* d, double* e, std::vector<PlaneRot>& rots) {
-  double f = 0.0, tst1 = 0.0;
-  const double eps = 2.220446049250313e-16;
-  e[n - 1] = 0.0;
-  for (int l = 0; l < n; ++l) {
-    tst1 = std::max(tst1, fabs(d[l]) + fabs(e[l]));
-    int m = l;
-    while (m < n) {
-      if (fabs(e[m]) <= eps * tst1) break;
-      ++m;
-    }
-    if (m > l) {
-      int iter = 0;
-      do {
-        ++iter;
-        double g = d[l];
-        double p = (d[l + 1] - g) / (2.0 * e[l]);
-        double r = pythag(p, 1.0);
-        if (p < 0) r = -r;
-        d[l] = e[l] / (p + r);
-        d[l + 1] = e[l] * (p + r);
-        const double dl1 = d[l + 1];
-        double h = g - d[l];
-        for (int i = l + 2; i < n; ++i) d[i] -= h;
-        f += h;
-        p = d[m];
-        double c = 1.0, c2 = c, c3 = c;
-        const double el1 = e[l + 1];
-        double s = 0.0, s2 = 0.0;
-        for (int i = m - 1; i >= l; --i) {
-          c3 = c2;
-          c2 = c;
-          s2 = s;
-          g = c * e[i];
-          h = c * p;
-          r = pythag(p, e[i]);
-          e[i + 1] = s * r;
-          s = e[i] / r;
-          c = p / r;
-          p = c * d[i] - s * g;
-          d[i + 1] = h + s * (c * g + s * d[i]);
-          rots.push_back(PlaneRot{i, c, s});
-        }
-        p = -s * s2 * c3 * el1 * e[l] / dl1;
-        e[l] = s * p;
-        d[l] = c * p;
-      } while (fabs(e[l]) > eps * tst1 && iter < 200);
-    }
-    d[l] = d[l] + f;
-    e[l] = 0.0;
-  }
-}
-
-// Host worker pool of one eigensolve: the Rayleigh-Ritz step has four short parallel sections per round (two b^3
-// products, the eigenvector rotations, W = T S); starting fresh threads for each cost as much as their arithmetic.
-// run(njobs, fn) calls fn(job) once per job on the workers and the calling thread and returns when all are done.  Which
-// thread takes which job varies, the arithmetic of a job does not: every output element belongs to exactly one job.
-class HostPool {
- public:
-  explicit HostPool(int workers) {
-    for (int t = 0; t < workers; ++t) th_.emplace_back([this]() { work(); });
-  }
-  ~HostPool() {
-    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; }
-    cv_.notify_all();
-    for (auto& x : th_) x.join();
-  }
-  HostPool(const HostPool&) = delete;
-  HostPool& operator=(const HostPool&) = delete;
-  int threads() const { return (int)th_.size() + 1; }
-  void run(int njobs, const std::function<void(int)>& fn) {
-    if (njobs <= 0) return;
-    std::unique_lock<std::mutex> lk(mu_);
-    job_ = &fn; njobs_ = njobs; next_ = 0; pending_ = njobs; ++gen_;
-    lk.unlock();
-    cv_.notify_all();
-    lk.lock();
-    take(lk);
-    done_.wait(lk, [&]() { return pending_ == 0; });
-    job_ = nullptr;
-  }
-  // fn(i) for i in [0, n): contiguous chunks of `chunk` rows as jobs
-  void rows(int n, int chunk, const std::function<void(int)>& fn) {
-    const int nj = (n + chunk - 1) / chunk;
-    const std::function<void(int)> job = [&](int j) {
-      const int i1 = std::min(n, (j + 1) * chunk);
-      for (int i = j * chunk; i < i1; ++i) fn(i);
-    };
-    run(nj, job);
-  }
-
- private:
-  void take(std::unique_lock<std::mutex>& lk) {      // called with the lock held
-    while (next_ < njobs_) {
-      const int j = next_++;
-      const std::function<void(int)>* f = job_;
-      lk.unlock();
-      (*f)(j);
-      lk.lock();
-      if (--pending_ == 0) done_.notify_all();
-    }
-  }
-  void work() {
-    uint64_t seen = 0;
-    std::unique_lock<std::mutex> lk(mu_);
-    for (;;) {
-      cv_.wait(lk, [&]() { return stop_ || gen_ != seen; });
-      if (stop_) return;
-      seen = gen_;
-      take(lk);
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex mu_;
-  std::condition_variable cv_, done_;
-  const std::function<void(int)>* job_ = nullptr;
-  int njobs_ = 0, next_ = 0, pending_ = 0;
-  uint64_t gen_ = 0;
-  bool stop_ = false;
-};
-
-int host_pool_workers() {
-  const unsigned hw = std::thread::hardware_concurrency();
-  return (int)std::min<unsigned>(hw ? hw : 1u, 8u) - 1;
-}
-
-// Gn (b x b, unit diagonal, symmetric positive definite) = C C^T; T = D C^-T (b x b) so that
-// T^T (D^-1 Gn D^-1) T = I.  False when a pivot falls under 1e-10 (relative to the unit diagonal): the caller
-// then needs the rank-revealing path.
-bool cholesky_whiten(int b, const std::vector<double>& Gn, const std::vector<double>& dg, std::vector<double>& T) {
-  // every inner loop walks rows: the dot products with four interleaved partial sums (a single running sum is a chain of
-  // dependent adds), the inverse row by row as axpys
-  std::vector<double> C((size_t)b * b, 0.0);
-  for (int i = 0; i < b; ++i) {
-    double* ci = &C[(size_t)i * b];
-    for (int j = 0; j < i; ++j) {
-      const double* cj = &C[(size_t)j * b];
-      ci[j] = (Gn[(size_t)i * b + j] - dot4(ci, cj, j)) / cj[j];
-    }
-    const double s = Gn[(size_t)i * b + i] - dot4(ci, ci, i);
-    if (!(s > 1e-10)) return false;
-    ci[i] = sqrt(s);
-  }
-  // Ci = C^-1 (lower): row i = (e_i - sum_{k < i} C[i][k] Ci[k][:]) / C[i][i]
-  std::vector<double> Ci((size_t)b * b, 0.0);
-  for (int i = 0; i < b; ++i) {
-    double* __restrict__ ri = &Ci[(size_t)i * b];
-    const double* ci = &C[(size_t)i * b];
-    for (int k = 0; k < i; ++k) {
-      const double c = ci[k];
-      const double* __restrict__ rk = &Ci[(size_t)k * b];
-      for (int j = 0; j <= k; ++j) ri[j] -= c * rk[j];
-    }
-    const double inv = 1.0 / ci[i];
-    for (int j = 0; j < i; ++j) ri[j] *= inv;
-    ri[i] = inv;
-  }
-  // T = D C^-T (upper triangular): T[i][j] = dg[i] * Ci[j][i]
-  T.assign((size_t)b * b, 0.0);
-  for (int i = 0; i < b; ++i)
-    for (int j = i; j < b; ++j) T[(size_t)i * b + j] = dg[i] * Ci[(size_t)j * b + i];
-  return true;
-}
-
-void jacobi_eigh(int n, std::vector<double>& A, std::vector<double>& evals, std::vector<double>& V, HostPool* pool = nullptr) {
-  // (name kept from the Jacobi days: every caller wants "eigh of a small symmetric matrix")
-  // Padded leading dimension: with ld = n a power-of-two n (block sizes 128, 256) maps the rows of a column slice onto
-  // a handful of L1 sets of the host CPU.
-  evals.resize(n);
-  V.assign((size_t)n * n, 0.0);
-  if (n == 1) { evals[0] = A[0]; V[0] = 1.0; return; }
-  const int ld = (n + 7) / 8 * 8 + 8;
-  std::vector<double> W((size_t)n * ld), hv((size_t)n * ld, 0.0), Zt((size_t)n * ld), d(n), e(n), tau(n, 0.0), p(n, 0.0), w(n);
-  for (int i = 0; i < n; ++i)      // use the symmetric part
-    for (int j = 0; j <= i; ++j) W[(size_t)i * ld + j] = 0.5 * (A[(size_t)i * n + j] + A[(size_t)j * n + i]);
-  const bool avx2 = __builtin_cpu_supports("avx2");
-  (avx2 ? householder_tridiag_avx2 : householder_tridiag_base)(n, ld, W.data(), d.data(), e.data(), hv.data(), tau.data(),
-                                                               p.data(), w.data());
-  auto accumulate = avx2 ? householder_accumulate_avx2 : householder_accumulate_base;
-  if (pool && n >= 64) {
-    // later rows pass through more reflectors: jobs of 8 rows, taken in turn by whoever is free
-    const int nj = (n + 7) / 8;
-    pool->run(nj, [&](int j) { accumulate(n, ld, hv.data(), tau.data(), Zt.data(), j * 8, std::min(n, j * 8 + 8)); });
-  } else {
-    accumulate(n, ld, hv.data(), tau.data(), Zt.data(), 0, n);
-  }
-  std::vector<PlaneRot> rots;
-  rots.reserve((size_t)n * n);
-  tridiag_ql(n, d.data(), e.data(), rots);
-  auto apply = avx2 ? apply_rots_avx2 : apply_rots_base;
-  // column slices of 32 (the last one takes the remainder); on the caller's pool when there is one
-  const int nsl = std::max(1, n / 32);
-  auto slice = [&](int t) {
-    const int k0 = t * 32, k1 = t + 1 == nsl ? n : (t + 1) * 32;
-    apply(n, ld, Zt.data(), rots, k0, k1);
-  };
-  if (nsl == 1) {
-    slice(0);
-  } else if (pool) {
-    pool->run(nsl, slice);
-  } else {
-    for (int q = 0; q < nsl; ++q) slice(q);
-  }
-  std::vector<int> order(n);
-  for (int i = 0; i < n; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return d[a] < d[b]; });
-  for (int j = 0; j < n; ++j) {
-    evals[j] = d[order[j]];
-    const double* z = &Zt[(size_t)order[j] * ld];
-    for (int k = 0; k < n; ++k) V[(size_t)k * n + j] = z[k];
-  }
-}
-
-// symmetric tridiagonal (alpha[k], beta[k-1]) eigenvalues + first components of eigenvectors
-void tridiag_eigh(int k, const std::vector<double>& alpha, const std::vector<double>& beta, std::vector<double>& evals,
-                  std::vector<double>& evecs) {
-  std::vector<double> T((size_t)k * k, 0.0);
-  for (int i = 0; i < k; ++i) {
-    T[(size_t)i * k + i] = alpha[i];
-    if (i + 1 < k) { T[(size_t)i * k + i + 1] = beta[i]; T[(size_t)(i + 1) * k + i] = beta[i]; }
-  }
-  jacobi_eigh(k, T, evals, evecs);
-}
-
-// largest Ritz value of (H, G) on the leading k of kfull basis vectors (G = K^T K, H = K^T L K, fp64): rank-revealing
-// whitening (directions under 1e-6 of the largest Gram eigenvalue are rounding of the fp32 vectors), then one small
-// symmetric eigensolve.  NaN when the Gram block is unusable.
-double top_ritz(int kfull, int k, const std::vector<double>& G, const std::vector<double>& H) {
-  std::vector<double> dg(k), Gn((size_t)k * k), lam, U;
-  for (int i = 0; i < k; ++i) {
-    const double g = G[(size_t)i * kfull + i];
-    if (!(g > 0.0) || !std::isfinite(g)) return NAN;
-    dg[i] = 1.0 / sqrt(g);
-  }
-  for (int i = 0; i < k; ++i)
-    for (int j = 0; j < k; ++j) Gn[(size_t)i * k + j] = 0.5 * (G[(size_t)i * kfull + j] + G[(size_t)j * kfull + i]) * dg[i] * dg[j];
-  jacobi_eigh(k, Gn, lam, U);
-  int k0 = 0;
-  while (k0 < k && !(lam[k0] > 1e-6 * lam[k - 1])) ++k0;
-  const int kept = k - k0;
-  if (kept < 1) return NAN;
-  std::vector<double> T((size_t)k * kept), HT((size_t)k * kept, 0.0), Hp((size_t)kept * kept, 0.0), th, S;
-  for (int i = 0; i < k; ++i)
-    for (int j = 0; j < kept; ++j) T[(size_t)i * kept + j] = dg[i] * U[(size_t)i * k + k0 + j] / sqrt(lam[k0 + j]);
-  for (int i = 0; i < k; ++i)
-    for (int l = 0; l < k; ++l) {
-      const double h = 0.5 * (H[(size_t)i * kfull + l] + H[(size_t)l * kfull + i]);
-      for (int j = 0; j < kept; ++j) HT[(size_t)i * kept + j] += h * T[(size_t)l * kept + j];
-    }
-  for (int j = 0; j < kept; ++j)
-    for (int i = 0; i < k; ++i) {
-      const double t = T[(size_t)i * kept + j];
-      for (int l = 0; l < kept; ++l) Hp[(size_t)j * kept + l] += t * HT[(size_t)i * kept + l];
-    }
-  jacobi_eigh(kept, Hp, th, S);
-  return th[kept - 1];
-}
-
 std::atomic<int> g_eig_bound_mode{1};   // 1: the filter's upper end from a Krylov estimate of lambda_max; 0: Gershgorin;
                             // 2 (tests): HALF the estimate, a bound that is certainly short -- the fallback must catch it
 
@@ -766,8 +356,331 @@ int launch_gram(const float* A, const float* B, int64_t n, int b, EigWork& w, do
 
 }  // namespace
 
-int mgp_kernel_block_ld(const float* Z1, int64_t n1, const float* Z2, int64_t n2, int m, float scale, float* K,
-                        int64_t ldk, void* stream);
+// ================================================================= the driver of mgp_lanczos_smallest
+// validate -> carve the workspace -> spectrum bounds -> start block -> rounds { filter, Rayleigh-Ritz + rotation, policy step }
+// -> outputs.  The host algebra of a round is eig_host.h, every decision between the launches eig_policy.h.
+namespace {
+
+// One call's state.  user_degree > 0: every round runs at it; trace: MGP_EIG_TIMING, read once per call; lab: lab builds
+// (-DMGP_LAB_EIG) take a fixed damping exponent for every round from MGP_EIG_TARGET.  bV / bLV: the buffers that hold the current
+// block V and L V (full width b); c0 .. c2: the three more that serve the filter.  rr: kept, Ritz values and W^T of the last
+// Rayleigh-Ritz step; tr0 / tr1: start of the round / everything of it queued.
+struct EigCtx {
+  const mgp_csr_t* L;
+  void* stream;
+  hipStream_t st;
+  int64_t n;
+  int m, b, user_degree;
+  uint64_t seed;
+  double tol, lab_target;
+  bool trace, lab, floor_hit;
+  EigWork w;
+  int bV, bLV, c0, c1, c2, rounds, nspmm, nconv, deg_used;
+  EigPolicy pol;
+  HostPool* pool;
+  std::vector<double> G, H, rp, res;
+  RitzStep rr;
+  HostClock::time_point tr0, tr1;
+  float *evals, *evecs, *resid, *block_evals, *block_evecs, *block_resid;     // the caller's outputs
+};
+
+int eig_setup(EigCtx& cx, const mgp_csr_t* L, int m, const mgp_lanczos_params_t* p, void* work, size_t work_bytes, void* stream) {
+  if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !cx.evals || !cx.evecs || !work) return MGP_ERR_ARG;
+  if (!mgp_spmv_lanes_ok(L->spmv_lanes)) return MGP_ERR_ARG;
+  const int64_t n = L->n;
+  if (n <= 0 || m <= 0 || m > n) return MGP_ERR_ARG;
+  int b = block_size_for(m, p);
+  if (b > n) b = (int)n;
+  if (b > 256) return MGP_ERR_UNSUPPORTED;   // one SpMM launch handles <= 256 columns
+  if (work_bytes < eig_bytes(n, m, p)) return MGP_ERR_WORKSPACE;
+  cx.L = L; cx.stream = stream; cx.st = mgp_stream(stream); cx.n = n; cx.m = m; cx.b = b;
+  cx.seed = p ? p->seed : 1337;
+  cx.tol = (p && p->tol > 0.f) ? p->tol : 1e-5f;
+  cx.user_degree = (p && p->degree > 0) ? p->degree : 0;
+  cx.trace = getenv("MGP_EIG_TIMING") != nullptr;
+  cx.lab = false;
+#ifdef MGP_LAB_EIG
+  if (const char* e = getenv("MGP_EIG_TARGET")) { cx.lab = true; cx.lab_target = atof(e); }
+#endif
+  EigWork& w = cx.w;
+  MgpArena ar(work, work_bytes);
+  for (int i = 0; i < 5; ++i) w.buf[i] = ar.take<float>((size_t)n * b);
+  chunking(n, &w.chunks, &w.rows_per_chunk, 96, 512);
+  chunking(n, &w.rchunks, &w.rrows, 256, 256);
+  w.gpart = ar.take<double>((size_t)w.chunks * b * b);
+  w.G = ar.take<double>((size_t)b * b);
+  w.H = ar.take<double>((size_t)b * b);
+  w.rpart = ar.take<double>((size_t)w.rchunks * b);
+  w.wt = ar.take<float>((size_t)b * b);
+  w.theta = ar.take<float>(b);
+  w.bmax = ar.take<float>(1024);
+  if (!ar.ok()) return MGP_ERR_WORKSPACE;
+  cx.G.resize((size_t)b * b); cx.H.resize((size_t)b * b); cx.rp.resize((size_t)w.rchunks * b);
+  return MGP_OK;
+}
+
+// Y = ca X + cl L X (+ cz Z) on C columns: one fused SpMM launch
+int eig_apply(EigCtx& cx, const float* X, int C, float* Y, double ca, double cl, const float* Z = nullptr, double cz = 0.0) {
+  return mgp_spmm_fused(cx.L, X, C, Y, (float)ca, (float)cl, nullptr, nullptr, Z, (float)cz, 1.f, nullptr, nullptr, cx.stream);
+}
+
+// Spectrum bounds -- ub: Gershgorin, always >= lambda_max; ubf: the filter's upper end -- and the cold policy on them.
+int eig_bounds(EigCtx& cx) {
+  const mgp_csr_t* L = cx.L;
+  const int64_t n = cx.n;
+  EigWork& w = cx.w;
+  hipStream_t st = cx.st;
+  const int gb = (int)std::min<int64_t>(1024, mgp_cdiv(n, kBlock));
+  hipLaunchKernelGGL(gershgorin_kernel, dim3(gb), dim3(kBlock), 0, st, n, L->rowptr, L->vals, L->diag, w.bmax);
+  MGP_LAUNCH_CHECK();
+  std::vector<float> hb(gb);
+  MGP_HIP_TRY(hipMemcpyAsync(hb.data(), w.bmax, gb * sizeof(float), hipMemcpyDeviceToHost, st));
+  MGP_HIP_TRY(hipStreamSynchronize(st));
+  double ub = 0.0;
+  for (float v : hb) ub = std::max(ub, (double)v);
+  ub *= 1.0 + 1e-6;
+  if (!(ub > 0.0)) return MGP_ERR_ARG;
+
+  // ---- the filter's upper end.  Gershgorin is rigorous and loose: on the k-NN graph Laplacians of this package lambda_max
+  // is about HALF of it (60k RMNIST-like graph: 15.4 of 29.7; 1M swiss roll: 649 of 1239), and the degree a Chebyshev filter
+  // needs grows with sqrt(ub - a) -- a bound twice too large costs 40 % more applies.  So: a 32-dimensional Krylov space of
+  // one random vector in the Chebyshev basis of [0, ub] (the same fused three-term SpMV launches as the filter, C = 1; the
+  // basis stays bounded and well conditioned, unlike the monomials), Rayleigh-Ritz with the Gram kernels, the largest
+  // Ritz value theta_32 <= lambda_max; the filter gets theta_32 + max(3 %, twice what the last 16 dimensions still moved).
+  // The residual test keeps the Gershgorin bound as its norm of L, so `tol` means what it meant.  An estimate that fell
+  // short would let the filter AMPLIFY the top of the spectrum; that shows as a Ritz value above the supposed bound in
+  // the next Rayleigh-Ritz step and is answered there (Gershgorin, fresh block).
+  double ubf = ub;
+  const int kk = 32;
+  const int bound_mode = g_eig_bound_mode;      // (lab switch: read once per call)
+  if (bound_mode && cx.b >= kk && n >= 8 * kk) {
+    float* K = w.buf[0];
+    float* LK = w.buf[1];
+    float* KT = w.buf[2];          // the kk Krylov vectors one after the other (b >= kk columns of room): vector j at KT + j n
+    const int g1 = (int)std::min<int64_t>(4096, mgp_cdiv(n, kBlock));
+    hipLaunchKernelGGL(random_cols_kernel, dim3(g1), dim3(kBlock), 0, st, KT, n, 1, 0, 1, cx.seed ^ 0x5bd1e995ULL);
+    MGP_LAUNCH_CHECK();
+    const double ce = ub / 2.0;     // centre = half width of [0, ub]
+    // T_1 = (L - c) / e
+    MGP_TRY(eig_apply(cx, KT, 1, KT + n, -1.0, 1.0 / ce));
+    for (int j = 2; j < kk; ++j) {
+      // T_j = 2 (L - c) / e T_{j-1} - T_{j-2}, written where it stays (round 5: no column copy behind every launch)
+      MGP_TRY(eig_apply(cx, KT + (int64_t)(j - 1) * n, 1, KT + (int64_t)j * n, -2.0, 2.0 / ce, KT + (int64_t)(j - 2) * n, -1.0));
+    }
+    hipLaunchKernelGGL(vecs_to_cols_kernel, dim3((unsigned)mgp_cdiv(n, 64)), dim3(256), 0, st, KT, n, kk, K);
+    MGP_LAUNCH_CHECK();
+    MGP_TRY(eig_apply(cx, K, kk, LK, 0.0, 1.0));
+    MGP_TRY(launch_gram(K, K, n, kk, w, w.G, st));
+    MGP_TRY(launch_gram(K, LK, n, kk, w, w.H, st));
+    std::vector<double> Gk((size_t)kk * kk), Hk((size_t)kk * kk);
+    MGP_HIP_TRY(hipMemcpyAsync(Gk.data(), w.G, (size_t)kk * kk * sizeof(double), hipMemcpyDeviceToHost, st));
+    MGP_HIP_TRY(hipMemcpyAsync(Hk.data(), w.H, (size_t)kk * kk * sizeof(double), hipMemcpyDeviceToHost, st));
+    MGP_HIP_TRY(hipStreamSynchronize(st));
+    const double th_full = top_ritz(kk, kk, Gk, Hk), th_half = top_ritz(kk, kk / 2, Gk, Hk);
+    if (std::isfinite(th_full) && std::isfinite(th_half) && th_full > 0.0) {
+      const double cand = th_full + std::max(0.03 * th_full, 2.0 * fabs(th_full - th_half));
+      if (cand < ub) ubf = cand;
+      if (bound_mode == 2) ubf = 0.5 * th_full;
+    }
+    if (cx.trace)
+      fprintf(stderr, "[eig] upper end: Gershgorin %.5g, Krylov(32) theta %.5g (16: %.5g) -> filter bound %.5g\n", ub, th_full, th_half, ubf);
+  }
+  cx.pol = eig_cold_start(ub, ubf, cx.user_degree);
+  return MGP_OK;
+}
+
+// V[:, c0:c1) <- fresh random columns
+int eig_random_cols(EigCtx& cx, float* V, int c0, int c1, uint64_t seed) {
+  const int rgrid = (int)std::min<int64_t>(4096, mgp_cdiv(cx.n * cx.b, kBlock));
+  hipLaunchKernelGGL(random_cols_kernel, dim3(rgrid), dim3(kBlock), 0, cx.st, V, cx.n, cx.b, c0, c1, seed);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+void eig_move_cols(EigCtx& cx, const float* src, int sld, int sc0, int mcols, float* dst, int dld, int dc0) {
+  const int grid = (int)std::min<int64_t>(4096, mgp_cdiv(cx.n * mcols, kBlock));
+  hipLaunchKernelGGL(move_cols_kernel, dim3(grid), dim3(kBlock), 0, cx.st, src, cx.n, sld, sc0, mcols, dst, dld, dc0);
+}
+
+// Scaled Chebyshev filter of degree pol.deg damping [a, ubf], normalised at a0, on the active columns; then the Gram blocks.
+// Soft locking: the leading pol.nlock columns are not filtered -- the recurrence and the L apply run on the remaining `ba`
+// columns, compacted to an [n, ba] block -- but stay in the Rayleigh-Ritz basis, so they keep being refined and the block
+// stays orthogonal.
+int eig_filter_round(EigCtx& cx) {
+  EigWork& w = cx.w;
+  const int b = cx.b, nlock = cx.pol.nlock, deg = cx.pol.deg;
+  cx.tr0 = HostClock::now();
+  const int ba = b - nlock;
+  cx.deg_used = deg;
+  const double e = (cx.pol.ubf - cx.pol.a) / 2.0, c = (cx.pol.ubf + cx.pol.a) / 2.0;
+  double sig = e / (cx.pol.a0 - c);
+  const double tau = 2.0 / sig;
+  int iX = cx.c0, iY = cx.c1, iN = cx.c2;
+  eig_move_cols(cx, w.buf[cx.bV], b, nlock, ba, w.buf[iX], ba, 0);
+  MGP_LAUNCH_CHECK();
+  // Y = (sig/e) (L X - c X)
+  MGP_TRY(eig_apply(cx, w.buf[iX], ba, w.buf[iY], -c * sig / e, sig / e));
+  ++cx.nspmm;
+  for (int i = 2; i <= deg; ++i) {
+    const double sn = 1.0 / (tau - sig);
+    // Ynew = (2 sn / e) (L Y - c Y) - (sig sn) X
+    MGP_TRY(eig_apply(cx, w.buf[iY], ba, w.buf[iN], -c * 2.0 * sn / e, 2.0 * sn / e, w.buf[iX], -sig * sn));
+    ++cx.nspmm;
+    const int t = iX; iX = iY; iY = iN; iN = t;
+    sig = sn;
+  }
+  // filtered active block in iY; L (filtered) into iN; both back into the active columns of V / L V
+  MGP_TRY(eig_apply(cx, w.buf[iY], ba, w.buf[iN], 0.0, 1.0));
+  ++cx.nspmm;
+  eig_move_cols(cx, w.buf[iY], ba, 0, ba, w.buf[cx.bV], b, nlock);
+  eig_move_cols(cx, w.buf[iN], ba, 0, ba, w.buf[cx.bLV], b, nlock);
+  MGP_LAUNCH_CHECK();
+  // ---- Rayleigh-Ritz: G = V^T V, H = V^T L V (fp64), generalized eigenproblem on the host
+  MGP_TRY(launch_gram(w.buf[cx.bV], w.buf[cx.bV], cx.n, b, w, w.G, cx.st));
+  MGP_TRY(launch_gram(w.buf[cx.bV], w.buf[cx.bLV], cx.n, b, w, w.H, cx.st));
+  cx.tr1 = HostClock::now();   // everything of this round is queued; the copies of the Rayleigh-Ritz step wait for it
+  return MGP_OK;
+}
+
+// The Rayleigh-Ritz step on the filtered block: Gram blocks to the host, rayleigh_ritz_host, rotation V <- V W and L V <- L V W
+// on the MFMA kernel, residuals into cx.res.  *fresh: the Ritz values proved the estimated bound short -- the policy is back on
+// Gershgorin, the block is a fresh random one and nothing was rotated.
+int eig_ritz_rotate(EigCtx& cx, bool* fresh) {
+  EigWork& w = cx.w;
+  const int64_t n = cx.n;
+  const int b = cx.b, outer = cx.rounds;
+  hipStream_t st = cx.st;
+  *fresh = false;
+  MGP_HIP_TRY(hipMemcpyAsync(cx.G.data(), w.G, (size_t)b * b * sizeof(double), hipMemcpyDeviceToHost, st));
+  MGP_HIP_TRY(hipMemcpyAsync(cx.H.data(), w.H, (size_t)b * b * sizeof(double), hipMemcpyDeviceToHost, st));
+  MGP_HIP_TRY(hipStreamSynchronize(st));
+  const auto tp0 = HostClock::now();
+  if (!rayleigh_ritz_host(b, cx.G, cx.H, *cx.pool, cx.rr)) return MGP_ERR_NOT_CONVERGED;
+  const auto tp4 = HostClock::now();
+  const int kept = cx.rr.kept;
+  const double top = cx.rr.th[kept - 1];
+  if (eig_bound_short(cx.pol, top)) {
+    if (cx.trace)
+      fprintf(stderr, "[eig] round %d: largest Ritz value %.5g against the estimated bound %.5g: back to Gershgorin %.5g\n", outer,
+              top, cx.pol.ubf, cx.pol.ub);
+    MGP_TRY(eig_random_cols(cx, w.buf[cx.bV], 0, b, cx.seed + 104729ULL * (outer + 1)));
+    cx.pol = eig_cold_start(cx.pol.ub, cx.pol.ub, cx.user_degree);
+    *fresh = true;
+    return MGP_OK;
+  }
+  if (cx.trace)
+    fprintf(stderr, "[eig] round %d: whiten %.2f  HT/Hp %.2f  eigh(Hp) %.2f  W %.2f ms\n", outer, cx.rr.ms[0], cx.rr.ms[1], cx.rr.ms[2],
+            cx.rr.ms[3]);
+  MGP_HIP_TRY(hipMemcpyAsync(w.wt, cx.rr.wt.data(), (size_t)b * b * sizeof(float), hipMemcpyHostToDevice, st));
+  MGP_HIP_TRY(hipMemcpyAsync(w.theta, cx.rr.thf.data(), b * sizeof(float), hipMemcpyHostToDevice, st));
+  // ---- rotate on the MFMA: Vn = V W, LVn = LV W   (K = Z1 Z2^T with Z2 = W^T)
+  const int iVn = cx.c0, iLVn = cx.c1;
+  MGP_TRY(mgp_kernel_block_ld(w.buf[cx.bV], n, w.wt, b, b, 1.f, w.buf[iVn], b, cx.stream));
+  MGP_TRY(mgp_kernel_block_ld(w.buf[cx.bLV], n, w.wt, b, b, 1.f, w.buf[iLVn], b, cx.stream));
+  hipLaunchKernelGGL(residual_kernel, dim3(w.rchunks), dim3(kBlock), 0, st, w.buf[iLVn], w.buf[iVn], w.theta, n, b,
+                     w.rrows, w.rpart);
+  MGP_LAUNCH_CHECK();
+  MGP_HIP_TRY(hipMemcpyAsync(cx.rp.data(), w.rpart, (size_t)w.rchunks * b * sizeof(double), hipMemcpyDeviceToHost, st));
+  MGP_HIP_TRY(hipStreamSynchronize(st));
+  if (cx.trace)
+    fprintf(stderr, "[eig] round %d: enqueue %.2f  filter + Gram on the GPU (wait) %.2f  host %.2f  rotate + residual %.2f ms\n", outer,
+            host_ms(cx.tr0, cx.tr1), host_ms(cx.tr1, tp0), host_ms(tp0, tp4), host_ms(tp4, HostClock::now()));
+  for (int j = 0; j < b; ++j) {
+    double s = 0.0;
+    for (int cch = 0; cch < w.rchunks; ++cch) s += cx.rp[(size_t)cch * b + j];
+    cx.res[j] = sqrt(s);
+  }
+  if (kept < b)     // refill dropped directions with fresh random vectors (their L V column is rebuilt by
+                    // the next round's filter: dropped directions sit at the end, locked ones at the start)
+    MGP_TRY(eig_random_cols(cx, w.buf[iVn], kept, b, cx.seed + 7919ULL * (outer + 1)));
+  { const int ov = cx.bV, olv = cx.bLV; cx.bV = iVn; cx.bLV = iLVn; cx.c0 = ov; cx.c1 = olv; }
+  return MGP_OK;
+}
+
+void eig_trace_step(const EigCtx& cx, const EigStep& s) {
+  const int outer = cx.rounds, m = cx.m;
+  fprintf(stderr, "[eig] round %d: deg %d, converged %d of %d (leading run %d), max resid %.3e (tol*ub %.3e)\n", outer,
+          cx.deg_used, s.nconv, m, s.lead, s.rmx, cx.tol * cx.pol.ub);
+  if (s.ruled)
+    fprintf(stderr, "[eig] round %d: a %.4e  theta_m %.4e  gap %.3e  exponent %.2f (finish %.2f, safe %.2f)  degree asked %d (e^-3: %d)\n",
+            outer, cx.pol.a, cx.rr.th[m - 1], s.gap, s.target, s.t_fin, s.t_safe, s.dask, s.dnew);
+}
+
+int eig_write_outputs(EigCtx& cx) {
+  const int64_t n = cx.n;
+  const int m = cx.m, b = cx.b, kept = cx.rr.kept;
+  const float* V = cx.w.buf[cx.bV];
+  const int cgrid = (int)std::min<int64_t>(4096, mgp_cdiv(n * m, kBlock));
+  hipLaunchKernelGGL(copy_cols_kernel, dim3(cgrid), dim3(kBlock), 0, cx.st, V, n, b, m, cx.evecs);
+  MGP_LAUNCH_CHECK();
+  if (cx.block_evecs) {     // the whole Rayleigh-Ritz block, guard columns included: [n, b] row-major
+    const int bgrid = (int)std::min<int64_t>(4096, mgp_cdiv(n * b, kBlock));
+    hipLaunchKernelGGL(copy_cols_kernel, dim3(bgrid), dim3(kBlock), 0, cx.st, V, n, b, b, cx.block_evecs);
+    MGP_LAUNCH_CHECK();
+  }
+  MGP_HIP_TRY(hipStreamSynchronize(cx.st));
+  for (int j = 0; j < m; ++j) {
+    cx.evals[j] = (kept >= m) ? (float)cx.rr.th[j] : 0.f;
+    if (cx.resid) cx.resid[j] = (float)cx.res[j];
+  }
+  for (int j = 0; j < b; ++j) {
+    if (cx.block_evals) cx.block_evals[j] = j < kept ? (float)cx.rr.th[j] : 0.f;
+    if (cx.block_resid) cx.block_resid[j] = (float)cx.res[j];
+  }
+  return MGP_OK;
+}
+
+// One solve of at most max_outer rounds on the carved workspace, from the warm block (nullable: random start) to the outputs.
+// Leaves rounds, nspmm, nconv and floor_hit in cx.
+int eig_solve(EigCtx& cx, const float* warm_block, const float* warm_evals, int max_outer) {
+  MGP_TRY(eig_bounds(cx));
+  cx.bV = 0; cx.bLV = 1; cx.c0 = 2; cx.c1 = 3; cx.c2 = 4;
+  if (warm_block) MGP_HIP_TRY(hipMemcpyAsync(cx.w.buf[0], warm_block, (size_t)cx.n * cx.b * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
+  else MGP_TRY(eig_random_cols(cx, cx.w.buf[0], 0, cx.b, cx.seed));
+  if (warm_block && warm_evals) eig_warm_start(cx.pol, warm_evals, cx.b, cx.m, cx.user_degree);
+  cx.nspmm = 0; cx.nconv = 0; cx.deg_used = 0; cx.floor_hit = false;
+  cx.res.assign(cx.b, 1e300);
+  cx.rr.kept = cx.b;
+  for (cx.rounds = 0; cx.rounds < max_outer; ++cx.rounds) {
+    bool fresh;
+    MGP_TRY(eig_filter_round(cx));
+    MGP_TRY(eig_ritz_rotate(cx, &fresh));
+    cx.nconv = 0;
+    if (fresh) continue;
+    const EigStep s = eig_round_step(cx.pol, cx.rr.th.data(), cx.res.data(), cx.m, cx.b, cx.rr.kept, cx.tol, cx.n, cx.deg_used,
+                                     !!cx.L->mt_img, cx.user_degree, cx.lab ? &cx.lab_target : nullptr);
+    cx.nconv = s.nconv;
+    if (cx.trace && cx.rr.kept >= cx.m) eig_trace_step(cx, s);
+    if (s.verdict != EIG_CONTINUE) { cx.floor_hit = s.verdict == EIG_FLOOR; ++cx.rounds; break; }
+  }
+  return eig_write_outputs(cx);
+}
+
+}  // namespace
+
+static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_params_t* p, float* evals, float* evecs, float* resid,
+                                 int32_t* info, float* block_evals, float* block_evecs, float* block_resid, const float* warm_block,
+                                 const float* warm_evals, void* work, size_t work_bytes, void* stream) {
+  EigCtx cx;
+  cx.evals = evals; cx.evecs = evecs; cx.resid = resid;
+  cx.block_evals = block_evals; cx.block_evecs = block_evecs; cx.block_resid = block_resid;
+  MGP_TRY(eig_setup(cx, L, m, p, work, work_bytes, stream));
+  HostPool pool(host_pool_workers());      // lives for this call: joined on every return path
+  cx.pool = &pool;
+  const int max_outer = (p && p->max_restarts > 0) ? p->max_restarts : 40;
+  int warm_rounds = 0, warm_nspmm = 0;
+  if (warm_block) {
+    // a warm start that has not converged within four rounds was not close enough (the matrix moved too far, or the wanted block
+    // sits in a cluster that no start resolves): the solve is then repeated from a cold start, with its own floor exits, and the
+    // rounds / block products of the abandoned warm attempt are added to the report
+    MGP_TRY(eig_solve(cx, warm_block, warm_evals, 4));
+    if (cx.nconv != m) { warm_rounds = cx.rounds; warm_nspmm = cx.nspmm; }
+  }
+  if (!warm_block || cx.nconv != m) MGP_TRY(eig_solve(cx, nullptr, nullptr, max_outer));
+  if (info) { info[0] = cx.rounds + warm_rounds; info[1] = cx.nspmm + warm_nspmm; info[2] = cx.nconv; info[3] = cx.b; }
+  if (cx.nconv == m) return MGP_OK;
+  return cx.floor_hit ? MGP_OK : MGP_ERR_NOT_CONVERGED;
+}
 
 // G = A^T A (b x b, fp64 accumulation of the fp32 entries' exact products) for a tall block A [n, b]:
 // the Gram kernel of the eigensolver behind the C-ABI.  rocBLAS' dgemm takes 53 ms for this shape at
@@ -802,7 +715,7 @@ extern "C" int mgp_host_symeig(int n, const double* A, double* evals, double* V)
   if (n <= 0 || !A || !evals || !V) return MGP_ERR_ARG;
   std::vector<double> a(A, A + (size_t)n * n), ev, vv;
   HostPool pool(n >= 64 ? host_pool_workers() : 0);      // as inside the block eigensolver
-  jacobi_eigh(n, a, ev, vv, &pool);
+  host_symeigh(n, a, ev, vv, &pool);
   memcpy(evals, ev.data(), (size_t)n * sizeof(double));
   memcpy(V, vv.data(), (size_t)n * n * sizeof(double));
   return MGP_OK;
@@ -826,10 +739,6 @@ extern "C" int mgp_lanczos_smallest(const mgp_csr_t* L, int m, const mgp_lanczos
   return mgp_lanczos_smallest_ex(L, m, p, evals, evecs, resid, info, nullptr, nullptr, nullptr, work, work_bytes, stream);
 }
 
-static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_params_t* p, float* evals, float* evecs, float* resid,
-                                 int32_t* info, float* block_evals, float* block_evecs, float* block_resid, const float* warm_block,
-                                 const float* warm_evals, void* work, size_t work_bytes, void* stream);
-
 extern "C" int mgp_lanczos_smallest_ex(const mgp_csr_t* L, int m, const mgp_lanczos_params_t* p, float* evals,
                                        float* evecs, float* resid, int32_t* info, float* block_evals, float* block_evecs,
                                        float* block_resid, void* work, size_t work_bytes, void* stream) {
@@ -849,423 +758,6 @@ extern "C" int mgp_lanczos_smallest_warm(const mgp_csr_t* L, int m, const mgp_la
   if (!warm_block || !warm_evals) return MGP_ERR_ARG;
   return lanczos_smallest_impl(L, m, p, evals, evecs, resid, info, block_evals, block_evecs, block_resid, warm_block, warm_evals, work,
                                work_bytes, stream);
-}
-
-static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_params_t* p, float* evals, float* evecs, float* resid,
-                                 int32_t* info, float* block_evals, float* block_evecs, float* block_resid, const float* warm_block,
-                                 const float* warm_evals, void* work, size_t work_bytes, void* stream) {
-  if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !evals || !evecs || !work) return MGP_ERR_ARG;
-  if (!mgp_spmv_lanes_ok(L->spmv_lanes)) return MGP_ERR_ARG;
-  const int64_t n = L->n;
-  if (n <= 0 || m <= 0 || m > n) return MGP_ERR_ARG;
-  int b = block_size_for(m, p);
-  if (b > n) b = (int)n;
-  if (b > 256) return MGP_ERR_UNSUPPORTED;   // one SpMM launch handles <= 256 columns
-  if (work_bytes < eig_bytes(n, m, p)) return MGP_ERR_WORKSPACE;
-  hipStream_t st = mgp_stream(stream);
-  const float tol = (p && p->tol > 0.f) ? p->tol : 1e-5f;
-  // a warm start that has not converged within four rounds was not close enough (the matrix moved too far, or the wanted block
-  // sits in a cluster that no start resolves): the solve is then repeated from a cold start, with its own floor exits
-  const int max_outer = warm_block ? 4 : ((p && p->max_restarts > 0) ? p->max_restarts : 40);
-  const uint64_t seed = p ? p->seed : 1337;
-
-  EigWork w;
-  MgpArena ar(work, work_bytes);
-  for (int i = 0; i < 5; ++i) w.buf[i] = ar.take<float>((size_t)n * b);
-  chunking(n, &w.chunks, &w.rows_per_chunk, 96, 512);
-  chunking(n, &w.rchunks, &w.rrows, 256, 256);
-  w.gpart = ar.take<double>((size_t)w.chunks * b * b);
-  w.G = ar.take<double>((size_t)b * b);
-  w.H = ar.take<double>((size_t)b * b);
-  w.rpart = ar.take<double>((size_t)w.rchunks * b);
-  w.wt = ar.take<float>((size_t)b * b);
-  w.theta = ar.take<float>(b);
-  w.bmax = ar.take<float>(1024);
-  if (!ar.ok()) return MGP_ERR_WORKSPACE;
-
-  // ---- spectrum upper bound (Gershgorin: always >= lambda_max)
-  const int gb = (int)std::min<int64_t>(1024, mgp_cdiv(n, kBlock));
-  hipLaunchKernelGGL(gershgorin_kernel, dim3(gb), dim3(kBlock), 0, st, n, L->rowptr, L->vals, L->diag, w.bmax);
-  MGP_LAUNCH_CHECK();
-  std::vector<float> hb(gb);
-  MGP_HIP_TRY(hipMemcpyAsync(hb.data(), w.bmax, gb * sizeof(float), hipMemcpyDeviceToHost, st));
-  MGP_HIP_TRY(hipStreamSynchronize(st));
-  double ub = 0.0;
-  for (float v : hb) ub = std::max(ub, (double)v);
-  ub *= 1.0 + 1e-6;
-  if (!(ub > 0.0)) return MGP_ERR_ARG;
-
-  // ---- the filter's upper end.  Gershgorin is rigorous and loose: on the k-NN graph Laplacians of this package lambda_max
-  // is about HALF of it (60k RMNIST-like graph: 15.4 of 29.7; 1M swiss roll: 649 of 1239), and the degree a Chebyshev filter
-  // needs grows with sqrt(ub - a) -- a bound twice too large costs 40 % more applies.  So: a 32-dimensional Krylov space of
-  // one random vector in the Chebyshev basis of [0, ub] (the same fused three-term SpMV launches as the filter, C = 1; the
-  // basis stays bounded and well conditioned, unlike the monomials), Rayleigh-Ritz with the Gram kernels, the largest
-  // Ritz value theta_32 <= lambda_max; the filter gets theta_32 + max(3 %, twice what the last 16 dimensions still moved).
-  // The residual test keeps the Gershgorin bound as its norm of L, so `tol` means what it meant.  An estimate that fell
-  // short would let the filter AMPLIFY the top of the spectrum; that shows as a Ritz value above the supposed bound in
-  // the next Rayleigh-Ritz step and is answered there (Gershgorin, fresh block).
-  double ubf = ub;
-  const int kk = 32;
-  const int bound_mode = g_eig_bound_mode;      // (lab switch: read once per call)
-  if (bound_mode && b >= kk && n >= 8 * kk) {
-    float* K = w.buf[0];
-    float* LK = w.buf[1];
-    float* KT = w.buf[2];          // the kk Krylov vectors one after the other (b >= kk columns of room): vector j at KT + j n
-    const int g1 = (int)std::min<int64_t>(4096, mgp_cdiv(n, kBlock));
-    hipLaunchKernelGGL(random_cols_kernel, dim3(g1), dim3(kBlock), 0, st, KT, n, 1, 0, 1, seed ^ 0x5bd1e995ULL);
-    MGP_LAUNCH_CHECK();
-    const double ce = ub / 2.0;     // centre = half width of [0, ub]
-    // T_1 = (L - c) / e
-    MGP_TRY(mgp_spmm_fused(L, KT, 1, KT + n, (float)(-1.0), (float)(1.0 / ce), nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
-                           nullptr, stream));
-    for (int j = 2; j < kk; ++j) {
-      // T_j = 2 (L - c) / e T_{j-1} - T_{j-2}, written where it stays (round 5: no column copy behind every launch)
-      MGP_TRY(mgp_spmm_fused(L, KT + (int64_t)(j - 1) * n, 1, KT + (int64_t)j * n, (float)(-2.0), (float)(2.0 / ce), nullptr, nullptr,
-                             KT + (int64_t)(j - 2) * n, -1.f, 1.f, nullptr, nullptr, stream));
-    }
-    hipLaunchKernelGGL(vecs_to_cols_kernel, dim3((unsigned)mgp_cdiv(n, 64)), dim3(256), 0, st, KT, n, kk, K);
-    MGP_LAUNCH_CHECK();
-    MGP_TRY(mgp_spmm_fused(L, K, kk, LK, 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, stream));
-    MGP_TRY(launch_gram(K, K, n, kk, w, w.G, st));
-    MGP_TRY(launch_gram(K, LK, n, kk, w, w.H, st));
-    std::vector<double> Gk((size_t)kk * kk), Hk((size_t)kk * kk);
-    MGP_HIP_TRY(hipMemcpyAsync(Gk.data(), w.G, (size_t)kk * kk * sizeof(double), hipMemcpyDeviceToHost, st));
-    MGP_HIP_TRY(hipMemcpyAsync(Hk.data(), w.H, (size_t)kk * kk * sizeof(double), hipMemcpyDeviceToHost, st));
-    MGP_HIP_TRY(hipStreamSynchronize(st));
-    const double th_full = top_ritz(kk, kk, Gk, Hk), th_half = top_ritz(kk, kk / 2, Gk, Hk);
-    if (std::isfinite(th_full) && std::isfinite(th_half) && th_full > 0.0) {
-      const double cand = th_full + std::max(0.03 * th_full, 2.0 * fabs(th_full - th_half));
-      if (cand < ub) ubf = cand;
-      if (bound_mode == 2) ubf = 0.5 * th_full;
-    }
-    if (getenv("MGP_EIG_TIMING"))
-      fprintf(stderr, "[eig] upper end: Gershgorin %.5g, Krylov(32) theta %.5g (16: %.5g) -> filter bound %.5g\n", ub, th_full, th_half, ubf);
-  }
-
-  const int rgrid = (int)std::min<int64_t>(4096, mgp_cdiv(n * b, kBlock));
-  if (warm_block) {
-    MGP_HIP_TRY(hipMemcpyAsync(w.buf[0], warm_block, (size_t)n * b * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else {
-    hipLaunchKernelGGL(random_cols_kernel, dim3(rgrid), dim3(kBlock), 0, st, w.buf[0], n, b, 0, b, seed);
-    MGP_LAUNCH_CHECK();
-  }
-
-  // Buffers: bV / bLV hold the current block V and L V (full width b); three more serve the filter.
-  // Soft locking: the leading run of converged Ritz vectors (a multiple of 4 columns) is no longer filtered --
-  // the Chebyshev recurrence and the L apply run on the remaining `ba` columns, compacted to an [n, ba]
-  // block -- but stays in the Rayleigh-Ritz basis, so it keeps being refined and the block stays orthogonal.
-  int bV = 0, bLV = 1, c0 = 2, c1 = 3, c2 = 4;
-  int nlock = 0;
-  // Degree cap: 200 was tuned with the Gershgorin bound as the filter's upper end (80: 8 rounds / 497 applies at m = 100, 200:
-  // 4 / 343, 300: 4 / 443).  What a degree buys goes with 1 / sqrt(ub - a), so under a tighter bound the same filter strength
-  // is degree 200 sqrt(ubf / ub) (146 when lambda_max is half of Gershgorin); more only over-solves the last round (60k graph,
-  // cap 120 / 146 / 200 / 240: 247 / 273 / 327 / 367 applies for residuals 2.7 / 2.6 / 1.9 / 1.9e-4, tolerance 3.0e-4).
-  int kCap = std::max(100, std::min(200, (int)lround(200.0 * sqrt(ubf / ub))));
-  double a = ubf / 4.0, a0 = 0.0;
-  double top_prev = 1e300;      // largest Ritz value of the previous round's block (they only come down)
-  int deg = (p && p->degree > 0) ? p->degree : 10;
-  if (warm_block && warm_evals && b > m) {
-    // the warm block's own Ritz values stand in for a first Rayleigh-Ritz round (a little margin on the interval's lower end: the
-    // matrix has moved since they were computed)
-    const double top = (double)warm_evals[b - 1], thm = (double)warm_evals[m - 1];
-    if (std::isfinite(top) && top > 0.0 && top < ubf && std::isfinite(thm) && thm < top) {
-      a = std::min(0.5 * (top + ubf), 1.02 * top);
-      a0 = std::min((double)warm_evals[0], 0.0);
-      const double gap = std::max(a - thm, 1e-12 * ub);
-      const int dnew = (int)ceil(3.0 / (2.0 * sqrt(gap / (ubf - a))));
-      if (!(p && p->degree > 0)) deg = std::min(std::max(dnew, 8), kCap);
-    }
-  }
-  HostPool pool(host_pool_workers());      // lives for this call: joined on every return path
-  std::vector<double> G((size_t)b * b), H((size_t)b * b), th, S, lam, U;
-  std::vector<float> wt((size_t)b * b), thf(b);
-  std::vector<double> rp((size_t)w.rchunks * b), res(b, 1e300);
-  int outer = 0, nspmm = 0, nconv = 0, kept = b;
-  double rmax_prev1 = 1e300;
-  int nconv_prev1 = 0, deg_used = 0;
-  bool floor_hit = false;
-  // the two early exits below hand the block back with MGP_OK and info[2] < m; they apply only once the largest residual
-  // is within 50 x the tolerance asked for, or within 10 x the measured fp32 floor (1.8e-6 ub, see there) for tolerances
-  // below it -- a block further out than that is NOT "at the floor" and keeps iterating / ends as MGP_ERR_NOT_CONVERGED
-  const double floor_guard = std::max(50.0 * tol, 2e-5);
-  auto move_cols = [&](const float* src, int sld, int sc0, int mcols, float* dst, int dld, int dc0) {
-    const int grid = (int)std::min<int64_t>(4096, mgp_cdiv(n * mcols, kBlock));
-    hipLaunchKernelGGL(move_cols_kernel, dim3(grid), dim3(kBlock), 0, st, src, n, sld, sc0, mcols, dst, dld, dc0);
-  };
-  for (outer = 0; outer < max_outer; ++outer) {
-    // ---- scaled Chebyshev filter of degree `deg` damping [a, ub], normalised at a0, on the active columns
-    const auto tr0 = std::chrono::steady_clock::now();
-    const int ba = b - nlock;
-    deg_used = deg;
-    const double e = (ubf - a) / 2.0, c = (ubf + a) / 2.0;
-    double sig = e / (a0 - c);
-    const double tau = 2.0 / sig;
-    int iX = c0, iY = c1, iN = c2;
-    move_cols(w.buf[bV], b, nlock, ba, w.buf[iX], ba, 0);
-    MGP_LAUNCH_CHECK();
-    // Y = (sig/e) (L X - c X)
-    MGP_TRY(mgp_spmm_fused(L, w.buf[iX], ba, w.buf[iY], (float)(-c * sig / e), (float)(sig / e), nullptr, nullptr,
-                           nullptr, 0.f, 1.f, nullptr, nullptr, stream));
-    ++nspmm;
-    for (int i = 2; i <= deg; ++i) {
-      const double sn = 1.0 / (tau - sig);
-      // Ynew = (2 sn / e) (L Y - c Y) - (sig sn) X
-      MGP_TRY(mgp_spmm_fused(L, w.buf[iY], ba, w.buf[iN], (float)(-c * 2.0 * sn / e), (float)(2.0 * sn / e),
-                             nullptr, nullptr, w.buf[iX], (float)(-sig * sn), 1.f, nullptr, nullptr, stream));
-      ++nspmm;
-      const int t = iX; iX = iY; iY = iN; iN = t;
-      sig = sn;
-    }
-    // filtered active block in iY; L (filtered) into iN; both back into the active columns of V / L V
-    MGP_TRY(mgp_spmm_fused(L, w.buf[iY], ba, w.buf[iN], 0.f, 1.f, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr,
-                           nullptr, stream));
-    ++nspmm;
-    move_cols(w.buf[iY], ba, 0, ba, w.buf[bV], b, nlock);
-    move_cols(w.buf[iN], ba, 0, ba, w.buf[bLV], b, nlock);
-    MGP_LAUNCH_CHECK();
-    const int iF = bV, iLV = bLV, iVn = c0, iLVn = c1;
-    // ---- Rayleigh-Ritz: G = V^T V, H = V^T L V (fp64), generalized eigenproblem on the host
-    MGP_TRY(launch_gram(w.buf[iF], w.buf[iF], n, b, w, w.G, st));
-    MGP_TRY(launch_gram(w.buf[iF], w.buf[iLV], n, b, w, w.H, st));
-    const auto tr1 = std::chrono::steady_clock::now();   // everything of this round is queued; the copies below wait for it
-    MGP_HIP_TRY(hipMemcpyAsync(G.data(), w.G, (size_t)b * b * sizeof(double), hipMemcpyDeviceToHost, st));
-    MGP_HIP_TRY(hipMemcpyAsync(H.data(), w.H, (size_t)b * b * sizeof(double), hipMemcpyDeviceToHost, st));
-    MGP_HIP_TRY(hipStreamSynchronize(st));
-    auto tp0 = std::chrono::steady_clock::now();
-    std::vector<double> dg(b);
-    for (int i = 0; i < b; ++i) {
-      const double g = G[(size_t)i * b + i];
-      if (!(g > 0.0) || !std::isfinite(g)) return MGP_ERR_NOT_CONVERGED;
-      dg[i] = 1.0 / sqrt(g);
-    }
-    std::vector<double> Gn((size_t)b * b);
-    for (int i = 0; i < b; ++i)
-      for (int j = 0; j < b; ++j) Gn[(size_t)i * b + j] = 0.5 * (G[(size_t)i * b + j] + G[(size_t)j * b + i]) * dg[i] * dg[j];
-    // whitening T (b x kept) with T^T G T = I: Cholesky Gn = C C^T, T = D C^-T (0.2 ms); a block that has
-    // (nearly) dependent columns -- pivot ratio under 1e-5, i.e. cond(Gn) ~ 1e10 -- takes the rank-revealing
-    // eigendecomposition instead (3 ms) and drops the dependent directions
-    std::vector<double> T;
-    bool tri = true;
-    if (cholesky_whiten(b, Gn, dg, T)) {
-      kept = b;
-    } else {
-      tri = false;
-      jacobi_eigh(b, Gn, lam, U, &pool);
-      const double lmax = lam[b - 1];
-      int k0 = 0;
-      while (k0 < b && lam[k0] <= 1e-10 * lmax) ++k0;
-      kept = b - k0;
-      // T = D U[:, k0:] Lambda^-1/2   (b x kept)
-      T.assign((size_t)b * kept, 0.0);
-      for (int i = 0; i < b; ++i)
-        for (int j = 0; j < kept; ++j) T[(size_t)i * kept + j] = dg[i] * U[(size_t)i * b + k0 + j] / sqrt(lam[k0 + j]);
-    }
-    auto tp1 = std::chrono::steady_clock::now();
-    // Hp = T^T Hs T   (rows of the outputs are independent: jobs of 8 rows on the pool, fixed order inside).  After the
-    // Cholesky whitening T is upper triangular (tri): T[l][j] = 0 for j < l, which leaves 1/2 and 1/3 of the two products.
-    std::vector<double> HT((size_t)b * kept, 0.0), Hp((size_t)kept * kept, 0.0);
-    pool.rows(b, 8, [&](int i) {
-      double* __restrict__ o = &HT[(size_t)i * kept];
-      for (int l = 0; l < b; ++l) {
-        const double h = 0.5 * (H[(size_t)i * b + l] + H[(size_t)l * b + i]);
-        if (h == 0.0) continue;
-        const double* __restrict__ t = &T[(size_t)l * kept];
-        for (int j = tri ? l : 0; j < kept; ++j) o[j] += h * t[j];
-      }
-    });
-    pool.rows(kept, 8, [&](int j) {
-      double* __restrict__ o = &Hp[(size_t)j * kept];
-      const int i1 = tri ? j + 1 : b;
-      for (int i = 0; i < i1; ++i) {
-        const double t = T[(size_t)i * kept + j];
-        const double* __restrict__ h = &HT[(size_t)i * kept];
-        for (int l = 0; l < kept; ++l) o[l] += t * h[l];
-      }
-    });
-    auto tp2 = std::chrono::steady_clock::now();
-    jacobi_eigh(kept, Hp, th, S, &pool);
-    auto tp3 = std::chrono::steady_clock::now();
-    // The estimated upper end fell short if a Ritz value lies above it (proof: Ritz values never exceed lambda_max), or if
-    // the block's largest Ritz value, which only comes down from round to round, jumps up towards the top of the spectrum
-    // (the filter amplified what it should have damped).  Then: Gershgorin from here on and a fresh block.
-    if (ubf < ub && (th[kept - 1] > ubf * (1.0 + 1e-3) || (th[kept - 1] > 2.0 * top_prev && th[kept - 1] > 0.25 * ubf))) {
-      if (getenv("MGP_EIG_TIMING"))
-        fprintf(stderr, "[eig] round %d: largest Ritz value %.5g against the estimated bound %.5g: back to Gershgorin %.5g\n", outer,
-                th[kept - 1], ubf, ub);
-      ubf = ub;
-      kCap = 200;
-      hipLaunchKernelGGL(random_cols_kernel, dim3(rgrid), dim3(kBlock), 0, st, w.buf[bV], n, b, 0, b, seed + 104729ULL * (outer + 1));
-      MGP_LAUNCH_CHECK();
-      nlock = 0;
-      a = ub / 4.0;
-      a0 = 0.0;
-      deg = (p && p->degree > 0) ? p->degree : 10;
-      top_prev = 1e300;
-      rmax_prev1 = 1e300;
-      nconv_prev1 = 0;
-      nconv = 0;
-      continue;
-    }
-    top_prev = th[kept - 1];
-    // W = T S (b x kept); upload W^T rows = Ritz directions, zero-padded to b
-    std::fill(wt.begin(), wt.end(), 0.f);
-    pool.rows(b, 8, [&](int i) {
-      std::vector<double> acc(kept, 0.0);
-      for (int l = tri ? i : 0; l < kept; ++l) {
-        const double t = T[(size_t)i * kept + l];
-        const double* __restrict__ sr = &S[(size_t)l * kept];
-        for (int j = 0; j < kept; ++j) acc[j] += t * sr[j];
-      }
-      for (int j = 0; j < kept; ++j) wt[(size_t)j * b + i] = (float)acc[j];
-    });
-    for (int j = 0; j < b; ++j) thf[j] = j < kept ? (float)th[j] : 0.f;
-    auto tp4 = std::chrono::steady_clock::now();
-    if (getenv("MGP_EIG_TIMING")) {
-      auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-      fprintf(stderr, "[eig] round %d: whiten %.2f  HT/Hp %.2f  eigh(Hp) %.2f  W %.2f ms\n", outer, ms(tp0, tp1), ms(tp1, tp2),
-              ms(tp2, tp3), ms(tp3, tp4));
-    }
-    MGP_HIP_TRY(hipMemcpyAsync(w.wt, wt.data(), (size_t)b * b * sizeof(float), hipMemcpyHostToDevice, st));
-    MGP_HIP_TRY(hipMemcpyAsync(w.theta, thf.data(), b * sizeof(float), hipMemcpyHostToDevice, st));
-    // ---- rotate on the MFMA: Vn = V W, LVn = LV W   (K = Z1 Z2^T with Z2 = W^T)
-    MGP_TRY(mgp_kernel_block_ld(w.buf[iF], n, w.wt, b, b, 1.f, w.buf[iVn], b, stream));
-    MGP_TRY(mgp_kernel_block_ld(w.buf[iLV], n, w.wt, b, b, 1.f, w.buf[iLVn], b, stream));
-    hipLaunchKernelGGL(residual_kernel, dim3(w.rchunks), dim3(kBlock), 0, st, w.buf[iLVn], w.buf[iVn], w.theta, n, b,
-                       w.rrows, w.rpart);
-    MGP_LAUNCH_CHECK();
-    MGP_HIP_TRY(hipMemcpyAsync(rp.data(), w.rpart, (size_t)w.rchunks * b * sizeof(double), hipMemcpyDeviceToHost, st));
-    MGP_HIP_TRY(hipStreamSynchronize(st));
-    if (getenv("MGP_EIG_TIMING")) {
-      auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-      const auto tr2 = std::chrono::steady_clock::now();
-      fprintf(stderr, "[eig] round %d: enqueue %.2f  filter + Gram on the GPU (wait) %.2f  host %.2f  rotate + residual %.2f ms\n", outer, ms(tr0, tr1), ms(tr1, tp0),
-              ms(tp0, tp4), ms(tp4, tr2));
-    }
-    for (int j = 0; j < b; ++j) {
-      double s = 0.0;
-      for (int cch = 0; cch < w.rchunks; ++cch) s += rp[(size_t)cch * b + j];
-      res[j] = sqrt(s);
-    }
-    if (kept < b) {   // refill dropped directions with fresh random vectors (their L V column is rebuilt by
-                      // the next round's filter: dropped directions sit at the end, locked ones at the start)
-      hipLaunchKernelGGL(random_cols_kernel, dim3(rgrid), dim3(kBlock), 0, st, w.buf[iVn], n, b, kept, b,
-                         seed + 7919ULL * (outer + 1));
-      MGP_LAUNCH_CHECK();
-    }
-    { const int ov = bV, olv = bLV; bV = iVn; bLV = iLVn; c0 = ov; c1 = olv; }
-    nconv = 0;
-    nlock = 0;
-    if (kept >= m) {
-      for (int j = 0; j < m; ++j) nconv += (res[j] <= tol * ub) ? 1 : 0;
-      if (getenv("MGP_EIG_TIMING")) {
-        int lead = 0;
-        while (lead < m && res[lead] <= tol * ub) ++lead;
-        double rmx = 0.0;
-        for (int j = 0; j < m; ++j) rmx = std::max(rmx, res[j]);
-        fprintf(stderr, "[eig] round %d: deg %d, converged %d of %d (leading run %d), max resid %.3e (tol*ub %.3e)\n", outer,
-                deg, nconv, m, lead, rmx, tol * ub);
-      }
-      if (nconv == m) { ++outer; break; }
-      // The attainable residual of an fp32 iteration is a few ulp of |L| (the SpMM's own rounding: measured 1.8e-6 ub on
-      // the 60k RMNIST-like graph, 7e-8 ub on the smooth modes of the dumbbell): a tolerance under that floor can never
-      // be met, and the rounds past it only shuffle round-off (60 rounds / 1.3 s where 5 reach the floor).  With the
-      // filter at its degree cap a round multiplies the error of the slowest wanted pair by <= e^-3 unless the gap
-      // behind the block is tiny; a round at the cap that does not even halve the largest residual, with no further
-      // pair converging, is therefore taken as the floor: the caller gets the block as it stands, the true residuals in
-      // `resid`, info[2] = pairs under tol (< m) and MGP_OK.
-      {
-        double rmx = 0.0;
-        for (int j = 0; j < m; ++j) rmx = std::max(rmx, res[j]);
-        if (deg_used >= kCap && rmx > 0.5 * rmax_prev1 && nconv <= nconv_prev1 && rmx <= floor_guard * ub) { floor_hit = true; ++outer; break; }
-        rmax_prev1 = rmx;
-        nconv_prev1 = nconv;
-      }
-      {
-        int lead = 0;
-        while (lead < m && res[lead] <= tol * ub) ++lead;
-        nlock = lead / 4 * 4;
-        if (b - nlock < 8) nlock = 0;
-        // the matrix-core tile SpMM serves 48 columns and more: a block locked down to fewer active columns falls back to the gather
-        // kernel, whose 28 columns cost MORE per product than 64 on the tiles (1M nodes, b = 64: 0.48 against 0.38 ms) -- keep 48
-        if (L->mt_img && b >= 48 && b - nlock < 48) nlock = (b - 48) / 4 * 4;
-      }
-      a = th[kept - 1];
-      a0 = std::min(th[0], 0.0);
-      const double gap = std::max(a - th[m - 1], 1e-12 * ub);
-      // dunit: the filter degree per unit of damping exponent at the measured gap; dnew: the degree of an e^-3 round (rounds 1-4
-      // ran every round at it; the exits below are written in it).
-      const double dunit = 1.0 / (2.0 * sqrt(gap / (ubf - a)));
-      int dnew = (int)ceil(3.0 * dunit);
-      // Round 5: a Rayleigh-Ritz round costs ~2 ms of host + Gram + rotation at b = 128 -- as much as 57 block products at 60k -- so
-      // a round should do what the arithmetic allows, and the last one no more than is left to do.  The largest wanted residual falls
-      // by ~exp(-t / 2) in a round of exponent t (measured: t = 3 / 4.5 / 9 -> x 0.22 / 0.1 / 0.01), so t_fin = 2 ln(r_max / (0.3 tol
-      // ub)) would finish; inside the wanted block the filter lifts mode 1 over mode m by exp(t (sqrt(a - th_1) - sqrt(gap)) /
-      // sqrt(gap)), which float32 columns survive up to ~1e4 (t_safe; more and mode m drops under the round-off of mode 1), and 9
-      // at most (t_cap, below).  Never less than the e^-3 round.  Conditioned 60k swiss roll: 7 rounds / 105 products / 18.3 ms -> 4 / ~120 /
-      // ~13.5 ms; RMNIST-like 60k (ends at the fp32 floor): 4 / 280 / 18.4 ms -> 3 / ~220 / ~14 ms.
-      double rmx_w = 0.0;
-      for (int j = 0; j < m; ++j) rmx_w = std::max(rmx_w, res[j]);
-      const double t_fin = 2.0 * log(std::max(rmx_w, 1e-300) / (0.3 * tol * ub));
-      const double s1 = sqrt(std::max(a - th[0], 0.0)), sm = sqrt(gap);
-      const double t_safe = s1 > sm ? log(1e4) * sm / (s1 - sm) : 9.0;
-      // ... where rounds are expensive against block products: a round is ~57 products at n b = 7.7e6 (60k x 128) but ~5 at
-      // 6.4e7 (1M x 64), where the stronger rounds only add products (530 against 438, 229 against 225 ms): the cap goes from 9
-      // under n b = 1.6e7 to the e^-3 round at 6.4e7 (logarithmically in between; deterministic, no timing involved).
-      const double nb = (double)n * (double)b;
-      const double t_cap = nb <= 1.6e7 ? 9.0 : nb >= 6.4e7 ? 3.0 : 9.0 - 6.0 * log(nb / 1.6e7) / log(4.0);
-      double target = std::min(std::max(t_fin, 3.0), std::min(t_cap, std::max(t_safe, 3.0)));
-      if (const char* e = getenv("MGP_EIG_TARGET")) target = atof(e);       // lab: fixed per-round damping exponent
-      const int dask = (int)ceil(target * dunit);
-      // degree cap 200 (80 until late in round 1: 8 rounds / 497 applies at m = 100 where 200 needs 4 / 343; the
-      // scaled three-term recurrence is normalised at a0, so the block does not overflow at these degrees)
-      deg = std::min(std::max(dask, 8), kCap);
-      if (getenv("MGP_EIG_TIMING"))
-        fprintf(stderr, "[eig] round %d: a %.4e  theta_m %.4e  gap %.3e  exponent %.2f (finish %.2f, safe %.2f)  degree asked %d (e^-3: %d)\n",
-                outer, a, th[m - 1], gap, target, t_fin, t_safe, dask, dnew);
-      if (p && p->degree > 0) deg = p->degree;
-      // The same exit, predicted instead of observed.  A round of degree d multiplies the slowest wanted pair's error by
-      // about exp(-3 d / dnew) (dnew = the degree that gives e^-3 at the measured gap between the wanted block and its
-      // last guard).  When a round at the cap has been run and the gap asks for more than ~4.3 caps (predicted factor
-      // > 0.5: the wanted modes sit in a cluster with their guards -- on the 60k RMNIST-like graph 128 Ritz values lie
-      // within 1e-6 lambda_max), every further 200-apply round would buy less than a factor 2: stop before running it
-      // (C3 at tol 1e-6: 4 rounds / 50 ms instead of 5 / 67 ms, same residual 2.5e-4 as tol 1e-5 reaches).
-      // (Round 5: 0.5 -> 0.36.  The largest RESIDUAL follows the square root of that factor -- see the exponent rule above -- so a
-      // cap round predicted at 0.36 improves it by less than 1.7 x for ~7 ms at 60k; and with the stronger early rounds the first
-      // cap round is reached a round sooner, at a gap that asks for ~3.8 caps instead of ~5.8: the same block quality -- RMNIST-like
-      // 60k: 2.4e-4 after 3 rounds / 249 products against 2.2e-4 after 4 / 280 -- must end the same way.)
-      if (!(p && p->degree > 0) && deg_used >= kCap && dnew > kCap && exp(-3.0 * kCap / (double)dnew) > 0.36) {
-        double rmx = 0.0;
-        for (int j = 0; j < m; ++j) rmx = std::max(rmx, res[j]);
-        if (rmx <= floor_guard * ub) { floor_hit = true; ++outer; break; }
-      }
-    }
-  }
-  const int cgrid = (int)std::min<int64_t>(4096, mgp_cdiv(n * m, kBlock));
-  hipLaunchKernelGGL(copy_cols_kernel, dim3(cgrid), dim3(kBlock), 0, st, w.buf[bV], n, b, m, evecs);
-  MGP_LAUNCH_CHECK();
-  if (block_evecs) {     // the whole Rayleigh-Ritz block, guard columns included: [n, b] row-major
-    const int bgrid = (int)std::min<int64_t>(4096, mgp_cdiv(n * b, kBlock));
-    hipLaunchKernelGGL(copy_cols_kernel, dim3(bgrid), dim3(kBlock), 0, st, w.buf[bV], n, b, b, block_evecs);
-    MGP_LAUNCH_CHECK();
-  }
-  MGP_HIP_TRY(hipStreamSynchronize(st));
-  for (int j = 0; j < m; ++j) {
-    evals[j] = (kept >= m) ? (float)th[j] : 0.f;
-    if (resid) resid[j] = (float)res[j];
-  }
-  for (int j = 0; j < b; ++j) {
-    if (block_evals) block_evals[j] = j < kept ? (float)th[j] : 0.f;
-    if (block_resid) block_resid[j] = (float)res[j];
-  }
-  if (warm_block && nconv != m) {
-    const int rc = lanczos_smallest_impl(L, m, p, evals, evecs, resid, info, block_evals, block_evecs, block_resid, nullptr, nullptr, work,
-                                         work_bytes, stream);
-    if (info) { info[0] += outer; info[1] += nspmm; }       // rounds / block products of the abandoned warm attempt included
-    return rc;
-  }
-  if (info) { info[0] = outer; info[1] = nspmm; info[2] = nconv; info[3] = b; }
-  if (nconv == m) return MGP_OK;
-  return floor_hit ? MGP_OK : MGP_ERR_NOT_CONVERGED;
 }
 
 // ================================================================= Lanczos tridiagonalisation

@@ -130,5 +130,9 @@ int mgp_knn_mfma_regroup(const void* table, const void* log, int64_t rows, int64
 size_t mgp_knn_mfma_table_entries(int64_t rows, int64_t N);
 int mgp_knn_mfma_log_shards(void);
 
+// K = scale Z1 Z2^T on the fp32 matrix cores with a leading dimension for K (features.hip; the eigensolver's rotation V <- V W)
+int mgp_kernel_block_ld(const float* Z1, int64_t n1, const float* Z2, int64_t n2, int m, float scale, float* K,
+                        int64_t ldk, void* stream);
+
 // fp64 operator apply from the fp32 matrix (true residual of the CG refinement); work64 = 4 n C doubles
 int mgp_operator_apply_f64(const mgp_operator_t* op, const double* X, int C, double* Y, double* work64, void* stream);

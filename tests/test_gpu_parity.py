@@ -575,6 +575,51 @@ def test_eigensolver_filter_bound_modes(mgp, dev):
     assert applies[2] > applies[1], applies              # the short bound cost a wasted round before the fallback
 
 
+def test_eigensolver_warm_block_that_does_not_converge_falls_back_to_the_cold_solve(mgp, dev):
+    """mgp_lanczos_smallest_warm gives a warm block four rounds; a block that has not converged by then is abandoned and the
+    solve repeated from a cold start, with the abandoned rounds / block products added to the report.  Forced here with a
+    tolerance below the fp32 residual floor (docs/kernels/eigen.md): no warm attempt can end with all pairs under it.  The
+    graph of test_eigensolver_filter_bound_modes (b = 64: the smallest shape here that runs the Krylov bound estimate).
+    The fallback's eigenpairs are bit-identical to the cold solve's (measured before the driver was split into phases, and
+    kept): the cold solve does not see what the warm attempt left in the workspace."""
+    import warnings
+    import scipy.linalg
+    from manifold_gp_amd.solvers import lanczos_smallest
+    rng = np.random.default_rng(11)
+    n, m = 4000, 24
+    t = rng.random(n)
+    x = (np.stack([np.cos(6.28318 * t), np.sin(6.28318 * t), 0.3 * np.cos(3 * 6.28318 * t)], 1)
+         + 0.01 * rng.normal(size=(n, 3))).astype(np.float32)
+    knn = mgp.utils.NearestNeighbors(T(x, dev))
+    idx, val = knn.graph(10)
+    op = mgp.operators.GraphLaplacianOperator(val, idx, n, torch.tensor([[0.05]], device=dev), "symmetric",
+                                              graph=knn.knn_graph)
+
+    def solve(**kw):
+        # the not-converged (plain UserWarning: MGP_ERR_NOT_CONVERGED) and floor (EigenFloorWarning: MGP_OK, info[2] < m)
+        # warnings are the return code as the Python entry shows it
+        with warnings.catch_warnings(record=True) as rec:
+            warnings.simplefilter("always")
+            evals, evecs, resid = lanczos_smallest(op.data, m, tol=1e-9, max_restarts=12, **kw)
+        rec = [r for r in rec if str(r.message).startswith("eigensolver stopped")]
+        assert len(rec) == 1, [str(r.message) for r in rec]
+        return evals, evecs, resid, list(lanczos_smallest.last_info), rec[0].category
+
+    solve(keep_warm=True)
+    warm = lanczos_smallest.last_warm
+    assert warm["block"].shape == (n, 64)
+    ev_c, V_c, res_c, info_c, rc_c = solve()
+    ev_w, V_w, res_w, info_w, rc_w = solve(warm=warm)
+    assert rc_w is rc_c, (rc_w, rc_c)
+    assert info_w[2] == info_c[2] < m and info_w[3] == info_c[3] == 64, (info_w, info_c)
+    assert info_c[0] < info_w[0] <= info_c[0] + 4, (info_w, info_c)
+    assert info_w[1] > info_c[1], (info_w, info_c)
+    assert torch.equal(ev_w, ev_c) and torch.equal(V_w, V_c) and res_w == res_c
+    A = op.to_dense().double().cpu().numpy()
+    w = scipy.linalg.eigvalsh(0.5 * (A + A.T), subset_by_index=[0, m - 1])
+    np.testing.assert_allclose(ev_w.cpu().numpy(), w, rtol=0, atol=5e-6 * np.abs(np.diag(A)).max())
+
+
 def test_eigensolver_on_unordered_nodes_uses_the_locality_order(mgp, dev):
     """Nodes handed over in random order: the graph carries tiles over a locality order and the eigensolver
     runs on the matrix relabelled by it (solvers.lanczos_smallest).  Eigenvalues against dense eigh and the
