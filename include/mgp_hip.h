@@ -507,10 +507,13 @@ int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* stream);
  * manifold_gp/kernels/riemann_kernel.py:121-125 and
  * GraphLaplacianOperator.diagonalization (graph_laplacian_operator.py:132-144).
  *   evals [m] ascending (host), evecs [n,m] row-major (device, orthonormal), resid [m] (host)
- *   = ||L v - lambda v||_2.  Synchronises `stream`. */
+ *   = ||L v - lambda v||_2.  Synchronises `stream`.
+ * Width: the block of b = min(mgp_lanczos_block_size(m, p), n) columns may have up to 512 columns -- with the default rule
+ * m <= 455, with max_basis = 512 m <= 510 --; block products run in balanced column chunks of at most 256 per SpMM launch.
+ * A wider block is MGP_ERR_UNSUPPORTED. */
 typedef struct {
-  int32_t max_basis;   /* block size b (0 = default: next multiple of 64 above m + max(m/8, 12)) */
-  int32_t degree;      /* Chebyshev filter degree (0 = adaptive 8..200) */
+  int32_t max_basis;   /* block size b (0 = default: next multiple of 64 above m + max(m/8, 12)); at least m + 2, at most 512 */
+  int32_t degree;      /* Chebyshev filter degree (0 = adaptive 8..200; no filter where the block is the whole space, b = n) */
   int32_t max_restarts;/* outer filter + Rayleigh-Ritz rounds (0 = 40) */
   float tol;           /* residual tolerance relative to lambda_max */
   uint64_t seed;

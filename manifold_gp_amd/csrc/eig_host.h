@@ -1,10 +1,14 @@
-// Host dense algebra of the eigensolver (fp64, standard C++ only: a host compiler builds this header alone, which is how
+// Host dense algebra of the eigensolver (fp64, standard C++ and the Linux affinity mask only: a host compiler builds this header alone, which is how
 // tests/test_eig_policy_cpu.py runs it): the small symmetric eigensolver, the worker pool, the whitening and the
 // Rayleigh-Ritz step of a round.  eigen.hip holds the kernels and the driver, eig_policy.h the round policy.
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
+#ifdef __linux__
+#include <sched.h>
+#endif
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -283,9 +287,26 @@ class HostPool {
   bool stop_ = false;
 };
 
-inline int host_pool_workers() {
-  const unsigned hw = std::thread::hardware_concurrency();
-  return (int)std::min<unsigned>(hw ? hw : 1u, 8u) - 1;
+// CPUs this process may run on: its affinity mask (what a container or a batch system grants; hardware_concurrency may
+// report the whole machine), and no more than OMP_NUM_THREADS where the launcher sets it.
+inline int host_cpus_granted() {
+  unsigned cpus = std::thread::hardware_concurrency();
+#ifdef __linux__
+  cpu_set_t set;
+  if (sched_getaffinity(0, sizeof(set), &set) == 0 && CPU_COUNT(&set) > 0) cpus = (unsigned)CPU_COUNT(&set);
+#endif
+  if (const char* e = getenv("OMP_NUM_THREADS")) {
+    const int v = atoi(e);
+    if (v > 0) cpus = std::min<unsigned>(cpus ? cpus : (unsigned)v, (unsigned)v);
+  }
+  return (int)std::max(1u, cpus);
+}
+
+// Workers beside the calling thread for a b x b host step: up to 8 threads for b <= 256 (the sections are short: more threads
+// cost more to wake than they do), up to 16 for the wider blocks, whose b^3 sections are 8 x longer.  The result does not
+// depend on the count.
+inline int host_pool_workers(int b = 0) {
+  return std::min(host_cpus_granted(), b > 256 ? 16 : 8) - 1;
 }
 
 // Gn (b x b, unit diagonal, symmetric positive definite) = C C^T; T = D C^-T (b x b) so that

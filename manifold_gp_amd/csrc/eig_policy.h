@@ -19,6 +19,7 @@ struct EigPolicy {
   int deg;
   double top_prev, rmax_prev;
   int nconv_prev, nlock;
+  bool whole;       // the block spans the whole space (b = n): no filter, see eig_whole_space
 };
 
 // Cold start on the bounds (ub, ubf); user_degree > 0 fixes the degree of every round.
@@ -28,8 +29,16 @@ struct EigPolicy {
 // cap 120 / 146 / 200 / 240: 247 / 273 / 327 / 367 applies for residuals 2.7 / 2.6 / 1.9 / 1.9e-4, tolerance 3.0e-4).
 inline EigPolicy eig_cold_start(double ub, double ubf, int user_degree) {
   const int kCap = std::max(100, std::min(200, (int)lround(200.0 * sqrt(ubf / ub))));
-  return EigPolicy{ub, ubf, kCap, ubf / 4.0, 0.0, user_degree > 0 ? user_degree : 10, 1e300, 1e300, 0, 0};
+  return EigPolicy{ub, ubf, kCap, ubf / 4.0, 0.0, user_degree > 0 ? user_degree : 10, 1e300, 1e300, 0, 0, false};
 }
+
+// A block as wide as the whole space (b = n) needs no filter: Rayleigh-Ritz on it is exact, and there is nothing outside the block to
+// damp -- the interval [a, ubf] above the block's largest Ritz value is then empty of eigenvalues, and a polynomial that is small
+// on that sliver grows over the WHOLE spectrum, so even the minimum degree lifts the lowest modes over mode m by more than float32
+// columns survive (n = 300, m = 250: the rounds never converged).  Such a solve runs rounds of degree 0 -- L V, Gram blocks,
+// Rayleigh-Ritz, rotation -- on all columns: the first on the random block, the second on its orthonormalised rotation, where the
+// fp32 rotation is accurate.  Set after eig_cold_start / eig_warm_start (a cold start clears it); a user degree is kept instead.
+inline void eig_whole_space(EigPolicy& s) { s.whole = true; s.deg = 0; s.nlock = 0; }
 
 // Warm start: the warm block's own Ritz values (warm_evals [b], ascending) stand in for a first Rayleigh-Ritz round (a little
 // margin on the interval's lower end: the matrix has moved since they were computed).  Values that cannot be used leave the
@@ -51,6 +60,25 @@ inline void eig_warm_start(EigPolicy& s, const float* warm_evals, int b, int m, 
 // (the filter amplified what it should have damped).  The answer is eig_cold_start(ub, ub, ...) and a fresh block.
 inline bool eig_bound_short(const EigPolicy& s, double top) {
   return s.ubf < s.ub && (top > s.ubf * (1.0 + 1e-3) || (top > 2.0 * s.top_prev && top > 0.25 * s.ubf));
+}
+
+// Block width.  One fused SpMM launch serves at most kEigChunkMax columns; a block of up to kEigMaxBlock columns runs its products
+// in column chunks (the Gram blocks, the rotation and the residuals take the whole width).
+constexpr int kEigChunkMax = 256;
+constexpr int kEigMaxBlock = 512;
+
+// The chunk rule of a block product on `ba` active columns: ceil(ba / 256) chunks of equal width rounded up to a multiple of 4,
+// the last one taking what is left -- 320 runs as 160 + 160, 300 as 152 + 148, never 256 + 64: with more than one chunk every
+// chunk has at least 125 columns (257 runs as 132 + 125), so none falls under the 48 the matrix-core SpMM needs, and every chunk
+// starts on a multiple of 4 (16-byte aligned rows in its own [n, width] buffer).  Every width is a multiple of 4 except that
+// the LAST chunk carries ba mod 4 (a block as wide as the whole space, b = n, need not be a multiple of 4).  ba <= 256 is one
+// chunk of ba columns: the launch there has always been.
+inline int eig_chunk_count(int ba) { return std::max(1, (ba + kEigChunkMax - 1) / kEigChunkMax); }
+// first column of chunk k (k = eig_chunk_count(ba): ba)
+inline int eig_chunk_start(int ba, int k) {
+  const int nc = eig_chunk_count(ba);
+  const int w = ((ba + nc - 1) / nc + 3) / 4 * 4;
+  return std::min(ba, k * w);
 }
 
 enum EigVerdict { EIG_CONTINUE = 0, EIG_CONVERGED = 1, EIG_FLOOR = 2 };
@@ -92,11 +120,15 @@ inline EigStep eig_round_step(EigPolicy& s, const double* th, const double* res,
   // behind the block is tiny; a round at the cap that does not even halve the largest residual, with no further
   // pair converging, is therefore taken as the floor: the caller gets the block as it stands, the true residuals in
   // `resid`, info[2] = pairs under tol (< m) and MGP_OK.
-  if (deg_used >= s.kCap && r.rmx > 0.5 * s.rmax_prev && r.nconv <= s.nconv_prev && r.rmx <= floor_guard * ub) { r.verdict = EIG_FLOOR; return r; }
+  if ((deg_used >= s.kCap || s.whole) && r.rmx > 0.5 * s.rmax_prev && r.nconv <= s.nconv_prev && r.rmx <= floor_guard * ub) { r.verdict = EIG_FLOOR; return r; }
   s.rmax_prev = r.rmx;
   s.nconv_prev = r.nconv;
+  if (s.whole) return r;       // the next round is another unfiltered one on all columns (deg 0, nlock 0 stay)
   // Soft locking: the leading run of converged Ritz vectors (a multiple of 4 columns) is no longer filtered -- the Chebyshev
-  // recurrence and the L apply run on the remaining columns -- but stays in the Rayleigh-Ritz basis.
+  // recurrence and the L apply run on the remaining columns -- but stays in the Rayleigh-Ritz basis.  Per chunk of the block
+  // products (eig_chunk_start) the same holds: the locked run is a multiple of 4, so every chunk of the b - nlock active columns
+  // starts on a multiple of 4, and the minimum of 8 (or 48) active columns below is a minimum per chunk, since more than one
+  // chunk means at least 125 columns in each.
   s.nlock = r.lead / 4 * 4;
   if (b - s.nlock < 8) s.nlock = 0;
   // the matrix-core tile SpMM serves 48 columns and more: a block locked down to fewer active columns falls back to the gather

@@ -227,32 +227,34 @@ __global__ void gram_reduce_kernel(const double* __restrict__ partial, int chunk
   }
 }
 
-// column partial sums of (LV[r,c] - theta[c] * V[r,c])^2 in fp64
+// column partial sums of (LV[r,c] - theta[c] * V[r,c])^2 in fp64.  blockIdx.y: the group of kBlock columns (one group up to
+// b = 256; a wider block's last group may be narrower and then takes several row slices per column, like a narrow block)
 __global__ __launch_bounds__(kBlock) void residual_kernel(const float* __restrict__ LV, const float* __restrict__ V,
                                                           const float* __restrict__ theta, int64_t n, int b,
                                                           int64_t rows_per_chunk, double* __restrict__ partial) {
   __shared__ double sh[kBlock];
+  const int cb = blockIdx.y * kBlock, bw = min(b - cb, kBlock);
   int TC = 1;
-  while (TC < b && TC < kBlock) TC <<= 1;
+  while (TC < bw && TC < kBlock) TC <<= 1;
   const int TS = kBlock / TC;
   const int cc = threadIdx.x % TC, sl = threadIdx.x / TC;
   const int64_t r0 = blockIdx.x * rows_per_chunk;
   int64_t r1 = r0 + rows_per_chunk;
   if (r1 > n) r1 = n;
   double acc = 0.0;
-  if (cc < b) {
-    const float th = theta[cc];
+  if (cc < bw) {
+    const float th = theta[cb + cc];
     for (int64_t r = r0 + sl; r < r1; r += TS) {
-      const float d = LV[r * b + cc] - th * V[r * b + cc];
+      const float d = LV[r * b + cb + cc] - th * V[r * b + cb + cc];
       acc += (double)d * (double)d;
     }
   }
   sh[threadIdx.x] = acc;
   __syncthreads();
-  if (sl == 0 && cc < b) {
+  if (sl == 0 && cc < bw) {
     double t = 0.0;
     for (int s = 0; s < TS; ++s) t += sh[s * TC + cc];
-    partial[(int64_t)blockIdx.x * b + cc] = t;
+    partial[(int64_t)blockIdx.x * b + cb + cc] = t;
   }
 }
 
@@ -314,10 +316,9 @@ int block_size_for(int m, const mgp_lanczos_params_t* p) {
   // at 80 the same sweep preferred ~2 m columns and took 138 ms / 0.84 s.)
   int b = (p && p->max_basis > 0) ? p->max_basis : m + std::max(m / 8, 12);
   if (b < m + 2) b = m + 2;
-  if (!(p && p->max_basis > 0)) {
-    b = (b + 63) / 64 * 64;
-    if (b > 256 && m + 2 <= 256) b = 256;
-  }
+  // (Until blocks wider than one SpMM launch ran in column chunks, m = 229 .. 254 was clamped to 256 columns -- fewer guards than
+  // the rule asks for -- so as to run at all; such m now gets its 320 columns.  Blocks above kEigMaxBlock are refused by the solve.)
+  if (!(p && p->max_basis > 0)) b = (b + 63) / 64 * 64;
   return b;
 }
 
@@ -391,7 +392,8 @@ int eig_setup(EigCtx& cx, const mgp_csr_t* L, int m, const mgp_lanczos_params_t*
   if (n <= 0 || m <= 0 || m > n) return MGP_ERR_ARG;
   int b = block_size_for(m, p);
   if (b > n) b = (int)n;
-  if (b > 256) return MGP_ERR_UNSUPPORTED;   // one SpMM launch handles <= 256 columns
+  if (b > kEigMaxBlock) return MGP_ERR_UNSUPPORTED;   // block products run in chunks of <= 256 columns up to this width; beyond it:
+                                                      // hard-locked sweeps (docs/kernels/eigen.md), not built
   if (work_bytes < eig_bytes(n, m, p)) return MGP_ERR_WORKSPACE;
   cx.L = L; cx.stream = stream; cx.st = mgp_stream(stream); cx.n = n; cx.m = m; cx.b = b;
   cx.seed = p ? p->seed : 1337;
@@ -419,7 +421,7 @@ int eig_setup(EigCtx& cx, const mgp_csr_t* L, int m, const mgp_lanczos_params_t*
   return MGP_OK;
 }
 
-// Y = ca X + cl L X (+ cz Z) on C columns: one fused SpMM launch
+// Y = ca X + cl L X (+ cz Z) on C <= 256 columns: one fused SpMM launch
 int eig_apply(EigCtx& cx, const float* X, int C, float* Y, double ca, double cl, const float* Z = nullptr, double cz = 0.0) {
   return mgp_spmm_fused(cx.L, X, C, Y, (float)ca, (float)cl, nullptr, nullptr, Z, (float)cz, 1.f, nullptr, nullptr, cx.stream);
 }
@@ -506,6 +508,12 @@ void eig_move_cols(EigCtx& cx, const float* src, int sld, int sc0, int mcols, fl
 // Soft locking: the leading pol.nlock columns are not filtered -- the recurrence and the L apply run on the remaining `ba`
 // columns, compacted to an [n, ba] block -- but stay in the Rayleigh-Ritz basis, so they keep being refined and the block
 // stays orthogonal.
+// Wide blocks: ba > 256 active columns run as the column chunks of eig_chunk_start, each compacted to its own [n, width] block at
+// column offset c0 of the three filter buffers (element offset n c0: 16-byte aligned, c0 is a multiple of 4).  The three-term
+// recurrence is column-independent, and each chunk runs its WHOLE degree before the next one starts: the matrix is streamed once
+// per launch either way, but the three vector blocks a chunk's recurrence cycles through are half the size of the whole block's
+// (60k x 192 x 3: 138 MB against 276 MB), so more of them is still in the last-level cache when the next launch asks for them.
+// One chunk (ba <= 256) is the launch sequence there has always been.
 int eig_filter_round(EigCtx& cx) {
   EigWork& w = cx.w;
   const int b = cx.b, nlock = cx.pol.nlock, deg = cx.pol.deg;
@@ -513,28 +521,40 @@ int eig_filter_round(EigCtx& cx) {
   const int ba = b - nlock;
   cx.deg_used = deg;
   const double e = (cx.pol.ubf - cx.pol.a) / 2.0, c = (cx.pol.ubf + cx.pol.a) / 2.0;
-  double sig = e / (cx.pol.a0 - c);
-  const double tau = 2.0 / sig;
-  int iX = cx.c0, iY = cx.c1, iN = cx.c2;
-  eig_move_cols(cx, w.buf[cx.bV], b, nlock, ba, w.buf[iX], ba, 0);
-  MGP_LAUNCH_CHECK();
-  // Y = (sig/e) (L X - c X)
-  MGP_TRY(eig_apply(cx, w.buf[iX], ba, w.buf[iY], -c * sig / e, sig / e));
-  ++cx.nspmm;
-  for (int i = 2; i <= deg; ++i) {
-    const double sn = 1.0 / (tau - sig);
-    // Ynew = (2 sn / e) (L Y - c Y) - (sig sn) X
-    MGP_TRY(eig_apply(cx, w.buf[iY], ba, w.buf[iN], -c * 2.0 * sn / e, 2.0 * sn / e, w.buf[iX], -sig * sn));
+  const int nch = eig_chunk_count(ba);
+  for (int k = 0; k < nch; ++k) {
+    const int c0 = eig_chunk_start(ba, k), cw = eig_chunk_start(ba, k + 1) - c0;
+    const size_t off = (size_t)cx.n * c0;
+    double sig = e / (cx.pol.a0 - c);
+    const double tau = 2.0 / sig;
+    int iX = cx.c0, iY = cx.c1, iN = cx.c2;
+    eig_move_cols(cx, w.buf[cx.bV], b, nlock + c0, cw, w.buf[iX] + off, cw, 0);
+    MGP_LAUNCH_CHECK();
+    if (deg == 0) {      // a block that spans the whole space (eig_whole_space): no filter, only L V behind the unchanged columns
+      MGP_TRY(eig_apply(cx, w.buf[iX] + off, cw, w.buf[iN] + off, 0.0, 1.0));
+      ++cx.nspmm;
+      eig_move_cols(cx, w.buf[iN] + off, cw, 0, cw, w.buf[cx.bLV], b, nlock + c0);
+      MGP_LAUNCH_CHECK();
+      continue;
+    }
+    // Y = (sig/e) (L X - c X)
+    MGP_TRY(eig_apply(cx, w.buf[iX] + off, cw, w.buf[iY] + off, -c * sig / e, sig / e));
     ++cx.nspmm;
-    const int t = iX; iX = iY; iY = iN; iN = t;
-    sig = sn;
+    for (int i = 2; i <= deg; ++i) {
+      const double sn = 1.0 / (tau - sig);
+      // Ynew = (2 sn / e) (L Y - c Y) - (sig sn) X
+      MGP_TRY(eig_apply(cx, w.buf[iY] + off, cw, w.buf[iN] + off, -c * 2.0 * sn / e, 2.0 * sn / e, w.buf[iX] + off, -sig * sn));
+      ++cx.nspmm;
+      const int t = iX; iX = iY; iY = iN; iN = t;
+      sig = sn;
+    }
+    // filtered active chunk in iY; L (filtered) into iN; both back into the active columns of V / L V
+    MGP_TRY(eig_apply(cx, w.buf[iY] + off, cw, w.buf[iN] + off, 0.0, 1.0));
+    ++cx.nspmm;
+    eig_move_cols(cx, w.buf[iY] + off, cw, 0, cw, w.buf[cx.bV], b, nlock + c0);
+    eig_move_cols(cx, w.buf[iN] + off, cw, 0, cw, w.buf[cx.bLV], b, nlock + c0);
+    MGP_LAUNCH_CHECK();
   }
-  // filtered active block in iY; L (filtered) into iN; both back into the active columns of V / L V
-  MGP_TRY(eig_apply(cx, w.buf[iY], ba, w.buf[iN], 0.0, 1.0));
-  ++cx.nspmm;
-  eig_move_cols(cx, w.buf[iY], ba, 0, ba, w.buf[cx.bV], b, nlock);
-  eig_move_cols(cx, w.buf[iN], ba, 0, ba, w.buf[cx.bLV], b, nlock);
-  MGP_LAUNCH_CHECK();
   // ---- Rayleigh-Ritz: G = V^T V, H = V^T L V (fp64), generalized eigenproblem on the host
   MGP_TRY(launch_gram(w.buf[cx.bV], w.buf[cx.bV], cx.n, b, w, w.G, cx.st));
   MGP_TRY(launch_gram(w.buf[cx.bV], w.buf[cx.bLV], cx.n, b, w, w.H, cx.st));
@@ -559,7 +579,7 @@ int eig_ritz_rotate(EigCtx& cx, bool* fresh) {
   const auto tp4 = HostClock::now();
   const int kept = cx.rr.kept;
   const double top = cx.rr.th[kept - 1];
-  if (eig_bound_short(cx.pol, top)) {
+  if (!cx.pol.whole && eig_bound_short(cx.pol, top)) {      // (an unfiltered round does not use the bound)
     if (cx.trace)
       fprintf(stderr, "[eig] round %d: largest Ritz value %.5g against the estimated bound %.5g: back to Gershgorin %.5g\n", outer,
               top, cx.pol.ubf, cx.pol.ub);
@@ -577,8 +597,8 @@ int eig_ritz_rotate(EigCtx& cx, bool* fresh) {
   const int iVn = cx.c0, iLVn = cx.c1;
   MGP_TRY(mgp_kernel_block_ld(w.buf[cx.bV], n, w.wt, b, b, 1.f, w.buf[iVn], b, cx.stream));
   MGP_TRY(mgp_kernel_block_ld(w.buf[cx.bLV], n, w.wt, b, b, 1.f, w.buf[iLVn], b, cx.stream));
-  hipLaunchKernelGGL(residual_kernel, dim3(w.rchunks), dim3(kBlock), 0, st, w.buf[iLVn], w.buf[iVn], w.theta, n, b,
-                     w.rrows, w.rpart);
+  hipLaunchKernelGGL(residual_kernel, dim3(w.rchunks, (unsigned)mgp_cdiv(b, kBlock)), dim3(kBlock), 0, st, w.buf[iLVn], w.buf[iVn],
+                     w.theta, n, b, w.rrows, w.rpart);
   MGP_LAUNCH_CHECK();
   MGP_HIP_TRY(hipMemcpyAsync(cx.rp.data(), w.rpart, (size_t)w.rchunks * b * sizeof(double), hipMemcpyDeviceToHost, st));
   MGP_HIP_TRY(hipStreamSynchronize(st));
@@ -638,6 +658,7 @@ int eig_solve(EigCtx& cx, const float* warm_block, const float* warm_evals, int 
   if (warm_block) MGP_HIP_TRY(hipMemcpyAsync(cx.w.buf[0], warm_block, (size_t)cx.n * cx.b * sizeof(float), hipMemcpyDeviceToDevice, cx.st));
   else MGP_TRY(eig_random_cols(cx, cx.w.buf[0], 0, cx.b, cx.seed));
   if (warm_block && warm_evals) eig_warm_start(cx.pol, warm_evals, cx.b, cx.m, cx.user_degree);
+  if (cx.b >= cx.n && !(cx.user_degree > 0)) eig_whole_space(cx.pol);
   cx.nspmm = 0; cx.nconv = 0; cx.deg_used = 0; cx.floor_hit = false;
   cx.res.assign(cx.b, 1e300);
   cx.rr.kept = cx.b;
@@ -665,7 +686,7 @@ static int lanczos_smallest_impl(const mgp_csr_t* L, int m, const mgp_lanczos_pa
   cx.evals = evals; cx.evecs = evecs; cx.resid = resid;
   cx.block_evals = block_evals; cx.block_evecs = block_evecs; cx.block_resid = block_resid;
   MGP_TRY(eig_setup(cx, L, m, p, work, work_bytes, stream));
-  HostPool pool(host_pool_workers());      // lives for this call: joined on every return path
+  HostPool pool(host_pool_workers(cx.b));      // lives for this call: joined on every return path
   cx.pool = &pool;
   const int max_outer = (p && p->max_restarts > 0) ? p->max_restarts : 40;
   int warm_rounds = 0, warm_nspmm = 0;
@@ -714,7 +735,7 @@ extern "C" int mgp_gram_set_mfma(int on) {
 extern "C" int mgp_host_symeig(int n, const double* A, double* evals, double* V) {
   if (n <= 0 || !A || !evals || !V) return MGP_ERR_ARG;
   std::vector<double> a(A, A + (size_t)n * n), ev, vv;
-  HostPool pool(n >= 64 ? host_pool_workers() : 0);      // as inside the block eigensolver
+  HostPool pool(n >= 64 ? host_pool_workers(n) : 0);      // as inside the block eigensolver
   host_symeigh(n, a, ev, vv, &pool);
   memcpy(evals, ev.data(), (size_t)n * sizeof(double));
   memcpy(V, vv.data(), (size_t)n * n * sizeof(double));

@@ -525,6 +525,19 @@ class EigenFloorWarning(UserWarning):
     """mgp_lanczos_smallest returned MGP_OK with info[2] < m (residual floor / unseparable guards)."""
 
 
+EIG_MAX_BLOCK = 512        # widest Rayleigh-Ritz block of mgp_lanczos_smallest (include/mgp_hip.h)
+
+
+def max_num_modes(n, max_basis=0):
+    """The largest m for which the eigensolver's block -- min(mgp_lanczos_block_size(m), n) columns -- is within EIG_MAX_BLOCK."""
+    prm = LanczosParamsT(int(max_basis), 0, 0, 0.0, 0)
+    best = 0
+    for m in range(1, min(int(n), EIG_MAX_BLOCK) + 1):
+        if min(int(lib().mgp_lanczos_block_size(m, ctypes.byref(prm))), int(n)) <= EIG_MAX_BLOCK:
+            best = m
+    return best
+
+
 def lanczos_smallest(lap_data, m, tol=1e-5, max_basis=0, degree=0, max_restarts=60, seed=1337, return_block=False, warm=None,
                      keep_warm=False):
     """m smallest eigenpairs of L_sym (CSR in `lap_data`) by the HIP filtered block iteration.
@@ -535,6 +548,10 @@ def lanczos_smallest(lap_data, m, tol=1e-5, max_basis=0, degree=0, max_restarts=
     from that block instead of a random one (mgp_lanczos_smallest_warm).  keep_warm=True leaves this call's block there."""
     g = lap_data.graph
     dev = g.device
+    prm = LanczosParamsT(int(max_basis), int(degree), int(max_restarts), float(tol), int(seed))
+    if 0 < int(m) <= g.n and min(int(lib().mgp_lanczos_block_size(int(m), ctypes.byref(prm))), g.n) > EIG_MAX_BLOCK:
+        raise ValueError("num_modes = %d needs an eigensolver block of more than %d columns; the largest num_modes for this graph "
+                         "(n = %d, max_basis = %d) is %d" % (m, EIG_MAX_BLOCK, g.n, max_basis, max_num_modes(g.n, max_basis)))
     # A graph whose nodes arrive without locality carries tiles over a locality order (graph.build_tiles_auto).
     # The block iteration gathers an X row per entry: on the CSR as given those rows are scattered over a
     # block of n x b floats (HBM-bound, 4.3 ms per 84-column SpMM at N = 1M); on the SAME matrix relabelled
@@ -548,7 +565,6 @@ def lanczos_smallest(lap_data, m, tol=1e-5, max_basis=0, degree=0, max_restarts=
         csr = rel.csr(wide=True)
     else:
         csr = lap_data.csr(wide=True)
-    prm = LanczosParamsT(int(max_basis), int(degree), int(max_restarts), float(tol), int(seed))
     wb = lib().mgp_lanczos_workspace_bytes(g.n, int(m), ctypes.byref(prm))
     work = torch.empty(wb, dtype=torch.uint8, device=dev)
     evals = (ctypes.c_float * m)()
