@@ -16,7 +16,13 @@ Contract, per column c:
   C4  max_iter exit: status 2, iters == max_iter, C3 holds.
   C5  a zero column gives x == 0 exactly and resid 0; mixed into a block it changes neither the other columns'
       iterations nor their C1.
-  C6  forward error against R2: ||x - x*|| / ||x*|| <= 2 cond(A) true_rel + 1e-5 (dumbbell: dense cond is cheap)."""
+  C6  forward error against R2: ||x - x*|| / ||x*|| <= 2 cond(A) true_rel + 1e-5 (dumbbell: dense cond is cheap).
+
+Past the caps (test_past_caps_*): C1-C5 again on a 300,071-node swiss roll (tests/_past_caps.py), where the SpMM families give a
+workgroup two tiles or several passes and leave 2,345 ... 9,378 delta partials: the C = 1 kernels with 16 delta slots, the
+complex-shift update past 1024 partials, the tail loop of cg_update_kernel, cg_reduce_kernel past its first trip.  Every case
+asserts its partial count and kernel family (mgp_spmm_dot_blocks_csr, mgp_spmm_kernel_choice on the plan's own CSR) and 20
+iterations or more; C6 is left out (it needs a dense matrix).  One-off cost: 0.5-0.7 s per operator for R1 and its norm."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -174,6 +180,38 @@ def swiss_roll(mgp, dev):
     for norm in ("symmetric", "randomwalk"):
         out[norm] = mgp.operators.GraphLaplacianOperator(val, idx, 20000, torch.tensor([[0.35]], device=dev), norm,
                                                          graph=knn.knn_graph)
+    return out
+
+
+# The 300,071-node swiss roll of tests/_past_caps.py: past every size cap of the solver's kernels (module docstring, "Past the caps").
+# Two conditions choose the systems: (a) every solve takes 20 iterations or more -- a near-identity system stops in two or three
+# steps and flips the parity buffers once --, (b) the module's rule F <= tol / 4 holds at tol 1e-3 and 1e-4.
+# B = tau I + L_sym has its spectrum in [tau, tau + 585] on this graph (the Laplacian scales with 1 / eps^2 = 503), so kappa is
+# chosen through tau = 2 nu / kappa^2; kappa = 4, nu = 2 (tau = 0.25) would give cond(A) = 5e6 and break (b).  Checked beforehand
+# with a float64 CG on oracle.laplacian.LaplacianOracle over k-d tree neighbours of the same points, Gaussian and one-hot
+# right-hand sides:
+#   form 0, nu 2.  tau = 73: 28 / 38 iterations (symmetric, tol 1e-3 / 1e-4) and 31 / 44 (random walk), F / tol at 1e-4 up to 0.11;
+#   tau = 40: 53 / 71 and 77 / 103, F / tol up to 0.22.  Used: tau = 55 (kappa = 0.2697, cond(A) = 135).  Measured on the GPU:
+#   40 / 53 and 58 / 78 iterations, F / tol <= 0.17.
+#   form 2, nu 2, symmetric, for the complex-shift solve alone.  tau = 5 (kappa = 0.8944), noise x scale = 1e-2, cond(A) = 2800:
+#   COCG 26 iterations at tol 1e-3 with F / tol = 0.07 (measured on the GPU: 41 and 0.11); at 1e-4 F / tol would be about 0.7, so this
+#   system runs at 1e-3 only.
+BIG_KAPPA, BIG_SCALE = 0.2697, 4e-6          # ||A||_2 ~ 1.6
+BIG_CX_KAPPA, BIG_CX_NOISE = 0.8944, 1e-2
+BIG_MIN_ITERS = 20
+
+
+@pytest.fixture(scope="module")
+def swiss300k(mgp, dev):
+    """Operators on the 300,071-node graphs: generation order (symmetric, randomwalk; the plans iterate on the relabelled matrix) and
+    Z-curve order (randomwalk).  The float64 systems R1 and their ||A||_2 are computed once each (`_big`)."""
+    import _past_caps
+    out = {"n": _past_caps.N, "sys": {}}
+    for order, norms in (("random", ("symmetric", "randomwalk")), ("morton", ("randomwalk",))):
+        g = _past_caps.swiss300k(mgp, dev, order)
+        out[order] = {norm: mgp.operators.GraphLaplacianOperator(g["val"], g["idx"], out["n"], torch.tensor([[g["eps"]]], device=dev),
+                                                                 norm, graph=g["graph"]) for norm in norms}
+    out["gauss"] = torch.randn(out["n"], 1, generator=torch.Generator().manual_seed(43)).to(dev)
     return out
 
 
@@ -453,3 +491,170 @@ def test_distributed_plan_world1_contract(mgp, dumbbell, dev):
             assert plan.status == 1
         finally:
             plan.close()
+
+
+# ----------------------------------------------------------------------------- past the caps (n = 300,071)
+def _big(mgp, G, dev, order, norm, cx=False):
+    """(lap, desc, R1) of one 300k operator; R1 and its norm2 (eigsh) once per operator."""
+    import time
+    key = (order, norm, cx)
+    if key not in G["sys"]:
+        lap = G[order][norm]
+        if cx:
+            desc = _desc(mgp, lap, 2, BIG_CX_KAPPA, dev, form=2, scale=1.0, noise=BIG_CX_NOISE)
+        else:
+            desc = _desc(mgp, lap, 2, BIG_KAPPA, dev, form=0, scale=BIG_SCALE)
+        t0 = time.time()
+        sys = R1(lap, desc)
+        print("R1 %s: ||A||_2 = %.4g (%.1f s)" % (key, sys.norm2, time.time() - t0))
+        G["sys"][key] = (lap, desc, sys)
+    return G["sys"][key]
+
+
+def _plan_geometry(desc, C):
+    """What a CgPlan of this descriptor and width multiplies with, read off a plan's own CSR while that plan is open (the geometry
+    depends on the descriptor, the width and the lab switches, not on tol / max_iter: the plans that _check_plan solves with bind
+    the same struct).  dict: nbs = dot partials of the C-column SpMM, family, nbs4 / family4 = the same for the four-column product
+    of the complex-shift solve, tile_rows, relabelled = the plan iterates on P A P^T."""
+    import ctypes
+    from manifold_gp_amd import _lib
+    from manifold_gp_amd.solvers import CgPlan
+    lib = _lib.lib()
+    plan = CgPlan(desc, C, tol=1e-3, max_iter=10, stop_mode=1)
+    try:
+        L = ctypes.byref(plan.op.L)
+        return dict(nbs=lib.mgp_spmm_dot_blocks_csr(L, C), family=lib.mgp_spmm_kernel_choice(L, C, 1, 0),
+                    nbs4=lib.mgp_spmm_dot_blocks_csr(L, 4), family4=lib.mgp_spmm_kernel_choice(L, 4, 1, 0),
+                    tile_rows=int(plan.op.L.tile_rows), relabelled=plan._rg is not None)
+    finally:
+        plan.close()
+
+
+def _big_check(sys, desc, rhs, tol, label, **kw):
+    """_check_plan with two solves (the first runs eager launches; the second captures the graphs and runs as their replay); every
+    uncapped solve takes BIG_MIN_ITERS steps or more, so that the parity buffers flip many times."""
+    recs, cx, out = _check_plan(sys, desc, rhs, tol, repeats=2, label=label, **kw)
+    if kw.get("max_iter", 20000) >= 100:
+        for _, its, _, _, _ in recs:
+            assert its >= BIG_MIN_ITERS, (label, its)
+    return recs, cx, out
+
+
+@pytest.mark.parametrize("decide", [1, 0])
+@pytest.mark.parametrize("norm", ["randomwalk", "symmetric"])
+def test_past_caps_real_cg_c1(mgp, swiss300k, dev, norm, decide):
+    """Real CG at C = 1 with 2,345 delta partials (more than 4 x 256): cg_update_c1_kernel<*, 16> and cg_decide_c1_kernel with 16
+    delta slots; random walk (pre / post) and symmetric (the init-free start; complex shift switched off, which form 0 would not
+    take anyway); the stopping decision inside the update and as launches of its own.
+    Measured: 58 / 78 iterations (random walk, tol 1e-3 / 1e-4) and 40 / 53 (symmetric), the same with either decision form and on
+    the graph replay; true_rel <= 0.95 tol; F <= 0.15 tol."""
+    from manifold_gp_amd import _lib
+    lib = _lib.lib()
+    lap, desc, sys = _big(mgp, swiss300k, dev, "random", norm)
+    prev_cx, prev_dec = lib.mgp_cg_set_complex_shift(0), lib.mgp_cg_set_decide_in_update(decide)
+    try:
+        geo = _plan_geometry(desc, 1)
+        assert geo["family"] == 1 and geo["nbs"] > 1024 and geo["relabelled"], geo        # tile SpMV, two tiles per workgroup
+        assert geo["nbs"] < -(-swiss300k["n"] // geo["tile_rows"]), geo
+        for tol in (1e-3, 1e-4):
+            _, cx, _ = _big_check(sys, desc, swiss300k["gauss"], tol, "300k C=1 %s decide %d" % (norm, decide))
+            assert not cx
+    finally:
+        lib.mgp_cg_set_complex_shift(prev_cx)
+        lib.mgp_cg_set_decide_in_update(prev_dec)
+
+
+def test_past_caps_complex_shift(mgp, swiss300k, dev):
+    """The complex-shift solve (form 2, nu 2, symmetric) with 2,345 four-column partials per product: cx_update_kernel past 1024.
+    Measured: 41 iterations at tol 1e-3, true_rel 0.66 tol, F 0.11 tol."""
+    from manifold_gp_amd import _lib
+    lib = _lib.lib()
+    lap, desc, sys = _big(mgp, swiss300k, dev, "random", "symmetric", cx=True)
+    prev = lib.mgp_cg_set_complex_shift(1)
+    try:
+        geo = _plan_geometry(desc, 1)
+        assert geo["family4"] == 2 and geo["nbs4"] > 1024, geo
+        _, cx, _ = _big_check(sys, desc, swiss300k["gauss"], 1e-3, "300k complex shift")
+        assert cx
+    finally:
+        lib.mgp_cg_set_complex_shift(prev)
+
+
+@pytest.mark.parametrize("C,stop_mode", [(5, 1), (8, 1), (9, 1), (12, 1), (16, 1), (12, 0)])
+def test_past_caps_multicolumn_tail_loop(mgp, swiss300k, dev, C, stop_mode):
+    """C = 5 ... 16: the element update (cg_update_kernel), every workgroup of which sums all 2,345 delta partials -- more than the
+    2 x 32 x TS its first round trip holds (2048 for 5 <= C <= 8, 1024 for 9 <= C <= 16), so the tail loop runs: one further batch
+    at C = 5 and 8, three at C = 9 ... 16, the last one partly masked.  C = 12 also carries a zero column and a duplicate column
+    (C5 of the contract).
+    Measured: 58 / 78 iterations at every width (stop_mode 0 at C = 12: 52 / 72), true_rel <= 1.0 tol per column, F <= 0.17 tol; the
+    zero-column and duplicate-column solves take the same 58 steps."""
+    lap, desc, sys = _big(mgp, swiss300k, dev, "random", "randomwalk")
+    n = swiss300k["n"]
+    geo = _plan_geometry(desc, C)
+    nbs, family = geo["nbs"], geo["family"]
+    TC = 1
+    while TC < C:
+        TC <<= 1
+    assert nbs > 2 * 32 * (256 // TC), (C, nbs)
+    assert family == (2 if C % 4 == 0 else 0), (C, family)
+    B = _block(n, C, dev, seed=300 + C)
+    for tol in (1e-3, 1e-4):
+        _big_check(sys, desc, B, tol, "300k C=%d stop %d" % (C, stop_mode), stop_mode=stop_mode)
+    if C == 12 and stop_mode == 1:
+        tol = 1e-3
+        Bz = B.clone()
+        Bz[:, -1] = 0.0
+        Bd = B.clone()
+        Bd[:, -1] = B[:, 0]
+        rz, _, _ = _check_plan(sys, desc, Bz, tol, repeats=1, label="300k C=12 zero column")
+        rd, _ = _plan_solves(desc, Bd, tol, repeats=1)
+        assert rz[0][1] == rd[0][1] and rz[0][1] >= BIG_MIN_ITERS, (rz[0][1], rd[0][1])
+        xz, xd = rz[0][0][:, :-1], rd[0][0][:, :-1]
+        assert float((xz - xd).abs().max()) <= 1e-6 * float(xd.abs().max())
+
+
+def test_past_caps_c17_reduce_once(mgp, swiss300k, dev):
+    """C = 17: cg_reduce_kernel over 3,126 delta partials (four trips of 1024) and 2 x nbv gamma / rr partials, the element
+    update behind it; the gather SpMM with a three-pass row range (96 rows per workgroup).
+    Measured: 58 iterations, true_rel <= 1.0 tol."""
+    lap, desc, sys = _big(mgp, swiss300k, dev, "random", "randomwalk")
+    n = swiss300k["n"]
+    geo = _plan_geometry(desc, 17)
+    nbs, family = geo["nbs"], geo["family"]
+    assert family == 0 and nbs == -(-n // 96) and nbs > 1024 and nbs < -(-n // 32), (family, nbs)
+    _big_check(sys, desc, _block(n, 17, dev, seed=317), 1e-3, "300k C=17")
+
+
+@pytest.mark.parametrize("quads", [1, 0])
+@pytest.mark.parametrize("order", ["random", "morton"])
+def test_past_caps_c100(mgp, swiss300k, dev, order, quads):
+    """C = 100: cg_reduce_kernel past its first trip on every array (about 2,000 update workgroups; 4,096 dictionary partials on the
+    generation-order graph, where the matrix-core image is switched off so that rule 4 of spmm_plan decides through big_x; 9,378
+    matrix-core partials on the Z-curve graph), the quad update and the element update (mgp_cg_set_update_quads).
+    Measured: 58 iterations in all four cases, true_rel <= 1.0 tol; about 2 s a case, most of it the float64 residual on the host."""
+    from manifold_gp_amd import _lib
+    lib = _lib.lib()
+    lap, desc, sys = _big(mgp, swiss300k, dev, order, "randomwalk")
+    n = swiss300k["n"]
+    prev_mt = lib.mgp_spmm_set_mt_mode(0 if order == "random" else 1)
+    lib.mgp_cg_set_update_quads(quads)
+    try:
+        geo = _plan_geometry(desc, 100)
+        nbs, family = geo["nbs"], geo["family"]
+        if order == "random":
+            assert family == 5 and nbs == 4096, (family, nbs)
+        else:
+            assert family == 3 and nbs > 4096, (family, nbs)
+        _big_check(sys, desc, _block(n, 100, dev, seed=400), 1e-3, "300k C=100 %s quads %d" % (order, quads))
+    finally:
+        lib.mgp_spmm_set_mt_mode(prev_mt)
+        lib.mgp_cg_set_update_quads(1)
+
+
+@pytest.mark.parametrize("C", [12, 1])
+def test_past_caps_max_iter_exit(mgp, swiss300k, dev, C):
+    """C4 on the tail-loop paths: five steps, status 2, and a `resid` that is honest about the unconverged solution."""
+    lap, desc, sys = _big(mgp, swiss300k, dev, "random", "randomwalk")
+    assert _plan_geometry(desc, C)["nbs"] > 1024
+    rhs = swiss300k["gauss"] if C == 1 else _block(swiss300k["n"], C, dev, seed=300 + C)
+    _big_check(sys, desc, rhs, 1e-4, "300k C=%d capped" % C, max_iter=5)
