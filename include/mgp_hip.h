@@ -499,6 +499,31 @@ int mgp_cg_solve(const mgp_operator_t* op, const float* B, int C, float* X, cons
  * contributions to the diagonal ignored for nu > 2 (exact for nu <= 2) */
 int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* stream);
 
+/* Marginal posterior variances in precision form (csrc/variance.hip, docs/kernels/sampling.md "Marginal variances"): the two
+ * kernels of the single-site Rao-Blackwell estimator  var_i = s / d_i + E[(delta_i - p_i / d_i)^2],  d = diag(W + s Q2).
+ *
+ * The EXACT diagonal of operator forms 0 (q_i), 2 (1 + s q_i) and 3 (w_i + s q_i), q_i = scale pre_i post_i diag((tau I + L_sym)^nu)_i,
+ * for nu = 1, 2, 3 in float64: diag_out [n] (device).  nu = 3 counts the triangles through every node (a wave per row, the row's
+ * own entries in LDS); the Jacobi routine above keeps its pure diagonal power there.  Reads the natural-order CSR only (rowptr, col,
+ * vals, diag; no tiles), pre / post and, for form 3, obs_w; the CSR is taken as symmetric (S_ji = S_ij, as the graph builders
+ * write it); entries with col == row or S_ij == 0 are skipped as in the GMRF noise routine; a row's columns may come in any
+ * order.  Products and sums in float64 from the float32 values; tau, scale and s enter as the doubles of the struct's floats.
+ * Deterministic, no atomics.  The kernel needs no scratch today: the workspace query returns 0 and `work` may be NULL (the
+ * pair is there so that a later layout can take one without a new signature).
+ * MGP_ERR_UNSUPPORTED for nu > 3 and form 1; MGP_ERR_ARG for null pointers, form 3 without obs_w and n >= 2^31. */
+size_t mgp_operator_diag_exact_workspace_bytes(const mgp_operator_t* op);
+int mgp_operator_diag_exact(const mgp_operator_t* op, double* diag_out, void* work, size_t work_bytes, void* stream);
+/* Row moments of a block of samples: for every row i of the row-major float32 blocks U, V, Pm [n, C], 1 <= C <= 256,
+ *   u_c = U_ic - (Pm ? Pm_ic rdiag_i : 0),  v_c likewise from V (V == NULL or V == U: v = u),
+ *   acc[i, 0] += sum_c u_c v_c,   acc[i, 1] += sum_c (u_c v_c)^2,
+ * all arithmetic in float64.  acc [n, 2] float64 is read-modify-written: the chunks of a larger sample count add into one
+ * state, which the caller zeroes first.  rdiag [n] float64 (read only with Pm).  U == V, Pm == NULL: the plain second and
+ * fourth moments; distinct U and V: cross moments.  A lane group per row, float4 loads where C % 4 == 0 and the blocks are
+ * 16-byte aligned, scalar loads otherwise; fixed reduction tree, one lane writes: deterministic.
+ * MGP_ERR_ARG for C < 1, C > 256, n < 1, null U or acc, Pm without rdiag. */
+int mgp_row_moments(const float* U, const float* V, const double* rdiag, const float* Pm, int64_t n, int C, double* acc,
+                    void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Eigensolve: the m smallest eigenpairs of L_sym by a Chebyshev-filtered block Krylov iteration
  * with Rayleigh-Ritz on L_sym itself (csrc/eigen.hip explains why not single-vector Lanczos; the

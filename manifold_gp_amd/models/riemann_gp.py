@@ -134,6 +134,21 @@ class RiemannGP(torch.nn.Module):
         desc, noise, y = self._sampling_args()
         return posterior_mean(desc, y, noise, tol=tol, observed=observed)
 
+    def precision_posterior_variance(self, num_samples=64, seed=None, observed=None, noisy=False, tol=1e-6,
+                                     method="rao-blackwell"):
+        """(var, se): the marginal variance of f | y at every graph node, diag((Q + W / noise)^-1), and the standard error of
+        the estimate: float64 [N] each, from num_samples perturb-and-MAP draws (sampling.posterior_variance: single-site
+        Rao-Blackwell for nu <= 3, method="samples" for the plain mean of squares).  observed as in sample_posterior;
+        noisy=True adds the likelihood noise."""
+        from ..sampling import posterior_variance
+        desc, noise, _ = self._sampling_args()
+        return posterior_variance(desc, noise, num_samples, seed, observed=observed, method=method, noisy=noisy, tol=tol)
+
+    def precision_posterior_stddev(self, num_samples=64, seed=None, observed=None, noisy=False, tol=1e-6,
+                                   method="rao-blackwell"):
+        """sqrt of precision_posterior_variance(...)[0]: float64 [N]."""
+        return self.precision_posterior_variance(num_samples, seed, observed, noisy, tol, method)[0].clamp_min(0).sqrt()
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)

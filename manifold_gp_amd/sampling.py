@@ -17,6 +17,10 @@ g and w come from mgp_gmrf_noise (one row-parallel pass over the CSR, noise rege
 the applies and solves are the library's own (Descriptor.apply, cg_solve).  Column j of a call is the sample of global
 index offset + j whatever the batch size: every sample is a function of (seed, its index) alone.  Streams: tag 0 node
 noise w, tag 1 edge noise (inside g), tag 2 w2, tag 3 w3.
+
+Marginal variances (posterior_variance): diag of the posterior covariance from the same draws, var_i = s / d_i +
+E[(delta_i - p_i / d_i)^2] with delta = A3^-1 p, p the perturbed right-hand side without the targets, d = diag(A3) exact
+(mgp_operator_diag_exact); the moments are summed in float64 by mgp_row_moments.
 """
 import ctypes
 import math
@@ -287,3 +291,87 @@ def posterior_mean(desc, y, noise, tol=1e-5, refine=0, max_iter=5000, observed=N
             return cg_solve(ob.descriptor(desc), rhs, jacobi=OBSERVED_JACOBI[0], **_solve_kw(tol, refine, max_iter))[0].view(-1)
         s = float(noise)
         return cg_solve(desc.with_(form=2, noise=s), _targets(desc, y), **_solve_kw(tol, refine, max_iter))[0].view(-1)
+
+
+# ---------------------------------------------------------------------------------------------- marginal variances
+RB_MAX_NU = 3        # mgp_operator_diag_exact: the exact diagonal of A3 exists for nu <= 3
+
+
+def operator_diag_exact(desc):
+    """The exact diagonal of a form 0 / 2 / 3 descriptor (nu <= 3): [n] float64 on the graph's device."""
+    op = desc.struct()
+    dev = desc.data.graph.device
+    d = torch.empty(desc.n, dtype=torch.float64, device=dev)
+    wb = lib().mgp_operator_diag_exact_workspace_bytes(ctypes.byref(op))
+    work = _lib.workspace(wb, "diag_exact", dev) if wb else None
+    check(lib().mgp_operator_diag_exact(ctypes.byref(op), ptr(d), ptr(work), wb, stream()), "mgp_operator_diag_exact")
+    return d
+
+
+def row_moments(acc, U, V=None, rdiag=None, Pm=None):
+    """acc [n, 2] float64 += (sum_c u v, sum_c (u v)^2) over the columns of U [n, C] float32, u = U - Pm rdiag, v likewise
+    from V (None: v = u); C <= 256 (mgp_row_moments)."""
+    n, C = U.shape
+    check(lib().mgp_row_moments(ptr(U), ptr(V), ptr(rdiag), ptr(Pm), int(n), int(C), ptr(acc), stream()), "mgp_row_moments")
+    return acc
+
+
+def _perturbation(desc, P, ob, s, C, seed, offset):
+    """p = s z + sqrt(s) W^1/2 w2 (columns offset .. offset + C - 1): the right-hand side of posterior_samples without the
+    targets; s = s_ref and W = diag(ob.w) for form 3, W = I for form 2 (ob None)."""
+    z = _precision_chunk(desc, P, C, seed, offset)
+    if ob is None:
+        p = gmrf_noise(desc.data, C, seed, offset, node_coef=math.sqrt(s), tag=2)
+    else:
+        p = gmrf_noise(desc.data, C, seed, offset, node_coef=1.0, tag=2)
+        p *= (s * ob.w).sqrt()
+    p += s * z
+    return p
+
+
+def posterior_variance(desc, noise, S=64, seed=None, observed=None, method="rao-blackwell", noisy=False, tol=1e-6, refine=1,
+                       max_iter=5000):
+    """(var, se): the marginal posterior variance diag((Q2 + W / s)^-1) at every node and the standard error of the estimate,
+    float64 [n] each, from S perturb-and-MAP draws delta = A3^-1 p around the mean (the targets do not enter).
+    method "rao-blackwell" (nu <= 3): var_i = s / d_i + mean_s (delta_is - p_is / d_i)^2 with d = diag(A3) exact -- the
+    variance of node i given all others plus the variance of its conditional mean; unbiased, and never more variable than
+    "samples", the plain mean_s delta_is^2 (any nu).  se_i = sqrt((mean e^4 - (mean e^2)^2) / S) of the averaged term.
+    noise / observed as in posterior_samples; noisy=True adds the noise variance sigma_i^2 (the variance of y*)."""
+    from .solvers import cg_solve
+    P = _check_desc(desc)
+    S, seed = _count(S), _seed(seed)
+    if method not in ("rao-blackwell", "samples"):
+        raise ValueError("method must be 'rao-blackwell' or 'samples', got %r" % (method,))
+    ob = _observation(desc, noise, observed)
+    rb = method == "rao-blackwell"
+    if rb and int(desc.nu) > RB_MAX_NU:
+        raise NotImplementedError("method='rao-blackwell' needs the exact diagonal of the system, which exists for nu <= %d "
+                                  "(nu = %d): use method='samples'" % (RB_MAX_NU, int(desc.nu)))
+    kw = _solve_kw(tol, refine, max_iter)
+    if ob is not None:
+        kw["jacobi"] = OBSERVED_JACOBI[0]
+        s, dsys = ob.s_ref, ob.descriptor(desc)
+    else:
+        s = float(noise)
+        dsys = desc.with_(form=2, noise=s)
+    dev = desc.data.graph.device
+    acc = torch.zeros(desc.n, 2, dtype=torch.float64, device=dev)
+    with torch.no_grad():
+        rdiag = operator_diag_exact(dsys).reciprocal() if rb else None
+        for c0 in range(0, S, CHUNK):
+            C = min(CHUNK, S - c0)
+            p = _perturbation(desc, P, ob, s, C, seed, c0)
+            row_moments(acc, _lib.f32c(cg_solve(dsys, p, **kw)[0]), None, rdiag, p if rb else None)
+        m2, m4 = acc[:, 0] / S, acc[:, 1] / S
+        var = m2 + s * rdiag if rb else m2
+        se = ((m4 - m2 * m2).clamp_min(0.0) / S).sqrt()
+        if noisy:
+            per_node = torch.is_tensor(noise) and noise.numel() != 1
+            var = var + (noise.to(device=dev, dtype=torch.float64) if per_node else float(noise))
+    return var, se
+
+
+def posterior_stddev(desc, noise, S=64, seed=None, observed=None, method="rao-blackwell", noisy=False, tol=1e-6, refine=1,
+                     max_iter=5000):
+    """The marginal posterior standard deviation at every node: sqrt of posterior_variance(...)[0], float64 [n]."""
+    return posterior_variance(desc, noise, S, seed, observed, method, noisy, tol, refine, max_iter)[0].clamp_min(0).sqrt()
