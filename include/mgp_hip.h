@@ -409,10 +409,12 @@ typedef struct {
                           that factor around the tolerance */
 } mgp_cg_params_t;
 
+/* what a plan on (op, C) carves from `work` (csrc/cg_policy.h: cg_carve), plus slack; 0 for arguments a plan would refuse */
 size_t mgp_cg_workspace_bytes(const mgp_operator_t* op, int C);
-/* ---- Lab-only switches (every mgp_*_set_* in this header): process-wide std::atomic<int> words for A/B measurements and tests.
+/* ---- Lab-only switches (every mgp_*_set_* in this header): process-wide words for A/B measurements and tests (std::atomic<int>;
+ * the CG family's six are the plain ints of one struct, CgKnobs in csrc/cg_policy.h).
  * The SpMM family reads them once per call, into the plan value that the call passes down; the CG
- * switches are read at plan creation; the kernel-block switch once per call; the k-NN / eigensolver switches where a call
+ * switches are read at plan creation (mgp_cg_set_poll_spin: once per chunk of a solve); the kernel-block switch once per call; the k-NN / eigensolver switches where a call
  * branches on them.  They are not part of the path's contract and are not meant to be flipped while another thread is inside a
  * call of the same family: two calls that size and launch the same product (mgp_spmm_dot_blocks_csr, then mgp_spmm_fused; the
  * k-NN workspace query, then the search) must see the same setting. */

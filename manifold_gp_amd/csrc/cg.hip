@@ -26,20 +26,16 @@
 #include <vector>
 #include <string.h>
 #include <algorithm>
-#include <atomic>
 #include "mgp_common.h"
 #include "mgp_internal.h"
 #include "cg_rule.h"
+#include "cg_policy.h"
 
 namespace {
 
-constexpr int kBlock = 256;
 #ifndef MGP_LAB_UPD
 #define MGP_LAB_UPD 0      // lab builds (tools/lab/upd_bounds.sh): 4 = never converge, alpha = beta = 0; | 1 skip the partial reads; | 2 skip the vector pass
 #endif
-constexpr int kMaxC = 256;
-constexpr int kMaxGridVec = 512;
-constexpr int kMaxPartials = 4096;   // capacity of the gamma / rr partial arrays
 
 typedef float mgp_cg_v4f __attribute__((ext_vector_type(4)));
 
@@ -406,7 +402,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(CgArgs a) {
 }
 
 // ---- Quad form of the update for C % 4 == 0 (the column counts of training: 12 probes, 32, 100 one-hot columns).
-// cg_update_kernel gives a lane one (row, column) ELEMENT: dword loads and stores, tile_cols(C) - C lanes idle (12 of 16, 100 of 128),
+// cg_update_kernel gives a lane one (row, column) ELEMENT: dword loads and stores, cg_tile_cols(C) - C lanes idle (12 of 16, 100 of 128),
 // a wave's stores covering 48-byte rows.  Here the [n, C] arrays are streams of float4: thread (slq, cq) owns column quad cq of the
 // rows slq, slq + TSQ, ... of its workgroup's contiguous row range -- CQ * TSQ of BLOCK threads active (255 of 256 at C = 12, 250
 // at C = 100), every load / store a dwordx4, a wave's accesses 1 KB contiguous.  Same arithmetic per element, same
@@ -558,15 +554,12 @@ __global__ __launch_bounds__(BLOCK) void cg_update_q_kernel(CgArgs a) {
 //     workgroup through LDS once, then EVERY lane derives alpha, beta and the stopping decision
 //     redundantly (no broadcast round), and the new partials take the second barrier.
 // Summation order is fixed (lane slots in order, xor tree, (w0 + w1) + (w2 + w3)).
-// C == 1 layout of the scalar block (plan_create_impl): fetched as one s_load_dwordx8.  Separate scalar
+// C == 1 layout of the scalar block (cg_carve: blk): fetched as one s_load_dwordx8.  Separate scalar
 // loads are not batched by hipcc (each is followed by lgkmcnt(0)): five of them cost five round trips.
 struct alignas(32) CgScalars {
   float go0, go1, ao0, ao1, bb, resid;
   int it, done;
 };
-
-constexpr int kC1GammaSlots = 2;    // nbv <= kMaxGridVec = 2 * 256
-constexpr int kC1DeltaSlots = 16;   // nbs <= 4096
 
 // DECIDE (the LAST update of a plan's first graph): the workgroup whose partials arrive last also takes the stopping decision
 // of the NEXT step -- ||r_k||^2 summed over the partials this very launch wrote, in cg_decide_c1_kernel's order, decided by
@@ -887,7 +880,6 @@ __global__ void cg_marker_kernel(int* state, int* host_state) {
 //     real relative residual.  `iters` reports the COCG steps of that x (the launch count less one: cg_plan_solve_body),
 //     and the max_iter exit waits one launch longer, so that it returns x = Re z_{max_iter} with iters = max_iter;
 ////   * state words, host flags, skip / tick and the chunked hipGraph replay are those of the real solver.
-constexpr int kCxDeltaSlots = 16;    // nbs4 <= 4096
 
 struct CxArgs {
   float2 *z, *r, *p, *s;     // [n] complex
@@ -1224,91 +1216,67 @@ void host_block_release(HostBlock b, hipStream_t stream) {
 struct CgPlan {
   bool poisoned = false;     // a solve ended in MGP_ERR_TIMEOUT: destroy leaks instead of waiting (mgp_cg_plan_solve)
   HostBlock host_block;
-  mgp_operator_t op;
-  MgpDist dist;             // row partition (is_dist): op.L holds the local rows only
-  bool is_dist;
-  int nb_loc;               // SpMM workgroups per rank that write dot partials
-  int C;
-  mgp_cg_params_t prm;
-  CgArgs args;
-  void* op_work;
-  size_t op_work_bytes;
-  float* pd_delta;
-  hipStream_t stream;       // caller's stream: all work is enqueued here
-  hipStream_t cap_stream;   // private stream used only to capture the iteration graph
-  hipGraphExec_t exec;        // `chunk` x (apply, update): continuation replays
-  hipGraph_t graph_first;     // cg_init + `len_first` x (apply, update): a short solve is ONE graph launch
-  hipGraphExec_t exec_first;
-  hipGraphNode_t init_node;   // the cg_init node of graph_first (its rhs argument is patched per solve)
-  bool has_graph, has_first;
-  int chunk, len_first;
-  int last_need;              // (apply, update) pairs the previous solve needed: len_first follows it
-  const float* patched_rhs;   // rhs the cg_init node currently points at
-  int solves;                 // run_cg calls so far (graphs are captured at the second one)
-  int64_t last_solve_ns;      // host time of the previous solve when it ended inside its first chunk (0: it did not)
-  int marker_seq;             // first graphs launched so far = what cg_marker_kernel will have counted when the newest ends
-  bool graphs_tried;
-  bool init_free;             // no cg_init launch: the first apply reads the rhs itself (CgArgs::pd_bb)
-  bool rebound;               // mgp_cg_plan_rebind since the last solve: the graphs are refreshed before they are launched again
-  int upd_quads;              // 0: cg_update_kernel; else the workgroup size of cg_update_q_kernel (C % 4 == 0)
-  bool decide_in_update;      // the first graph's last update decides + marks (mgp_cg_set_decide_in_update at plan creation)
-  bool cx;                    // complex-shift solve (cx_update_kernel): form 2, nu = 2, symmetric normalisation, C = 1
-  CxArgs cxa;
-  mgp_operator_t opB;         // B = tau I + L_sym (one launch of the 4-column SpMM per iteration)
-  float* pd4;                 // [nb4][4] partials of u . B u
-  int nb4;
-  void* op_work4;
-  size_t op_work4_bytes;
-  float* pd_bb;               // [nbs] partials of ||b||^2 written by the first apply
-  char first_record[MGP_SPMM_RECORD_BYTES];   // launch arguments of the first graph's root SpMV (rhs patched per solve)
-  int32_t* host_state;      // pinned
-  float* host_resid;        // pinned
-  float *xacc, *rbuf, *tbuf, *rpart;   // refinement: accumulated solution, residual rhs, A x, partials
-  double *xacc64, *t64, *work64, *rpart64;   // single GPU: the same in fp64 (true residual from an fp64 apply)
-  float* host_true_rel;     // host-mapped [C]: true relative residuals
-  float* dev_true_rel;
+  mgp_operator_t op{};
+  MgpDist dist{};           // row partition (is_dist): op.L holds the local rows only
+  bool is_dist = false;
+  int nb_loc = 0;           // SpMM workgroups per rank that write dot partials
+  int C = 0;
+  mgp_cg_params_t prm{};
+  CgChoice ch{};            // kernel family and grid (cg_choose at creation)
+  CgBuffers buf{};          // the workspace as carved (cg_carve)
+  CgArgs args{};
+  hipStream_t stream = nullptr;       // caller's stream: all work is enqueued here
+  hipStream_t cap_stream = nullptr;   // private stream used only to capture the iteration graph
+  hipGraphExec_t exec = nullptr;        // `chunk` x (apply, update): continuation replays
+  hipGraph_t graph_first = nullptr;     // cg_init + `len_first` x (apply, update): a short solve is ONE graph launch
+  hipGraphExec_t exec_first = nullptr;
+  hipGraphNode_t init_node = nullptr;   // the cg_init node of graph_first (its rhs argument is patched per solve)
+  bool has_graph = false, has_first = false;
+  int chunk = 0, len_first = 0;
+  int last_need = 0;                    // (apply, update) pairs the previous solve needed: len_first follows it
+  const float* patched_rhs = nullptr;   // rhs the cg_init node currently points at
+  int solves = 0;                       // run_cg calls so far (graphs are captured at the second one)
+  int64_t last_solve_ns = 0;            // host time of the previous solve when it ended inside its first chunk (0: it did not)
+  int marker_seq = 0;                   // first graphs launched so far = what cg_marker_kernel will have counted when the newest ends
+  bool graphs_tried = false;
+  bool rebound = false;                 // mgp_cg_plan_rebind since the last solve: the graphs are refreshed before they are launched again
+  bool decide_in_update = false;        // the first graph's last update decides + marks (CgKnobs::decide_in_update at plan creation)
+  CxArgs cxa{};                         // complex-shift solve (ch.cx)
+  mgp_operator_t opB{};                 // B = tau I + L_sym (one launch of the 4-column SpMM per iteration)
+  char first_record[MGP_SPMM_RECORD_BYTES] = {};   // launch arguments of the first graph's root SpMV (rhs patched per solve)
+  int32_t* host_state = nullptr;        // pinned
+  float* host_resid = nullptr;          // pinned
+  float* host_true_rel = nullptr;       // host-mapped [C]: true relative residuals
+  float* dev_true_rel = nullptr;
 };
 
-int tile_cols(int C) {
-  int t = 1;
-  while (t < C) t <<= 1;
-  return t;
+CgKnobs g_knobs;   // the lab switches (mgp_cg_set_*)
+
+// What a plan on `op` is created from.  minv, stop_mode: whatever the caller has when only the workspace is sized (no buffer depends on them).
+CgShape cg_shape(const mgp_operator_t* op, int C, int world, bool is_dist, bool has_minv, int stop_mode) {
+  CgShape sh{};
+  sh.n = op->L.n; sh.world = world; sh.is_dist = is_dist; sh.C = C;
+  sh.nb_loc = mgp_spmm_dot_blocks_for(&op->L, C);
+  sh.nb4 = (C == 1 && !is_dist) ? mgp_spmm_dot_blocks_for(&op->L, 4) : 0;
+  sh.has_minv = has_minv; sh.has_pre = op->pre != nullptr; sh.has_post = op->post != nullptr;
+  sh.form = op->form; sh.nu = op->nu; sh.noise_scale = op->noise * op->scale;
+  sh.stop_mode = stop_mode;
+  sh.tile_plan = C == 1 && mgp_tile_plan(&op->L) != 0;
+  return sh;
 }
 
-size_t cg_bytes(const mgp_operator_t* op, int C, int world = 1) {
-  const size_t nc = mgp_align((size_t)op->L.n * world * C * sizeof(float));
-  const int nbs = mgp_spmm_dot_blocks_for(&op->L, C) * world;
-  size_t b = 10 * nc;                                  // x r u w p s us + refinement xacc rbuf tbuf
-  b += 4 * nc + 256;                                   // operator chain scratch (global length)
-  b += 4 * mgp_align((size_t)kMaxPartials * C * sizeof(float));  // pd_gamma[2], pd_rr[2]
-  b += 2 * mgp_align((size_t)nbs * C * sizeof(float));          // pd_delta, pd_bb
-  b += mgp_align((6 * (size_t)C + 16 + 1024 + 8192) * sizeof(float));   // gamma_old[2] alpha_old[2] bb resid state (+ lab stamps)
-  b += mgp_align(3 * (size_t)C * sizeof(float));                 // tot (cg_reduce_kernel)
-  b += mgp_align(9 * 32 * sizeof(int));                         // arrival counters (cg_update_c1_kernel<true>)
-  b += mgp_align((size_t)256 * C * 2 * sizeof(float));          // refinement partials
-  b += 6 * 2 * nc + mgp_align((size_t)256 * C * 2 * sizeof(double));   // fp64 refinement: xacc, A x, 4 chain buffers
-  if (C == 1 && world == 1) {
-    // complex-shift solve: z r p s (float2), u4 w4 y4 (float4), the 4-column chain scratch, partials, scalars
-    const size_t n = (size_t)op->L.n;
-    b += 4 * mgp_align(n * 8) + 3 * mgp_align(n * 16) + 4 * mgp_align(n * 16) + 256;
-    b += mgp_align((size_t)kCxDeltaSlots * kBlock * 4 * sizeof(float)) + mgp_align((size_t)2 * kMaxGridVec * 4 * sizeof(float)) + 256;
-  }
-  return b + 1024;
+size_t cg_bytes(const mgp_operator_t* op, int C, int world, bool is_dist) {
+  const CgShape sh = cg_shape(op, C, world, is_dist, false, 0);
+  return cg_workspace_bytes(sh, cg_choose(sh, g_knobs));
 }
 
-constexpr int kReduceOnceAbove = 16;
-std::atomic<int> g_cg_complex_shift{1};   // form 2, nu = 2, symmetric normalisation, C = 1: the complex-shift solve (mgp_cg_set_complex_shift(0): CG on A)
-std::atomic<int> g_cg_reduce_once{1};   // mgp_cg_set_reduce_once(0): every update workgroup re-reduces the partials at any C (A/B, tests)
-std::atomic<int> g_cg_update_quads{1};   // C % 4 == 0 plans update through cg_update_q_kernel (mgp_cg_set_update_quads(0): the element form at every C)
-std::atomic<int> g_cg_poll_spin{64};    // flag reads between two looks at the clock in the flag-only poll window; 0: no such window (mgp_cg_set_poll_spin)
-std::atomic<int> g_cg_init_free{1};   // C == 1 plans start without a cg_init launch (mgp_cg_set_init_free(0): classic start)
-std::atomic<int> g_cg_decide_in_update{1};   // the first graph's last update decides + marks (mgp_cg_set_decide_in_update(0): separate launches)
-
-// The single-column kernel family (cg_update_c1_kernel, cg_decide_c1_kernel, cx_update_kernel) can run this plan: one column
-// whose partials fit the slots a lane of those kernels sums.  (One column on one device always does: the update grid is at most
-// kMaxGridVec and the SpMV grids at most 4096 workgroups; a row-partitioned plan has `world` times the SpMV partials.)
-bool c1_family(const CgArgs& a) {
-  return a.C == 1 && a.nbv <= kC1GammaSlots * kBlock && a.nbs <= kC1DeltaSlots * kBlock;
+// The operator of the complex-shift solve's one product per step: B = tau I + L_sym, from the (K + s I) operator in precision form
+mgp_operator_t cx_operator(const mgp_operator_t* op) {
+  mgp_operator_t b = mgp_operator_copy(op);
+  b.nu = 1;
+  b.kappa = op->kappa / sqrtf(2.0f);       // tau_B = 2 / kappa_B^2 = 2 nu / kappa^2
+  b.scale = 1.0f; b.form = 0; b.noise = 0.f;
+  return b;
 }
 
 // one CG step = operator apply (w = A u, partials of u . w, ticks the iteration counter; skipped once
@@ -1326,28 +1294,28 @@ void launch_update_c1(CgPlan* pl, hipStream_t st, bool decide_last) {
 }
 
 int enqueue_body(CgPlan* pl, hipStream_t st, bool decide_last = false) {
-  if (pl->cx) {
+  if (pl->ch.cx) {
     // B u on the 4-column tile SpMM (partials of u . B u ride along; skipped once decided; ticks the iteration), then the
     // complex update
     MGP_TRY(mgp_operator_apply_dist(&pl->opB, nullptr, reinterpret_cast<const float*>(pl->cxa.u4), nullptr, 4,
                                     const_cast<float*>(reinterpret_cast<const float*>(pl->cxa.y4)),
-                                    reinterpret_cast<const float*>(pl->cxa.w4), pl->pd4, pl->nb4, pl->args.state + 1,
-                                    pl->args.state, pl->op_work4, pl->op_work4_bytes, st));
+                                    reinterpret_cast<const float*>(pl->cxa.w4), pl->buf.pd4, pl->cxa.nbs4, pl->args.state + 1,
+                                    pl->args.state, pl->buf.op_work4, pl->buf.op_work4_bytes, st));
     hipLaunchKernelGGL(cx_update_kernel, dim3(pl->args.nbv), dim3(kBlock), 0, st, pl->args, pl->cxa);
     MGP_LAUNCH_CHECK();
     return MGP_OK;
   }
   MGP_TRY(mgp_operator_apply_dist(&pl->op, pl->is_dist ? &pl->dist : nullptr, pl->args.u, pl->args.us, pl->C,
-                                  pl->args.w, pl->args.u, pl->pd_delta, pl->nb_loc, pl->args.state + 1,
-                                  pl->args.state, pl->op_work, pl->op_work_bytes, st));
-  if (c1_family(pl->args)) {
+                                  pl->args.w, pl->args.u, pl->buf.pd_delta, pl->nb_loc, pl->args.state + 1,
+                                  pl->args.state, pl->buf.op_work, pl->buf.op_work_bytes, st));
+  if (pl->ch.c1_family) {
     launch_update_c1(pl, st, decide_last);
   } else {
     if (pl->args.tot) {
       hipLaunchKernelGGL(cg_reduce_kernel, dim3((unsigned)mgp_cdiv(pl->C, 4), 3), dim3(kBlock), 0, st, pl->args);
       MGP_LAUNCH_CHECK();
     }
-    if (pl->upd_quads) hipLaunchKernelGGL(cg_update_q_kernel<kBlock>, dim3(pl->args.nbv), dim3(kBlock), 0, st, pl->args);
+    if (pl->ch.upd_quads) hipLaunchKernelGGL(cg_update_q_kernel<kBlock>, dim3(pl->args.nbv), dim3(kBlock), 0, st, pl->args);
     else hipLaunchKernelGGL(cg_update_kernel, dim3(pl->args.nbv), dim3(kBlock), 0, st, pl->args);
   }
   MGP_LAUNCH_CHECK();
@@ -1358,8 +1326,8 @@ int enqueue_body(CgPlan* pl, hipStream_t st, bool decide_last = false) {
 // copies it to r), leaves the partials of r . A r and ||r||^2 and resets the iteration state; the update then runs
 // as iteration 1 with p = s = x = 0.  One launch (cg_init, ~3.8 us at N = 60k) less per solve.
 int enqueue_first_body(CgPlan* pl, hipStream_t st, const float* rhs, bool record, bool decide_last = false) {
-  MGP_TRY(mgp_operator_apply_first(&pl->op, rhs, pl->args.r, pl->args.w, pl->pd_delta, pl->pd_bb, pl->args.state,
-                                   record ? pl->first_record : nullptr, pl->op_work, pl->op_work_bytes, st));
+  MGP_TRY(mgp_operator_apply_first(&pl->op, rhs, pl->args.r, pl->args.w, pl->buf.pd_delta, pl->buf.pd_bb, pl->args.state,
+                                   record ? pl->first_record : nullptr, pl->buf.op_work, pl->buf.op_work_bytes, st));
   launch_update_c1(pl, st, decide_last);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
@@ -1371,14 +1339,13 @@ bool record_first(CgPlan* pl, int len, hipGraph_t* out) {
   if (!pl->cap_stream || len < 1) return false;
   if (hipStreamBeginCapture(pl->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
   int rc = MGP_OK;
-  // `len` = steps until the stopping rule fires: the last of them only detects (see cg_decide_c1_kernel)
-  const bool decide = len >= 2 && !pl->is_dist && c1_family(pl->args);
+  const bool decide = cg_last_step_decides(len, pl->is_dist, pl->ch.c1_family);
   const int bodies = decide ? len - 1 : len;
   int done_bodies = 0;
-  // decide: the graph's LAST update also takes the next step's decision and leaves the end-of-graph mark (g_cg_decide_in_update;
+  // decide: the graph's LAST update also takes the next step's decision and leaves the end-of-graph mark (CgKnobs::decide_in_update;
   // 0: the separate cg_decide_c1_kernel + cg_marker_kernel launches of rounds 1-3)
   const bool in_update = decide && pl->decide_in_update;
-  if (pl->init_free) {
+  if (pl->ch.init_free) {
     // root node = launch 0 of the first apply, reading a placeholder rhs that is patched before every launch
     rc = enqueue_first_body(pl, pl->cap_stream, (const float*)pl->args.x, true, in_update && bodies == 1);
     done_bodies = 1;
@@ -1428,7 +1395,7 @@ void capture_first(CgPlan* pl, int len) {
 // point the cg_init node of the first graph at this solve's right-hand side
 bool patch_first_rhs(CgPlan* pl, const float* rhs) {
   if (rhs == pl->patched_rhs) return true;
-  if (pl->init_free) {
+  if (pl->ch.init_free) {
     if (mgp_spmm_patch_node(pl->exec_first, pl->init_node, pl->first_record, (const float*)pl->args.x, rhs) != MGP_OK) {
       (void)hipGetLastError();
       return false;
@@ -1451,7 +1418,7 @@ bool patch_first_rhs(CgPlan* pl, const float* rhs) {
 
 extern "C" size_t mgp_cg_workspace_bytes(const mgp_operator_t* op, int C) {
   if (!op || C <= 0 || C > kMaxC || op->L.n <= 0 || !mgp_spmv_lanes_ok(op->L.spmv_lanes)) return 0;
-  return cg_bytes(op, C);
+  return cg_bytes(op, C, 1, false);
 }
 
 // stream-capture `chunk` bodies (the continuation graph) into *out
@@ -1526,10 +1493,8 @@ static void capture_graphs(CgPlan* pl) {
   }
   pl->has_graph = ok;
   (void)hipGetLastError();   // a failed capture falls back to eager launches
-  if (ok && !pl->cx) {      // (the complex-shift solve runs tens of iterations: init launch + chunk graphs, no single-graph form)
-    int len = pl->last_need >= 1 && pl->last_need <= 64 ? pl->last_need : (pl->chunk < 4 ? pl->chunk : 4);
-    capture_first(pl, len);
-  }
+  // (the complex-shift solve runs tens of iterations: init launch + chunk graphs, no single-graph form)
+  if (ok && !pl->ch.cx) capture_first(pl, cg_first_len(pl->last_need, pl->chunk));
 }
 
 static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, const mgp_cg_params_t* params,
@@ -1540,129 +1505,55 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
   if (dist && (dist->n_loc != op->L.n || dist->world < 1 || dist->rank < 0 || dist->rank >= dist->world))
     return MGP_ERR_ARG;
   if (dist && op->form == 3) return MGP_ERR_UNSUPPORTED;       // form 3: single-GPU plans only
-  if (work_bytes < cg_bytes(op, C, world)) return MGP_ERR_WORKSPACE;
+  mgp_cg_params_t prm = *params;
+  if (prm.max_iter <= 0) prm.max_iter = 1000;
+  if (prm.min_iter < 0) prm.min_iter = 0;
+  const CgKnobs knobs = g_knobs;      // (lab knobs: read once, at plan creation)
+  const CgShape sh = cg_shape(op, C, world, dist != nullptr, minv != nullptr, prm.stop_mode);
+  const CgChoice ch = cg_choose(sh, knobs);
+  if (work_bytes < cg_workspace_bytes(sh, ch)) return MGP_ERR_WORKSPACE;
   CgPlan* pl = new (std::nothrow) CgPlan();
   if (!pl) return MGP_ERR_ARG;
-  memset(pl, 0, sizeof(*pl));
+  MgpArena ar(work, work_bytes);
+  cg_carve(ar, sh, ch, &pl->buf);
+  if (!ar.ok()) { delete pl; return MGP_ERR_WORKSPACE; }
+  const CgBuffers& b = pl->buf;
   pl->op = mgp_operator_copy(op);
   pl->is_dist = dist != nullptr;
   if (dist) pl->dist = *dist;
-  pl->C = C;
-  pl->prm = *params;
-  if (pl->prm.max_iter <= 0) pl->prm.max_iter = 1000;
-  if (pl->prm.min_iter < 0) pl->prm.min_iter = 0;
-  pl->chunk = pl->prm.check_every > 0 ? pl->prm.check_every : 10;
+  pl->C = C; pl->prm = prm; pl->ch = ch; pl->nb_loc = sh.nb_loc;
+  pl->decide_in_update = knobs.decide_in_update != 0;
+  pl->chunk = prm.check_every > 0 ? prm.check_every : 10;
   pl->stream = mgp_stream(stream);
-  const int64_t n = op->L.n * world;        // global vector length
-  const size_t nc = (size_t)n * C;
-  MgpArena ar(work, work_bytes);
   CgArgs& a = pl->args;
-  a.n = n; a.C = C; a.TC = tile_cols(C); a.TS = kBlock / a.TC;
-  a.x = ar.take<float>(nc); a.r = ar.take<float>(nc);
-  float* ubuf = ar.take<float>(nc);
-  a.w = ar.take<float>(nc); a.p = ar.take<float>(nc); a.s = ar.take<float>(nc);
-  float* usbuf = ar.take<float>(nc);
-  a.minv = minv;
-  a.u = minv ? ubuf : a.r;
-  a.pre = op->pre;
-  a.us = op->pre ? usbuf : nullptr;
-  pl->op_work_bytes = 4 * mgp_align(nc * sizeof(float)) + 256;
-  pl->op_work = ar.take<char>(pl->op_work_bytes);
-  // contiguous row ranges per workgroup, at most kMaxGridVec workgroups.  C > 1: every workgroup of the
-  // update kernel re-reduces ALL dot partials of ALL columns (nbv x (2 nbv + nbs) x C loads per launch),
-  // so the grid is kept to one workgroup per CU (their loads go out in batches of 8 / 32 per lane)
-  // C > 16: the partials are summed once by cg_reduce_kernel, the update grid is free to fill the chip
-  const int reduce_mode = g_cg_reduce_once;      // (lab knobs: read once, at plan creation)
-  pl->decide_in_update = g_cg_decide_in_update != 0;
-  const bool reduce_once = reduce_mode && C > (reduce_mode == 2 ? 1 : kReduceOnceAbove);
-  int max_grid_vec = (C == 1) ? kMaxGridVec : (reduce_once ? 2048 : 256);
-  int64_t rpb = a.TS;
-  // C % 4 == 0 behind cg_reduce_kernel (C > 16): the quad form of the update (cg_update_q_kernel).  Up to 16 columns, where every
-  // workgroup re-reduces the partials, the element form stays: measured at 60k x 12 (tools/lab/cg12.py) 12.2 us against 15.4 for the
-  // quad form in 1024-thread workgroups and 17.4 in 512-thread ones (the kernel can do it: lab switch below)
-  pl->upd_quads = (C % 4 == 0 && reduce_once && g_cg_update_quads != 0) ? kBlock : 0;
-  a.CQ = C / 4; a.TSQ = 0;
-  if (pl->upd_quads) {
-    a.TSQ = pl->upd_quads / a.CQ;
-    rpb = a.TSQ;
-  }
-  int64_t nbv = mgp_cdiv(n, rpb);
-  {
-    const int64_t step = pl->upd_quads ? a.TSQ : a.TS;
-    if (nbv > max_grid_vec) { rpb = mgp_cdiv(mgp_cdiv(n, max_grid_vec), step) * step; nbv = mgp_cdiv(n, rpb); }
-  }
-  a.rows_per_block = rpb; a.nbv = (int)nbv;
-  a.pd_gamma = ar.take<float>(2 * (size_t)kMaxPartials * C);
-  a.pd_rr = ar.take<float>(2 * (size_t)kMaxPartials * C);
-  pl->nb_loc = mgp_spmm_dot_blocks_for(&op->L, C);
-  a.nbs = pl->nb_loc * world;
-  pl->pd_delta = ar.take<float>((size_t)a.nbs * C);
-  a.pd_delta = pl->pd_delta;
-  // one contiguous block: for C == 1 {gamma_old[2], alpha_old[2], bb, resid, state[0], state[1]} are 32
-  // consecutive bytes, which the C == 1 kernels fetch with a single scalar load (CgScalars)
-#ifdef MGP_STAMP
-  float* blk = ar.take<float>(6 * (size_t)C + 16 + 1024 + 8192);
-  MGP_HIP_TRY(hipMemsetAsync(blk, 0, (6 * (size_t)C + 16 + 1024 + 8192) * sizeof(float), pl->stream));
-#else
-  float* blk = ar.take<float>(6 * (size_t)C + 16);
-#endif
-  a.gamma_old = blk;
-  a.alpha_old = blk + 2 * (size_t)C;
-  a.bb = blk + 4 * (size_t)C;
-  a.resid = blk + 5 * (size_t)C;
-  a.state = reinterpret_cast<int*>(blk + 6 * (size_t)C);
-  (void)hipMemsetAsync(a.state, 0, 16 * sizeof(int), pl->stream);      // (state[5]: cg_marker_kernel's count)
-  {
-    float* tot = ar.take<float>(3 * (size_t)C);
-    a.tot = reduce_once ? tot : nullptr;
-  }
-  pl->xacc = ar.take<float>(nc); pl->rbuf = ar.take<float>(nc); pl->tbuf = ar.take<float>(nc);
-  pl->rpart = ar.take<float>((size_t)256 * C * 2);
-  pl->xacc64 = ar.take<double>(nc); pl->t64 = ar.take<double>(nc); pl->work64 = ar.take<double>(4 * nc);
-  pl->rpart64 = ar.take<double>((size_t)256 * C * 2);
-  a.tol = pl->prm.tol; a.max_iter = pl->prm.max_iter; a.min_iter = pl->prm.min_iter;
-  a.stop_mode = pl->prm.stop_mode;
-  pl->cx = false;
-  if (C == 1 && !dist) {
-    // the complex-shift solve's buffers (taken whenever the shape could use them: cg_bytes counts them)
-    const size_t nn = (size_t)n;
+  a.n = sh.n * world; a.C = C; a.TC = ch.TC; a.TS = ch.TS; a.CQ = ch.CQ; a.TSQ = ch.TSQ;
+  a.rows_per_block = ch.rows_per_block; a.nbv = ch.nbv; a.nbs = ch.nbs;
+  a.x = b.x; a.r = b.r; a.w = b.w; a.p = b.p; a.s = b.s;
+  a.minv = minv; a.u = minv ? b.ubuf : a.r;
+  a.pre = op->pre; a.us = op->pre ? b.usbuf : nullptr;
+  a.pd_gamma = b.pd_gamma; a.pd_rr = b.pd_rr; a.pd_delta = b.pd_delta;
+  a.gamma_old = b.blk; a.alpha_old = b.blk + 2 * (size_t)C; a.bb = b.blk + 4 * (size_t)C; a.resid = b.blk + 5 * (size_t)C;
+  a.state = reinterpret_cast<int*>(b.blk + 6 * (size_t)C);
+  a.tot = ch.reduce_once ? b.tot : nullptr;
+  a.pd_bb = ch.init_free ? b.pd_bb : nullptr;
+  a.arrive = b.arrive;
+  a.tol = prm.tol; a.max_iter = prm.max_iter; a.min_iter = prm.min_iter; a.stop_mode = prm.stop_mode;
+  (void)hipMemsetAsync(a.state, 0, (16 + kStampWords) * sizeof(int), pl->stream);      // (state[5]: cg_marker_kernel's count)
+  MGP_HIP_TRY(hipMemsetAsync(a.arrive, 0, 9 * 32 * sizeof(int), pl->stream));
+  if (b.cz) {
     CxArgs& cx = pl->cxa;
-    cx.z = ar.take<float2>(nn); cx.r = ar.take<float2>(nn); cx.p = ar.take<float2>(nn); cx.s = ar.take<float2>(nn);
-    cx.u4 = ar.take<mgp_cg_v4f>(nn); cx.w4 = ar.take<mgp_cg_v4f>(nn);
-    cx.y4 = ar.take<mgp_cg_v4f>(nn);
-    pl->op_work4_bytes = 4 * mgp_align(nn * 16) + 256;
-    pl->op_work4 = ar.take<char>(pl->op_work4_bytes);
-    pl->pd4 = ar.take<float>((size_t)kCxDeltaSlots * kBlock * 4);
-    cx.pd_g = ar.take<float>((size_t)2 * kMaxGridVec * 4);
-    cx.sc = ar.take<float>(64);
-    cx.pd4 = pl->pd4;
-    const float cc = op->noise * op->scale;
-    if (g_cg_complex_shift && !minv && op->form == 2 && op->nu == 2 && !op->pre && !op->post && cc > 0.f && ar.ok() &&
-        c1_family(a) && pl->prm.stop_mode == 1) {
-      pl->opB = mgp_operator_copy(op);
-      pl->opB.nu = 1;
-      pl->opB.kappa = op->kappa / sqrtf(2.0f);       // tau_B = 2 / kappa_B^2 = 2 nu / kappa^2
-      pl->opB.scale = 1.0f; pl->opB.form = 0; pl->opB.noise = 0.f;
-      pl->nb4 = mgp_spmm_dot_blocks_for(&pl->opB.L, 4);
-      if (pl->nb4 >= 1 && pl->nb4 <= kCxDeltaSlots * kBlock) {
-        cx.nbs4 = pl->nb4;
-        cx.sigma = sqrtf(cc);
-        MGP_HIP_TRY(hipMemsetAsync(cx.sc, 0, 64 * sizeof(float), pl->stream));
-        pl->cx = true;
-      }
-    }
+    cx.z = reinterpret_cast<float2*>(b.cz); cx.r = reinterpret_cast<float2*>(b.cr);
+    cx.p = reinterpret_cast<float2*>(b.cp); cx.s = reinterpret_cast<float2*>(b.cs);
+    cx.u4 = reinterpret_cast<mgp_cg_v4f*>(b.u4); cx.w4 = reinterpret_cast<mgp_cg_v4f*>(b.w4);
+    cx.y4 = reinterpret_cast<const mgp_cg_v4f*>(b.y4);
+    cx.pd4 = b.pd4; cx.pd_g = b.pd_g; cx.sc = b.sc;
   }
-  pl->pd_bb = ar.take<float>((size_t)a.nbs * C);
-  a.pd_bb = nullptr;
-  a.arrive = ar.take<int>(9 * 32);
-  if (a.arrive) MGP_HIP_TRY(hipMemsetAsync(a.arrive, 0, 9 * 32 * sizeof(int), pl->stream));
-  pl->init_free = false;
-  if (g_cg_init_free && c1_family(a) && !dist && !minv && !pl->cx && (op->form == 0 || op->form == 2) &&
-      mgp_tile_plan(&op->L)) {
-    pl->init_free = true;
-    a.pd_bb = pl->pd_bb;
+  if (ch.cx) {
+    pl->opB = cx_operator(op);
+    pl->cxa.nbs4 = sh.nb4;
+    pl->cxa.sigma = sqrtf(sh.noise_scale);
+    MGP_HIP_TRY(hipMemsetAsync(pl->cxa.sc, 0, 64 * sizeof(float), pl->stream));
   }
-  if (!ar.ok()) { delete pl; return MGP_ERR_WORKSPACE; }
   // one pooled host-mapped block: [16 int32 state | C resid | C true_rel], each part on its own 64-byte line
   const size_t rbytes = (((size_t)C * sizeof(float)) + 63) & ~size_t(63);
   if (!host_block_acquire(64 + 2 * rbytes, &pl->host_block)) { delete pl; return (int)hipErrorOutOfMemory; }
@@ -1680,41 +1571,17 @@ static int plan_create_impl(const mgp_operator_t* op, int C, const float* minv, 
   return MGP_OK;
 }
 
-extern "C" int mgp_cg_set_init_free(int on) {
-  g_cg_init_free = on ? 1 : 0;
-  return MGP_OK;
-}
-
-extern "C" int mgp_cg_set_poll_spin(int spins) {
-  g_cg_poll_spin = spins < 0 ? 0 : spins;
-  return MGP_OK;
-}
-
-extern "C" int mgp_cg_set_reduce_once(int on) {
-  g_cg_reduce_once = on == 2 ? 2 : (on ? 1 : 0);      // 2: from two columns up (A/B runs)
-  return MGP_OK;
-}
-
-extern "C" int mgp_cg_set_update_quads(int on) {
-  g_cg_update_quads = on ? 1 : 0;
-  return MGP_OK;
-}
-
-extern "C" int mgp_cg_set_complex_shift(int on) {
-  const int prev = g_cg_complex_shift;
-  g_cg_complex_shift = on ? 1 : 0;
-  return prev;
-}
+// The lab switches (include/mgp_hip.h) write g_knobs; the last two return the previous setting.
+extern "C" int mgp_cg_set_init_free(int on) { g_knobs.init_free = on ? 1 : 0; return MGP_OK; }
+extern "C" int mgp_cg_set_poll_spin(int spins) { g_knobs.poll_spin = spins < 0 ? 0 : spins; return MGP_OK; }
+extern "C" int mgp_cg_set_reduce_once(int on) { g_knobs.reduce_once = on == 2 ? 2 : (on ? 1 : 0); return MGP_OK; }   // 2: from two columns up (A/B runs)
+extern "C" int mgp_cg_set_update_quads(int on) { g_knobs.update_quads = on ? 1 : 0; return MGP_OK; }
+extern "C" int mgp_cg_set_complex_shift(int on) { const int prev = g_knobs.complex_shift; g_knobs.complex_shift = on ? 1 : 0; return prev; }
+extern "C" int mgp_cg_set_decide_in_update(int on) { const int prev = g_knobs.decide_in_update; g_knobs.decide_in_update = on ? 1 : 0; return prev; }
 
 extern "C" int mgp_cg_plan_is_complex_shift(void* plan) {
   CgPlan* pl = static_cast<CgPlan*>(plan);
-  return pl && pl->cx ? 1 : 0;
-}
-
-extern "C" int mgp_cg_set_decide_in_update(int on) {
-  const int prev = g_cg_decide_in_update;
-  g_cg_decide_in_update = on ? 1 : 0;
-  return prev;
+  return pl && pl->ch.cx ? 1 : 0;
 }
 
 extern "C" int mgp_cg_plan_create(const mgp_operator_t* op, int C, const float* minv,
@@ -1744,14 +1611,11 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
                     op->L.mt_steps == o.L.mt_steps && op->L.spmv_lanes == o.L.spmv_lanes &&
                     mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc;
   if (!same) return MGP_ERR_UNSUPPORTED;
-  if (pl->cx) {
+  if (pl->ch.cx) {
     const float cc = op->noise * op->scale;
     if (!(cc > 0.f)) return MGP_ERR_UNSUPPORTED;
-    pl->opB = mgp_operator_copy(op);
-    pl->opB.nu = 1;
-    pl->opB.kappa = op->kappa / sqrtf(2.0f);
-    pl->opB.scale = 1.0f; pl->opB.form = 0; pl->opB.noise = 0.f;
-    if (mgp_spmm_dot_blocks_for(&pl->opB.L, 4) != pl->nb4) return MGP_ERR_UNSUPPORTED;
+    pl->opB = cx_operator(op);
+    if (mgp_spmm_dot_blocks_for(&pl->opB.L, 4) != pl->cxa.nbs4) return MGP_ERR_UNSUPPORTED;
     pl->cxa.sigma = sqrtf(cc);
   }
   pl->op = mgp_operator_copy(op);
@@ -1763,7 +1627,7 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
 
 extern "C" size_t mgp_cg_dist_workspace_bytes(const mgp_operator_t* op_local, int C, int world) {
   if (!op_local || C <= 0 || C > kMaxC || op_local->L.n <= 0 || world < 1 || !mgp_spmv_lanes_ok(op_local->L.spmv_lanes)) return 0;
-  return cg_bytes(op_local, C, world);
+  return cg_bytes(op_local, C, world, true);
 }
 
 extern "C" int mgp_cg_plan_create_dist(const mgp_operator_t* op_local, int C, const float* minv,
@@ -1788,10 +1652,10 @@ static int run_cg(CgPlan* pl, const float* rhs, float* Xcopy) {
   if (pl->has_first && !patch_first_rhs(pl, rhs)) pl->has_first = false;
   int eager_done = 0;           // bodies of the first eager chunk already enqueued
   if (!pl->has_first) {
-    if (pl->cx) {
+    if (pl->ch.cx) {
       hipLaunchKernelGGL(cx_init_kernel, dim3(pl->args.nbv), dim3(kBlock), 0, st, pl->args, pl->cxa, rhs);
       MGP_LAUNCH_CHECK();
-    } else if (pl->init_free) {
+    } else if (pl->ch.init_free) {
       MGP_TRY(enqueue_first_body(pl, st, rhs, false));
       eager_done = 1;
     } else {
@@ -1811,7 +1675,7 @@ static int run_cg(CgPlan* pl, const float* rhs, float* Xcopy) {
     } else if (pl->has_graph) {
       MGP_HIP_TRY(hipGraphLaunch(pl->exec, st));
     } else {
-      const int len = (first && pl->chunk > 4) ? 4 : pl->chunk;   // eager path: short solves stop early
+      const int len = cg_eager_len(first, pl->chunk);
       for (int i = first ? eager_done : 0; i < len; ++i) MGP_TRY(enqueue_body(pl, st));
     }
     first = false;
@@ -1843,12 +1707,10 @@ static int run_cg(CgPlan* pl, const float* rhs, float* Xcopy) {
       pl->host_state[1] = 1;
       return true;
     };
-    const int poll_spin = g_cg_poll_spin;      // (lab knob: read once per chunk)
+    const int poll_spin = g_knobs.poll_spin;      // (lab knob: read once per chunk)
     if (launched_first && poll_spin > 0) {
-      // (not even one query every 20 us: two or three of them during a 55 us solve took the whole gain back.)  The
-      // graph's last node (cg_marker_kernel) reports a first graph that ran to its end undecided; the time budget --
-      // ten times the last decided solve, at least 2 ms -- is only the guard against a marker that never comes.
-      const int64_t budget = 10 * pl->last_solve_ns + 2000000;
+      // (not even one query every 20 us: two or three of them during a 55 us solve took the whole gain back.)
+      const int64_t budget = cg_poll_budget_ns(pl->last_solve_ns);
       const auto t_spin = std::chrono::steady_clock::now();
       volatile int32_t* marker = pl->host_state + 4;
       while (!decided() && *marker != pl->marker_seq) {
@@ -1865,20 +1727,14 @@ static int run_cg(CgPlan* pl, const float* rhs, float* Xcopy) {
       if (q != hipErrorNotReady) return (int)q;
     }
     if (decided()) break;
-    if (++guard > pl->prm.max_iter / (pl->chunk < 4 ? pl->chunk : 4) + 4) break;
+    if (++guard > cg_guard_chunks(pl->prm.max_iter, pl->chunk)) break;
   }
-  // the first graph follows the workload: when two solves in a row needed the same number of steps and
-  // it is not the captured length, re-capture (a few hundred us, once) so that the next solve of
-  // this kind is exactly one graph launch with no skipped launches behind the stopping decision
   pl->last_solve_ns = 0;
   if (pl->host_state[1]) {
     if (guard == 0)      // decided inside the first chunk: how long such a solve takes (the next one's flag-only poll window)
       pl->last_solve_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
     const int need = pl->host_state[0];
-    // longer than the captured graph: re-capture at once (an undecided first graph costs the flag-only window above
-    // and a second launch); shorter: only when two solves in a row agree (the extra bodies of a graph that is one or
-    // two steps too long return at their first load)
-    if (pl->exec_first && need >= 1 && need <= 64 && (need > pl->len_first || (need < pl->len_first && need == pl->last_need))) {
+    if (pl->exec_first && cg_recapture_first(need, pl->len_first, pl->last_need)) {
       MGP_HIP_TRY(hipStreamSynchronize(st));   // the graph being replaced may still be draining
       capture_first(pl, need);
     }
@@ -1895,7 +1751,7 @@ static int cg_plan_solve_body(void* plan, const float* B, float* X, int32_t* ite
   const size_t nc = (size_t)pl->args.n * pl->C;
   const int max_refine = (pl->prm.stop_mode == 1) ? pl->prm.max_refine : 0;
   // COCG decides one step behind (cx_update_kernel): its x has one step fewer than the launches that ran
-  const int lag = pl->cx ? 1 : 0;
+  const int lag = pl->ch.cx ? 1 : 0;
   if (max_refine <= 0) {
     MGP_TRY(run_cg(pl, B, X));
     if (iters) *iters = std::max(pl->host_state[0] - 1 - lag, 0);
@@ -1913,41 +1769,41 @@ static int cg_plan_solve_body(void* plan, const float* B, float* X, int32_t* ite
     total_iters += std::max(pl->host_state[0] - 1 - lag, 0);
     last_status = pl->host_state[2];
     if (f64) {
-      hipLaunchKernelGGL(refine_accumulate64_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->xacc64, pl->args.x, (int64_t)nc,
+      hipLaunchKernelGGL(refine_accumulate64_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->buf.xacc64, pl->args.x, (int64_t)nc,
                          ref == 0 ? 1 : 0);
       MGP_LAUNCH_CHECK();
-      MGP_TRY(mgp_operator_apply_f64(&pl->op, pl->xacc64, pl->C, pl->t64, pl->work64, st));
-      hipLaunchKernelGGL(refine_residual64_kernel, dim3(rgrid), dim3(kBlock), 0, st, B, pl->t64, pl->rbuf, pl->args.n, pl->C,
-                         pl->rpart64);
+      MGP_TRY(mgp_operator_apply_f64(&pl->op, pl->buf.xacc64, pl->C, pl->buf.t64, pl->buf.work64, st));
+      hipLaunchKernelGGL(refine_residual64_kernel, dim3(rgrid), dim3(kBlock), 0, st, B, pl->buf.t64, pl->buf.rbuf, pl->args.n, pl->C,
+                         pl->buf.rpart64);
       MGP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(refine_finalize64_kernel, dim3(1), dim3(kBlock), 0, st, pl->rpart64, rgrid, pl->C, pl->dev_true_rel);
+      hipLaunchKernelGGL(refine_finalize64_kernel, dim3(1), dim3(kBlock), 0, st, pl->buf.rpart64, rgrid, pl->C, pl->dev_true_rel);
       MGP_LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL(refine_accumulate_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->xacc, pl->args.x, (int64_t)nc,
+      hipLaunchKernelGGL(refine_accumulate_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->buf.xacc, pl->args.x, (int64_t)nc,
                          ref == 0 ? 1 : 0);
       MGP_LAUNCH_CHECK();
       // true residual R = B - A xacc
-      MGP_TRY(mgp_operator_apply_dist(&pl->op, &pl->dist, pl->xacc, nullptr, pl->C, pl->tbuf, nullptr, nullptr, 0, nullptr,
-                                      nullptr, pl->op_work, pl->op_work_bytes, st));
-      hipLaunchKernelGGL(refine_residual_kernel, dim3(rgrid), dim3(kBlock), 0, st, B, pl->tbuf, pl->rbuf, pl->args.n,
-                         pl->C, pl->rpart);
+      MGP_TRY(mgp_operator_apply_dist(&pl->op, &pl->dist, pl->buf.xacc, nullptr, pl->C, pl->buf.tbuf, nullptr, nullptr, 0, nullptr,
+                                      nullptr, pl->buf.op_work, pl->buf.op_work_bytes, st));
+      hipLaunchKernelGGL(refine_residual_kernel, dim3(rgrid), dim3(kBlock), 0, st, B, pl->buf.tbuf, pl->buf.rbuf, pl->args.n,
+                         pl->C, pl->buf.rpart);
       MGP_LAUNCH_CHECK();
-      hipLaunchKernelGGL(refine_finalize_kernel, dim3(1), dim3(kBlock), 0, st, pl->rpart, rgrid, pl->C, pl->dev_true_rel);
+      hipLaunchKernelGGL(refine_finalize_kernel, dim3(1), dim3(kBlock), 0, st, pl->buf.rpart, rgrid, pl->C, pl->dev_true_rel);
       MGP_LAUNCH_CHECK();
     }
     MGP_STREAM_WAIT(st, pl->is_dist && pl->dist.world > 1);
     bool ok = true;
     for (int c = 0; c < pl->C; ++c) ok = ok && (pl->host_true_rel[c] <= 2.0f * pl->prm.tol);
     if (ok || ref == max_refine || last_status == 3) break;
-    rhs = pl->rbuf;
+    rhs = pl->buf.rbuf;
   }
   // publish the accumulated solution in the plan buffer (mgp_cg_plan_x) and, if asked, in X
   if (f64) {
-    hipLaunchKernelGGL(refine_publish64_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->xacc64, pl->args.x, X, (int64_t)nc);
+    hipLaunchKernelGGL(refine_publish64_kernel, dim3(egrid), dim3(kBlock), 0, st, pl->buf.xacc64, pl->args.x, X, (int64_t)nc);
     MGP_LAUNCH_CHECK();
   } else {
-    MGP_HIP_TRY(hipMemcpyAsync(pl->args.x, pl->xacc, nc * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (X) MGP_HIP_TRY(hipMemcpyAsync(X, pl->xacc, nc * sizeof(float), hipMemcpyDeviceToDevice, st));
+    MGP_HIP_TRY(hipMemcpyAsync(pl->args.x, pl->buf.xacc, nc * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (X) MGP_HIP_TRY(hipMemcpyAsync(X, pl->buf.xacc, nc * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
   MGP_STREAM_WAIT(st, pl->is_dist && pl->dist.world > 1);
   if (iters) *iters = total_iters;
@@ -1992,7 +1848,7 @@ extern "C" int mgp_cg_plan_debug_stamps(void* plan, unsigned long long* out256, 
 
 extern "C" double* mgp_cg_plan_x64(void* plan) {
   CgPlan* pl = static_cast<CgPlan*>(plan);
-  return (pl && !pl->is_dist) ? pl->xacc64 : nullptr;
+  return (pl && !pl->is_dist) ? pl->buf.xacc64 : nullptr;
 }
 
 // A solve that ends in MGP_ERR_TIMEOUT leaves kernels / collectives queued on the stream that still reference the plan's

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "mgp_hip.h"
+#include "mgp_arena.h"
 
 #define MGP_WAVE 64
 #define MGP_NXCD 8
@@ -52,25 +53,6 @@ static inline int mgp_stream_wait_bounded(hipStream_t st) {
     if (multi_rank) { MGP_TRY(mgp_stream_wait_bounded(st)); }             \
     else { MGP_HIP_TRY(hipStreamSynchronize(st)); }                       \
   } while (0)
-static inline int64_t mgp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline size_t mgp_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-// bump allocator over the caller's workspace
-struct MgpArena {
-  char* base;
-  size_t cap;
-  size_t off;
-  MgpArena(void* p, size_t bytes) : base(static_cast<char*>(p)), cap(bytes), off(0) {}
-  template <typename T>
-  T* take(size_t count) {
-    size_t bytes = mgp_align(count * sizeof(T));
-    if (off + bytes > cap) { off = cap + 1; return nullptr; }
-    T* r = reinterpret_cast<T*>(base + off);
-    off += bytes;
-    return r;
-  }
-  bool ok() const { return off <= cap; }
-};
 
 // XCD-aware logical block id: physical blocks are dealt round-robin over the 8 XCDs, so
 // blocks b and b+8 share an L2.  Map them to CONTIGUOUS logical ids so that one XCD streams a
