@@ -412,7 +412,7 @@ typedef struct {
 /* what a plan on (op, C) carves from `work` (csrc/cg_policy.h: cg_carve), plus slack; 0 for arguments a plan would refuse */
 size_t mgp_cg_workspace_bytes(const mgp_operator_t* op, int C);
 /* ---- Lab-only switches (every mgp_*_set_* in this header): process-wide words for A/B measurements and tests (std::atomic<int>;
- * the CG family's six are the plain ints of one struct, CgKnobs in csrc/cg_policy.h).
+ * the CG family's seven are the plain ints of one struct, CgKnobs in csrc/cg_policy.h).
  * The SpMM family reads them once per call, into the plan value that the call passes down; the CG
  * switches are read at plan creation (mgp_cg_set_poll_spin: once per chunk of a solve); the kernel-block switch once per call; the k-NN / eigensolver switches where a call
  * branches on them.  They are not part of the path's contract and are not meant to be flipped while another thread is inside a
@@ -442,6 +442,19 @@ int mgp_cg_set_decide_in_update(int on);
  * setting; read at plan creation.  mgp_cg_plan_is_complex_shift: 1 when the plan took that form. */
 int mgp_cg_set_complex_shift(int on);
 int mgp_cg_plan_is_complex_shift(void* plan);
+/* Folded CG step (round 6).  C == 1 plans with nu = 2, form 0 or 2, no preconditioner, ONE vector P as pre and post (op->pre ==
+ * op->post as pointers: sqrt(D) of the random-walk normalisation, or both NULL), on the 64-row tile SpMV with the init-free
+ * start: A = [I +] c P B^2 P and u = r give u . A u = [gamma +] c |B P u|^2, which the FIRST SpMV of the apply can sum
+ * (t = B P u is its output).  Every scalar of the step is then known when the second SpMV starts, and the row-local update
+ * (s, p, x, r, pre (.) r, the partials of the new ||r||^2) runs in its epilogue, in the lane that holds (A u)_i: a step is two
+ * launches, spmv_tile_kernel<.., true> and spmv_tile_cgstep_kernel, with no update launch.  Every other plan keeps the
+ * (apply, update) launches.  Every SpMV workgroup of the step kernel re-reduces the step's partials, so the gain is for graphs
+ * of up to 1024 SpMV workgroups (65,536 nodes; measured at 60k: 54.0 -> 48.2 us per 3-step solve) and turns into a loss
+ * beyond (300k nodes, 2345 workgroups: 34.3 -> 36.7 us per iteration).  1 (default) = up to 1024 workgroups; 2 = wherever the
+ * shape allows (tests, A/B runs); 0 = the update launches everywhere; returns the previous setting; read at plan creation.
+ * mgp_cg_plan_is_folded: 1 when the plan took that form. */
+int mgp_cg_set_fold_update(int on);
+int mgp_cg_plan_is_folded(void* plan);
 /* Plans with more than 16 columns sum the dot-product partials of a step ONCE (cg_reduce_kernel, one small launch
  * ahead of the update) instead of in every workgroup of the update kernel.  Default 1; 0 = the every-workgroup
  * scheme at any C (A/B measurements, tests); affects plans created afterwards. */

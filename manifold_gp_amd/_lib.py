@@ -101,6 +101,8 @@ SIGNATURES = {
     "mgp_cg_set_decide_in_update": (c_int, [c_int]),
     "mgp_cg_set_complex_shift": (c_int, [c_int]),
     "mgp_cg_plan_is_complex_shift": (c_int, [_P]),
+    "mgp_cg_set_fold_update": (c_int, [c_int]),
+    "mgp_cg_plan_is_folded": (c_int, [_P]),
     "mgp_cg_set_reduce_once": (c_int, [c_int]),
     "mgp_cg_set_update_quads": (c_int, [c_int]),
     "mgp_cg_set_poll_spin": (c_int, [c_int]),

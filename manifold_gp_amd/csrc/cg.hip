@@ -30,6 +30,7 @@
 #include "mgp_internal.h"
 #include "cg_rule.h"
 #include "cg_policy.h"
+#include "cg_handoff.h"
 
 namespace {
 
@@ -554,28 +555,15 @@ __global__ __launch_bounds__(BLOCK) void cg_update_q_kernel(CgArgs a) {
 //     workgroup through LDS once, then EVERY lane derives alpha, beta and the stopping decision
 //     redundantly (no broadcast round), and the new partials take the second barrier.
 // Summation order is fixed (lane slots in order, xor tree, (w0 + w1) + (w2 + w3)).
-// C == 1 layout of the scalar block (cg_carve: blk): fetched as one s_load_dwordx8.  Separate scalar
-// loads are not batched by hipcc (each is followed by lgkmcnt(0)): five of them cost five round trips.
-struct alignas(32) CgScalars {
-  float go0, go1, ao0, ao1, bb, resid;
-  int it, done;
-};
-
+// The scalar block (CgScalars) and the hand-off of the deciding launch are in cg_handoff.h, shared with the folded step
+// (spmv_tile_cgstep_kernel, spmm.hip).
+//
 // DECIDE (the LAST update of a plan's first graph): the workgroup whose partials arrive last also takes the stopping decision
 // of the NEXT step -- ||r_k||^2 summed over the partials this very launch wrote, in cg_decide_c1_kernel's order, decided by
 // cg_rule.h -- and leaves the end-of-graph mark.  The single-workgroup decision launch + the marker launch (4.5 + 4.0 us
-// and two kernel boundaries of a ~57 us solve at N = 60k) go away.  Hand-off inside the launch: lane 0 of every workgroup
-// stores its ||r||^2 partial write-through (sc1), drains its stores (s_waitcnt vmcnt(0)), makes one returning agent-scope
-// atomic add on its group's arrival counter (CgArgs::arrive); the lane that completes the count joins the workgroup barrier, then all lanes of that workgroup
-// read the partials with sc1 loads (MI355X_MICROARCH.md, inter-workgroup visibility, table of sc1 hand-offs: "one lane of
-// each storing workgroup ... the workgroup whose add came last, told by the value its add returned").  The counter needs no reset between solves:
-// in a launch either every workgroup arrives or none does (the early exits below are taken by all of them or by none), and
-// the last arriver puts it back to zero.
-__device__ __forceinline__ void cg_mark_end_of_graph(const CgArgs& a) {
-  const int c = a.state[5] + 1;
-  a.state[5] = c;
-  __threadfence_system();
-  a.host_state[4] = c;
+// and two kernel boundaries of a ~57 us solve at N = 60k) go away (cg_handoff_decide).
+__device__ __forceinline__ CgHandoff cg_handoff_of(const CgArgs& a) {
+  return CgHandoff{a.arrive, a.state, a.host_state, a.resid, a.tol, a.max_iter, a.min_iter, a.stop_mode};
 }
 
 // DS: slots of 256 SpMV-workgroup partials a lane sums (4 covers nbs <= 1024, i.e. graphs up to 65 536 nodes: each slot is two
@@ -657,7 +645,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
     // (b = 0 or not finite) before this workgroup started -- the solve ends here and x, which nobody has
     // initialised, must still come out zero (every workgroup that gets to the decision itself does the same below)
     if (a.pd_bb != nullptr && it == 1) for (int64_t r = rf; r < r1; r += kBlock) a.x[r] = 0.f;
-    if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(a);     // decided earlier: nobody arrives below
+    if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(a.state, a.host_state);     // decided earlier: nobody arrives below
     return;
   }
   const int par = it & 1, prev = par ^ 1;
@@ -684,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
   if (done) {
     // an init-free solve that ends before its first update (b = 0): nobody has zeroed x
     if (fresh) for (int64_t r = rf; r < r1; r += kBlock) a.x[r] = 0.f;
-    if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(a);     // every workgroup takes this exit: nobody arrives
+    if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(a.state, a.host_state);     // every workgroup takes this exit: nobody arrives
     return;
   }
 
@@ -729,33 +717,13 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
   nrr = mgp_wave_sum(nrr);
   if (lane == 0) { sh_o[wave][0] = ng; sh_o[wave][1] = nrr; }
   __syncthreads();
+  float o_rr = 0.f;
   if (tid == 0) {
     const float o_g = (sh_o[0][0] + sh_o[1][0]) + (sh_o[2][0] + sh_o[3][0]);
     const float o_r = (sh_o[0][1] + sh_o[1][1]) + (sh_o[2][1] + sh_o[3][1]);
-    if (!DECIDE) {
-      a.pd_gamma[(int64_t)par * a.nbv + lb] = o_g;
-      a.pd_rr[(int64_t)par * a.nbv + lb] = o_r;
-    } else {
-      // write-through (sc1) stores, drained, then the arrive; the last arriver reads the partials with sc1 loads below.
-      // (An agent-scope release fence here writes back every dirty L2 line of the vectors this launch has just stored:
-      // measured +3.4 us per solve against the separate decision launch it was meant to save.)
-      a.pd_gamma[(int64_t)par * a.nbv + lb] = o_g;                     // read by the next launch only
-      __hip_atomic_store(&a.pd_rr[(int64_t)par * a.nbv + lb], o_r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      // two levels (one word takes ~88 arrivals per us: 235 workgroups on it were 3 us of the launch): the workgroups
-      // with equal blockIdx % 8 -- one XCD under round-robin placement, which only speed depends on -- count on a line of
-      // their own, the last of each group counts on the top word
-      const int grp = blockIdx.x & 7, members = ((int)gridDim.x - grp + 7) >> 3, groups = (int)gridDim.x < 8 ? (int)gridDim.x : 8;
-      int last = 0;
-      if (__hip_atomic_fetch_add(a.arrive + 32 * grp, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1) {
-        __hip_atomic_store(a.arrive + 32 * grp, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__hip_atomic_fetch_add(a.arrive + 32 * 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == groups - 1) {
-          __hip_atomic_store(a.arrive + 32 * 8, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          last = 1;
-        }
-      }
-      sh_last = last;
-    }
+    a.pd_gamma[(int64_t)par * a.nbv + lb] = o_g;                     // read by the next launch only
+    if (!DECIDE) a.pd_rr[(int64_t)par * a.nbv + lb] = o_r;
+    else o_rr = o_r;                                                   // stored by the hand-off
   }
 #ifdef MGP_STAMP
   if (blockIdx.x == 0 && tid == 0) {
@@ -764,44 +732,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
   }
 #endif
   if (!DECIDE) return;
-  __syncthreads();
-  if (!sh_last) return;
-  // ---- the last arriver: stopping decision of step it + 1 (cg_rule.h; the sums in cg_decide_c1_kernel's order)
-  {
-    const int itn = it + 1;
-    float t2 = 0.f;
-#pragma unroll
-    for (int q = 0; q < kC1GammaSlots; ++q) {
-      const int b = tid + q * kBlock;
-      const float v = __hip_atomic_load(&a.pd_rr[(int64_t)par * a.nbv + (b < a.nbv ? b : a.nbv - 1)], __ATOMIC_RELAXED,
-                                        __HIP_MEMORY_SCOPE_AGENT);
-      t2 += (b < a.nbv) ? v : 0.f;
-    }
-    t2 = mgp_wave_sum(t2);
-    __syncthreads();                          // sh_o is reused below: everyone has read sh_last / the first use is over
-    if (lane == 0) sh_o[wave][0] = t2;
-    __syncthreads();
-    if (tid != 0) return;
-    const float rr2n = (sh_o[0][0] + sh_o[1][0]) + (sh_o[2][0] + sh_o[3][0]);
-    const float reln = cg_rel(rr2n, bb);
-    const CgStop stn = cg_stop(a.stop_mode, a.min_iter, a.max_iter, a.tol, itn, reln);
-    // The host reads nothing but host-mapped words (the solution stays in stream order).  The decision travels as ONE
-    // naturally aligned 8-byte record {residual bits, step << 8 | status << 4 | 3} at host_state[8..9], written by one store
-    // instruction (one PCIe write, observed whole by the host's 8-byte read): no drain between "the details" and "the
-    // flag" -- that wait for a host-memory write to be acknowledged was ~1 us of every solve -- and no
-    // __threadfence_system(), which would also write back every dirty L2 line of the vectors this launch has just stored.
-    // run_cg clears the record before every solve and unpacks it into the words the other deciding kernels write.
-    const int c = a.state[5] + 1;
-    a.state[5] = c;
-    a.resid[0] = reln;                        // the only writer of this word in a deciding launch that goes on (see above)
-    if (stn.done) {
-      a.state[2] = stn.status; a.state[1] = 1;
-      const unsigned long long rec = (unsigned long long)__builtin_bit_cast(unsigned, reln) |
-                                     ((unsigned long long)(unsigned)((itn << 8) | (stn.status << 4) | 3) << 32);
-      __hip_atomic_store(reinterpret_cast<unsigned long long*>(a.host_state + 8), rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __hip_atomic_store(a.host_state + 4, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);       // end-of-graph mark
-  }
+  cg_handoff_decide<kC1GammaSlots>(cg_handoff_of(a), a.pd_rr + (int64_t)par * a.nbv, a.nbv, lb, o_rr, it, bb, &sh_o[0][0], &sh_last);
 }
 
 // ---- Stopping decision alone (C == 1).  The update kernel of step k+1 is where ||r_k|| <= tol is noticed, after
@@ -810,6 +741,9 @@ __global__ __launch_bounds__(kBlock) void cg_update_c1_kernel(CgArgs a) {
 // (apply, update) pair -- the one that only detects -- is replaced by this single-workgroup launch: the same
 // partial sums in the same order, decided and published through cg_rule.h as cg_update_c1_kernel would at
 // it + 1.  Not converged: it writes nothing and the continuation graph carries on as before.
+// SLOTS: partials a lane sums; a.nbv is their count and the stride between the two parities -- the update grid (kC1GammaSlots),
+// or the SpMV grid of a folded plan (its ||r||^2 partials come from spmv_tile_cgstep_kernel: 4 slots up to 1024, else 16).
+template <int SLOTS>
 __global__ __launch_bounds__(kBlock) void cg_decide_c1_kernel(CgArgs a) {
   __shared__ float sh_w[kBlock / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -825,7 +759,7 @@ __global__ __launch_bounds__(kBlock) void cg_decide_c1_kernel(CgArgs a) {
   const int prev = (it & 1) ^ 1;            // slot the last update wrote
   float t = 0.f;
 #pragma unroll
-  for (int q = 0; q < kC1GammaSlots; ++q) {
+  for (int q = 0; q < SLOTS; ++q) {
     const int b = tid + q * kBlock;
     const float v = a.pd_rr[(int64_t)prev * a.nbv + (b < a.nbv ? b : a.nbv - 1)];
     t += (b < a.nbv) ? v : 0.f;
@@ -1262,6 +1196,8 @@ CgShape cg_shape(const mgp_operator_t* op, int C, int world, bool is_dist, bool 
   sh.form = op->form; sh.nu = op->nu; sh.noise_scale = op->noise * op->scale;
   sh.stop_mode = stop_mode;
   sh.tile_plan = C == 1 && mgp_tile_plan(&op->L) != 0;
+  sh.pre_is_post = op->pre == op->post;
+  sh.tile_rows = (C == 1 && mgp_spmm_cgstep_fits(&op->L)) ? op->L.tile_rows : 0;
   return sh;
 }
 
@@ -1293,7 +1229,22 @@ void launch_update_c1(CgPlan* pl, hipStream_t st, bool decide_last) {
   }
 }
 
+// What the folded step's kernel takes from the plan (CgChoice::fold).  Its ||r||^2 partials live in pd_rr, one per SpMV workgroup
+// and nbs apart per parity; pd_gamma is not used (gamma = ||r||^2 without a preconditioner).
+MgpCgStep fold_step(const CgPlan* pl) {
+  const CgArgs& a = pl->args;
+  MgpCgStep cs{};
+  cs.r = a.r; cs.x = a.x; cs.p = a.p; cs.s = a.s; cs.us = a.us; cs.pre = a.pre;
+  cs.pd_rr = a.pd_rr; cs.pd_delta = a.pd_delta; cs.nbs = a.nbs;
+  cs.blk = a.gamma_old; cs.state = a.state; cs.host_state = a.host_state; cs.host_resid = a.host_resid; cs.arrive = a.arrive;
+  cs.tol = a.tol; cs.max_iter = a.max_iter; cs.min_iter = a.min_iter; cs.stop_mode = a.stop_mode;
+  return cs;
+}
+
 int enqueue_body(CgPlan* pl, hipStream_t st, bool decide_last = false) {
+  if (pl->ch.fold)       // two launches: t = B P u with the partials of |t|^2 (ticks the iteration; skipped once decided), then the step
+    return mgp_operator_apply_cgstep(&pl->op, pl->args.us ? pl->args.us : pl->args.r, false, nullptr, fold_step(pl), decide_last,
+                                     pl->buf.op_work, pl->buf.op_work_bytes, st);
   if (pl->ch.cx) {
     // B u on the 4-column tile SpMM (partials of u . B u ride along; skipped once decided; ticks the iteration), then the
     // complex update
@@ -1326,6 +1277,9 @@ int enqueue_body(CgPlan* pl, hipStream_t st, bool decide_last = false) {
 // copies it to r), leaves the partials of r . A r and ||r||^2 and resets the iteration state; the update then runs
 // as iteration 1 with p = s = x = 0.  One launch (cg_init, ~3.8 us at N = 60k) less per solve.
 int enqueue_first_body(CgPlan* pl, hipStream_t st, const float* rhs, bool record, bool decide_last = false) {
+  if (pl->ch.fold)
+    return mgp_operator_apply_cgstep(&pl->op, rhs, true, record ? pl->first_record : nullptr, fold_step(pl), decide_last,
+                                     pl->buf.op_work, pl->buf.op_work_bytes, st);
   MGP_TRY(mgp_operator_apply_first(&pl->op, rhs, pl->args.r, pl->args.w, pl->buf.pd_delta, pl->buf.pd_bb, pl->args.state,
                                    record ? pl->first_record : nullptr, pl->buf.op_work, pl->buf.op_work_bytes, st));
   launch_update_c1(pl, st, decide_last);
@@ -1356,7 +1310,12 @@ bool record_first(CgPlan* pl, int len, hipGraph_t* out) {
   }
   for (int i = done_bodies; i < bodies && rc == MGP_OK; ++i) rc = enqueue_body(pl, pl->cap_stream, in_update && i == bodies - 1);
   if (decide && !in_update && rc == MGP_OK) {
-    hipLaunchKernelGGL(cg_decide_c1_kernel, dim3(1), dim3(kBlock), 0, pl->cap_stream, pl->args);
+    if (pl->ch.fold) {
+      CgArgs d = pl->args;          // the step kernel's partials: one per SpMV workgroup, nbs apart per parity
+      d.nbv = d.nbs;
+      if (d.nbs <= 4 * kBlock) hipLaunchKernelGGL(cg_decide_c1_kernel<4>, dim3(1), dim3(kBlock), 0, pl->cap_stream, d);
+      else hipLaunchKernelGGL(cg_decide_c1_kernel<kC1DeltaSlots>, dim3(1), dim3(kBlock), 0, pl->cap_stream, d);
+    } else hipLaunchKernelGGL(cg_decide_c1_kernel<kC1GammaSlots>, dim3(1), dim3(kBlock), 0, pl->cap_stream, pl->args);
     rc = hipGetLastError() == hipSuccess ? MGP_OK : 1;
   }
   if (!in_update && rc == MGP_OK) {
@@ -1579,6 +1538,13 @@ extern "C" int mgp_cg_set_update_quads(int on) { g_knobs.update_quads = on ? 1 :
 extern "C" int mgp_cg_set_complex_shift(int on) { const int prev = g_knobs.complex_shift; g_knobs.complex_shift = on ? 1 : 0; return prev; }
 extern "C" int mgp_cg_set_decide_in_update(int on) { const int prev = g_knobs.decide_in_update; g_knobs.decide_in_update = on ? 1 : 0; return prev; }
 
+extern "C" int mgp_cg_set_fold_update(int on) { const int prev = g_knobs.fold_update; g_knobs.fold_update = on == 2 ? 2 : (on ? 1 : 0); return prev; }   // 2: at any partial count
+
+extern "C" int mgp_cg_plan_is_folded(void* plan) {
+  CgPlan* pl = static_cast<CgPlan*>(plan);
+  return pl && pl->ch.fold ? 1 : 0;
+}
+
 extern "C" int mgp_cg_plan_is_complex_shift(void* plan) {
   CgPlan* pl = static_cast<CgPlan*>(plan);
   return pl && pl->ch.cx ? 1 : 0;
@@ -1609,7 +1575,8 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
                     (op->L.tile_rowid != nullptr) == (o.L.tile_rowid != nullptr) &&
                     (op->L.mt_img != nullptr) == (o.L.mt_img != nullptr) && op->L.mt_tiles == o.L.mt_tiles &&
                     op->L.mt_steps == o.L.mt_steps && op->L.spmv_lanes == o.L.spmv_lanes &&
-                    mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc;
+                    mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc &&
+                    (!pl->ch.fold || op->pre == op->post);        // the folded step's identity needs ONE vector P
   if (!same) return MGP_ERR_UNSUPPORTED;
   if (pl->ch.cx) {
     const float cc = op->noise * op->scale;

@@ -30,6 +30,8 @@ struct CgKnobs {
   int poll_spin = 64;       // flag reads between two looks at the clock in the flag-only poll window; 0: no such window
   int init_free = 1;        // C == 1 plans start without a cg_init launch (0: classic start)
   int decide_in_update = 1; // the first graph's last update decides + marks (0: separate launches)
+  int fold_update = 1;      // nu = 2, C == 1: delta from |B P u|^2, the vector update in the epilogue of the apply's second SpMV (0: update
+                            // launches; 1: where it was measured to win, nbs <= 4 kBlock; 2: wherever the shape allows)
 };
 
 // What a plan is created from.  nb_loc: SpMM workgroups per rank that write dot partials (mgp_spmm_dot_blocks_for(L, C)); nb4: the
@@ -45,6 +47,9 @@ struct CgShape {
   float noise_scale;        // noise * scale
   int stop_mode;
   bool tile_plan;
+  bool pre_is_post;         // op->pre == op->post as pointers, both null included: Q2 = scale P B^nu P with one vector P
+  int tile_rows;            // rows per tile of the C == 1 tile SpMV when the step kernel can run on it (mgp_spmm_cgstep_fits: 64-row tiles,
+                            // four waves per workgroup, LDS room for the step's words), else 0
 };
 
 struct CgChoice {
@@ -55,6 +60,7 @@ struct CgChoice {
   bool reduce_once;         // cg_reduce_kernel sums the partials of a step once; the update reads 3 C totals
   int upd_quads;            // 0: cg_update_kernel; else the workgroup size of cg_update_q_kernel
   bool c1_family, cx, init_free;
+  bool fold;                // a step is two launches: the first SpMV with the self dot, then spmv_tile_cgstep_kernel (no update launch)
 };
 
 inline int cg_tile_cols(int C) { int t = 1; while (t < C) t <<= 1; return t; }   // least power of two >= C
@@ -91,6 +97,14 @@ inline CgChoice cg_choose(const CgShape& sh, const CgKnobs& k) {
          sh.noise_scale > 0.f && c.c1_family && sh.stop_mode == 1 && sh.nb4 >= 1 && sh.nb4 <= kCxDeltaSlots * kBlock;
   // init-free start: no cg_init launch, the first apply (tile SpMV) reads the right-hand side itself
   c.init_free = k.init_free && c.c1_family && !sh.is_dist && !sh.has_minv && !c.cx && (sh.form == 0 || sh.form == 2) && sh.tile_plan;
+  // folded step: with A = [I +] c P B^2 P and u = r, u . A u = [gamma +] c |B P u|^2 is known after the FIRST SpMV of the apply, so
+  // the second one takes the whole step in its epilogue.  It builds on the init-free start (the first SpMV leaves ||b||^2 where the
+  // step looks for gamma) and on the 64-row tile kernel; its ||r||^2 partials, one per SpMV workgroup, share pd_rr with stride nbs.
+  // Every one of the nbs SpMV workgroups re-reduces 3 nbs partials: free at 235 workgroups (60k nodes: -6 us per 3-step solve),
+  // 66 MB of L2 reads per launch at 2345 (300k nodes: measured +2.4 us per iteration against the update launch, whose grid is capped
+  // at kMaxGridVec for the same reason) -- so the default takes it up to 4 slots of kBlock partials per lane
+  c.fold = k.fold_update && c.init_free && sh.nu == 2 && sh.pre_is_post && sh.tile_rows == 64 && c.nbs <= kMaxPartials &&
+           (k.fold_update == 2 || c.nbs <= 4 * kBlock);
   return c;
 }
 

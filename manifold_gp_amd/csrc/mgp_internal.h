@@ -44,7 +44,41 @@ struct MgpSpmmOpts {
   const int* skip = nullptr;
   int* tick = nullptr;
   const MgpFirst* first = nullptr;   // MGP_ERR_UNSUPPORTED unless the C == 1 tile kernel runs
+  // self dot (C == 1 tile kernel only, else MGP_ERR_UNSUPPORTED): dot_partials takes the partials of y . y (dotw is not read), and
+  // first->dot2_partials those of the raw input, sum x[row]^2 -- the first SpMV of a folded CG step (cg.hip)
+  bool self_dot = false;
 };
+// The CG step in the epilogue of the apply's second SpMV (spmv_tile_cgstep_kernel, spmm.hip; docs/kernels/cg.md, round 6).
+// A = [I +] c P B^2 P, u = r: the first SpMV left t = B P u and the partials of |t|^2, so delta = [gamma +] c |t|^2, alpha, beta and
+// the stopping decision are known when this kernel starts; the lane that forms w_i = (A u)_i updates s, p, x, r, us of its row.
+struct MgpCgStep {
+  float *r, *x, *p, *s;
+  float* us;             // nullable: pre (.) r, the next step's SpMV input (op->pre != NULL)
+  const float* pre;      // op->pre
+  float* pd_rr;          // [2][nbs] partials of ||r||^2 (= gamma: no preconditioner) per parity, one per SpMV workgroup
+  const float* pd_delta; // [nbs] partials of |t|^2 from the first SpMV
+  int nbs;
+  float* blk;            // the scalar block (CgScalars, cg_handoff.h)
+  int* state;
+  int* host_state;
+  float* host_resid;
+  int* arrive;
+  float tol;
+  int max_iter, min_iter, stop_mode;
+  float dcoef;           // c: scale (form 0), noise * scale (form 2)
+  int dgamma;            // form 2: delta = gamma + c |t|^2 and w = r + ...
+};
+// w = cb r + co post (.) (a t + b L t) row by row on the tile kernel and the step on top of it; decide: the launch also takes the
+// stopping decision of the next step and leaves the end-of-graph mark.  MGP_ERR_UNSUPPORTED unless the 64-row tile kernel runs on L.
+int mgp_spmm_cgstep(const mgp_csr_t* L, const float* T, float a, float b, const float* post, float co, const MgpCgStep& cs,
+                    bool decide, void* stream);
+// 1 when the step kernel can run on L (64-row C == 1 tile plan whose dynamic LDS leaves room for the step's static words)
+int mgp_spmm_cgstep_fits(const mgp_csr_t* L);
+// One folded CG step on op (nu = 2, form 0 or 2, pre == post): the first SpMV of the chain with the self dot, then the step kernel.
+// first: `in` is the caller's right-hand side (pre-scaled in the kernel, copied to cs.r, ||b||^2 partials to parity 0 of cs.pd_rr,
+// state reset, launch arguments left in `record`); else `in` is cs.us / cs.r and the launch honours the skip flag.
+int mgp_operator_apply_cgstep(const mgp_operator_t* op, const float* in, bool first, void* record, const MgpCgStep& cs, bool decide,
+                              void* work, size_t work_bytes, void* stream);
 int mgp_spmm_fused_opts(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b, const float* pre,
                         const float* post, const float* base, float cb, float co, const float* dotw, float* dot_partials,
                         const MgpSpmmOpts& opts, void* stream);

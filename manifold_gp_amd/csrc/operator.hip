@@ -174,6 +174,36 @@ int mgp_operator_apply_first(const mgp_operator_t* op, const float* rhs, float* 
   return q2_chain(op, nullptr, 0, rhs, nullptr, 1, Y, rv, 1.f, op->noise, t0, t1, &hk, stream);
 }
 
+// One folded CG step (cg.hip, CgChoice::fold): nu = 2, form 0 or 2, one vector P = pre = post (or none).  Launch 1 is the first SpMV
+// of the chain, t = B P u, with the partials of |t|^2 (self dot), the iteration tick and the skip flag; launch 2 forms
+// w = [u +] c P B t row by row and takes the CG step in the same lane (mgp_spmm_cgstep).  `first`: the step opens an init-free
+// solve -- launch 1 reads the caller's right-hand side, copies it to r, leaves the partials of ||b||^2 in parity 0 of the
+// ||r||^2 partials (what the step at iteration 1 sums as gamma), resets the state and leaves its launch record.
+int mgp_operator_apply_cgstep(const mgp_operator_t* op, const float* in, bool first, void* record, const MgpCgStep& cs_in, bool decide,
+                              void* work, size_t work_bytes, void* stream) {
+  MGP_TRY(check_op(op));
+  if (!in || op->nu != 2 || (op->form != 0 && op->form != 2) || op->pre != op->post) return MGP_ERR_UNSUPPORTED;
+  if (!work || work_bytes < 4 * mgp_align((size_t)op->L.n * sizeof(float))) return MGP_ERR_WORKSPACE;
+  MgpArena ar(work, work_bytes);
+  float* t0 = ar.take<float>((size_t)op->L.n);
+  if (!ar.ok()) return MGP_ERR_WORKSPACE;
+  const float tau = 2.0f * (float)op->nu / (op->kappa * op->kappa);
+  MgpCgStep cs = cs_in;
+  cs.pre = op->pre;
+  cs.dgamma = op->form == 2 ? 1 : 0;
+  cs.dcoef = (op->form == 2 ? op->noise : 1.0f) * op->scale;       // `co` of the chain's last launch (q2_chain)
+  MgpFirst fst{first ? cs.r : nullptr, first ? cs.pd_rr : nullptr, first ? 1 : 0, first ? record : nullptr};
+  MgpSpmmOpts o;
+  o.skip = first ? nullptr : cs.state + 1;
+  o.tick = cs.state;
+  o.first = first ? &fst : nullptr;
+  o.self_dot = true;
+  // later steps read us = pre (.) r, which the step kernel wrote; the first one scales the right-hand side in the kernel
+  MGP_TRY(mgp_spmm_fused_opts(&op->L, in, 1, t0, tau, 1.0f, first ? op->pre : nullptr, nullptr, nullptr, 0.f, 1.0f, nullptr,
+                              const_cast<float*>(cs.pd_delta), o, stream));
+  return mgp_spmm_cgstep(&op->L, t0, tau, 1.0f, op->post, cs.dcoef, cs, decide, stream);
+}
+
 // ---------------------------------------------------------------- fp64 apply (iterative refinement only)
 // Y = cb base + co post (.) (a xs + b (diag (.) xs - S xs)), xs = pre (.) X, everything accumulated in
 // fp64 from the fp32 matrix: used once per refinement round of the CG to form the TRUE residual, so that

@@ -27,6 +27,8 @@
 #include <type_traits>
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "cg_rule.h"
+#include "cg_handoff.h"
 #include <hip/hip_ext.h>
 #include <vector>
 
@@ -239,8 +241,16 @@ struct TileArgs {
 
 typedef unsigned short mgp_v4h __attribute__((ext_vector_type(4)));
 
-template <bool PRE, int BS, bool CBV>
-__global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
+// The body serves three kernels through its MODE (an epilogue policy resolved at compile time: the code of a mode holds nothing
+// of the others):
+//   kTilePlain    spmv_tile_kernel<.., false>: the epilogue above, partials of dotw . y (and of dotw^2: init-free CG start)
+//   kTileSelfDot  spmv_tile_kernel<.., true>: partials of y . y (and of the raw input squared) -- the first SpMV of a folded CG step
+//   kTileCgStep   spmv_tile_cgstep_kernel: w = (A u)_i stays in its lane, which takes the whole CG step of row i (see that kernel)
+enum { kTilePlain = 0, kTileSelfDot = 1, kTileCgStep = 2 };
+struct NoCgStep {};
+
+template <bool PRE, int BS, bool CBV, int MODE, bool DECIDE, int DS, class CS>
+__device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs t, const CS cs) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
   // the CG graph's skip flag / iteration tick: loaded here, consumed only after the first tile's
   // metadata loads have been issued, so that the flag costs no round trip of its own
@@ -280,6 +290,32 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
   float dsum = 0.f, dsum2 = 0.f;
   const int64_t t0 = (int64_t)lb * t.tiles_per_block;
   const int64_t t1 = t0 + t.tiles_per_block < t.ntiles ? t0 + t.tiles_per_block : t.ntiles;
+  // ---- kTileCgStep, prologue: everything the step's scalars are made of is requested here, in front of the first tile's own
+  // loads (loads retire in issue order: what the tile waits for anyway covers them) -- the scalar block in one load, both
+  // parities of the ||r||^2 partials and the |t|^2 partials of the first SpMV, DS slots of BS per lane on clamped addresses
+  __shared__ float cg_sh_w[MODE == kTileCgStep ? BS / MGP_WAVE : 1][3];
+  __shared__ float cg_sh_o[MODE == kTileCgStep ? BS / MGP_WAVE : 1];
+  __shared__ int cg_sh_state[MODE == kTileCgStep ? 2 : 1];
+  __shared__ int cg_sh_last[1];
+  [[maybe_unused]] float cg_rv[2][DS], cg_dv[DS];
+  [[maybe_unused]] float cg_go0 = 0.f, cg_go1 = 0.f, cg_ao0 = 0.f, cg_ao1 = 0.f, cg_bb_old = 0.f;
+  [[maybe_unused]] int cg_st_it = 0, cg_st_done = 0;
+  [[maybe_unused]] float cg_alpha = 0.f, cg_beta = 0.f, cg_bb = 0.f, cg_nrr = 0.f;
+  [[maybe_unused]] int cg_it = 0;
+  [[maybe_unused]] bool cg_fresh = false;
+  if constexpr (MODE == kTileCgStep) {
+    static_assert(BS == 256, "the step's sums are written for four waves");
+    const CgScalars sc = *reinterpret_cast<const CgScalars*>(cs.blk);
+    cg_go0 = sc.go0; cg_go1 = sc.go1; cg_ao0 = sc.ao0; cg_ao1 = sc.ao1; cg_bb_old = sc.bb; cg_st_it = sc.it; cg_st_done = sc.done;
+#pragma unroll
+    for (int q = 0; q < DS; ++q) {
+      const int b = tid + q * BS;
+      const int bc = b < cs.nbs ? b : cs.nbs - 1;
+      cg_rv[0][q] = cs.pd_rr[bc];
+      cg_rv[1][q] = cs.pd_rr[cs.nbs + bc];
+      cg_dv[q] = cs.pd_delta[bc];
+    }
+  }
   for (int64_t tile = t0; tile < t1; ++tile) {
     skipl = *skip_ptr;
     tickl = *tick_ptr;
@@ -345,8 +381,35 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
     const float e_base = p.base ? l_base : 0.f;
     const float e_dotw = p.dotw ? l_dotw : 0.f;
     const float e_cb = CBV ? p.cbv[grr] : p.cb;
+    // kTileCgStep: the row's r, s, p, x and pre, in the same round trip (r is also the `base` of form 2)
+    [[maybe_unused]] float f_r = 0.f, f_s = 0.f, f_p = 0.f, f_x = 0.f, f_pre = 1.f;
+    if constexpr (MODE == kTileCgStep) {
+      f_r = cs.r[grr]; f_s = cs.s[grr]; f_p = cs.p[grr]; f_x = cs.x[grr];
+      const float l_pre = (cs.us ? cs.pre : x)[grr];
+      f_pre = cs.us ? l_pre : 1.f;
+    }
     __builtin_amdgcn_sched_barrier(0);
     if (p.skip && skipl) return;          // CG converged: every load above went to a valid address, nothing is written
+    if constexpr (MODE == kTileCgStep) {
+      if (tile == t0) {
+        // fixed order: lane slots in order, the wave sum, then (w0 + w1) + (w2 + w3) behind the barrier below
+        float s3[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < DS; ++q) {
+          const bool on = tid + q * BS < cs.nbs;
+          s3[0] += on ? cg_rv[0][q] : 0.f; s3[1] += on ? cg_rv[1][q] : 0.f; s3[2] += on ? cg_dv[q] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s3[k] = mgp_wave_sum(s3[k]);
+        if ((tid & 63) == 0) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) cg_sh_w[tid >> 6][k] = s3[k];
+        }
+        // workgroup 0 may raise the done flag while this launch runs: one lane's view of the state is published, so that all
+        // waves of a workgroup take the same branch (the tile's first barrier carries it)
+        if (tid == 0) { cg_sh_state[0] = cg_st_it; cg_sh_state[1] = cg_st_done; }
+      }
+    }
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
       const int j = tid + k * BS;
@@ -359,6 +422,54 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
       xl[j] = gg;
     }
     __syncthreads();
+    if constexpr (MODE == kTileCgStep) {
+      if (tile == t0) {
+        // every lane derives alpha, beta and the decision redundantly through cg_rule.h, as cg_update_c1_kernel does
+        const int it = cg_sh_state[0];
+        const bool fresh = it == 1;             // a folded plan starts init-free: r = b, p = s = x = 0 whatever the buffers hold
+        // x of this workgroup's rows, which nobody has initialised when the solve ends before its first update
+        auto zero_x = [&]() {
+          for (int64_t tl = t0; tl < t1; ++tl) {
+            const int64_t pos = tl * TR + tid;
+            if (tid < TR && pos < p.n) cs.x[t.rowid ? (int64_t)t.rowid[pos] : pos] = 0.f;
+          }
+        };
+        if (cg_sh_state[1]) {
+          // flag already up.  At iteration 1 the first SpMV reset it, so workgroup 0 raised it in THIS launch (b = 0 or not finite)
+          if (fresh) zero_x();
+          if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(cs.state, cs.host_state);    // nobody arrives
+          return;
+        }
+        const int par = it & 1, prev = par ^ 1;
+        float tt3[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tt3[k] = (cg_sh_w[0][k] + cg_sh_w[1][k]) + (cg_sh_w[2][k] + cg_sh_w[3][k]);
+        const float rr2 = prev ? tt3[1] : tt3[0];        // = gamma: u = r.  Iteration 1: ||b||^2, left in parity 0 by the first SpMV
+        const float gamma = rr2;
+        const float delta = (cs.dgamma ? gamma : 0.f) + cs.dcoef * tt3[2];      // u . A u = [gamma +] c |B P u|^2
+        const float bb = (it == 1) ? rr2 : cg_bb_old;
+        const float rel = cg_rel(rr2, bb);
+        const CgCoef kc = cg_coef(it == 1, cg_frozen(cs.stop_mode, cs.tol, rel), gamma, delta, prev ? cg_go1 : cg_go0,
+                                  prev ? cg_ao1 : cg_ao0);
+        const CgStop st = cg_stop(cs.stop_mode, cs.min_iter, cs.max_iter, cs.tol, it, rel);
+        if (blockIdx.x == 0 && tid == 0) {
+          float* gamma_old = cs.blk;
+          float* alpha_old = cs.blk + 2;
+          gamma_old[par] = gamma;
+          alpha_old[par] = kc.alpha;
+          if (it == 1) cs.blk[4] = bb;
+          // DECIDE and not done: the last arriver of this launch writes the residual of step it + 1 to the same word
+          if (!DECIDE || st.done) cs.blk[5] = rel;
+          if (st.done) cg_publish(cs.state, cs.host_state, cs.host_resid, &rel, 1, it, st.status);
+        }
+        if (st.done) {
+          if (fresh) zero_x();
+          if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(cs.state, cs.host_state);    // every workgroup leaves here
+          return;
+        }
+        cg_alpha = kc.alpha; cg_beta = kc.beta; cg_bb = bb; cg_it = it; cg_fresh = fresh;
+      }
+    }
     // phase 2: quad products
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
@@ -396,13 +507,48 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
     if (valid && sub == 0) {
       const float lx = e_diag * e_x - acc;
       const float tt = (p.a * e_x + p.b * lx) * e_post;
-      const float y = p.co * tt + e_cb * e_base;
-      p.Y[grr] = y;
-      dsum = fmaf(e_dotw, y, dsum);
-      dsum2 = fmaf(e_dotw, e_dotw, dsum2);
-      if (p.copy_x) p.copy_x[grr] = raw_x;
+      if constexpr (MODE == kTileCgStep) {
+        // w_i never goes to memory: the Chronopoulos-Gear update of row i, element for element as cg_update_c1_kernel has it
+        const float w = p.co * tt + (cs.dgamma ? e_cb * f_r : 0.f);
+        const float po = cg_fresh ? 0.f : f_p, so = cg_fresh ? 0.f : f_s, xo = cg_fresh ? 0.f : f_x;
+        const float pn = fmaf(cg_beta, po, f_r);
+        const float sn = fmaf(cg_beta, so, w);
+        cs.p[grr] = pn;
+        cs.s[grr] = sn;
+        cs.x[grr] = fmaf(cg_alpha, pn, xo);
+        const float rn = fmaf(-cg_alpha, sn, f_r);
+        cs.r[grr] = rn;
+        if (cs.us) cs.us[grr] = f_pre * rn;
+        cg_nrr = fmaf(rn, rn, cg_nrr);
+      } else {
+        const float y = p.co * tt + e_cb * e_base;
+        p.Y[grr] = y;
+        if constexpr (MODE == kTileSelfDot) {
+          dsum = fmaf(y, y, dsum);
+          dsum2 = fmaf(raw_x, raw_x, dsum2);
+        } else {
+          dsum = fmaf(e_dotw, y, dsum);
+          dsum2 = fmaf(e_dotw, e_dotw, dsum2);
+        }
+        if (p.copy_x) p.copy_x[grr] = raw_x;
+      }
     }
     if (tile + 1 < t1) __syncthreads();                // the next tile overwrites xl / part
+  }
+  if constexpr (MODE == kTileCgStep) {
+    // the new ||r||^2 partial of this workgroup, into the parity of this step; DECIDE: through the hand-off, whose last arriver
+    // decides step it + 1 (no workgroup waits for another)
+    cg_nrr = mgp_wave_sum(cg_nrr);
+    if ((tid & 63) == 0) cg_sh_o[tid >> 6] = cg_nrr;
+    __syncthreads();
+    float o_r = 0.f;
+    if (tid == 0) o_r = (cg_sh_o[0] + cg_sh_o[1]) + (cg_sh_o[2] + cg_sh_o[3]);
+    float* rr_par = cs.pd_rr + (int64_t)(cg_it & 1) * cs.nbs;
+    if constexpr (DECIDE) {
+      const CgHandoff h{cs.arrive, cs.state, cs.host_state, cs.blk + 5, cs.tol, cs.max_iter, cs.min_iter, cs.stop_mode};
+      cg_handoff_decide<DS>(h, rr_par, cs.nbs, lb, o_r, cg_it, cg_bb, cg_sh_o, cg_sh_last);
+    } else if (tid == 0) rr_par[lb] = o_r;
+    return;
   }
   if (p.tick && blockIdx.x == 0 && tid == 0 && !(p.skip && skipl)) {
     if (p.tick_reset) { p.tick[0] = 1; p.tick[1] = 0; p.tick[2] = 0; }
@@ -429,6 +575,26 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
   }
   if (st_base && tid == 0 && blockIdx.x < 2048) reinterpret_cast<unsigned long long*>(st_base + 16)[256 + 2 * blockIdx.x + 1] = wall_clock64();
 #endif
+}
+
+// SELF: the self dot of MgpSpmmOpts (partials of y . y and of the raw input squared instead of the weighted ones)
+template <bool PRE, int BS, bool CBV, bool SELF>
+__global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
+  spmv_tile_body<PRE, BS, CBV, SELF ? kTileSelfDot : kTilePlain, false, 1>(p, t, NoCgStep{});
+}
+
+// ---- The CG step of a nu = 2 solve in the epilogue of the apply's second SpMV (docs/kernels/cg.md, round 6).  With
+// A = [I +] c P B^2 P and u = r (no preconditioner), u . A u = [gamma +] c |B P u|^2, and t = B P u with the partials of |t|^2 is
+// what the FIRST SpMV of the apply left (spmv_tile_kernel<.., true>): alpha, beta and the decision on ||r_{k-1}|| are known when
+// this kernel starts.  The lane that holds w_i = (A u)_i therefore runs the update of row i -- s, p, x, r, us -- and the workgroup
+// leaves its partial of the new ||r||^2, one per SpMV workgroup.  The kernel gathers t, never r: it reads and writes r in its own
+// rows only, so no workgroup depends on another's stores.  What cg_update_c1_kernel does at the edges is kept: the fresh first
+// step, x zeroed when the solve ends at step 1, the workgroup that sees the flag raised during the launch, workgroup 0 writing
+// gamma_old / alpha_old / bb / resid and publishing, DECIDE through the same hand-off (cg_handoff.h).
+// DS: slots of 256 partials a lane sums (4 for nbs <= 1024, else 16), as cg_update_c1_kernel<*, DS>.
+template <int BS, int DS, bool DECIDE>
+__global__ __launch_bounds__(BS) void spmv_tile_cgstep_kernel(SpmmArgs p, TileArgs t, MgpCgStep cs) {
+  spmv_tile_body<false, BS, false, kTileCgStep, DECIDE, DS>(p, t, cs);
 }
 
 // ---------------------------------------------------------------- C > 1
@@ -1842,6 +2008,17 @@ int mgp_tile_plan(const mgp_csr_t* L) {
   return pl.err == MGP_OK && pl.family == SpmmFamily::TileC1;
 }
 
+// Static LDS of spmv_tile_cgstep_kernel on top of the tile SpMV's dynamic LDS (wave sums, state, hand-off words: 76 bytes, rounded up);
+// the plain tile kernel has 32 bytes and spmm_plan leaves 64 under the 64 KB of a workgroup
+constexpr size_t kCgStepStaticLds = 128;
+
+// 1 when spmv_tile_cgstep_kernel can run on L: the 64-row C == 1 tile plan, with room for the step's static LDS
+int mgp_spmm_cgstep_fits(const mgp_csr_t* L) {
+  if (!L) return 0;
+  const SpmmPlan pl = spmm_plan(L, 1, 0, true);
+  return pl.err == MGP_OK && pl.family == SpmmFamily::TileC1 && L->tile_rows == 64 && pl.lds + kCgStepStaticLds <= 65536;
+}
+
 int mgp_spmm_dot_blocks_for(const mgp_csr_t* L, int C) {
   if (!L) return MGP_ERR_ARG;
   const SpmmPlan pl = spmm_plan(L, C, 0, false);
@@ -1937,7 +2114,7 @@ static bool aligned16(const void* a, const void* b, const void* c = nullptr, con
 // (every kernel family has a CBV instantiation of its own, so the code of the cbv == NULL calls is what it was before the
 // per-row coefficient existed)
 template <bool CB>
-int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArgs& p, hipStream_t st) {
+int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArgs& p, hipStream_t st, bool self_dot = false) {
   const int C = p.C, grid = pl.grid;
   const size_t lds = pl.lds;
   const bool pre = p.pre != nullptr;
@@ -1954,7 +2131,7 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
     }
     auto tiles = [&](auto bs) { with_pre(pre, [&](auto P) {
       constexpr int BS = decltype(bs)::value;
-      const auto kernel = &spmv_tile_kernel<decltype(P)::value, BS, CB>;
+      const auto kernel = self_dot ? &spmv_tile_kernel<decltype(P)::value, BS, CB, true> : &spmv_tile_kernel<decltype(P)::value, BS, CB, false>;
       if (g_spmv_timer.on && 2 * g_spmv_timer.used + 1 < (int)g_spmv_timer.ev.size()) {
         hipEvent_t e0 = g_spmv_timer.ev[2 * g_spmv_timer.used], e1 = g_spmv_timer.ev[2 * g_spmv_timer.used + 1];
         ++g_spmv_timer.used;
@@ -2068,22 +2245,53 @@ int mgp_spmm_fused_opts(const mgp_csr_t* L, const float* X, int C, float* Y, flo
   if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !X || !Y) return MGP_ERR_ARG;
   if (L->n <= 0 || C <= 0 || C > 256) return C > 256 ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
   if (X == Y) return MGP_ERR_ARG;  // rows gather other rows of X: never in place
-  const SpmmPlan pl = spmm_plan(L, C, o.row_offset, dotw && dot_partials);
+  const bool self_dot = o.self_dot && dot_partials;
+  const SpmmPlan pl = spmm_plan(L, C, o.row_offset, (dotw || self_dot) && dot_partials);
   if (pl.err != MGP_OK) return pl.err;
+  if (o.self_dot && (pl.family != SpmmFamily::TileC1 || dotw || o.cbv || !dot_partials)) return MGP_ERR_UNSUPPORTED;
   SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, X, Y, C, a, b, pre, post, base, cb, co,
-             dotw, dotw ? dot_partials : nullptr, 0, o.skip, o.tick, o.row_offset, nullptr, nullptr, 0, o.cbv};
+             dotw, (dotw || self_dot) ? dot_partials : nullptr, 0, o.skip, o.tick, o.row_offset, nullptr, nullptr, 0, o.cbv};
 #ifdef MGP_STAMP
   p.stamp_on = g_stamp_enable;
 #endif
   if (o.first) {
     if (pl.family != SpmmFamily::TileC1) return MGP_ERR_UNSUPPORTED;
     p.copy_x = o.first->copy_x;
-    p.dot2_partials = (dotw && dot_partials) ? o.first->dot2_partials : nullptr;
+    p.dot2_partials = ((dotw || self_dot) && dot_partials) ? o.first->dot2_partials : nullptr;
     p.tick_reset = o.first->tick_reset;
   }
   void* record_to = o.first ? o.first->record : nullptr;
   hipStream_t st = mgp_stream(stream);
-  return o.cbv ? spmm_launch<true>(pl, L, record_to, p, st) : spmm_launch<false>(pl, L, record_to, p, st);
+  return o.cbv ? spmm_launch<true>(pl, L, record_to, p, st) : spmm_launch<false>(pl, L, record_to, p, st, self_dot);
+}
+
+// see mgp_internal.h.  The same plan, grid and dynamic LDS as the tile SpMV on L: one ||r||^2 partial per SpMV workgroup
+// (cs.nbs == mgp_spmm_dot_blocks_for(L, 1), which sized cs.pd_rr and cs.pd_delta).
+int mgp_spmm_cgstep(const mgp_csr_t* L, const float* T, float a, float b, const float* post, float co, const MgpCgStep& cs,
+                    bool decide, void* stream) {
+  if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !T || L->n <= 0) return MGP_ERR_ARG;
+  if (!cs.r || !cs.x || !cs.p || !cs.s || !cs.pd_rr || !cs.pd_delta || !cs.blk || !cs.state || !cs.host_state || !cs.host_resid ||
+      !cs.arrive || (cs.us && !cs.pre) || T == cs.r || T == cs.us) return MGP_ERR_ARG;
+  const SpmmPlan pl = spmm_plan(L, 1, 0, true);
+  if (pl.err != MGP_OK) return pl.err;
+  if (pl.family != SpmmFamily::TileC1 || L->tile_rows != 64 || pl.lds + kCgStepStaticLds > 65536) return MGP_ERR_UNSUPPORTED;
+  if (cs.nbs != pl.dot_blocks || cs.nbs < 1 || cs.nbs > 16 * 256) return MGP_ERR_ARG;
+  // X = t; base = r enters through cs (form 2: dgamma), cb = 1; Y, the dot hooks, skip and tick are not used by this kernel:
+  // the done flag and the iteration come with the scalar block, and the first SpMV of the step has ticked
+  SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, T, nullptr, 1, a, b, nullptr, post, nullptr, 1.f, co,
+             nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  const TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+  const dim3 grid(pl.grid), block(256);
+  hipStream_t st = mgp_stream(stream);
+  if (cs.nbs <= 4 * 256) {
+    if (decide) hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 4, true>), grid, block, pl.lds, st, p, ta, cs);
+    else hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 4, false>), grid, block, pl.lds, st, p, ta, cs);
+  } else {
+    if (decide) hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 16, true>), grid, block, pl.lds, st, p, ta, cs);
+    else hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 16, false>), grid, block, pl.lds, st, p, ta, cs);
+  }
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
 }
 
 extern "C" int mgp_spmm_fused(const mgp_csr_t* L, const float* X, int C, float* Y, float a, float b,

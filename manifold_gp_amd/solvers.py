@@ -113,6 +113,12 @@ class CgPlan:
         iterations of ONE four-column product with B each."""
         return bool(lib().mgp_cg_plan_is_complex_shift(self.handle))
 
+    @property
+    def folded(self):
+        """True when a step of the plan is two launches, the vector update folded into the second SpMV of the apply
+        (include/mgp_hip.h: mgp_cg_set_fold_update)."""
+        return bool(lib().mgp_cg_plan_is_folded(self.handle))
+
     def solution_view(self):
         """The plan's own solution buffer as a tensor view (no copy; overwritten by the next solve).  NOTE: when the plan iterates
         on the relabelled matrix P A P^T (`self._rg` set: a graph handed over without locality), the rows of this view are in THAT

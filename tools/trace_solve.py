@@ -5,9 +5,11 @@ import csv, glob, os, re, sys
 base = sys.argv[1]
 f = max(glob.glob(base + "/**/*kernel_trace.csv", recursive=True), key=os.path.getmtime)
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
-# (round 4: a solve's first graph ends in the deciding update launch, cg_update_c1_kernel<true, ..>; older traces: cg_decide)
-dec = [i for i, r in enumerate(rows) if "cg_update_c1_kernel<true" in r["Kernel_Name"] or "cg_decide" in r["Kernel_Name"]]
-cands = dec[::-1] if dec else [max(i for i, r in enumerate(rows) if "cg_update" in r["Kernel_Name"])]
+# (round 4: a solve's first graph ends in the deciding update launch, cg_update_c1_kernel<true, ..>; round 6: in the deciding step
+# launch of a folded plan, spmv_tile_cgstep_kernel<.., .., true>; older traces: cg_decide)
+dec = [i for i, r in enumerate(rows) if "cg_update_c1_kernel<true" in r["Kernel_Name"] or "cg_decide" in r["Kernel_Name"]
+       or re.search(r"spmv_tile_cgstep_kernel<\d+, \d+, true", r["Kernel_Name"])]
+cands = dec[::-1] if dec else [max(i for i, r in enumerate(rows) if "cg_update" in r["Kernel_Name"] or "cgstep" in r["Kernel_Name"])]
 # walk back to the start of that solve: the gap before its first kernel is a host round trip (>= 8 us).  Under the profiler a
 # replay now and then shows such a gap INSIDE a solve: among the last 200 solves take the last one of the most common length
 import collections
