@@ -514,6 +514,15 @@ int mgp_cg_solve(const mgp_operator_t* op, const float* B, int C, float* X, cons
  * contributions to the diagonal ignored for nu > 2 (exact for nu <= 2) */
 int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* stream);
 
+/* The operator in float64 from the float32 matrix: Y = A X for X, Y [n,C] float64 (device, X != Y), every product and sum of
+ * the chain in float64 (the kernels behind the true residual of the refined CG solves).  Reads the natural-order CSR only.
+ * For callers that need A x to the rounding of its result, not of the chain: with tau I + L_sym applied nu times in float32 a
+ * smooth x loses up to a few thousand float32 roundings against A x (docs/kernels/classification.md).
+ * work: mgp_operator_apply_double_workspace_bytes(op, C) bytes (4 n C doubles), 8-byte aligned; MGP_ERR_WORKSPACE otherwise. */
+size_t mgp_operator_apply_double_workspace_bytes(const mgp_operator_t* op, int C);
+int mgp_operator_apply_double(const mgp_operator_t* op, const double* X, int C, double* Y, void* work, size_t work_bytes,
+                              void* stream);
+
 /* Marginal posterior variances in precision form (csrc/variance.hip, docs/kernels/sampling.md "Marginal variances"): the two
  * kernels of the single-site Rao-Blackwell estimator  var_i = s / d_i + E[(delta_i - p_i / d_i)^2],  d = diag(W + s Q2).
  *
@@ -538,6 +547,32 @@ int mgp_operator_diag_exact(const mgp_operator_t* op, double* diag_out, void* wo
  * MGP_ERR_ARG for C < 1, C > 256, n < 1, null U or acc, Pm without rdiag. */
 int mgp_row_moments(const float* U, const float* V, const double* rdiag, const float* Pm, int64_t n, int C, double* acc,
                     void* stream);
+
+/* Laplace approximation for 0/1 labels with a Bernoulli-logit likelihood (csrc/laplace.hip, docs/kernels/classification.md):
+ * the two per-node kernels of classification.laplace_fit.
+ *
+ * The likelihood stage of one Newton step.  f [n] latent values, qf [n] = Q2 f (NULL: zeros, the start at f = 0), y [n]
+ * labels (class 1 where y > 0.5; read at observed nodes only, NaN allowed elsewhere), obs [n] bytes (non-zero: observed; NULL:
+ * every node), all on the device.  Per node in float64 from the float32 inputs, with t in {0, 1}, a = (2 t - 1) f, e = exp(-|f|):
+ *   log p = min(a, 0) - log1p(e),   pi = f >= 0 ? 1 / (1 + e) : e / (1 + e),   g = t - pi,   h = e / (1 + e)^2
+ * (g = h = 0 at unobserved nodes), and
+ *   w_i = (float)(s_ref h_i),   rhs_i = (float)(s_ref (g_i - qf_i)),
+ *   sums [4] float64 (device) = { sum_obs log p,  sum_i f_i qf_i,  max_i |g_i - qf_i|,  sum_i (g_i - qf_i)^2 }.
+ * w is the obs_w of operator form 3 with noise = s_ref, rhs the Newton right-hand side; finite for any finite f (|f| = 1e4:
+ * log p = -1e4, h = 0).  The sums go through one partial per workgroup and a second launch that adds the partials: fixed order,
+ * no atomics, repeated calls are bitwise equal.  `work`: mgp_bernoulli_site_workspace_bytes(n) bytes, 8-byte aligned.
+ * float4 loads and stores where f, qf, y, w, rhs are 16-byte and obs 4-byte aligned, scalar ones otherwise.
+ * link: 0 = logit; any other MGP_ERR_UNSUPPORTED.  MGP_ERR_ARG for null f, y, w, rhs or sums and n < 1; MGP_ERR_WORKSPACE for
+ * a null, misaligned or short `work`. */
+size_t mgp_bernoulli_site_workspace_bytes(int64_t n);
+int mgp_bernoulli_site(const float* f, const float* qf, const float* y, const uint8_t* obs, int64_t n, double s_ref, int link,
+                       float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream);
+/* Predictive class probability  prob_i = int sigma(mean_i + sqrt(var_i) u) phi(u) du  by the `points`-point trapezoid rule
+ * on [-8, 8]: sum_k D phi(u_k) sigma(mean_i + sqrt(var_i) u_k), u_k = -8 + k D, D = 16 / (points - 1), k ascending, all in
+ * float64 (classification.md has the rule's error against 30-digit quadrature).  mean [n] float32, var [n] float64, prob [n]
+ * float64, on the device.  var < 0 counts as 0 (prob = sigma(mean)); NaN in mean or var gives NaN; prob <= 1.
+ * MGP_ERR_ARG for null pointers, n < 1 and points even or outside 9 .. 1025. */
+int mgp_bernoulli_predict(const float* mean, const double* var, int64_t n, int points, double* prob, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Eigensolve: the m smallest eigenpairs of L_sym by a Chebyshev-filtered block Krylov iteration

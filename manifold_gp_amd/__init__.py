@@ -17,6 +17,7 @@ from . import _compat
 from ._compat import settings
 from . import kernels, operators, utils, models  # noqa: F401
 from . import sampling  # noqa: F401
+from . import classification  # noqa: F401
 
 __version__ = "0.1.0"
 

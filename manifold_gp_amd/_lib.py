@@ -141,9 +141,14 @@ SIGNATURES = {
     "mgp_operator_apply": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, c_size_t, _P]),
     "mgp_operator_apply_dot": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_operator_jacobi": (c_int, [POINTER(OperatorT), _P, _P]),
+    "mgp_operator_apply_double_workspace_bytes": (c_size_t, [POINTER(OperatorT), c_int]),
+    "mgp_operator_apply_double": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, c_size_t, _P]),
     "mgp_operator_diag_exact_workspace_bytes": (c_size_t, [POINTER(OperatorT)]),
     "mgp_operator_diag_exact": (c_int, [POINTER(OperatorT), _P, _P, c_size_t, _P]),
     "mgp_row_moments": (c_int, [_P, _P, _P, _P, c_int64, c_int, _P, _P]),
+    "mgp_bernoulli_site_workspace_bytes": (c_size_t, [c_int64]),
+    "mgp_bernoulli_site": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "mgp_bernoulli_predict": (c_int, [_P, _P, c_int64, c_int, _P, _P]),
     "mgp_cg_workspace_bytes": (c_size_t, [POINTER(OperatorT), c_int]),
     "mgp_cg_solve": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, POINTER(CgParamsT), POINTER(c_int32),
                              POINTER(c_float), _P, c_size_t, _P]),

@@ -1,0 +1,228 @@
+// Laplace approximation for a Bernoulli-logit likelihood on the graph nodes (docs/kernels/classification.md): the two
+// per-node kernels that classification.laplace_fit adds to the form-3 solver.
+//
+// 1. mgp_bernoulli_site: the likelihood stage of one Newton step.  Per node, in float64 from the float32 inputs, with
+//    t = (y > 0.5), a = (2 t - 1) f and e = exp(-|f|):
+//      log p = min(a, 0) - log1p(e)          pi = f >= 0 ? 1 / (1 + e) : e / (1 + e)
+//      g = t - pi                            h = e / (1 + e)^2                          (no overflow, h without cancellation)
+//    w = s_ref h (0 at unobserved nodes) and rhs = s_ref (g - qf) (g = 0 at unobserved nodes) leave as float32, and four
+//    float64 sums -- sum_obs log p, sum f qf, max |g - qf|, sum (g - qf)^2 -- through per-workgroup partials: a thread adds
+//    its nodes in index order, xor tree over the wave, the waves in order, and a second single-workgroup launch adds the
+//    partials in a fixed order.  No atomics: repeated calls are bitwise equal.  18 bytes per node (f, qf, y, obs in; w, rhs
+//    out): a float4 / uchar4 per lane and step where the arrays are 16-byte (obs 4-byte) aligned, scalar otherwise and
+//    for the last n % 4 nodes.
+//
+// 2. mgp_bernoulli_predict: p_i = sum_k D phi(u_k) sigma(m_i + sqrt(v_i) u_k), u_k = -8 + k D, D = 16 / (K - 1): the K-point
+//    trapezoid rule on [-8, 8] in float64.  The workgroup fills (u_k, D phi(u_k)) in LDS once; a thread per node sums k in
+//    ascending order.
+#include "mgp_common.h"
+#include "mgp_internal.h"
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / MGP_WAVE;
+constexpr int kSiteMaxBlocks = 1024;      // grid cap of the site kernel: 1024 x 256 threads x 4 nodes per step
+constexpr int kPredictMaxBlocks = 2048;   // grid cap of the predict kernel: 2048 x 256 threads x 1 node per step
+constexpr int kMaxPoints = 1025;
+
+struct SiteAcc {
+  double lp, fq, mx, sq;
+};
+
+__device__ __forceinline__ void site_node(float f32, float qf32, float y32, bool obs, double s_ref, float& w, float& rhs,
+                                          SiteAcc& acc) {
+  const double f = (double)f32, qf = (double)qf32;
+  double g = 0.0, h = 0.0;
+  if (obs) {
+    const bool t = y32 > 0.5f;
+    const double a = t ? f : -f;
+    const double e = exp(-fabs(f));
+    const double d = 1.0 + e;
+    const double pi = f >= 0.0 ? 1.0 / d : e / d;
+    acc.lp += (a < 0.0 ? a : 0.0) - log1p(e);
+    g = (t ? 1.0 : 0.0) - pi;
+    h = e / (d * d);
+  }
+  const double r = g - qf;
+  w = (float)(s_ref * h);
+  rhs = (float)(s_ref * r);
+  acc.fq += f * qf;
+  const double ar = fabs(r);
+  acc.mx = ar > acc.mx ? ar : acc.mx;
+  acc.sq += r * r;
+}
+
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double other = __shfl_xor(v, o, 64);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+
+// the workgroup's four numbers from its threads': xor tree over each wave, the waves in order.  Valid in thread 0.
+__device__ __forceinline__ SiteAcc block_reduce(SiteAcc a) {
+  __shared__ double s_part[kWaves][4];
+  const int lane = threadIdx.x & (MGP_WAVE - 1), wave = threadIdx.x / MGP_WAVE;
+  a.lp = mgp_wave_sum_d(a.lp);
+  a.fq = mgp_wave_sum_d(a.fq);
+  a.mx = wave_max_d(a.mx);
+  a.sq = mgp_wave_sum_d(a.sq);
+  if (lane == 0) {
+    s_part[wave][0] = a.lp;
+    s_part[wave][1] = a.fq;
+    s_part[wave][2] = a.mx;
+    s_part[wave][3] = a.sq;
+  }
+  __syncthreads();
+  SiteAcc r = {s_part[0][0], s_part[0][1], s_part[0][2], s_part[0][3]};
+  for (int k = 1; k < kWaves; ++k) {
+    r.lp += s_part[k][0];
+    r.fq += s_part[k][1];
+    r.mx = s_part[k][2] > r.mx ? s_part[k][2] : r.mx;
+    r.sq += s_part[k][3];
+  }
+  return r;
+}
+
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void bernoulli_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
+                                                                const float* __restrict__ y,
+                                                                const uint8_t* __restrict__ obs, int64_t n, double s_ref,
+                                                                float* __restrict__ w, float* __restrict__ rhs,
+                                                                double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      // labels are read where a node of the quad is observed (they may be NaN elsewhere: never compared)
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 wv, rv;
+      site_node(fv.x, qv.x, yv.x, ov.x != 0, s_ref, wv.x, rv.x, acc);
+      site_node(fv.y, qv.y, yv.y, ov.y != 0, s_ref, wv.y, rv.y, acc);
+      site_node(fv.z, qv.z, yv.z, ov.z != 0, s_ref, wv.z, rv.z, acc);
+      site_node(fv.w, qv.w, yv.w, ov.w != 0, s_ref, wv.w, rv.w, acc);
+      *reinterpret_cast<float4*>(w + i0) = wv;
+      *reinterpret_cast<float4*>(rhs + i0) = rv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float wi, ri;
+        site_node(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, o, s_ref, wi, ri, acc);
+        w[i] = wi;
+        rhs[i] = ri;
+      }
+    }
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
+// sums[4] from the partials of `nblk` workgroups: thread t takes partials t, t + 256, ... in order, then the same tree
+__global__ __launch_bounds__(kBlock) void bernoulli_site_sum_kernel(const double* __restrict__ partials, int nblk,
+                                                                    double* __restrict__ sums) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < nblk; b += kBlock) {
+    const double* p = partials + 4 * (int64_t)b;
+    acc.lp += p[0];
+    acc.fq += p[1];
+    acc.mx = p[2] > acc.mx ? p[2] : acc.mx;
+    acc.sq += p[3];
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    sums[0] = r.lp;
+    sums[1] = r.fq;
+    sums[2] = r.mx;
+    sums[3] = r.sq;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* __restrict__ mean,
+                                                                   const double* __restrict__ var, int64_t n, int K,
+                                                                   double* __restrict__ prob) {
+  __shared__ double s_u[kMaxPoints];
+  __shared__ double s_wt[kMaxPoints];
+  const double step = 16.0 / (double)(K - 1);
+  for (int k = threadIdx.x; k < K; k += kBlock) {
+    const double u = -8.0 + (double)k * step;
+    s_u[k] = u;
+    s_wt[k] = step * (0.3989422804014327 * exp(-0.5 * u * u));        // D phi(u_k), 1 / sqrt(2 pi)
+  }
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+    const double m = (double)mean[i];
+    const double v = var[i];
+    const double sd = sqrt(v < 0.0 ? 0.0 : v);                         // (a NaN variance stays NaN)
+    double p = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const double x = m + sd * s_u[k];
+      const double e = exp(-fabs(x));
+      p += s_wt[k] * (x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e));
+    }
+    prob[i] = p > 1.0 ? 1.0 : p;                                       // the weights sum to 1 up to rounding
+  }
+}
+
+int site_blocks(int64_t n) {
+  const int64_t b = mgp_cdiv((n + 3) >> 2, (int64_t)kBlock);
+  return (int)(b > kSiteMaxBlocks ? kSiteMaxBlocks : b);
+}
+
+bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" size_t mgp_bernoulli_site_workspace_bytes(int64_t n) {
+  return n < 1 ? 0 : (size_t)site_blocks(n) * 4 * sizeof(double);
+}
+
+extern "C" int mgp_bernoulli_site(const float* f, const float* qf, const float* y, const uint8_t* obs, int64_t n,
+                                  double s_ref, int link, float* w, float* rhs, double* sums, void* work,
+                                  size_t work_bytes, void* stream) {
+  if (!f || !y || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
+  if (link != 0) return MGP_ERR_UNSUPPORTED;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_bernoulli_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(obs, 4) && aligned_to(w, 16) &&
+                    aligned_to(rhs, 16);
+  if (vec4)
+    hipLaunchKernelGGL(bernoulli_site_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), f, qf, y,
+                       obs, n, s_ref, w, rhs, partials);
+  else
+    hipLaunchKernelGGL(bernoulli_site_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), f, qf, y,
+                       obs, n, s_ref, w, rhs, partials);
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" int mgp_bernoulli_predict(const float* mean, const double* var, int64_t n, int points, double* prob,
+                                     void* stream) {
+  if (!mean || !var || !prob || n < 1) return MGP_ERR_ARG;
+  if (points < 9 || points > kMaxPoints || (points & 1) == 0) return MGP_ERR_ARG;
+  int64_t blocks = mgp_cdiv(n, (int64_t)kBlock);
+  if (blocks > kPredictMaxBlocks) blocks = kPredictMaxBlocks;
+  hipLaunchKernelGGL(bernoulli_predict_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), mean, var, n,
+                     points, prob);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}

@@ -318,6 +318,20 @@ int mgp_operator_apply_f64(const mgp_operator_t* op, const double* X, int C, dou
   return MGP_ERR_ARG;
 }
 
+extern "C" size_t mgp_operator_apply_double_workspace_bytes(const mgp_operator_t* op, int C) {
+  if (check_op(op) != MGP_OK || C <= 0) return 0;
+  return 4 * (size_t)op->L.n * C * sizeof(double);
+}
+
+extern "C" int mgp_operator_apply_double(const mgp_operator_t* op, const double* X, int C, double* Y, void* work,
+                                         size_t work_bytes, void* stream) {
+  MGP_TRY(check_op(op));
+  if (!X || !Y || X == Y || C <= 0) return MGP_ERR_ARG;
+  if (!work || (reinterpret_cast<uintptr_t>(work) & 7u) || work_bytes < mgp_operator_apply_double_workspace_bytes(op, C))
+    return MGP_ERR_WORKSPACE;
+  return mgp_operator_apply_f64(op, X, C, Y, static_cast<double*>(work), stream);
+}
+
 extern "C" int mgp_operator_apply(const mgp_operator_t* op, const float* X, int C, float* Y, void* work,
                                   size_t work_bytes, void* stream) {
   return mgp_operator_apply_ex(op, X, C, Y, nullptr, nullptr, nullptr, nullptr, work, work_bytes, stream);

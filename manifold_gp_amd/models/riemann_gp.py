@@ -149,6 +149,15 @@ class RiemannGP(torch.nn.Module):
         """sqrt of precision_posterior_variance(...)[0]: float64 [N]."""
         return self.precision_posterior_variance(num_samples, seed, observed, noisy, tol, method)[0].clamp_min(0).sqrt()
 
+    def laplace_posterior(self, observed=None, **kw):
+        """Classify the graph nodes: train_targets are 0/1 labels, read at `observed` (bool [N]; None: every node; NaN allowed
+        elsewhere).  The Laplace approximation of the latent posterior under a Bernoulli-logit likelihood, a
+        classification.LaplaceFit (mode, latent variances and samples, class probabilities); kw as classification.laplace_fit.
+        The Gaussian likelihood's noise is not used."""
+        from ..classification import laplace_fit
+        desc, _, y = self._sampling_args()
+        return laplace_fit(desc, y, observed, **kw)
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)

@@ -94,6 +94,20 @@ class Descriptor:
                 out[:, c0:c0 + 256] = Yc
         return out.squeeze(-1) if squeeze else out
 
+    def apply_f64(self, X):
+        """Y = A X in float64 from the float32 matrix, X [n, C] or [n] float64 on device, C <= 256
+        (mgp_operator_apply_double: no float32 rounding inside the chain)."""
+        _lib.require_device(X)
+        squeeze = X.dim() == 1
+        X = (X.unsqueeze(-1) if squeeze else X).to(torch.float64).contiguous()
+        op = self.struct()
+        out = torch.empty_like(X)
+        wb = lib().mgp_operator_apply_double_workspace_bytes(ctypes.byref(op), X.shape[1])
+        work = _lib.workspace(wb, "operator_f64", X.device)
+        check(lib().mgp_operator_apply_double(ctypes.byref(op), ptr(X), X.shape[1], ptr(out), ptr(work), work.numel(),
+                                              stream()), "mgp_operator_apply_double")
+        return out.squeeze(-1) if squeeze else out
+
     def jacobi(self):
         op = self.struct()
         minv = torch.empty(self.n, dtype=torch.float32, device=self.data.graph.device)
