@@ -574,6 +574,45 @@ int mgp_bernoulli_site(const float* f, const float* qf, const float* y, const ui
  * MGP_ERR_ARG for null pointers, n < 1 and points even or outside 9 .. 1025. */
 int mgp_bernoulli_predict(const float* mean, const double* var, int64_t n, int points, double* prob, void* stream);
 
+/* C-class labels with a softmax likelihood (csrc/laplace.hip, csrc/softmax_cg.hip, docs/kernels/classification.md): the kernels of
+ * classification.laplace_fit_multiclass.  Blocks are row-major [n, C] float32, 2 <= C <= 64; the C latent functions share the
+ * form-0 precision Q2.
+ *
+ * The likelihood stage of one Newton step.  f [n, C] latent values, qf [n, C] = Q2 F (NULL: zeros), labels [n] int32 (read at
+ * observed nodes only), obs [n] bytes (non-zero: observed; NULL: every node).  Per row in float64 from the float32 inputs:
+ *   m = max_c f_c,  e_c = exp(f_c - m),  Z = sum_c e_c,  pi_c = e_c / Z,  log p = f_t - m - log Z,  G = onehot(t) - pi
+ * (pi = G = 0 on unobserved rows; G_t = 1 - pi_t is formed as sum_{c != t} e_c / Z, without the cancellation), and
+ *   pi [n, C] = (float) pi,   rhs [n, C] = (float)(G - qf),
+ *   sums [4] float64 (device) = { sum_obs log p,  sum f . qf,  max |G - qf|,  sum (G - qf)^2 }.
+ * Finite for |f| up to 1e4.  A label is only compared with the class index, never used as an address: a label outside [0, C)
+ * gives a row with G = -pi and no log p term (the Python layer validates labels).  A group of TC lanes (least power of two
+ * >= C) owns a row; the sums go through one partial per workgroup and a second launch, fixed order, no atomics: repeated calls
+ * are bitwise equal.  `work`: mgp_softmax_site_workspace_bytes(n, C) bytes, 8-byte aligned.
+ * MGP_ERR_ARG for null f, labels, pi, rhs or sums, n < 1 and C outside 2 .. 64; MGP_ERR_WORKSPACE for a null, misaligned or
+ * short `work`.  The checks precede every launch. */
+size_t mgp_softmax_site_workspace_bytes(int64_t n, int C);
+int mgp_softmax_site(const float* f, const float* qf, const int32_t* labels, const uint8_t* obs, int64_t n, int C, float* pi,
+                     float* rhs, double* sums, void* work, size_t work_bytes, void* stream);
+/* Y_i += pi_i o x_i - pi_i (pi_i . x_i) for every row: the softmax Hessian H(pi) X added to Y (X != Y), float32, the row's dot
+ * product by an xor tree over its lane group.  A row of zeros in pi leaves its row of Y as it is.  The epilogue of a step of
+ * mgp_softmax_cg, exported for tests and restatements.  MGP_ERR_ARG for null pointers, X == Y, n < 1, C outside 2 .. 64. */
+int mgp_softmax_hessian_add(const float* pi, const float* X, int64_t n, int C, float* Y, void* stream);
+/* CG on (Q2 (x) I_C + H(pi)) X = B as ONE system of size n C: one alpha and one beta per step (cg_rule.h on one column of
+ * length n C), the Chronopoulos-Gear single-reduction recurrence, float32 vectors, float64 per-workgroup partials summed in a
+ * fixed order (no atomics: a repeated solve, or one with another check_every, is bitwise equal).  A step is the operator chain
+ * on C columns, mgp_softmax_hessian_add with the partials of R . R and R . W, and one update launch that forms the scalars,
+ * updates P, S, X, R and decides  ||r||_2 <= tol ||b||_2  over all n C entries.  Eager launches; a device flag turns the
+ * launches behind the decision into no-ops; the host reads the state once per check_every steps (0 = 8) and the call
+ * returns when it has seen the decision (it synchronises `stream`).  op: form 0 only (MGP_ERR_UNSUPPORTED otherwise);
+ * pi [n, C] rows of a softmax or zeros; X starts from 0 (B = 0: X = 0, status 1).  Host outputs (nullable): iters = updates
+ * made, resid = the recurrence's relative residual at the decision, status 1 converged / 2 max_iter / 3 not finite, as
+ * mgp_cg_plan_solve.  No preconditioner, no hipGraph.  `work`: mgp_softmax_cg_workspace_bytes(op, C) bytes (0 for arguments
+ * the solve refuses), 16-byte aligned.  MGP_ERR_ARG for null op, pi, B, X, B == X, C outside 2 .. 64, tol < 0 or NaN,
+ * max_iter < 1, check_every < 0 and an invalid operator; the checks precede every launch. */
+size_t mgp_softmax_cg_workspace_bytes(const mgp_operator_t* op, int C);
+int mgp_softmax_cg(const mgp_operator_t* op, const float* pi, int C, const float* B, float* X, float tol, int max_iter,
+                   int check_every, int32_t* iters, float* resid, int32_t* status, void* work, size_t work_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Eigensolve: the m smallest eigenpairs of L_sym by a Chebyshev-filtered block Krylov iteration
  * with Rayleigh-Ritz on L_sym itself (csrc/eigen.hip explains why not single-vector Lanczos; the

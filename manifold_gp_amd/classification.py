@@ -14,7 +14,20 @@ Jacobi-preconditioned CG (cg_solve).  The Laplace posterior
 N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets f_hat + g / h: variances and
 samples are sampling.posterior_variance / posterior_samples, nothing else.  The predictive class probability integrates
 the logistic against the latent marginal (mgp_bernoulli_predict).
+
+C classes (laplace_fit_multiclass): labels t_i in {0 .. C-1}, F [n, C] row-major, the C latent functions with independent priors
+of the same precision Q2, p(t_i | F_i) = softmax(F_i)[t_i].  The softmax ties the classes together at every observed node:
+with Pi = softmax(F) row by row and G = onehot(t) - Pi (both 0 at unobserved rows) a step solves
+
+    (Q2 (x) I_C + H) Delta = G - Q2 F          (H X)_i = pi_i o x_i - pi_i (pi_i . x_i)
+
+ONE SPD system of size n C, which neither the multi-column CG (one set of scalars per column) nor form 3 (one weight vector
+for all columns) expresses: mgp_softmax_cg solves it with one alpha and one beta per step, mgp_softmax_site is the per-row
+likelihood stage.  The Newton loop itself (_newton) is the binary fit's, stated once.  At the mode every row of F sums to 0
+(the prior fixes the softmax gauge).  Samples are perturb-and-MAP on the coupled system (MulticlassLaplaceFit.latent_samples),
+class probabilities the samples' mean softmax.
 """
+import ctypes
 import math
 import warnings
 
@@ -174,6 +187,50 @@ class LaplaceFit:
         return bernoulli_predict(self.mean, var, points), var
 
 
+def _newton(name, site, q2, solve, zero, f0, rtol, max_newton):
+    """Newton's method with step halving on psi, stated once for both fits.  site(f, qf) -> (aux, rhs, sums) with sums a list
+    (the one host read of an evaluation); q2(f) = Q2 f as float32; solve(aux, rhs) -> (delta, CG iterations); zero: the point
+    f = 0; f0: the start (None: zero, where Q2 0 = 0 needs no apply).  Stops when sums[2] <= rtol times its value at f = 0;
+    a trial point is taken when psi does not decrease beyond _slack, after at most MAX_HALVINGS halvings.
+    Returns (f, aux, sums, converged, steps, history)."""
+    if f0 is None:
+        f = zero
+        aux, rhs, sums = site(f, None)
+        grad0 = sums[2]
+    else:
+        grad0 = site(zero, None)[2][2]
+        f = f0
+        aux, rhs, sums = site(f, q2(f))
+    history, converged, its = [], False, 0
+    while True:
+        if not all(math.isfinite(v) for v in sums):
+            raise RuntimeError("%s: the latent values are not finite" % name)
+        if sums[2] <= rtol * grad0:
+            converged = True
+            break
+        if its >= max_newton:
+            break
+        delta, cg_its = solve(aux, rhs)
+        step, trial = 1.0, None
+        for _ in range(MAX_HALVINGS + 1):
+            ft = f + step * delta
+            auxt, rhst, sumst = site(ft, q2(ft))
+            if _psi(sumst) >= _psi(sums) - max(_slack(sums), _slack(sumst)):
+                trial = (ft, auxt, rhst, sumst)
+                break
+            step *= 0.5
+        if trial is None:
+            warnings.warn("%s: no ascent after %d halvings of the Newton step (relative gradient %.3g)"
+                          % (name, MAX_HALVINGS, sums[2] / grad0))
+            break
+        f, aux, rhs, sums = trial
+        its += 1
+        history.append((_psi(sums), sums[2] / grad0, step, int(cg_its)))
+    if not converged and its >= max_newton:
+        warnings.warn("%s: not converged in %d Newton steps (relative gradient %.3g)" % (name, its, sums[2] / grad0))
+    return f, aux, sums, converged, its, history
+
+
 def laplace_fit(desc, y, observed=None, link="logit", rtol=1e-5, max_newton=30, cg_tol=1e-3, max_iter=5000, f0=None):
     """The mode of the latent posterior given 0/1 labels y [n] at the observed nodes (bool [n]; None: every node; labels at
     the other nodes are not read and may be NaN), by Newton's method with step halving: LaplaceFit.
@@ -191,43 +248,244 @@ def laplace_fit(desc, y, observed=None, link="logit", rtol=1e-5, max_newton=30, 
         w, rhs, sums = bernoulli_site(f, qf, y, obs, S_REF, link)
         return w, rhs, sums.tolist()                      # the one host read of an evaluation
 
+    def solve(w, rhs):
+        # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
+        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=S_REF, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
+                                    jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
+        return delta, cg_its
+
     with torch.no_grad():
         zero = torch.zeros(n, dtype=torch.float32, device=dev)
-        if f0 is None:
-            f = zero
-            w, rhs, sums = site(f, None)                  # Q2 0 = 0: no apply at the start
-            grad0 = sums[2]
-        else:
-            grad0 = site(zero, None)[2][2]
-            f = _lib.f32c(f0.to(dev).reshape(-1))
-            w, rhs, sums = site(f, _q2(desc, f))
-        history, converged, its = [], False, 0
-        while True:
-            if not all(math.isfinite(v) for v in sums):
-                raise RuntimeError("laplace_fit: the latent values are not finite")
-            if sums[2] <= rtol * grad0:
-                converged = True
-                break
-            if its >= max_newton:
-                break
-            # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
-            delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=S_REF, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
-                                        jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
-            step, trial = 1.0, None
-            for _ in range(MAX_HALVINGS + 1):
-                ft = f + step * delta
-                wt, rhst, sumst = site(ft, _q2(desc, ft))
-                if _psi(sumst) >= _psi(sums) - max(_slack(sums), _slack(sumst)):
-                    trial = (ft, wt, rhst, sumst)
-                    break
-                step *= 0.5
-            if trial is None:
-                warnings.warn("laplace_fit: no ascent after %d halvings of the Newton step (relative gradient %.3g)"
-                              % (MAX_HALVINGS, sums[2] / grad0))
-                break
-            f, w, rhs, sums = trial
-            its += 1
-            history.append((_psi(sums), sums[2] / grad0, step, int(cg_its)))
-    if not converged and its >= max_newton:
-        warnings.warn("laplace_fit: not converged in %d Newton steps (relative gradient %.3g)" % (its, sums[2] / grad0))
+        start = None if f0 is None else _lib.f32c(f0.to(dev).reshape(-1))
+        f, _, sums, converged, its, history = _newton("laplace_fit", site, lambda v: _q2(desc, v), solve, zero, start, rtol,
+                                                      max_newton)
     return LaplaceFit(desc, y, obs, f, converged, its, history, sums[0])
+
+
+# ------------------------------------------------------------------------------------------------ C classes: softmax
+MAX_CLASSES = 64
+
+
+def _block(t, n, C, name):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != n or t.shape[1] != C:
+        raise ValueError("%s must be a tensor [%d, %d], got %s" % (name, n, C, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+    return _lib.f32c(t)
+
+
+def _classes(num_classes):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= MAX_CLASSES:
+        raise ValueError("num_classes must be an int in 2 .. %d, got %r" % (MAX_CLASSES, num_classes))
+    return num_classes
+
+
+def softmax_site(f, qf, labels, observed=None):
+    """(pi, rhs, sums) of mgp_softmax_site as fresh tensors: pi = softmax(f) row by row (rows of zeros at unobserved nodes)
+    and rhs = onehot(labels) - pi - qf, float32 [n, C]; sums [4] float64 on the device (sum_obs log p, sum f . qf,
+    max |rhs|, sum rhs^2).  f [n, C] float32, 2 <= C <= 64; qf [n, C] or None (zeros); labels [n] int32, read at the
+    observed nodes; observed [n] bool or None (every node)."""
+    if not torch.is_tensor(f) or f.dim() != 2:
+        raise ValueError("f must be a tensor [n, C]")
+    n, C = f.shape
+    _classes(int(C))
+    if n < 1:
+        raise ValueError("f has no rows")
+    if qf is not None:
+        qf = _block(qf, n, C, "qf")
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError("labels must be an int32 tensor [%d]" % n)
+    if observed is not None and (not torch.is_tensor(observed) or observed.dtype != torch.bool or observed.dim() != 1
+                                 or observed.shape[0] != n):
+        raise ValueError("observed must be a bool tensor [%d]" % n)
+    _lib.require_device(f, qf, labels, observed)
+    f, labels = _lib.f32c(f), labels.contiguous()
+    observed = None if observed is None else observed.contiguous()
+    pi, rhs = torch.empty_like(f), torch.empty_like(f)
+    sums = torch.empty(4, dtype=torch.float64, device=f.device)
+    wb = lib().mgp_softmax_site_workspace_bytes(n, C)
+    work = _lib.workspace(wb, "softmax_site", f.device)
+    check(lib().mgp_softmax_site(ptr(f), ptr(qf), ptr(labels), ptr(observed), n, C, ptr(pi), ptr(rhs), ptr(sums), ptr(work),
+                                 work.numel(), stream()), "mgp_softmax_site")
+    return pi, rhs, sums
+
+
+def softmax_hessian_add(pi, X, Y):
+    """Y += H(pi) X in place, (H X)_i = pi_i o x_i - pi_i (pi_i . x_i): mgp_softmax_hessian_add, the epilogue of a step of
+    softmax_cg_solve.  pi, X, Y [n, C] float32 contiguous on the device, X and Y distinct.  Returns Y."""
+    if not torch.is_tensor(pi) or pi.dim() != 2:
+        raise ValueError("pi must be a tensor [n, C]")
+    n, C = pi.shape
+    _classes(int(C))
+    for name, t in (("pi", pi), ("X", X), ("Y", Y)):
+        if not torch.is_tensor(t) or t.shape != pi.shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float32 tensor [%d, %d]" % (name, n, C))
+    _lib.require_device(pi, X, Y)
+    check(lib().mgp_softmax_hessian_add(ptr(pi), ptr(X), n, C, ptr(Y), stream()), "mgp_softmax_hessian_add")
+    return Y
+
+
+def softmax_noise_factor(pi, eps):
+    """R eps with R_i R_i^T = H_i = diag(pi_i) - pi_i pi_i^T (the rows of pi sum to 1 or are 0):
+    (R eps)_ic = sqrt(pi_ic) eps_ic - pi_ic sum_k sqrt(pi_ik) eps_ik.  pi, eps [n, C]; the dtype of eps."""
+    root = pi.to(eps.dtype).sqrt()
+    return root * eps - pi.to(eps.dtype) * (root * eps).sum(-1, keepdim=True)
+
+
+def softmax_cg_solve(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8):
+    """Solve (Q2 (x) I_C + H(pi)) X = rhs as one system of size n C (mgp_softmax_cg): (X [n, C] float32, iterations, relative
+    residual of the recurrence).  desc: a form-0 precision descriptor; pi, rhs [n, C].  Where the graph has a locality order
+    the solve runs on the relabelled descriptor, rows permuted in and out, as cg_solve does.  Warns when max_iter is reached,
+    raises on a non-finite residual."""
+    from .solvers import RELABEL_SOLVES
+    if int(desc.form) != 0:
+        raise NotImplementedError("softmax_cg_solve needs a form-0 precision descriptor")
+    if not torch.is_tensor(pi) or pi.dim() != 2 or pi.shape[0] != desc.n:
+        raise ValueError("pi must be a tensor [%d, C]" % desc.n)
+    n, C = pi.shape
+    _classes(int(C))
+    pi, rhs = _block(pi, n, C, "pi"), _block(rhs, n, C, "rhs")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError("max_iter must be a positive int, got %r" % (max_iter,))
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+        raise ValueError("check_every must be a positive int, got %r" % (check_every,))
+    if not tol >= 0.0:
+        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    _lib.require_device(pi, rhs)
+    rg = None
+    if RELABEL_SOLVES[0]:
+        rdesc, rg = desc.relabelled()
+        if rdesc is not None:
+            desc, pi, rhs = rdesc, rg.permute(pi).contiguous(), rg.permute(rhs).contiguous()
+        else:
+            rg = None
+    op = desc.struct()
+    X = torch.empty_like(rhs)
+    wb = lib().mgp_softmax_cg_workspace_bytes(ctypes.byref(op), C)
+    if wb == 0:
+        raise RuntimeError("mgp_softmax_cg_workspace_bytes: unsupported operator / class count %d" % C)
+    work = _lib.workspace(wb, "softmax_cg", rhs.device)
+    iters, status, resid = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_float(0.0)
+    check(lib().mgp_softmax_cg(ctypes.byref(op), ptr(pi), C, ptr(rhs), ptr(X), float(tol), max_iter, check_every,
+                               ctypes.byref(iters), ctypes.byref(resid), ctypes.byref(status), ptr(work), work.numel(),
+                               stream()), "mgp_softmax_cg")
+    if status.value == 2:
+        warnings.warn("CG did not converge in %d iterations (residual %.3g)" % (iters.value, resid.value))
+    elif status.value == 3:
+        raise RuntimeError("NaNs encountered in CG")
+    if rg is not None:
+        X = rg.unpermute(X)
+    return X, int(iters.value), float(resid.value)
+
+
+def _validate_multiclass(desc, labels, num_classes, observed, f0):
+    """The host-side argument checks of laplace_fit_multiclass: (labels [n] int32, observed [n] bool or None), on whatever
+    device they came."""
+    sampling._check_desc(desc)
+    C = _classes(num_classes)
+    n = desc.n
+    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != n or labels.dtype == torch.bool:
+        raise ValueError("labels must be a tensor of %d class indices, got %s"
+                         % (n, tuple(labels.shape) if torch.is_tensor(labels) else type(labels)))
+    if observed is not None:
+        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
+            raise ValueError("observed must be a bool tensor [n]")
+        if observed.dim() != 1 or observed.shape[0] != n:
+            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
+        if not bool(observed.any()):
+            raise ValueError("observed selects no node")
+        observed = observed.to(labels.device)
+    seen = labels if observed is None else labels[observed]
+    if not bool(((seen >= 0) & (seen < C) & (seen == seen.round() if seen.is_floating_point() else True)).all()):
+        raise ValueError("labels at the observed nodes must all be integers in [0, %d)" % C)
+    if f0 is not None and (not torch.is_tensor(f0) or f0.dim() != 2 or f0.shape[0] != n or f0.shape[1] != C):
+        raise ValueError("f0 must be a tensor [%d, %d] of latent values" % (n, C))
+    # the observed entries are in [0, C) by now; the rest is never read but has to survive the cast to int32.  Integer labels
+    # are widened first: clamp(-1, .) on a uint8 tensor would wrap the bound to 255 and turn every label into MAX_CLASSES
+    if labels.is_floating_point():
+        labels = torch.nan_to_num(labels, nan=-1.0, posinf=-1.0, neginf=-1.0).clamp(-1.0, float(MAX_CLASSES))
+    else:
+        labels = labels.to(torch.int64).clamp(-1, MAX_CLASSES)
+    return labels.to(torch.int32), observed
+
+
+class MulticlassLaplaceFit:
+    """The Laplace approximation N(mean, (Q2 (x) I + H)^-1) of the latent posterior of C classes (laplace_fit_multiclass).
+    mean [n, C] float32: the mode, rows summing to 0 up to the solver's tolerance; converged, iterations; history: one
+    (psi, relative gradient, step, CG iterations) per Newton step; log_likelihood: sum_obs log softmax(mean_i)[t_i];
+    pi [n, C] float32: softmax(mean) on the observed rows, 0 elsewhere (the weights of H)."""
+
+    def __init__(self, desc, labels, observed, mean, pi, converged, iterations, history, log_likelihood):
+        self.desc, self.labels, self.observed = desc, labels, observed
+        self.mean, self.pi, self.converged, self.iterations = mean, pi, converged, iterations
+        self.history, self.log_likelihood = history, log_likelihood
+
+    @property
+    def num_classes(self):
+        return self.mean.shape[1]
+
+    def map_proba(self):
+        """softmax(mean) row by row: the class probabilities at the mode, [n, C] float64 (ignores the latent variance)."""
+        return torch.softmax(self.mean.double(), dim=-1)
+
+    def _samples(self, S, seed, tol, max_iter):
+        """Sample s = 0 .. S - 1 as [n, C] float32, one at a time."""
+        S, seed = sampling._count(S), sampling._seed(seed)
+        desc, C = self.desc, self.num_classes
+        P = sampling._check_desc(desc)
+        with torch.no_grad():
+            for s in range(S):
+                z = sampling._precision_chunk(desc, P, C, seed, s * C)
+                eps = sampling.gmrf_noise(desc.data, C, seed, s * C, tag=2)
+                delta = softmax_cg_solve(desc, self.pi, z + softmax_noise_factor(self.pi, eps), tol=tol, max_iter=max_iter)[0]
+                yield self.mean + delta
+
+    def latent_samples(self, S, seed=None, tol=1e-5, max_iter=5000):
+        """F ~ N(mean, A^-1), A = Q2 (x) I + H: [S, n, C] float32, by perturb-and-MAP on the coupled system:
+        delta = A^-1 (z + R eps) with z_c ~ N(0, Q2) independent per class (sampling._precision_chunk) and eps ~ N(0, I)
+        (gmrf_noise, tag 2) through softmax_noise_factor.  Sample s takes the noise offsets s C .. s C + C - 1 of both streams:
+        it depends on (seed, s) alone.  One softmax_cg_solve per sample, to the relative residual tol."""
+        S = sampling._count(S)
+        out = torch.empty(S, self.desc.n, self.num_classes, dtype=torch.float32, device=self.mean.device)
+        for s, x in enumerate(self._samples(S, seed, tol, max_iter)):
+            out[s] = x
+        return out
+
+    def predict_proba(self, S=64, seed=None):
+        """The mean over S latent samples (latent_samples(S, seed)) of softmax(F_s) row by row, float64 [n, C]: the Monte-Carlo
+        estimate of the class probabilities under the Laplace posterior (rows sum to 1).  The samples are summed as they are
+        drawn, in the order s = 0 .. S - 1: O(n C) memory at any S."""
+        S, seed = sampling._count(S), sampling._seed(seed)     # (one seed for all samples when it is drawn here)
+        acc = torch.zeros(self.desc.n, self.num_classes, dtype=torch.float64, device=self.mean.device)
+        for x in self._samples(S, seed, 1e-5, 5000):
+            acc += torch.softmax(x.double(), dim=-1)
+        return acc / S
+
+
+def laplace_fit_multiclass(desc, labels, num_classes, observed=None, rtol=1e-5, max_newton=30, cg_tol=1e-3, max_iter=5000,
+                           f0=None):
+    """The mode of the latent posterior of num_classes (2 .. 64) classes under a softmax likelihood, by Newton's method with
+    step halving: MulticlassLaplaceFit.  labels [n]: class indices in [0, num_classes) at the observed nodes (bool [n]; None:
+    every node), an integer tensor or a float tensor of whole numbers; the other entries are not read and may be NaN.
+    desc: a form-0 precision descriptor as the samplers take; the C latent functions share it as independent priors.
+    Stops when max |G - Q2 F| <= rtol times its value at F = 0; every step is one coupled CG solve (softmax_cg_solve) to the
+    relative residual cg_tol.  f0 [n, C]: the starting point (default 0)."""
+    labels, observed = _validate_multiclass(desc, labels, num_classes, observed, f0)
+    _lib.require_device(labels, f0)
+    dev = desc.data.graph.device
+    n, C = desc.n, num_classes
+    labels = labels.to(dev).contiguous()
+    obs = None if observed is None else observed.to(dev).contiguous()
+
+    def site(f, qf):
+        pi, rhs, sums = softmax_site(f, qf, labels, obs)
+        return pi, rhs, sums.tolist()                     # the one host read of an evaluation
+
+    def solve(pi, rhs):
+        delta, cg_its, _ = softmax_cg_solve(desc, pi, rhs, tol=cg_tol, max_iter=max_iter)
+        return delta, cg_its
+
+    with torch.no_grad():
+        zero = torch.zeros(n, C, dtype=torch.float32, device=dev)
+        start = None if f0 is None else _lib.f32c(f0.to(dev))
+        f, pi, sums, converged, its, history = _newton("laplace_fit_multiclass", site, lambda v: _q2(desc, v), solve, zero,
+                                                       start, rtol, max_newton)
+    return MulticlassLaplaceFit(desc, labels, obs, f, pi, converged, its, history, sums[0])

@@ -15,14 +15,24 @@
 // 2. mgp_bernoulli_predict: p_i = sum_k D phi(u_k) sigma(m_i + sqrt(v_i) u_k), u_k = -8 + k D, D = 16 / (K - 1): the K-point
 //    trapezoid rule on [-8, 8] in float64.  The workgroup fills (u_k, D phi(u_k)) in LDS once; a thread per node sums k in
 //    ascending order.
+//
+// 3. mgp_softmax_site: the likelihood stage of a C-class fit (classification.laplace_fit_multiclass).  F, Q2 F, pi and rhs are
+//    row-major [n, C]; a group of TC lanes (the least power of two >= C) owns a row, lane c its class: consecutive lanes read
+//    consecutive floats of the block.  Per row in float64: m = max_c f_c, e_c = exp(f_c - m), Z = sum e_c (xor trees inside
+//    the group), pi_c = e_c / Z, log p = f_t - m - log Z; G = onehot(t) - pi on observed rows (G_t = sum_{c != t} e_c / Z, a second
+//    xor tree: 1 - pi_t cancels where pi_t -> 1), 0 elsewhere, rhs = G - qf.  The
+//    label is only compared with the lane's class, never used as an index.  The four sums leave through SiteAcc, block_reduce
+//    and bernoulli_site_sum_kernel as above.
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "softmax_rows.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / MGP_WAVE;
-constexpr int kSiteMaxBlocks = 1024;      // grid cap of the site kernel: 1024 x 256 threads x 4 nodes per step
+constexpr int kSiteMaxBlocks = 1024;      // grid cap of the site kernels: 1024 x 256 threads x 4 nodes per step (Bernoulli),
+                                          // 1024 x 256 / TC rows per step (softmax)
 constexpr int kPredictMaxBlocks = 2048;   // grid cap of the predict kernel: 2048 x 256 threads x 1 node per step
 constexpr int kMaxPoints = 1025;
 
@@ -180,6 +190,56 @@ __global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* 
   }
 }
 
+template <int TC>
+__global__ __launch_bounds__(kBlock) void softmax_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
+                                                              const int32_t* __restrict__ labels,
+                                                              const uint8_t* __restrict__ obs, int64_t n, int C,
+                                                              float* __restrict__ pi, float* __restrict__ rhs,
+                                                              double* __restrict__ partials) {
+  constexpr int kRows = kBlock / TC;                                   // rows a workgroup takes per step
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const int c = threadIdx.x & (TC - 1), g = threadIdx.x / TC;
+  const int64_t stride = (int64_t)gridDim.x * kRows;
+  const int64_t steps = (n + stride - 1) / stride;                           // the same for every lane: the shuffles stay convergent
+  for (int64_t k = 0; k < steps; ++k) {
+    const int64_t i = k * stride + (int64_t)blockIdx.x * kRows + g;
+    const bool live = i < n && c < C;
+    const int64_t at = i * C + c;
+    const bool o = live && (obs ? obs[i] != 0 : true);
+    const bool mine = o && labels[i] == c;                             // compared, never an index
+    const double fv = live ? (double)f[at] : -INFINITY;
+    const double m = mgp_group_max_d<TC>(fv);
+    const double e = live ? exp(fv - m) : 0.0;
+    const double Z = mgp_group_sum_d<TC>(e);
+    const double rest = mgp_group_sum_d<TC>(mine ? 0.0 : e);               // Z without the label's term
+    if (!live) continue;                                               // (after the group's shuffles)
+    const double q = qf ? (double)qf[at] : 0.0;
+    double p = 0.0, gr = 0.0;
+    if (o) {
+      p = e / Z;
+      gr = mine ? rest / Z : -p;                                       // 1 - pi_t = rest / Z: no cancellation where pi_t -> 1
+      if (mine) acc.lp += fv - m - log(Z);
+    }
+    const double r = gr - q;
+    pi[at] = (float)p;
+    rhs[at] = (float)r;
+    acc.fq += fv * q;
+    const double ar = fabs(r);
+    acc.mx = ar > acc.mx ? ar : acc.mx;
+    acc.sq += r * r;
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
+int softmax_site_blocks(int64_t n, int C) { return mgp_softmax_blocks(n, C, kBlock, kSiteMaxBlocks); }
+
 int site_blocks(int64_t n) {
   const int64_t b = mgp_cdiv((n + 3) >> 2, (int64_t)kBlock);
   return (int)(b > kSiteMaxBlocks ? kSiteMaxBlocks : b);
@@ -211,6 +271,27 @@ extern "C" int mgp_bernoulli_site(const float* f, const float* qf, const float* 
                        obs, n, s_ref, w, rhs, partials);
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_softmax_site_workspace_bytes(int64_t n, int C) {
+  return (n < 1 || C < 2 || C > 64) ? 0 : (size_t)softmax_site_blocks(n, C) * 4 * sizeof(double);
+}
+
+extern "C" int mgp_softmax_site(const float* f, const float* qf, const int32_t* labels, const uint8_t* obs, int64_t n, int C,
+                                float* pi, float* rhs, double* sums, void* work, size_t work_bytes, void* stream) {
+  if (!f || !labels || !pi || !rhs || !sums || n < 1 || C < 2 || C > 64) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_softmax_site_workspace_bytes(n, C)) return MGP_ERR_WORKSPACE;
+  const int blocks = softmax_site_blocks(n, C);
+  double* partials = static_cast<double*>(work);
+  hipStream_t st = mgp_stream(stream);
+  mgp_softmax_dispatch(C, [&](auto tc) {
+    hipLaunchKernelGGL(softmax_site_kernel<decltype(tc)::value>, dim3((unsigned)blocks), dim3(kBlock), 0, st, f, qf, labels, obs,
+                       n, C, pi, rhs, partials);
+  });
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

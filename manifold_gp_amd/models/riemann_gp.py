@@ -158,6 +158,15 @@ class RiemannGP(torch.nn.Module):
         desc, _, y = self._sampling_args()
         return laplace_fit(desc, y, observed, **kw)
 
+    def laplace_posterior_multiclass(self, num_classes, observed=None, **kw):
+        """Classify the graph nodes into num_classes classes: train_targets are class indices in [0, num_classes), read at
+        `observed` (bool [N]; None: every node; NaN allowed elsewhere).  The Laplace approximation of the latent posterior
+        under a softmax likelihood, a classification.MulticlassLaplaceFit (mode, latent samples, class probabilities); kw as
+        classification.laplace_fit_multiclass.  The Gaussian likelihood's noise is not used."""
+        from ..classification import laplace_fit_multiclass
+        desc, _, y = self._sampling_args()
+        return laplace_fit_multiclass(desc, y, num_classes, observed, **kw)
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)
