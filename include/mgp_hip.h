@@ -612,6 +612,31 @@ int mgp_softmax_hessian_add(const float* pi, const float* X, int64_t n, int C, f
 size_t mgp_softmax_cg_workspace_bytes(const mgp_operator_t* op, int C);
 int mgp_softmax_cg(const mgp_operator_t* op, const float* pi, int C, const float* B, float* X, float tol, int max_iter,
                    int check_every, int32_t* iters, float* resid, int32_t* status, void* work, size_t work_bytes, void* stream);
+/* S right-hand sides of that system at once (csrc/softmax_cg_block.hip, layout in csrc/softmax_block.h): A X_s = B_s, s = 0 .. S - 1,
+ * with A = Q2 (x) I_C + H(pi) and pi [n, C] shared.  B and X are row-major [n, S, C] (node i, sample s, class c at (i S + s) C + c),
+ * so the operator chain runs once per step on S C columns; 2 <= C <= 64, S >= 1, S C <= 256.  Every sample keeps the scalars of
+ * its own CG (gamma_s, delta_s, alpha_s, beta_s, ||b_s||^2, rel_s; cg_rule.h with a sample in the place of a column).  A step is
+ * the chain, the block epilogue (W_is += H(pi_i) r_is with float64 partials of gamma_s and delta_s per workgroup), a reduce launch
+ * (one workgroup per sample, fixed order) and the update.  A sample with rel_s <= tol is frozen: alpha_s = beta_s = 0 and X_s, R_s
+ * are not written again.  The solve ends when every sample is frozen (status 1), at step > max_iter (2) or on a non-finite
+ * residual (3).  No atomics: sample s depends on (op, pi, C, S, B_s, tol, max_iter) and its slot alone -- not on the other
+ * (finite) right-hand sides, on check_every or on repetition.  Eager launches, a device flag, one host read per check_every steps
+ * (0 = 8), as mgp_softmax_cg.  Host outputs (nullable): iters [S] = updates applied to each sample, resid [S] = its last rel_s
+ * (B_s = 0: X_s = 0, iters 0, resid 0), status one word.  `work`: mgp_softmax_cg_block_workspace_bytes(op, C, S) bytes (0 for
+ * arguments the solve refuses), 16-byte aligned.  MGP_ERR_ARG for null op, pi, B, X, B == X, C outside 2 .. 64, S < 1,
+ * S C > 256, tol < 0 or NaN, max_iter < 1, check_every < 0 and an invalid operator; MGP_ERR_UNSUPPORTED for forms 1-3;
+ * MGP_ERR_WORKSPACE for a null, misaligned or short `work`.  The checks precede every launch. */
+size_t mgp_softmax_cg_block_workspace_bytes(const mgp_operator_t* op, int C, int S);
+int mgp_softmax_cg_block(const mgp_operator_t* op, const float* pi, int C, int S, const float* B, float* X, float tol,
+                         int max_iter, int check_every, int32_t* iters, float* resid, int32_t* status, void* work,
+                         size_t work_bytes, void* stream);
+/* The block epilogue alone, for tests: Y_is += pi_i o x_is - pi_i (pi_i . x_is) on X, Y [n, S, C] with pi [n, C], and, when `sums`
+ * (device [S][2] float64) is given, the reduce launch: sums[s] = { sum x_s . x_s, sum x_s . y_s } with y the updated Y.  `work`:
+ * mgp_softmax_hessian_add_block_workspace_bytes(n, C, S) bytes, 16-byte aligned, read only when sums is given.  MGP_ERR_ARG for
+ * null pi, X, Y, X == Y, n < 1 and a shape the solver refuses (workspace size 0); MGP_ERR_WORKSPACE as above. */
+size_t mgp_softmax_hessian_add_block_workspace_bytes(int64_t n, int C, int S);
+int mgp_softmax_hessian_add_block(const float* pi, const float* X, int64_t n, int C, int S, float* Y, double* sums, void* work,
+                                  size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Eigensolve: the m smallest eigenpairs of L_sym by a Chebyshev-filtered block Krylov iteration

@@ -23,7 +23,7 @@ with Pi = softmax(F) row by row and G = onehot(t) - Pi (both 0 at unobserved row
 
 ONE SPD system of size n C, which neither the multi-column CG (one set of scalars per column) nor form 3 (one weight vector
 for all columns) expresses: mgp_softmax_cg solves it with one alpha and one beta per step, mgp_softmax_site is the per-row
-likelihood stage.  The Newton loop itself (_newton) is the binary fit's, stated once.  At the mode every row of F sums to 0
+likelihood stage; mgp_softmax_cg_block solves S such systems with the same matrix at once (the samples of a fit, block=).  The Newton loop itself (_newton) is the binary fit's, stated once.  At the mode every row of F sums to 0
 (the prior fixes the softmax gauge).  Samples are perturb-and-MAP on the coupled system (MulticlassLaplaceFit.latent_samples),
 class probabilities the samples' mean softmax.
 """
@@ -376,6 +376,78 @@ def softmax_cg_solve(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8):
     return X, int(iters.value), float(resid.value)
 
 
+MAX_BLOCK_COLUMNS = sampling.CHUNK       # S C <= 256: the operator path's column cap
+
+
+def _block_width(block, C):
+    """`block` of latent_samples / predict_proba / latent_variance: None (one solve per sample) or the samples per solve."""
+    if block is None:
+        return None
+    if isinstance(block, bool) or not isinstance(block, int) or block < 1:
+        raise ValueError("block must be None or a positive int, got %r" % (block,))
+    if block * C > MAX_BLOCK_COLUMNS:
+        raise ValueError("block = %d samples of %d classes are %d columns: the limit is %d" % (block, C, block * C,
+                                                                                            MAX_BLOCK_COLUMNS))
+    return block
+
+
+def softmax_cg_solve_block(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8):
+    """Solve (Q2 (x) I_C + H(pi)) X_s = rhs_s for the S right-hand sides rhs [n, S, C] in one block (mgp_softmax_cg_block):
+    (X [n, S, C] float32, iterations per sample, relative residual of each sample's recurrence).  Every sample runs the CG of
+    softmax_cg_solve with its own scalars and stops updating when its residual is <= tol; the operator chain runs once per step
+    on the S C <= 256 columns.  desc and pi [n, C] as softmax_cg_solve; the solve runs on the relabelled descriptor, rows
+    permuted in and out, and from 48 columns on it takes the matrix-core tile SpMM on the chain-relabelled matrix where the
+    graph has one, as cg_solve does.  Warns when max_iter is reached, naming the samples above tol; raises on a non-finite
+    residual."""
+    from .solvers import RELABEL_SOLVES
+    if int(desc.form) != 0:
+        raise NotImplementedError("softmax_cg_solve_block needs a form-0 precision descriptor")
+    if not torch.is_tensor(pi) or pi.dim() != 2 or pi.shape[0] != desc.n:
+        raise ValueError("pi must be a tensor [%d, C]" % desc.n)
+    n, C = pi.shape
+    _classes(int(C))
+    if not torch.is_tensor(rhs) or rhs.dim() != 3 or rhs.shape[0] != n or rhs.shape[1] < 1 or rhs.shape[2] != C:
+        raise ValueError("rhs must be a tensor [%d, S, %d], got %s" % (n, C, tuple(rhs.shape) if torch.is_tensor(rhs) else type(rhs)))
+    S = int(rhs.shape[1])
+    if S * C > MAX_BLOCK_COLUMNS:
+        raise ValueError("rhs holds S C = %d x %d = %d columns: the limit is %d" % (S, C, S * C, MAX_BLOCK_COLUMNS))
+    pi, rhs = _block(pi, n, C, "pi"), _lib.f32c(rhs)
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError("max_iter must be a positive int, got %r" % (max_iter,))
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+        raise ValueError("check_every must be a positive int, got %r" % (check_every,))
+    if not tol >= 0.0:
+        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    _lib.require_device(pi, rhs)
+    rg = None
+    wide = S * C >= 48               # 48 columns and more: the matrix-core tile SpMM on the chain-relabelled matrix, as CgPlan
+    if RELABEL_SOLVES[0]:
+        rdesc, rg = desc.relabelled(wide=wide)
+        if rdesc is not None:
+            desc, pi, rhs = rdesc, rg.permute(pi).contiguous(), rg.permute(rhs.view(n, S * C)).contiguous().view(n, S, C)
+        else:
+            rg = None
+    op = desc.struct(wide=wide)
+    X = torch.empty_like(rhs)
+    wb = lib().mgp_softmax_cg_block_workspace_bytes(ctypes.byref(op), C, S)
+    if wb == 0:
+        raise RuntimeError("mgp_softmax_cg_block_workspace_bytes: unsupported operator / %d samples of %d classes" % (S, C))
+    work = _lib.workspace(wb, "softmax_cg_block", rhs.device)
+    iters, resid, status = (ctypes.c_int32 * S)(), (ctypes.c_float * S)(), ctypes.c_int32(0)
+    check(lib().mgp_softmax_cg_block(ctypes.byref(op), ptr(pi), C, S, ptr(rhs), ptr(X), float(tol), max_iter, check_every, iters,
+                                     resid, ctypes.byref(status), ptr(work), work.numel(), stream()), "mgp_softmax_cg_block")
+    iters, resid = [int(v) for v in iters], [float(v) for v in resid]
+    if status.value == 2:
+        late = [k for k in range(S) if not resid[k] <= tol]
+        warnings.warn("CG did not converge in %d iterations: samples %s of the block are above tol (largest residual %.3g)"
+                      % (max(iters), late, max(resid)))
+    elif status.value == 3:
+        raise RuntimeError("NaNs encountered in CG")
+    if rg is not None:
+        X = rg.unpermute(X.view(n, S * C)).view(n, S, C)
+    return X, iters, resid
+
+
 def _validate_multiclass(desc, labels, num_classes, observed, f0):
     """The host-side argument checks of laplace_fit_multiclass: (labels [n] int32, observed [n] bool or None), on whatever
     device they came."""
@@ -426,38 +498,72 @@ class MulticlassLaplaceFit:
         """softmax(mean) row by row: the class probabilities at the mode, [n, C] float64 (ignores the latent variance)."""
         return torch.softmax(self.mean.double(), dim=-1)
 
-    def _samples(self, S, seed, tol, max_iter):
-        """Sample s = 0 .. S - 1 as [n, C] float32, one at a time."""
+    def _samples(self, S, seed, tol, max_iter, block=None):
+        """Sample s = 0 .. S - 1 as [n, C] float32: one at a time (block None), or drawn `block` per solve (views into the
+        block's [n, block, C] solution, which lives until the next block is drawn)."""
         S, seed = sampling._count(S), sampling._seed(seed)
         desc, C = self.desc, self.num_classes
+        b = _block_width(block, C)
         P = sampling._check_desc(desc)
         with torch.no_grad():
-            for s in range(S):
-                z = sampling._precision_chunk(desc, P, C, seed, s * C)
-                eps = sampling.gmrf_noise(desc.data, C, seed, s * C, tag=2)
-                delta = softmax_cg_solve(desc, self.pi, z + softmax_noise_factor(self.pi, eps), tol=tol, max_iter=max_iter)[0]
-                yield self.mean + delta
+            if b is None:
+                for s in range(S):
+                    z = sampling._precision_chunk(desc, P, C, seed, s * C)
+                    eps = sampling.gmrf_noise(desc.data, C, seed, s * C, tag=2)
+                    delta = softmax_cg_solve(desc, self.pi, z + softmax_noise_factor(self.pi, eps), tol=tol, max_iter=max_iter)[0]
+                    yield self.mean + delta
+                return
+            _lib.require_device(self.mean, self.pi)
+            n, pi = desc.n, self.pi[:, None, :]
+            for s0 in range(0, S, b):
+                # every block has width b, the last one too: sample s then depends on (seed, s, b) alone, not on S
+                z = sampling._precision_chunk(desc, P, b * C, seed, s0 * C).view(n, b, C)
+                eps = sampling.gmrf_noise(desc.data, b * C, seed, s0 * C, tag=2).view(n, b, C)
+                rhs = z + softmax_noise_factor(pi, eps)
+                if s0 + b > S:
+                    rhs[:, S - s0:] = 0.0
+                x = self.mean[:, None, :] + softmax_cg_solve_block(desc, self.pi, rhs, tol=tol, max_iter=max_iter)[0]
+                for k in range(min(b, S - s0)):
+                    yield x[:, k]
 
-    def latent_samples(self, S, seed=None, tol=1e-5, max_iter=5000):
+    def latent_samples(self, S, seed=None, tol=1e-5, max_iter=5000, block=None):
         """F ~ N(mean, A^-1), A = Q2 (x) I + H: [S, n, C] float32, by perturb-and-MAP on the coupled system:
         delta = A^-1 (z + R eps) with z_c ~ N(0, Q2) independent per class (sampling._precision_chunk) and eps ~ N(0, I)
         (gmrf_noise, tag 2) through softmax_noise_factor.  Sample s takes the noise offsets s C .. s C + C - 1 of both streams:
-        it depends on (seed, s) alone.  One softmax_cg_solve per sample, to the relative residual tol."""
+        it depends on (seed, s) alone.  block None: one softmax_cg_solve per sample, to the relative residual tol.
+        block = b (b C <= 256): the samples s0 .. s0 + b - 1 come from one softmax_cg_solve_block on b C columns, every sample to
+        the same tol with its own CG scalars; the noise offsets are the same, the SpMM kernel and so the rounding are not:
+        sample s then depends on (seed, s, b)."""
         S = sampling._count(S)
         out = torch.empty(S, self.desc.n, self.num_classes, dtype=torch.float32, device=self.mean.device)
-        for s, x in enumerate(self._samples(S, seed, tol, max_iter)):
+        for s, x in enumerate(self._samples(S, seed, tol, max_iter, block)):
             out[s] = x
         return out
 
-    def predict_proba(self, S=64, seed=None):
-        """The mean over S latent samples (latent_samples(S, seed)) of softmax(F_s) row by row, float64 [n, C]: the Monte-Carlo
-        estimate of the class probabilities under the Laplace posterior (rows sum to 1).  The samples are summed as they are
-        drawn, in the order s = 0 .. S - 1: O(n C) memory at any S."""
+    def predict_proba(self, S=64, seed=None, block=None):
+        """The mean over S latent samples (latent_samples(S, seed, block=block)) of softmax(F_s) row by row, float64 [n, C]: the
+        Monte-Carlo estimate of the class probabilities under the Laplace posterior (rows sum to 1).  The samples are summed as
+        they are drawn, in the order s = 0 .. S - 1: O(n C) memory at any S (O(n b C) with block = b)."""
         S, seed = sampling._count(S), sampling._seed(seed)     # (one seed for all samples when it is drawn here)
         acc = torch.zeros(self.desc.n, self.num_classes, dtype=torch.float64, device=self.mean.device)
-        for x in self._samples(S, seed, 1e-5, 5000):
+        for x in self._samples(S, seed, 1e-5, 5000, block):
             acc += torch.softmax(x.double(), dim=-1)
         return acc / S
+
+    def latent_variance(self, S=64, seed=None, block=None):
+        """(var, se): the marginal variances diag(A^-1) of the latent posterior as [n, C] and the standard error of the estimate,
+        float64 each, from the S samples of latent_samples(S, seed, block=block): delta_s = F_s - mean has mean 0 exactly, so
+        var = mean_s delta_s^2 and se = sqrt((mean_s delta_s^4 - var^2) / S).  The plain estimator: its error falls as
+        sqrt(2 / S) var; accumulated in float64 as the samples are drawn."""
+        S, seed = sampling._count(S), sampling._seed(seed)
+        mean = self.mean.double()
+        m2, m4 = torch.zeros_like(mean), torch.zeros_like(mean)
+        for x in self._samples(S, seed, 1e-5, 5000, block):
+            d2 = (x.double() - mean) ** 2
+            m2 += d2
+            m4 += d2 * d2
+        m2, m4 = m2 / S, m4 / S
+        return m2, ((m4 - m2 * m2).clamp_min(0.0) / S).sqrt()
 
 
 def laplace_fit_multiclass(desc, labels, num_classes, observed=None, rtol=1e-5, max_newton=30, cg_tol=1e-3, max_iter=5000,

@@ -162,7 +162,8 @@ class RiemannGP(torch.nn.Module):
         """Classify the graph nodes into num_classes classes: train_targets are class indices in [0, num_classes), read at
         `observed` (bool [N]; None: every node; NaN allowed elsewhere).  The Laplace approximation of the latent posterior
         under a softmax likelihood, a classification.MulticlassLaplaceFit (mode, latent samples, class probabilities); kw as
-        classification.laplace_fit_multiclass.  The Gaussian likelihood's noise is not used."""
+        classification.laplace_fit_multiclass.  The Gaussian likelihood's noise is not used.  The fit's latent_samples,
+        predict_proba and latent_variance take block=b to draw b samples per solve (b num_classes <= 256)."""
         from ..classification import laplace_fit_multiclass
         desc, _, y = self._sampling_args()
         return laplace_fit_multiclass(desc, y, num_classes, observed, **kw)

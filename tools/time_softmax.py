@@ -4,9 +4,13 @@ another class) at two output scales: the wall time of the fit with its Newton an
 mgp_softmax_cg, the event times of mgp_softmax_site, of mgp_softmax_hessian_add and of the operator chain on C columns (what
 is left of a step is the update launch and the host's share), and -- in the same process, alternating with the HIP solver --
 the same recurrence restated in torch ops (desc.apply plus row ops, scalars kept on the device, one host read per check_every
-steps).  Prints one JSON line.  Nothing here is an acceptance bar.
+steps).  The block path (mgp_softmax_cg_block, block=): predict_proba(16, seed=3) with block=None and with block=16 in the same
+process, warmed, taking turns; one block solve of 16 posterior right-hand sides at the mode's weights (iterations per sample,
+wall time, time per step issued); and the largest difference between the two estimates of the class probabilities.
+Prints one JSON line.  Nothing here is an acceptance bar.
 
     python tools/time_softmax.py [--reps 5]
+    python tools/time_softmax.py --trace-block        # only warmed block solves at outputscale 1: the program of a kernel trace
 """
 import argparse
 import json
@@ -72,9 +76,24 @@ def _alternate(fns, reps):
     return [float(np.median(t)) for t in ts]
 
 
+BLOCK = 16
+
+
+def _block_rhs(fit, b, seed):
+    """The right-hand sides of the first block of b posterior samples, [n, b, C], as MulticlassLaplaceFit._samples builds them."""
+    from manifold_gp_amd import classification as cl, sampling
+    desc, n = fit.desc, fit.desc.n
+    P = sampling._check_desc(desc)
+    z = sampling._precision_chunk(desc, P, b * C, seed, 0).view(n, b, C)
+    eps = sampling.gmrf_noise(desc.data, b * C, seed, 0, tag=2).view(n, b, C)
+    return z + cl.softmax_noise_factor(fit.pi[:, None, :], eps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--trace-block", action="store_true",
+                    help="run two block solves of 16 samples at outputscale 1 and nothing else (for a kernel trace of a block step)")
     args = ap.parse_args()
     import manifold_gp_amd as mgp
     from manifold_gp_amd import classification as cl
@@ -95,9 +114,16 @@ def main():
     model = RiemannGP(x, y, GaussianLikelihood(1e-2).to(dev), ScaleKernel(kern, 1.0).to(dev)).to(dev)
     desc0, _, _ = model._sampling_args()
     res = dict(tool="time_softmax", n=n, classes=C)
-    for outputscale in (1.0, 100.0):
+    for outputscale in (1.0,) if args.trace_block else (1.0, 100.0):
         desc = desc0.with_(scale=float(desc0.scale) / outputscale)      # the precision of outputscale x the kernel
         fit = cl.laplace_fit_multiclass(desc, y, C, obs)
+        if args.trace_block:
+            rhs = _block_rhs(fit, BLOCK, 3)
+            for _ in range(2):
+                _, its, _ = cl.softmax_cg_solve_block(desc, fit.pi, rhs, tol=1e-5)
+            torch.cuda.synchronize()
+            print(json.dumps(dict(tool="time_softmax", trace_block=True, iterations=its)))
+            return
         r = dict(converged=bool(fit.converged), newton_steps=fit.iterations, cg_iterations=[h[3] for h in fit.history],
                  steps=[h[2] for h in fit.history], max_abs_mode=round(float(fit.mean.abs().max()), 3),
                  fit_wall_ms=round(_wall_ms(lambda: cl.laplace_fit_multiclass(desc, y, C, obs), args.reps), 3))
@@ -124,6 +150,19 @@ def main():
         prob = fit.predict_proba(16, seed=3)
         r["predict_proba_16_wall_ms"] = round(_wall_ms(lambda: fit.predict_proba(16, seed=3), 1), 3)
         r["accuracy_unobserved"] = round(float((prob.argmax(1) == y.long())[~obs].float().mean()), 4)
+        # the block path against the per-sample path of the same tree, warmed, taking turns
+        prob_b = fit.predict_proba(BLOCK, seed=3, block=BLOCK)
+        single_ms, block_ms = _alternate([lambda: fit.predict_proba(BLOCK, seed=3), lambda: fit.predict_proba(BLOCK, seed=3, block=BLOCK)],
+                                         args.reps)
+        rhs = _block_rhs(fit, BLOCK, 3)
+        Xb, its_b, resid_b = cl.softmax_cg_solve_block(desc, pi, rhs, tol=1e-5)
+        solve_b_ms = _wall_ms(lambda: cl.softmax_cg_solve_block(desc, pi, rhs, tol=1e-5), args.reps)
+        steps_b = -(-(max(its_b) + 1) // 8) * 8                          # launches are issued up to the next host read
+        r["block"] = dict(samples=BLOCK, predict_proba_single_ms=round(single_ms, 3), predict_proba_block_ms=round(block_ms, 3),
+                          single_over_block=round(single_ms / block_ms, 3), max_abs_prob_diff=float((prob_b - prob).abs().max()),
+                          accuracy_unobserved=round(float((prob_b.argmax(1) == y.long())[~obs].float().mean()), 4),
+                          solve_iterations=its_b, solve_max_resid=round(max(resid_b), 8), solve_ms=round(solve_b_ms, 3),
+                          steps_issued=steps_b, step_us=round(solve_b_ms * 1e3 / steps_b, 2))
         res["outputscale_%g" % outputscale] = r
     print(json.dumps(res))
 
