@@ -574,6 +574,30 @@ int mgp_bernoulli_site(const float* f, const float* qf, const float* y, const ui
  * MGP_ERR_ARG for null pointers, n < 1 and points even or outside 9 .. 1025. */
 int mgp_bernoulli_predict(const float* mean, const double* var, int64_t n, int points, double* prob, void* stream);
 
+/* Counts at the nodes (csrc/laplace.hip, docs/kernels/counts.md): the likelihood stage of one Newton step of
+ * counts.laplace_fit_counts, with the contract of mgp_bernoulli_site.  f, qf (NULL: zeros), obs (NULL: every node) as there;
+ * y [n] counts and aux [n] are read at observed nodes only (NaN allowed elsewhere).  Per observed node in float64 from the
+ * float32 inputs, eta = f + mean + (family 0 ? aux : 0):
+ *   family 0, Poisson, aux = log-exposure (NULL: zeros):
+ *     mu = exp(min(eta, 700)),   l = y eta - mu,   g = y - mu,   h = mu       (-lgamma(y + 1) is left to the caller)
+ *   family 1, binomial, aux = trials N (NULL: MGP_ERR_ARG), e = exp(-|eta|), d = 1 + e:
+ *     pi = eta >= 0 ? 1 / d : e / d,   1 - pi = eta >= 0 ? e / d : 1 / d,
+ *     l = -(N - y)(max(eta, 0) + log1p(e)) - y (max(-eta, 0) + log1p(e)),   g = y (1 - pi) - (N - y) pi,   h = N e / d^2
+ *                                                                             (log C(N, y) is left to the caller)
+ * (g = h = 0 at unobserved nodes), and
+ *   w_i = (float)(s_ref h_i),   rhs_i = (float)(s_ref (g_i - qf_i)),   both saturated at +-FLT_MAX,
+ *   sums [4] float64 (device) = { sum_obs l,  sum_i f_i qf_i,  max_i |g_i - qf_i|,  sum_i (g_i - qf_i)^2 }.
+ * For finite inputs with |f| <= 1e4 and counts <= 2^24 the first three sums are finite term by term; the fourth may be +inf.
+ * One partial per workgroup and a second launch that adds them: fixed order, no atomics, repeated calls are bitwise equal.
+ * `work`: mgp_count_site_workspace_bytes(n) bytes, 8-byte aligned.  float4 / uchar4 accesses where f, qf, y, aux, w, rhs
+ * are 16-byte and obs 4-byte aligned, scalar ones otherwise.  MGP_ERR_ARG for null f, y, w, rhs or sums and n < 1;
+ * MGP_ERR_UNSUPPORTED for any other family; MGP_ERR_WORKSPACE for a null, misaligned or short `work`.  The checks precede
+ * every launch. */
+size_t mgp_count_site_workspace_bytes(int64_t n);
+int mgp_count_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
+                   double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work, size_t work_bytes,
+                   void* stream);
+
 /* C-class labels with a softmax likelihood (csrc/laplace.hip, csrc/softmax_cg.hip, docs/kernels/classification.md): the kernels of
  * classification.laplace_fit_multiclass.  Blocks are row-major [n, C] float32, 2 <= C <= 64; the C latent functions share the
  * form-0 precision Q2.

@@ -18,6 +18,7 @@ from ._compat import settings
 from . import kernels, operators, utils, models  # noqa: F401
 from . import sampling  # noqa: F401
 from . import classification  # noqa: F401
+from . import counts  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -187,11 +187,13 @@ class LaplaceFit:
         return bernoulli_predict(self.mean, var, points), var
 
 
-def _newton(name, site, q2, solve, zero, f0, rtol, max_newton):
-    """Newton's method with step halving on psi, stated once for both fits.  site(f, qf) -> (aux, rhs, sums) with sums a list
+def _newton(name, site, q2, solve, zero, f0, rtol, max_newton, step_tol=None):
+    """Newton's method with step halving on psi, stated once for every fit.  site(f, qf) -> (aux, rhs, sums) with sums a list
     (the one host read of an evaluation); q2(f) = Q2 f as float32; solve(aux, rhs) -> (delta, CG iterations); zero: the point
     f = 0; f0: the start (None: zero, where Q2 0 = 0 needs no apply).  Stops when sums[2] <= rtol times its value at f = 0;
     a trial point is taken when psi does not decrease beyond _slack, after at most MAX_HALVINGS halvings.
+    step_tol (None: off, the classification fits): an accepted full step with max |delta| <= step_tol ends the iteration as
+    converged too -- the Newton step is the distance to the mode up to its square (counts.py); one more host read per step.
     Returns (f, aux, sums, converged, steps, history)."""
     if f0 is None:
         f = zero
@@ -226,6 +228,9 @@ def _newton(name, site, q2, solve, zero, f0, rtol, max_newton):
         f, aux, rhs, sums = trial
         its += 1
         history.append((_psi(sums), sums[2] / grad0, step, int(cg_its)))
+        if step_tol is not None and step == 1.0 and float(abs(delta).max()) <= step_tol:
+            converged = True
+            break
     if not converged and its >= max_newton:
         warnings.warn("%s: not converged in %d Newton steps (relative gradient %.3g)" % (name, its, sums[2] / grad0))
     return f, aux, sums, converged, its, history

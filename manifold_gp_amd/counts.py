@@ -1,0 +1,282 @@
+"""Count data at the graph nodes: the Laplace approximation of a graph Matern GP with a Poisson or a binomial likelihood
+(docs/kernels/counts.md).
+
+With Q2 the form-0 precision of sampling.py, f the latent function and eta_i = f_i + mean (+ log E_i) the linear predictor,
+
+    poisson:   y_i ~ Poisson(E_i exp(eta_i))            l = y eta - mu,                    g = y - mu,               h = mu
+    binomial:  y_i ~ Binomial(N_i, sigma(eta_i))        l = y log pi + (N - y) log(1 - pi),  g = y (1 - pi) - (N - y) pi,  h = N pi (1 - pi)
+
+at the observed nodes (g = h = 0 elsewhere), the mode of psi(f) = sum_obs l_i - 1/2 f^T Q2 f is found by the Newton loop of
+classification.py (_newton): a step solves (H + Q2) delta = g - Q2 f, which multiplied by s_ref is operator form 3 with
+obs_w = s_ref h and noise = s_ref.  The per-node stage is one kernel (mgp_count_site); Q2 f comes from the float64 chain
+(classification._q2); the solve is the library's Jacobi-preconditioned CG.
+
+s_ref is a power of two fixed once per fit from the data, so one CG plan serves every step and (float)(s_ref h) is the scaled
+correctly rounded h: 2^-ceil(log2 max(1, max y)) for Poisson (h = mu is about y at the mode; at a trial point w may exceed
+1, which nothing in form 3 depends on: the operator, its Jacobi diagonal and the CG take any w >= 0) and 4 * 2^-ceil(log2 max N)
+for the binomial (h <= N / 4, so w <= 1; at N = 1 this is the Bernoulli fit's 4).
+
+The iteration stops by the size of an accepted full Newton step (step_tol), not by the gradient relative to max |g(0)|:
+for counts max |g(0)| is the size of the largest count, and a gradient rule relative to it stops hundreds of times further
+from the mode than the same rule does for 0/1 labels (docs/kernels/counts.md has the numbers).
+
+The Laplace posterior N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets
+f_hat + g / h: CountLaplaceFit restates _pseudo() for the family and inherits latent_variance / latent_samples.
+"""
+import math
+
+import torch
+
+from . import _lib, sampling
+from ._lib import check, lib, ptr, stream
+from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2, bernoulli_predict
+
+FAMILIES = {"poisson": 0, "binomial": 1}
+MAX_COUNT = 2 ** 24          # counts and trials are float32 on the device: integers are exact up to here
+ETA_MAX = 700.0              # mu = exp(min(eta, ETA_MAX)) stays finite in float64
+
+
+def _family(family):
+    if family not in FAMILIES:
+        raise ValueError("family must be one of %s, got %r" % (sorted(FAMILIES), family))
+    return FAMILIES[family]
+
+
+def count_site(f, qf, y, aux, observed, s_ref, mean, family):
+    """(w, rhs, sums) of mgp_count_site: w = s_ref h and rhs = s_ref (g - qf) as fresh float32 [n] tensors (saturated at
+    +-FLT_MAX), sums [4] float64 on the device (sum_obs l without the f-independent constant, sum f qf, max |g - qf|,
+    sum (g - qf)^2).  f, y [n] float32; qf [n] or None (zeros); aux [n]: the log-exposure (family "poisson"; None: zeros) or the
+    trials (family "binomial"); observed [n] bool or None (every node); mean: the constant added to f in the linear predictor."""
+    fam = _family(family)
+    if fam == 1 and aux is None:
+        raise ValueError("the binomial family needs the trials in aux")
+    _lib.require_device(f, qf, y, aux, observed)
+    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
+    n = f.shape[0]
+    qf = None if qf is None else _lib.f32c(qf.reshape(-1))
+    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
+    if observed is not None:
+        if observed.dtype != torch.bool:
+            raise ValueError("observed must be a bool tensor [n]")
+        observed = observed.reshape(-1).contiguous()
+    for name, t in (("qf", qf), ("y", y), ("aux", aux), ("observed", observed)):
+        if t is not None and t.shape[0] != n:
+            raise ValueError("%s has %d entries, f %d" % (name, t.shape[0], n))
+    w, rhs = torch.empty_like(f), torch.empty_like(f)
+    sums = torch.empty(4, dtype=torch.float64, device=f.device)
+    wb = lib().mgp_count_site_workspace_bytes(n)
+    work = _lib.workspace(wb, "count_site", f.device)
+    check(lib().mgp_count_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), fam, ptr(w),
+                               ptr(rhs), ptr(sums), ptr(work), work.numel(), stream()), "mgp_count_site")
+    return w, rhs, sums
+
+
+def _node_vector(t, n, name):
+    if not torch.is_tensor(t) or t.numel() != n or t.dtype == torch.bool:
+        raise ValueError("%s must be a tensor of %d values, got %s" % (name, n, tuple(t.shape) if torch.is_tensor(t) else type(t)))
+    return t.reshape(-1).to(torch.float64)
+
+
+def _real(v, name):
+    """float(v) of a real scalar: a Python or numpy number, or a tensor of one element"""
+    if isinstance(v, (bool, str)) or (torch.is_tensor(v) and (v.numel() != 1 or v.dtype == torch.bool)):
+        raise ValueError("%s must be a real scalar, got %r" % (name, v))
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a real scalar (a number or a tensor of one element), got %s" % (name, type(v).__name__))
+
+
+def _ceil_log2(m):
+    """ceil(log2 m) of an integer m >= 1, exactly"""
+    return (int(m) - 1).bit_length()
+
+
+def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0):
+    """The host-side argument checks of laplace_fit_counts, before any device call.  Returns (y, observed, extra, mean, s_ref)
+    with y and extra (exposure or trials; None: ones) float64 [n] on the device they came on."""
+    sampling._check_desc(desc)
+    fam = _family(family)
+    n = desc.n
+    y = _node_vector(y, n, "y")
+    if observed is not None:
+        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
+            raise ValueError("observed must be a bool tensor [n]")
+        if observed.dim() != 1 or observed.shape[0] != n:
+            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
+        if not bool(observed.any()):
+            raise ValueError("observed selects no node")
+        observed = observed.to(y.device)
+    pick = (lambda t: t) if observed is None else (lambda t: t[observed.to(t.device)])
+    seen = pick(y)
+    if not bool(((seen >= 0) & (seen <= MAX_COUNT) & (seen == seen.round())).all()):
+        raise ValueError("counts at the observed nodes must all be integers in [0, 2^24]")
+    if fam == 0:
+        if trials is not None:
+            raise ValueError("trials belong to the binomial family; the Poisson family takes exposure")
+        extra = None if exposure is None else _node_vector(exposure, n, "exposure")
+        if extra is not None and not bool((torch.isfinite(pick(extra)) & (pick(extra) > 0)).all()):
+            raise ValueError("exposure at the observed nodes must be finite and positive")
+    else:
+        if exposure is not None:
+            raise ValueError("exposure belongs to the Poisson family; the binomial family takes trials")
+        if trials is None:
+            raise ValueError("the binomial family needs trials")
+        extra = _node_vector(trials, n, "trials")
+        N = pick(extra)
+        if not bool(((N >= 1) & (N <= MAX_COUNT) & (N == N.round())).all()):
+            raise ValueError("trials at the observed nodes must all be integers in [1, 2^24]")
+        if not bool((N >= seen.to(N.device)).all()):
+            raise ValueError("trials must be at least the counts at the observed nodes")
+    if mean is not None:
+        mean = _real(mean, "mean")
+        if not math.isfinite(mean):
+            raise ValueError("mean must be finite, got %r" % (mean,))
+    if not _real(step_tol, "step_tol") > 0.0:
+        raise ValueError("step_tol must be positive, got %r" % (step_tol,))
+    if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != n):
+        raise ValueError("f0 must be a tensor of %d latent values" % n)
+    if fam == 0:
+        total = float(seen.sum())
+        if mean is None:
+            if total == 0.0:
+                raise ValueError("every observed count is 0: the intercept-only estimate of the mean is -inf; pass mean=")
+            mean = math.log(total / (float(seen.numel()) if extra is None else float(pick(extra).sum())))
+        s_ref = 2.0 ** -_ceil_log2(max(1.0, float(seen.max())))
+    else:
+        mean = 0.0 if mean is None else mean
+        s_ref = 4.0 * 2.0 ** -_ceil_log2(float(pick(extra).max()))
+    return y, observed, extra, float(mean), s_ref
+
+
+def _site64(family, eta, y, extra):
+    """(g, h) in float64 with the formulas of mgp_count_site; eta already holds the mean (and the log-exposure)."""
+    if family == "poisson":
+        mu = torch.exp(eta.clamp_max(ETA_MAX))
+        return y - mu, mu
+    e = torch.exp(-eta.abs())
+    d = 1.0 + e
+    pi = torch.where(eta >= 0, 1.0 / d, e / d)
+    pib = torch.where(eta >= 0, e / d, 1.0 / d)
+    return y * pib - (extra - y) * pi, extra * e / (d * d)
+
+
+class CountLaplaceFit(LaplaceFit):
+    """The Laplace approximation N(mean, (Q2 + H)^-1) of the latent posterior given counts (laplace_fit_counts).
+    mean [n] float32: the mode f_hat of the latent function (the linear predictor is eta_hat = f_hat + prior_mean, plus the
+    log-exposure inside the Poisson rate); converged, iterations; history: one (psi, relative gradient, step, CG iterations)
+    per Newton step, psi without the likelihood's constant; log_likelihood: sum_obs log p(y_i | eta_hat_i) with the constant
+    (-lgamma(y + 1) or log C(N, y)); family, prior_mean, s_ref; exposure / trials: float64 [n], 1 where none was given
+    (prediction at unobserved nodes is per unit exposure / per trial there)."""
+
+    def __init__(self, desc, y, observed, mean, converged, iterations, history, log_likelihood, family, prior_mean, s_ref,
+                 aux, extra):
+        super().__init__(desc, y, observed, mean, converged, iterations, history, log_likelihood)
+        self.family, self.prior_mean, self.s_ref = family, prior_mean, s_ref
+        self._aux = aux                       # what the kernel read: float32 log-exposure (or None) / float32 trials
+        if family == "poisson":
+            self.exposure, self.trials = extra, None
+        else:
+            self.exposure, self.trials = None, extra
+
+    def eta(self):
+        """f_hat + prior_mean: the linear predictor at the mode without the exposure, float64 [n]."""
+        return self.mean.double() + self.prior_mean
+
+    def _pseudo(self):
+        """(pseudo-targets f_hat + g / h, pseudo-noise 1 / h, obs_eff) in float64 from the mode, with the family's g and h;
+        entries outside obs_eff are 0 and 1."""
+        f = self.mean.double()
+        obs = torch.ones_like(f, dtype=torch.bool) if self.observed is None else self.observed
+        y = torch.where(obs, self.y.double(), torch.zeros_like(f))
+        if self.family == "poisson":                      # (_aux is finite at every node: laplace_fit_counts)
+            g, h = _site64(self.family, self.eta() if self._aux is None else self.eta() + self._aux.double(), y, None)
+        else:
+            g, h = _site64(self.family, self.eta(), y, self._aux.double())
+        eff = obs & (h >= H_FLOOR)
+        if not bool(eff.any()):
+            raise RuntimeError("no observed node has a curvature above %g: the latent values have run away" % H_FLOOR)
+        one, zero = torch.ones((), dtype=f.dtype, device=f.device), torch.zeros((), dtype=f.dtype, device=f.device)
+        noise = torch.where(eff, 1.0 / h.clamp_min(H_FLOOR), one)
+        targets = torch.where(eff, f + g * noise, zero)
+        return targets, noise, eff
+
+    def map_proba(self):
+        raise NotImplementedError("a count fit has no class probability: see map_mean and predict_mean")
+
+    def predict_proba(self, *a, **kw):
+        raise NotImplementedError("a count fit has no class probability: see map_mean and predict_mean")
+
+    def map_mean(self):
+        """E exp(eta_hat) (Poisson) or N sigma(eta_hat) (binomial): the expected count at the mode, [n] float64 (ignores the
+        latent variance)."""
+        if self.family == "poisson":
+            return self.exposure * torch.exp(self.eta())
+        return self.trials * torch.sigmoid(self.eta())
+
+    def predict_mean(self, S=64, seed=None, points=129):
+        """(mean, var, latent_var): the mean and the variance of a new count at every node under the Laplace posterior, and the
+        latent marginal variance v they used (latent_variance(S, seed)[0]); float64 [n] each.
+        Poisson, in closed form (the rate is log-normal): m = E exp(eta_hat + v / 2), var = m + m^2 (e^v - 1).
+        Binomial: p = int sigma(eta) N(eta; eta_hat, v) d eta by the trapezoid rule of bernoulli_predict (eta_hat as float32, the
+        kernel's input format), mean = N p, var = N p (1 - p): the variance of a draw with the success probability p."""
+        points = _points(points)
+        v = self.latent_variance(S, seed)[0]
+        if self.family == "poisson":
+            m = self.exposure * torch.exp(self.eta() + 0.5 * v)
+            return m, m + m * m * torch.expm1(v), v
+        p = bernoulli_predict(self.eta().float(), v, points)
+        return self.trials * p, self.trials * p * (1.0 - p), v
+
+
+def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, trials=None, mean=None, step_tol=1e-3,
+                       max_newton=30, cg_tol=1e-3, max_iter=5000, f0=None):
+    """The mode of the latent posterior given counts y [n] at the observed nodes (bool [n]; None: every node; counts at the
+    other nodes are not read and may be NaN), by Newton's method with step halving: CountLaplaceFit.
+    family "poisson": y_i ~ Poisson(exposure_i exp(f_i + mean)); exposure [n] finite and positive at the observed nodes (None:
+    ones); mean: the constant prior mean of the linear predictor, default log(sum_obs y / sum_obs exposure), the
+    intercept-only maximum-likelihood estimate.  family "binomial": y_i ~ Binomial(trials_i, sigma(f_i + mean)); trials [n]
+    integers >= max(1, y_i) at the observed nodes; mean defaults to 0.  Counts and trials are integers up to 2^24.
+    Exposure / trials at unobserved nodes are used by predict_mean where they are valid and count as 1 elsewhere.
+    desc: a form-0 precision descriptor as the samplers take.  Stops after an accepted full Newton step with
+    max |delta| <= step_tol; every step is a form-3 CG solve to the relative residual cg_tol.  f0 [n]: the start (default 0)."""
+    from .solvers import cg_solve
+    y, observed, extra, mean, s_ref = _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0)
+    _lib.require_device(y, f0, extra)
+    dev = desc.data.graph.device
+    n = desc.n
+    y = y.to(dev)
+    obs = None if observed is None else observed.to(dev).contiguous()
+    seen = torch.ones(n, dtype=torch.bool, device=dev) if obs is None else obs
+    one, zero = torch.ones((), dtype=torch.float64, device=dev), torch.zeros((), dtype=torch.float64, device=dev)
+    y = torch.where(seen, y, zero)                        # (NaN at unobserved nodes: never read, dropped here)
+    if extra is None:
+        extra, aux = torch.ones(n, dtype=torch.float64, device=dev), None
+    else:
+        extra = extra.to(dev)
+        valid = torch.isfinite(extra) & (extra > 0) if family == "poisson" else (extra >= 1) & (extra == extra.round())
+        extra = torch.where(seen | valid, extra, one)
+        aux = (extra.log() if family == "poisson" else extra).float().contiguous()
+    if family == "poisson":
+        const = -float(torch.lgamma(y[seen] + 1.0).sum())
+    else:
+        N = extra[seen]
+        const = float((torch.lgamma(N + 1.0) - torch.lgamma(y[seen] + 1.0) - torch.lgamma(N - y[seen] + 1.0)).sum())
+    y32 = y.float().contiguous()
+
+    def site(f, qf):
+        w, rhs, sums = count_site(f, qf, y32, aux, obs, s_ref, mean, family)
+        return w, rhs, sums.tolist()                      # the one host read of an evaluation
+
+    def solve(w, rhs):
+        # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
+        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=s_ref, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
+                                    jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
+        return delta, cg_its
+
+    with torch.no_grad():
+        start = None if f0 is None else _lib.f32c(f0.to(dev).reshape(-1))
+        f, _, sums, converged, its, history = _newton("laplace_fit_counts", site, lambda v: _q2(desc, v), solve,
+                                                      torch.zeros(n, dtype=torch.float32, device=dev), start, 0.0, max_newton,
+                                                      step_tol=float(step_tol))
+    return CountLaplaceFit(desc, y32, obs, f, converged, its, history, sums[0] + const, family, mean, s_ref, aux, extra)

@@ -23,6 +23,14 @@
 //    xor tree: 1 - pi_t cancels where pi_t -> 1), 0 elsewhere, rhs = G - qf.  The
 //    label is only compared with the lane's class, never used as an index.  The four sums leave through SiteAcc, block_reduce
 //    and bernoulli_site_sum_kernel as above.
+//
+// 4. mgp_count_site: the likelihood stage of a count fit (counts.laplace_fit_counts, docs/kernels/counts.md), the layout and
+//    the sums of kernel 1 with one more input array.  eta = f + mean (+ log-exposure); Poisson: mu = exp(min(eta, 700)),
+//    l = y eta - mu, g = y - mu, h = mu; binomial with N trials: e = exp(-|eta|), l = -(N - y)(max(eta, 0) + log1p(e))
+//    - y (max(-eta, 0) + log1p(e)), g = y (1 - pi) - (N - y) pi with 1 - pi formed without the subtraction, h = N e / (1 + e)^2.
+//    h is unbounded here: w and rhs saturate at +-FLT_MAX instead of leaving as inf.
+#include <cfloat>
+
 #include "mgp_common.h"
 #include "mgp_internal.h"
 #include "softmax_rows.h"
@@ -190,6 +198,97 @@ __global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* 
   }
 }
 
+// a float64 result as float32, +-FLT_MAX where the cast would leave as inf (NaN stays NaN)
+__device__ __forceinline__ float sat_f32(double v) {
+  const double m = (double)FLT_MAX;
+  return (float)(v > m ? m : (v < -m ? -m : v));
+}
+
+// one node of mgp_count_site.  FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials
+template <int FAMILY>
+__device__ __forceinline__ void count_node(float f32, float qf32, float y32, float a32, bool obs, double s_ref, double mean,
+                                           float& w, float& rhs, SiteAcc& acc) {
+  const double f = (double)f32, qf = (double)qf32;
+  double g = 0.0, h = 0.0;
+  if (obs) {
+    const double y = (double)y32;
+    if (FAMILY == 0) {
+      const double eta = f + mean + (double)a32;
+      const double mu = exp(eta < 700.0 ? eta : 700.0);
+      acc.lp += y * eta - mu;
+      g = y - mu;
+      h = mu;
+    } else {
+      const double eta = f + mean;
+      const double N = (double)a32;
+      const double m = N - y;                                          // failures: exact, both are integers <= 2^24
+      const double e = exp(-fabs(eta));
+      const double d = 1.0 + e;
+      const double l1 = log1p(e);
+      const double pi = eta >= 0.0 ? 1.0 / d : e / d;
+      const double pib = eta >= 0.0 ? e / d : 1.0 / d;                 // 1 - pi without the subtraction
+      acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
+      g = y * pib - m * pi;
+      h = N * e / (d * d);
+    }
+  }
+  const double r = g - qf;
+  w = sat_f32(s_ref * h);
+  rhs = sat_f32(s_ref * r);
+  acc.fq += f * qf;
+  const double ar = fabs(r);
+  acc.mx = ar > acc.mx ? ar : acc.mx;
+  acc.sq += r * r;
+}
+
+// the layout of bernoulli_site_kernel with one more input: aux (NULL: zeros), read like y where a node of the quad is observed
+template <bool VEC4, int FAMILY>
+__global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
+                                                            const float* __restrict__ y, const float* __restrict__ aux,
+                                                            const uint8_t* __restrict__ obs, int64_t n, double s_ref,
+                                                            double mean, float* __restrict__ w, float* __restrict__ rhs,
+                                                            double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : zero;
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : zero;
+      const float4 av = (any && aux) ? *reinterpret_cast<const float4*>(aux + i0) : zero;
+      float4 wv, rv;
+      count_node<FAMILY>(fv.x, qv.x, yv.x, av.x, ov.x != 0, s_ref, mean, wv.x, rv.x, acc);
+      count_node<FAMILY>(fv.y, qv.y, yv.y, av.y, ov.y != 0, s_ref, mean, wv.y, rv.y, acc);
+      count_node<FAMILY>(fv.z, qv.z, yv.z, av.z, ov.z != 0, s_ref, mean, wv.z, rv.z, acc);
+      count_node<FAMILY>(fv.w, qv.w, yv.w, av.w, ov.w != 0, s_ref, mean, wv.w, rv.w, acc);
+      *reinterpret_cast<float4*>(w + i0) = wv;
+      *reinterpret_cast<float4*>(rhs + i0) = rv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float wi, ri;
+        count_node<FAMILY>(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, s_ref, mean, wi, ri, acc);
+        w[i] = wi;
+        rhs[i] = ri;
+      }
+    }
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
 template <int TC>
 __global__ __launch_bounds__(kBlock) void softmax_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
                                                               const int32_t* __restrict__ labels,
@@ -271,6 +370,38 @@ extern "C" int mgp_bernoulli_site(const float* f, const float* qf, const float* 
                        obs, n, s_ref, w, rhs, partials);
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_count_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
+                              double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work,
+                              size_t work_bytes, void* stream) {
+  if (!f || !y || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
+  if (family != 0 && family != 1) return MGP_ERR_UNSUPPORTED;
+  if (family == 1 && !aux) return MGP_ERR_ARG;                         // the trials have no default
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_count_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) &&
+                    aligned_to(w, 16) && aligned_to(rhs, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (family == 0) {
+    if (vec4)
+      hipLaunchKernelGGL((count_site_kernel<true, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+    else
+      hipLaunchKernelGGL((count_site_kernel<false, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+  } else {
+    if (vec4)
+      hipLaunchKernelGGL((count_site_kernel<true, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+    else
+      hipLaunchKernelGGL((count_site_kernel<false, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+  }
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

@@ -168,6 +168,16 @@ class RiemannGP(torch.nn.Module):
         desc, _, y = self._sampling_args()
         return laplace_fit_multiclass(desc, y, num_classes, observed, **kw)
 
+    def laplace_posterior_counts(self, observed=None, **kw):
+        """Counts at the graph nodes: train_targets are counts, read at `observed` (bool [N]; None: every node; NaN allowed
+        elsewhere).  The Laplace approximation of the latent posterior under a Poisson (with exposure=) or a binomial (with
+        trials=) likelihood, a counts.CountLaplaceFit (mode, latent variances and samples, predicted counts); kw as
+        counts.laplace_fit_counts (family, exposure, trials, mean, step_tol, ...).  The Gaussian likelihood's noise is not
+        used."""
+        from ..counts import laplace_fit_counts
+        desc, _, y = self._sampling_args()
+        return laplace_fit_counts(desc, y, observed, **kw)
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)
