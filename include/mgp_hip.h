@@ -598,6 +598,30 @@ int mgp_count_site(const float* f, const float* qf, const float* y, const float*
                    double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work, size_t work_bytes,
                    void* stream);
 
+/* The Laplace evidence at the mode (csrc/laplace.hip, docs/kernels/evidence.md): the per-node stage of
+ * evidence.laplace_evidence.  f [n] the mode, y, aux, obs as mgp_count_site (read in quads that hold an observed node only; NaN
+ * allowed elsewhere); family 0 Poisson, 1 binomial, 2 Bernoulli-logit (class 1 where y > 0.5 as mgp_bernoulli_site; aux is not
+ * read); var [n] float64 the latent marginal variances diag((Q2 + H)^-1), nullable.  Per observed node in float64 from the float32
+ * inputs, eta, l and h as mgp_count_site (family 2: one trial), and h' = dh / df:
+ *   Poisson  h' = mu;     binomial, Bernoulli  h' = h ((1 - pi) - pi),  (1 - pi) - pi = -+(-expm1(-|eta|)) / (1 + e)  (- for eta >= 0)
+ * and, on the observed nodes with h >= h_floor (0 at every other node),
+ *   root_h_i = (float) sqrt(h_i),   corr_i = (float)(var_i h'_i),   both saturated at +-FLT_MAX;
+ *   sums [4] float64 (device) = { sum_obs l,  m = nodes kept,  sum_i corr_i,  max_i |corr_i| }   (corr before the float cast).
+ * corr is not written, and sums 2 and 3 are 0, when var or corr is NULL.  One partial per workgroup and the second launch of
+ * mgp_bernoulli_site: fixed order, no atomics, repeated calls are bitwise equal.  `work`:
+ * mgp_laplace_evidence_site_workspace_bytes(n) bytes, 8-byte aligned.  float4 / uchar4 / double2 accesses where f, y, aux,
+ * var, root_h, corr are 16-byte and obs 4-byte aligned, scalar ones otherwise.  MGP_ERR_ARG for null f, y, root_h or sums, n < 1,
+ * h_floor negative or NaN and family 1 without aux; MGP_ERR_UNSUPPORTED for any other family; MGP_ERR_WORKSPACE for a null,
+ * misaligned or short `work`.  The checks precede every launch. */
+size_t mgp_laplace_evidence_site_workspace_bytes(int64_t n);
+int mgp_laplace_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var, int64_t n,
+                              double mean, int family, double h_floor, float* root_h, float* corr, double* sums, void* work,
+                              size_t work_bytes, void* stream);
+/* Row scaling of a row-major [n, P] float32 block, 1 <= P <= 256:  out_ij = s_i V_ij  (X NULL)  or  fmaf(s_i, X_ij, V_ij).
+ * out may be V or X.  float4 accesses where P % 4 == 0 and V, X, out are 16-byte aligned.  MGP_ERR_ARG for null s, V or out,
+ * n < 1 and P outside 1 .. 256. */
+int mgp_scale_rows(const float* s, const float* V, const float* X, int64_t n, int P, float* out, void* stream);
+
 /* C-class labels with a softmax likelihood (csrc/laplace.hip, csrc/softmax_cg.hip, docs/kernels/classification.md): the kernels of
  * classification.laplace_fit_multiclass.  Blocks are row-major [n, C] float32, 2 <= C <= 64; the C latent functions share the
  * form-0 precision Q2.

@@ -19,6 +19,7 @@ from . import kernels, operators, utils, models  # noqa: F401
 from . import sampling  # noqa: F401
 from . import classification  # noqa: F401
 from . import counts  # noqa: F401
+from . import evidence  # noqa: F401
 
 __version__ = "0.1.0"
 

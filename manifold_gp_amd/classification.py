@@ -186,6 +186,12 @@ class LaplaceFit:
         var = self.latent_variance(S, seed)[0]
         return bernoulli_predict(self.mean, var, points), var
 
+    def evidence(self, **kw):
+        """The Laplace approximation of log p(y) at this mode, an evidence.LaplaceEvidence; kw as evidence.laplace_evidence
+        (operator= for the hyper-parameter gradient, num_probes, steps, seed, method, ...)."""
+        from .evidence import laplace_evidence
+        return laplace_evidence(self, **kw)
+
 
 def _newton(name, site, q2, solve, zero, f0, rtol, max_newton, step_tol=None):
     """Newton's method with step halving on psi, stated once for every fit.  site(f, qf) -> (aux, rhs, sums) with sums a list
@@ -502,6 +508,9 @@ class MulticlassLaplaceFit:
     def map_proba(self):
         """softmax(mean) row by row: the class probabilities at the mode, [n, C] float64 (ignores the latent variance)."""
         return torch.softmax(self.mean.double(), dim=-1)
+
+    def evidence(self, **kw):
+        raise NotImplementedError("the Laplace evidence of the softmax fit is not built: see docs/scope.md")
 
     def _samples(self, S, seed, tol, max_iter, block=None):
         """Sample s = 0 .. S - 1 as [n, C] float32: one at a time (block None), or drawn `block` per solve (views into the

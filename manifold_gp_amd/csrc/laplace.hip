@@ -29,6 +29,13 @@
 //    l = y eta - mu, g = y - mu, h = mu; binomial with N trials: e = exp(-|eta|), l = -(N - y)(max(eta, 0) + log1p(e))
 //    - y (max(-eta, 0) + log1p(e)), g = y (1 - pi) - (N - y) pi with 1 - pi formed without the subtraction, h = N e / (1 + e)^2.
 //    h is unbounded here: w and rhs saturate at +-FLT_MAX instead of leaving as inf.
+//
+// 5. mgp_laplace_evidence_site: the per-node stage of the Laplace evidence at the mode (evidence.laplace_evidence,
+//    docs/kernels/evidence.md), the layout of kernel 4 for the three families: sqrt(h) and var h' (h' = dh / df) on the observed
+//    nodes with h >= h_floor, 0 elsewhere, and the sums { sum_obs l, nodes kept, sum corr, max |corr| } through the same partials.
+//
+// 6. mgp_scale_rows: out = s_i V_ij or fmaf(s_i, X_ij, V_ij) on row-major [n, P] blocks: the two row scalings around the solve in a
+//    product with B = I + S Q2^-1 S.  Both are bandwidth-trivial and launch-bound at 60k nodes.
 #include <cfloat>
 
 #include "mgp_common.h"
@@ -151,9 +158,10 @@ __global__ __launch_bounds__(kBlock) void bernoulli_site_kernel(const float* __r
   }
 }
 
-// sums[4] from the partials of `nblk` workgroups: thread t takes partials t, t + 256, ... in order, then the same tree
+// sums[4] from the partials of `nblk` workgroups: thread t takes partials t, t + 256, ... in order, then the same tree.
+// sum_first: the sum slot leaves before the max slot (mgp_laplace_evidence_site: { .., sum corr, max |corr| })
 __global__ __launch_bounds__(kBlock) void bernoulli_site_sum_kernel(const double* __restrict__ partials, int nblk,
-                                                                    double* __restrict__ sums) {
+                                                                    double* __restrict__ sums, bool sum_first = false) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nblk; b += kBlock) {
     const double* p = partials + 4 * (int64_t)b;
@@ -166,8 +174,8 @@ __global__ __launch_bounds__(kBlock) void bernoulli_site_sum_kernel(const double
   if (threadIdx.x == 0) {
     sums[0] = r.lp;
     sums[1] = r.fq;
-    sums[2] = r.mx;
-    sums[3] = r.sq;
+    sums[2] = sum_first ? r.sq : r.mx;
+    sums[3] = sum_first ? r.mx : r.sq;
   }
 }
 
@@ -289,6 +297,137 @@ __global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restr
   }
 }
 
+// one node of mgp_laplace_evidence_site at the mode.  FAMILY 0: Poisson (a32 the log-exposure), 1: binomial (a32 the trials),
+// 2: Bernoulli-logit (one trial, y the label).  acc: lp = sum l, fq = nodes kept, sq = sum corr, mx = max |corr|
+template <int FAMILY>
+__device__ __forceinline__ void evidence_node(float f32, float y32, float a32, bool obs, double var, bool has_var, double mean,
+                                              double h_floor, float& root, float& corr, SiteAcc& acc) {
+  root = 0.f;
+  corr = 0.f;
+  if (!obs) return;
+  double h, hp;
+  if (FAMILY == 0) {
+    const double y = (double)y32;
+    const double eta = (double)f32 + mean + (double)a32;
+    const double mu = exp(eta < 700.0 ? eta : 700.0);
+    acc.lp += y * eta - mu;
+    h = mu;
+    hp = mu;
+  } else {
+    const double eta = (double)f32 + mean;
+    const double N = FAMILY == 1 ? (double)a32 : 1.0;
+    const double y = FAMILY == 1 ? (double)y32 : (y32 > 0.5f ? 1.0 : 0.0);
+    const double m = N - y;
+    const double e = exp(-fabs(eta));
+    const double d = 1.0 + e;
+    const double l1 = log1p(e);
+    acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
+    h = N * e / (d * d);
+    const double gap = -expm1(-fabs(eta)) / d;                         // |(1 - pi) - pi| = (1 - e) / (1 + e), no cancellation
+    hp = h * (eta >= 0.0 ? -gap : gap);
+  }
+  if (!(h >= h_floor)) return;
+  acc.fq += 1.0;
+  root = sat_f32(sqrt(h));
+  if (has_var) {
+    const double m = (double)FLT_MAX;
+    double c = var * hp;
+    c = c > m ? m : (c < -m ? -m : c);
+    corr = (float)c;
+    acc.sq += c;
+    const double ac = fabs(c);
+    acc.mx = ac > acc.mx ? ac : acc.mx;
+  }
+}
+
+// the layout of count_site_kernel; var (NULL: no corr) is float64, two double2 per quad on the vector path
+template <bool VEC4, int FAMILY>
+__global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __restrict__ f, const float* __restrict__ y,
+                                                               const float* __restrict__ aux, const uint8_t* __restrict__ obs,
+                                                               const double* __restrict__ var, int64_t n, double mean,
+                                                               double h_floor, float* __restrict__ root_h,
+                                                               float* __restrict__ corr, double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const bool has_var = var != nullptr && corr != nullptr;
+  const int64_t nq = (n + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : zero;
+      const float4 av = (any && aux) ? *reinterpret_cast<const float4*>(aux + i0) : zero;
+      double2 v0 = make_double2(0.0, 0.0), v1 = v0;
+      if (has_var && any) {
+        v0 = *reinterpret_cast<const double2*>(var + i0);
+        v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
+      }
+      float4 rv, cv;
+      evidence_node<FAMILY>(fv.x, yv.x, av.x, ov.x != 0, v0.x, has_var, mean, h_floor, rv.x, cv.x, acc);
+      evidence_node<FAMILY>(fv.y, yv.y, av.y, ov.y != 0, v0.y, has_var, mean, h_floor, rv.y, cv.y, acc);
+      evidence_node<FAMILY>(fv.z, yv.z, av.z, ov.z != 0, v1.x, has_var, mean, h_floor, rv.z, cv.z, acc);
+      evidence_node<FAMILY>(fv.w, yv.w, av.w, ov.w != 0, v1.y, has_var, mean, h_floor, rv.w, cv.w, acc);
+      *reinterpret_cast<float4*>(root_h + i0) = rv;
+      if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float ri, ci;
+        evidence_node<FAMILY>(f[i], o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, (o && has_var) ? var[i] : 0.0, has_var, mean,
+                              h_floor, ri, ci, acc);
+        root_h[i] = ri;
+        if (has_var) corr[i] = ci;
+      }
+    }
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
+constexpr int kScaleMaxBlocks = 2048;     // grid cap of mgp_scale_rows: 2048 x 256 threads x 4 (or 1) entries per step
+
+// out = s_i V_ij, or fmaf(s_i, X_ij, V_ij): one entry (or one float4 inside a row, P % 4 == 0) per thread and step.  out may be
+// V or X: an entry is read before it is written, by the same thread.
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void scale_rows_kernel(const float* __restrict__ s, const float* V, const float* X,
+                                                            int64_t n, int P, float* out) {
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t start = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (VEC4) {
+    const int P4 = P >> 2;
+    const int64_t total = n * P4;
+    for (int64_t q = start; q < total; q += stride) {
+      const float si = s[q / P4];
+      const float4 v = reinterpret_cast<const float4*>(V)[q];
+      float4 o;
+      if (X) {
+        const float4 x = reinterpret_cast<const float4*>(X)[q];
+        o = make_float4(fmaf(si, x.x, v.x), fmaf(si, x.y, v.y), fmaf(si, x.z, v.z), fmaf(si, x.w, v.w));
+      } else {
+        o = make_float4(si * v.x, si * v.y, si * v.z, si * v.w);
+      }
+      reinterpret_cast<float4*>(out)[q] = o;
+    }
+  } else {
+    const int64_t total = n * P;
+    for (int64_t e = start; e < total; e += stride) {
+      const float si = s[e / P];
+      const float v = V[e];
+      out[e] = X ? fmaf(si, X[e], v) : si * v;
+    }
+  }
+}
+
 template <int TC>
 __global__ __launch_bounds__(kBlock) void softmax_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
                                                               const int32_t* __restrict__ labels,
@@ -369,7 +508,7 @@ extern "C" int mgp_bernoulli_site(const float* f, const float* qf, const float* 
     hipLaunchKernelGGL(bernoulli_site_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), f, qf, y,
                        obs, n, s_ref, w, rhs, partials);
   MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums);
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums, false);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }
@@ -401,7 +540,54 @@ extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, c
       hipLaunchKernelGGL((count_site_kernel<false, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
   }
   MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums);
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_laplace_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_laplace_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
+                                         int64_t n, double mean, int family, double h_floor, float* root_h, float* corr,
+                                         double* sums, void* work, size_t work_bytes, void* stream) {
+  if (!f || !y || !root_h || !sums || n < 1 || !(h_floor >= 0.0)) return MGP_ERR_ARG;
+  if (family < 0 || family > 2) return MGP_ERR_UNSUPPORTED;
+  if (family == 1 && !aux) return MGP_ERR_ARG;                         // the trials have no default
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_laplace_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  if (family == 2) aux = nullptr;                                      // the Bernoulli family takes none
+  if (!var || !corr) var = nullptr, corr = nullptr;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
+                    aligned_to(root_h, 16) && aligned_to(corr, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+#define MGP_EVIDENCE_LAUNCH(V, F) \
+  hipLaunchKernelGGL((evidence_site_kernel<V, F>), grid, block, 0, st, f, y, aux, obs, var, n, mean, h_floor, root_h, corr, partials)
+  if (family == 0) {
+    if (vec4) MGP_EVIDENCE_LAUNCH(true, 0); else MGP_EVIDENCE_LAUNCH(false, 0);
+  } else if (family == 1) {
+    if (vec4) MGP_EVIDENCE_LAUNCH(true, 1); else MGP_EVIDENCE_LAUNCH(false, 1);
+  } else {
+    if (vec4) MGP_EVIDENCE_LAUNCH(true, 2); else MGP_EVIDENCE_LAUNCH(false, 2);
+  }
+#undef MGP_EVIDENCE_LAUNCH
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" int mgp_scale_rows(const float* s, const float* V, const float* X, int64_t n, int P, float* out, void* stream) {
+  if (!s || !V || !out || n < 1 || P < 1 || P > 256) return MGP_ERR_ARG;
+  const bool vec4 = (P & 3) == 0 && aligned_to(V, 16) && aligned_to(X, 16) && aligned_to(out, 16);
+  const int64_t work = vec4 ? n * (P >> 2) : n * (int64_t)P;
+  int64_t blocks = mgp_cdiv(work, (int64_t)kBlock);
+  if (blocks > kScaleMaxBlocks) blocks = kScaleMaxBlocks;
+  if (vec4)
+    hipLaunchKernelGGL(scale_rows_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), s, V, X, n, P, out);
+  else
+    hipLaunchKernelGGL(scale_rows_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), s, V, X, n, P, out);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }
@@ -422,7 +608,7 @@ extern "C" int mgp_softmax_site(const float* f, const float* qf, const int32_t* 
                        n, C, pi, rhs, partials);
   });
   MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums);
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

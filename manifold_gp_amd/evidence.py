@@ -1,0 +1,313 @@
+"""The Laplace evidence of the node fits and its hyper-parameter gradient (docs/kernels/evidence.md).
+
+With Q the form-0 precision, f the mode of a LaplaceFit / CountLaplaceFit, h = -l''(f) and h' = dh / df (0 off the observed
+nodes), A = Q + H, S = diag(sqrt h) and m the observed nodes with h >= H_FLOOR,
+
+    log Z ~= sum_obs l_i(f) - 1/2 f^T Q f - 1/2 logdet B,      B = I + S Q^-1 S,      logdet B = logdet A - logdet Q.
+
+B is the identity off the m nodes and well conditioned where Q is not, so logdet B is Lanczos quadrature on B itself with
+Rademacher probes that live on the m nodes (logdet_b, method "slq"), or, for small m, the float64 Cholesky of the m x m block
+(method "dense").  A product B V = V + s o Q^-1 (s o V) is one multi-column cg_solve between two mgp_scale_rows launches.
+
+For a kernel hyper-parameter theta with Q' = dQ / d theta (the likelihood's mean, exposure and trials held fixed)
+
+    d log Z / d theta = -1/2 f^T Q' f + 1/2 u^T Q' f + 1/(2 P) sum_p x_p^T Q' y_p
+    u = A^-1 (v o h'),  v = diag(A^-1),      X = Q^-1 (s o Z),  Y = A^-1 (s o Z),  Z the probes
+
+every term a bilinear form in Q(theta) between detached vectors: one differentiable operator.matmul of the block [f | Y],
+added to the value as sur - sur.detach() the way solvers.inv_quad_logdet does.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, sampling
+from ._lib import check, lib, ptr, stream
+from .classification import H_FLOOR, S_REF
+
+FAMILIES = {"poisson": 0, "binomial": 1, "bernoulli": 2}
+DENSE_MAX = 512           # method "auto": the m x m Cholesky up to here
+MAX_COLUMNS = sampling.CHUNK
+
+
+def _family(family):
+    if family not in FAMILIES:
+        raise ValueError("family must be one of %s, got %r" % (sorted(FAMILIES), family))
+    return FAMILIES[family]
+
+
+def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR):
+    """(root_h, corr, sums) of mgp_laplace_evidence_site at the mode f [n] float32: root_h = sqrt(h) and corr = variance h' as
+    fresh float32 [n] tensors (0 off the observed nodes with h >= h_floor; corr None when variance is None), sums [4] float64 on
+    the device (sum_obs l without the f-independent constant, m = nodes kept, sum corr, max |corr|).  y [n]; aux [n]: the
+    log-exposure (family "poisson"; None: zeros) or the trials ("binomial"); family "bernoulli" reads y as labels and takes no
+    aux; observed [n] bool or None (every node); variance [n] (taken as float64) or None; mean: the constant of the linear
+    predictor."""
+    fam = _family(family)
+    if fam == 1 and aux is None:
+        raise ValueError("the binomial family needs the trials in aux")
+    if fam == 2 and aux is not None:
+        raise ValueError("the bernoulli family takes no aux")
+    if not float(h_floor) >= 0.0:
+        raise ValueError("h_floor must be >= 0, got %r" % (h_floor,))
+    for name, t in (("f", f), ("y", y)):
+        if not torch.is_tensor(t):
+            raise ValueError("%s must be a tensor [n]" % name)
+    n = f.numel()
+    if observed is not None and (not torch.is_tensor(observed) or observed.dtype != torch.bool):
+        raise ValueError("observed must be a bool tensor [n]")
+    for name, t in (("y", y), ("aux", aux), ("observed", observed), ("variance", variance)):
+        if t is not None and (not torch.is_tensor(t) or t.numel() != n):
+            raise ValueError("%s has %s entries, f %d" % (name, t.numel() if torch.is_tensor(t) else type(t), n))
+    if n < 1:
+        raise ValueError("f has no entries")
+    _lib.require_device(f, y, aux, observed, variance)
+    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
+    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
+    observed = None if observed is None else observed.reshape(-1).contiguous()
+    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
+    root_h = torch.empty_like(f)
+    corr = None if variance is None else torch.empty_like(f)
+    sums = torch.empty(4, dtype=torch.float64, device=f.device)
+    wb = lib().mgp_laplace_evidence_site_workspace_bytes(n)
+    work = _lib.workspace(wb, "evidence_site", f.device)
+    check(lib().mgp_laplace_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), fam,
+                                          float(h_floor), ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),
+          "mgp_laplace_evidence_site")
+    return root_h, corr, sums
+
+
+def scale_rows(s, V, X=None, out=None):
+    """out = s_i V_ij (X None) or fmaf(s_i, X_ij, V_ij) on float32 blocks [n, P], P <= 256 (mgp_scale_rows).  s [n]; V, X, out
+    contiguous float32 [n, P]; out (default: a fresh tensor) may be V or X.  Returns out."""
+    if not torch.is_tensor(V) or V.dim() != 2 or V.dtype != torch.float32 or not V.is_contiguous():
+        raise ValueError("V must be a contiguous float32 tensor [n, P]")
+    n, P = V.shape
+    if n < 1 or not 1 <= P <= MAX_COLUMNS:
+        raise ValueError("V is [%d, %d]: n >= 1 and 1 <= P <= %d" % (n, P, MAX_COLUMNS))
+    if not torch.is_tensor(s) or s.numel() != n:
+        raise ValueError("s must be a tensor of %d row factors" % n)
+    for name, t in (("X", X), ("out", out)):
+        if t is not None and (not torch.is_tensor(t) or t.shape != V.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous float32 tensor [%d, %d]" % (name, n, P))
+    _lib.require_device(s, V, X, out)
+    s = _lib.f32c(s.reshape(-1))
+    out = torch.empty_like(V) if out is None else out
+    check(lib().mgp_scale_rows(ptr(s), ptr(V), ptr(X), n, P, ptr(out), stream()), "mgp_scale_rows")
+    return out
+
+
+class _BOperator:
+    """V -> B V = V + s o Q^-1 (s o V): the `matmul` the generic block Lanczos calls.  Counts its solves' CG iterations."""
+
+    def __init__(self, desc, root_h, solve_tol, max_iter):
+        self.desc, self.s = desc, root_h
+        self.kw = dict(tol=float(solve_tol), stop_mode=1, max_iter=int(max_iter))
+        self.shape = (desc.n, desc.n)
+        self.solves = self.iterations = 0
+        self._rhs = None
+
+    def solve(self, V):
+        """Q^-1 V as a fresh float32 tensor"""
+        from .solvers import cg_solve
+        X, its, _ = cg_solve(self.desc, V, **self.kw)
+        self.solves += 1
+        self.iterations += int(its)
+        return _lib.f32c(X)
+
+    def matmul(self, V):
+        # s o V lands in one buffer kept between the steps, the second scaling overwrites the solve's own result: the two
+        # launches allocate nothing
+        V = _lib.f32c(V)
+        if self._rhs is None or self._rhs.shape != V.shape:
+            self._rhs = torch.empty_like(V)
+        X = self.solve(scale_rows(self.s, V, out=self._rhs))
+        if X.data_ptr() == self._rhs.data_ptr():          # (a solve that handed its input back: never the case today)
+            X = X.clone()
+        return scale_rows(self.s, V, X, out=X)
+
+
+def effective_probes(root_h, num_probes, seed):
+    """[n, num_probes] float32 on root_h's device: +-1 from a seeded CPU generator on the nodes with root_h > 0, exactly 0
+    elsewhere (||z||^2 = m)."""
+    gen = torch.Generator(device="cpu").manual_seed(int(seed))
+    Z = torch.randint(0, 2, (root_h.numel(), int(num_probes)), generator=gen).float() * 2 - 1
+    return Z.to(root_h.device) * (root_h.reshape(-1, 1) > 0).float()
+
+
+def _positive_int(v, name):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError("%s must be a positive int, got %r" % (name, v))
+    return v
+
+
+def _check_logdet_args(desc, root_h, m, num_probes, steps, solve_tol, method, probes):
+    sampling._check_desc(desc)
+    n = desc.n
+    if not torch.is_tensor(root_h) or root_h.numel() != n:
+        raise ValueError("root_h must be a tensor of %d values" % n)
+    _positive_int(m, "m")
+    if m > n:
+        raise ValueError("m = %d exceeds the %d nodes" % (m, n))
+    _positive_int(num_probes, "num_probes")
+    _positive_int(steps, "steps")
+    if not float(solve_tol) > 0.0:
+        raise ValueError("solve_tol must be positive, got %r" % (solve_tol,))
+    if method not in ("auto", "slq", "dense"):
+        raise ValueError("method must be 'auto', 'slq' or 'dense', got %r" % (method,))
+    if probes is not None and (not torch.is_tensor(probes) or probes.dim() != 2 or probes.shape[0] != n or probes.shape[1] < 2):
+        raise ValueError("probes must be a tensor [%d, P] with P >= 2" % n)
+
+
+def logdet_b(desc, root_h, m, num_probes=16, steps=12, seed=1337, solve_tol=1e-6, method="auto", probes=None, max_iter=5000):
+    """(value, se, per_probe) of logdet B, B = I + S Q^-1 S with S = diag(root_h) (0 off the m effective nodes).
+    method "slq": value = mean of per_probe, per_probe_p = m e_1^T log(T_p) e_1 from `steps` Lanczos steps on B started at probe p
+    (slq._lanczos_block_generic in batches of <= 16 probes; every product one cg_solve on form 0 to the relative residual
+    solve_tol between two scale_rows), se = the sample standard deviation of per_probe / sqrt(P).  probes [n, P] (default:
+    effective_probes(root_h, num_probes, seed)) must be +-1 on the effective nodes and 0 elsewhere.
+    method "dense": exact up to the solves: the m columns Q^-1 (s o e_j) in chunks of <= 256, float64 Cholesky of the m x m B;
+    se = 0, per_probe None.  "auto": dense for m <= 512."""
+    _check_logdet_args(desc, root_h, m, num_probes, steps, solve_tol, method, probes)
+    _lib.require_device(root_h, probes)
+    root_h = _lib.f32c(root_h.reshape(-1))
+    if method == "auto":
+        method = "dense" if m <= DENSE_MAX else "slq"
+    op = _BOperator(desc, root_h, solve_tol, max_iter)
+    with torch.no_grad():
+        if method == "dense":
+            eff = torch.nonzero(root_h > 0).reshape(-1)
+            if eff.numel() != m:
+                raise ValueError("root_h has %d positive entries, m = %d" % (eff.numel(), m))
+            s_eff = root_h[eff].double()
+            B = torch.empty(m, m, dtype=torch.float64, device=root_h.device)
+            for c0 in range(0, m, MAX_COLUMNS):
+                cols = eff[c0:c0 + MAX_COLUMNS]
+                E = torch.zeros(desc.n, cols.numel(), dtype=torch.float32, device=root_h.device)
+                E[cols, torch.arange(cols.numel(), device=root_h.device)] = root_h[cols]
+                B[:, c0:c0 + cols.numel()] = s_eff.view(-1, 1) * op.solve(E)[eff].double()
+            B = 0.5 * (B + B.t()) + torch.eye(m, dtype=torch.float64, device=root_h.device)
+            value = 2.0 * float(torch.linalg.cholesky(B).diagonal().log().sum())
+            return value, 0.0, None
+        from .slq import _lanczos_block_generic, _quadrature_log_each
+        Z = effective_probes(root_h, num_probes, seed) if probes is None else _lib.f32c(probes)
+        P = Z.shape[1]
+        k = min(int(steps), m)
+        per = []
+        for c0 in range(0, P, 16):
+            a, b = _lanczos_block_generic(op, Z[:, c0:c0 + 16].contiguous(), k)
+            per.append(_quadrature_log_each(a, b))
+        per = m * np.concatenate(per)
+    value = float(per.mean())
+    se = float(per.std(ddof=1) / math.sqrt(P)) if P > 1 else float("nan")
+    return value, se, per
+
+
+class LaplaceEvidence:
+    """The Laplace evidence of a node fit (laplace_evidence).  value: log Z as a float64 torch scalar on the device, carrying the
+    gradient surrogate when it was asked for; se: its standard error (logdet_se / 2); log_likelihood: sum_obs log p(y_i | f_i)
+    with the constants; quad: f^T Q f / 2; logdet: logdet B with logdet_se; method: "slq" or "dense"; m: the effective observed
+    nodes; per_probe: the probes' estimates of logdet B (slq); solves: None, or with the gradient the dict of what it was made
+    of (Z, root_h, corr, w, s_ref, Y float32; u, X float64); site_sums: the four sums of mgp_laplace_evidence_site (sum_obs l
+    without the families' constants, m, sum corr, max |corr|)."""
+
+    def __init__(self, value, se, log_likelihood, quad, logdet, logdet_se, method, m, per_probe, solves, site_sums=None):
+        self.value, self.se, self.log_likelihood, self.quad = value, se, log_likelihood, quad
+        self.logdet, self.logdet_se, self.method, self.m = logdet, logdet_se, method, m
+        self.per_probe, self.solves, self.site_sums = per_probe, solves, site_sums
+
+    def __repr__(self):
+        return "LaplaceEvidence(value=%.6f, se=%.3g, method=%r, m=%d)" % (float(self.value), self.se, self.method, self.m)
+
+
+def _site_of(fit):
+    """(family, mean, aux, s_ref) of a binary or a count fit."""
+    family = getattr(fit, "family", None)
+    if family is None:
+        return "bernoulli", 0.0, None, S_REF
+    return family, fit.prior_mean, fit._aux, fit.s_ref
+
+
+def _weights(fit, family, mean, aux, s_ref):
+    """obs_w = (float)(s_ref h) of the fit's own form-3 system at the mode, from the kernel its Newton steps used."""
+    if family == "bernoulli":
+        from .classification import bernoulli_site
+        return bernoulli_site(fit.mean, None, fit.y, fit.observed, s_ref)[0]
+    from .counts import count_site
+    return count_site(fit.mean, None, fit.y, aux, fit.observed, s_ref, mean, family)[0]
+
+
+REFINE_ROUNDS = 4         # refinement rounds of the float64 solves of the gradient (they stop at a true residual of 2 tol)
+
+
+def _solve64(desc, B, kw):
+    """A^-1 B as the float64 solution a refined plan accumulates (CgPlan.solution64_view), [n, C] with C <= 256, in the caller's
+    order; its true residual on the float64 matrix is <= 2 tol where the plan reports convergence."""
+    import warnings
+    from .solvers import _cached_plan
+    B = _lib.f32c(B)
+    plan = _cached_plan(desc, B.shape[1], kw)
+    plan.solve(B, copy=False)
+    if plan.status == 3:
+        raise RuntimeError("NaNs encountered in CG")
+    if plan.status == 2:
+        warnings.warn("CG did not converge in %d iterations (residuals up to %.3g)" % (plan.iters, max(plan.resid)))
+    return plan.solution64_view().clone()
+
+
+def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_probes=16, steps=12, seed=1337, solve_tol=1e-6,
+                     method="auto", probes=None, max_iter=5000):
+    """log Z of a LaplaceFit or a CountLaplaceFit: a LaplaceEvidence.  logdet B by logdet_b(num_probes, steps, seed, solve_tol,
+    method, probes).  operator: the model's precision(noise=False), the operator fit.desc describes; when one of its
+    _hyper_tensors() requires grad, value carries d log Z / d theta of the module docstring: corr = variance h' from variance
+    [n] (default fit.latent_variance(var_samples)[0]), X by one form-0 solve and Y, u by form-3 solves with the fit's s_ref and
+    weights, all refined to solve_tol on the true residual (X and u kept as the float64 solutions, _solve64), the probes those
+    of logdet B (drawn from num_probes and seed also when method is "dense")."""
+    from .autograd import needs_grad
+    from .solvers import cg_solve
+    if not hasattr(fit, "_pseudo") or fit.mean.dim() != 1:
+        raise NotImplementedError("laplace_evidence takes a binary or a count fit")
+    desc = fit.desc
+    family, mean, aux, s_ref = _site_of(fit)
+    grad = operator is not None and needs_grad(*getattr(operator, "_hyper_tensors", lambda: [])())
+    with torch.no_grad():
+        f = fit.mean
+        if grad and variance is None:
+            variance = fit.latent_variance(var_samples)[0]
+        root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family)
+        sums = sums.tolist()                              # the one host read of the site stage
+        m = int(sums[1])
+        if m < 1:
+            raise RuntimeError("no observed node has a curvature above %g: the latent values have run away" % H_FLOOR)
+        quad = 0.5 * float(torch.dot(f.double(), desc.apply_f64(f.double())))
+        if method == "auto":
+            method = "dense" if m <= DENSE_MAX else "slq"
+        Z = None
+        if method == "slq" or grad:
+            Z = effective_probes(root_h, num_probes, seed) if probes is None else _lib.f32c(probes)
+        logdet, logdet_se, per = logdet_b(desc, root_h, m, num_probes, steps, seed, solve_tol, method, Z if method == "slq" else None,
+                                          max_iter)
+    ll = float(fit.log_likelihood)
+    value = torch.tensor(ll - quad - 0.5 * logdet, dtype=torch.float64, device=f.device)
+    solves = None
+    if grad:
+        with torch.no_grad():
+            P = Z.shape[1]
+            # X and u only weight the operator's output, so they enter the bilinear forms as the float64 solutions the refined
+            # solves accumulate: a float32 X cannot hold a true residual of 2 solve_tol on Q itself (its rounding alone leaves
+            # 2.4e-6 on the 1546-node dumbbell, cond Q = 1e3; the unrefined factorised solve of the Lanczos products 4.8e-6).
+            # Y goes through the float32 operator chain and stays float32 (refined as sampling.posterior_variance solves form 3).
+            kw = dict(tol=float(solve_tol), stop_mode=1, max_iter=int(max_iter))
+            w = _weights(fit, family, mean, aux, s_ref)
+            d3 = desc.with_(form=3, noise=s_ref, obs_w=w)
+            kw3 = dict(kw, jacobi=sampling.OBSERVED_JACOBI[0])
+            SZ = scale_rows(root_h, Z)
+            X = _solve64(desc, SZ, dict(kw, refine=REFINE_ROUNDS))
+            Y = cg_solve(d3, SZ * s_ref, **dict(kw3, refine=1))[0]
+            u = _solve64(d3, (corr * s_ref).view(-1, 1), dict(kw3, refine=REFINE_ROUNDS)).view(-1)
+            V = torch.cat([f.view(-1, 1), Y], 1).contiguous()
+            W = torch.cat([0.5 * (u - f.double()).view(-1, 1), X * (0.5 / P)], 1)
+            solves = dict(Z=Z, root_h=root_h, corr=corr, w=w, s_ref=s_ref, u=u, X=X, Y=Y)
+        sur = (W * operator.matmul(V).double()).sum()
+        value = value + (sur - sur.detach())
+    return LaplaceEvidence(value, 0.5 * logdet_se, ll, quad, logdet, logdet_se, method, m, per, solves, sums)

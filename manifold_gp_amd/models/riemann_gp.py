@@ -178,6 +178,32 @@ class RiemannGP(torch.nn.Module):
         desc, _, y = self._sampling_args()
         return laplace_fit_counts(desc, y, observed, **kw)
 
+    def _laplace_fit(self, observed, family, **kw):
+        """The binary fit (family "bernoulli") or the count fit ("poisson", "binomial") of train_targets."""
+        if family == "bernoulli":
+            return self.laplace_posterior(observed, **kw)
+        return self.laplace_posterior_counts(observed, family=family, **kw)
+
+    def laplace_evidence(self, observed=None, family="bernoulli", **kw):
+        """Fit the nodes (family "bernoulli": laplace_posterior; "poisson" / "binomial": laplace_posterior_counts) and return the
+        Laplace approximation of log p(train_targets[observed]), an evidence.LaplaceEvidence.  kw: the arguments of the fit
+        (exposure, trials, mean, f0, tolerances) go to it, the others to evidence.laplace_evidence (num_probes, steps, seed,
+        method, ...).  max_iter is an argument of both and goes to the FIT; fit_kw= and evidence_kw= (dicts, as
+        utils.laplace_train takes them) name the receiver explicitly and win over the split: evidence_kw=dict(max_iter=...)
+        caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta."""
+        import inspect
+        from ..classification import laplace_fit
+        from ..counts import laplace_fit_counts
+        from ..evidence import _family, laplace_evidence
+        _family(family)
+        kw = dict(kw)
+        fit_kw, evidence_kw = dict(kw.pop("fit_kw", None) or {}), dict(kw.pop("evidence_kw", None) or {})
+        names = set(inspect.signature(laplace_fit if family == "bernoulli" else laplace_fit_counts).parameters)
+        fit_kw = dict({k: v for k, v in kw.items() if k in names}, **fit_kw)
+        evidence_kw = dict({k: v for k, v in kw.items() if k not in names}, **evidence_kw)
+        fit = self._laplace_fit(observed, family, **fit_kw)
+        return laplace_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
+
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):
         edge_value, _ = self.base_kernel.knn.search(x, 1)

@@ -120,7 +120,30 @@ def _quadrature_log_sum(a, b, fun=None):
     return total
 
 
-HIP_GENERIC_LANCZOS = [True]   # False: the torch form of the step below at every shape (A/B runs, tests; it stays for P > 16)
+def _quadrature_log_each(a, b, fun=None):
+    """e_1^T log(fun(T_p)) e_1 of every probe (columns of a / b [steps, P]) as a float64 array [P]: the terms _quadrature_log_sum
+    adds, kept apart for estimators that report the spread over the probes (evidence.logdet_b)."""
+    k, P = a.shape
+    ok = np.isfinite(b[:k - 1]).all(0) & (np.abs(b[:k - 1]) >= 1e-6 * np.maximum(np.abs(a[:k - 1]), 1e-30)).all(0) if k > 1 \
+        else np.ones(P, bool)
+    out = np.empty(P)
+    idx = np.nonzero(ok)[0]
+    if idx.size:
+        T = np.zeros((idx.size, k, k))
+        r = np.arange(k)
+        T[:, r, r] = a[:, idx].T
+        if k > 1:
+            T[:, r[:-1], r[1:]] = b[:k - 1, idx].T
+            T[:, r[1:], r[:-1]] = b[:k - 1, idx].T
+        theta, S = np.linalg.eigh(T)
+        theta = fun(theta) if fun is not None else theta
+        out[idx] = np.sum(S[:, 0, :] ** 2 * np.log(np.maximum(theta, 1e-30)), axis=1)
+    for p in np.nonzero(~ok)[0]:
+        out[p] = _quadrature_log(a[:, p], b[:, p], fun)
+    return out
+
+
+HIP_GENERIC_LANCZOS = [True]  # False: the torch form of the step below at every shape (A/B runs, tests; it stays for P > 16)
 
 
 def _lanczos_block_generic(operator, Z, steps):

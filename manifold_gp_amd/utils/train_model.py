@@ -95,6 +95,47 @@ def manifold_informed_train(model, optimizer, max_iter=100, tolerance=1e-2, upda
     return loss.item()
 
 
+def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=50, tolerance=1e-2, fit_kw=None, evidence_kw=None,
+                  verbose=False):
+    """Train the kernel hyper-parameters of `model` (a RiemannGP) on the Laplace evidence of its node fit: the loss is
+    -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
+    model.train_targets), "poisson" or "binomial" (counts; fit_kw carries exposure / trials / mean).  Every epoch refits the mode
+    from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
+    the last loss."""
+    from ..evidence import _family, laplace_evidence
+    _family(family)
+    model.train()
+    fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
+    graph = getattr(getattr(model.base_kernel, "knn", None), "knn_graph", None)
+    if graph is not None and hasattr(graph, "wide_relabelled"):
+        graph.wide_relabelled()
+    epoch, prev_loss, f0 = 0, None, fit_kw.pop("f0", None)
+    loss = torch.zeros(())
+    while epoch <= max_iter:
+        optimizer.zero_grad()
+        fit = model._laplace_fit(observed, family, f0=f0, **fit_kw)
+        f0 = fit.mean
+        ev = laplace_evidence(fit, operator=model.precision(noise=False), **evidence_kw)
+        loss = -ev.value
+        for _, module, prior, closure, _ in _named_priors(model):
+            loss = loss - prior.log_prob(closure(module)).sum().to(loss)
+        loss = loss / ev.m
+        if verbose:
+            msg = ["Iteration: %d, Loss: %0.4f (log Z %0.3f +- %0.3f)" % (epoch, loss.item(), float(ev.value), ev.se)]
+            if hasattr(model.covar_module, "outputscale"):
+                msg += ["Signal Variance: %0.3f" % model.covar_module.outputscale.item()]
+            msg += ["Lengthscale: %0.3f, Graphbandwidth: %0.3f" % (model.base_kernel.lengthscale.item(),
+                                                                   model.base_kernel.graphbandwidth.item())]
+            print(",\t".join(msg))
+        loss.backward()
+        optimizer.step()
+        epoch += 1
+        if prev_loss is not None and abs(loss.item() - prev_loss) <= tolerance:
+            break
+        prev_loss = loss.item()
+    return loss.item()
+
+
 def exact_mll_lowrank(model):
     """-(1/N) log p(y) for K = s Z Z^T + noise I (what gpytorch's ExactMarginalLogLikelihood returns, negated),
     differentiable wrt noise / output scale / length scale / constant mean."""
