@@ -598,6 +598,29 @@ int mgp_count_site(const float* f, const float* qf, const float* y, const float*
                    double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work, size_t work_bytes,
                    void* stream);
 
+/* The predictive pmf of a count fit (csrc/count_predict.hip, docs/kernels/count_predict.md): per node and count k,
+ *   pmf(k) = (2 pi v)^-1/2 int exp(g(x)) dx,   Poisson   g = k (x + a) - exp(x + a) - lgamma(k + 1) - (x - m)^2 / 2v,
+ *                                              binomial  g = log C(N, k) - k softplus(-x) - (N - k) softplus(x) - (x - m)^2 / 2v,
+ * with m = eta_i (the linear predictor at the mode WITHOUT the exposure, float64), v = var_i (float64) and aux as
+ * mgp_count_site: the float32 log-exposure a (family 0; NULL: zeros) or the float32 trials N (family 1; NULL: MGP_ERR_ARG).
+ * The quadrature is placed per (node, k), all in float64: the mode x* of g by a safeguarded Newton iteration, a window
+ * [x* - t_L, x* + t_R] at whose ends g has dropped by 40 (doubling from (-g''(x*))^-1/2, six bisections), and the `points`-point
+ * trapezoid rule of exp(g(x* + t) - g(x*)) there, t ascending, the difference formed without cancellation;
+ * log pmf = g(x*) + log(h sum / sqrt(2 pi v)).  v <= 2^-76 (zero and negative variances included) is the plain log pmf at
+ * x = m; k > N gives pmf 0 (log: -inf); NaN in eta, var or y gives NaN.  exp(x + a) is taken at min(x + a, 700).
+ * mgp_count_predict_pmf writes the counts k0 .. k0 + K - 1 of every node to out [n, K] row-major: the pmf, or its log when
+ * log_out is non-zero; 1 <= K <= 65536, 0 <= k0, k0 + K - 1 <= 2^24.  A wave per (node, 64 counts).
+ * mgp_count_predict_logpmf writes the log pmf of the one count y_i (a float32 integer in [0, 2^24], not validated) per node to
+ * out [n]; y is read only where `at` [n] bytes is non-zero (NULL: every node), out is NaN at the other nodes.  It is bitwise
+ * the matching entry of mgp_count_predict_pmf with log_out.
+ * points: odd, 17 .. 257.  No workspace, no atomics: repeated calls are bitwise equal.  Element alignment only.
+ * MGP_ERR_ARG for null eta, var, out (y), n < 1, K, k0 or points out of range and family 1 without aux; MGP_ERR_UNSUPPORTED for
+ * any other family.  The checks precede every launch. */
+int mgp_count_predict_pmf(const double* eta, const double* var, const float* aux, int64_t n, int family, int64_t k0, int K,
+                          int points, int log_out, double* out, void* stream);
+int mgp_count_predict_logpmf(const double* eta, const double* var, const float* aux, const float* y, const uint8_t* at,
+                             int64_t n, int family, int points, double* out, void* stream);
+
 /* The Laplace evidence at the mode (csrc/laplace.hip, docs/kernels/evidence.md): the per-node stage of
  * evidence.laplace_evidence.  f [n] the mode, y, aux, obs as mgp_count_site (read in quads that hold an observed node only; NaN
  * allowed elsewhere); family 0 Poisson, 1 binomial, 2 Bernoulli-logit (class 1 where y > 0.5 as mgp_bernoulli_site; aux is not

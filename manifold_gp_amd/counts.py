@@ -22,6 +22,10 @@ from the mode than the same rule does for 0/1 labels (docs/kernels/counts.md has
 
 The Laplace posterior N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets
 f_hat + g / h: CountLaplaceFit restates _pseudo() for the family and inherits latent_variance / latent_samples.
+
+The predictive distribution of a new count -- its pmf, the log density of held-out counts, exceedance probabilities and
+equal-tailed intervals (CountLaplaceFit.predict_pmf / predict_log_density / predict_exceedance / predict_interval) -- comes from
+one quadrature per (node, count) in float64 (mgp_count_predict_pmf / mgp_count_predict_logpmf, docs/kernels/count_predict.md).
 """
 import math
 
@@ -34,6 +38,8 @@ from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2, bernoull
 FAMILIES = {"poisson": 0, "binomial": 1}
 MAX_COUNT = 2 ** 24          # counts and trials are float32 on the device: integers are exact up to here
 ETA_MAX = 700.0              # mu = exp(min(eta, ETA_MAX)) stays finite in float64
+PMF_POINTS = 65              # the default rule of the predictive pmf (docs/kernels/count_predict.md)
+PMF_MAX_BLOCK = 65536        # counts per node in one mgp_count_predict_pmf call
 
 
 def _family(family):
@@ -69,6 +75,76 @@ def count_site(f, qf, y, aux, observed, s_ref, mean, family):
     check(lib().mgp_count_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), fam, ptr(w),
                                ptr(rhs), ptr(sums), ptr(work), work.numel(), stream()), "mgp_count_site")
     return w, rhs, sums
+
+
+def _pmf_points(points):
+    if isinstance(points, bool) or not isinstance(points, int) or not 17 <= points <= 257 or points % 2 == 0:
+        raise ValueError("points must be an odd int in 17 .. 257, got %r" % (points,))
+    return points
+
+
+def _int(v, name):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError("%s must be an int, got %r" % (name, v))
+    return v
+
+
+def _count_range(kmin, kmax):
+    kmin, kmax = _int(kmin, "kmin"), _int(kmax, "kmax")
+    if not 0 <= kmin <= kmax <= MAX_COUNT or kmax - kmin + 1 > PMF_MAX_BLOCK:
+        raise ValueError("counts kmin .. kmax must lie in [0, 2^24] and number at most %d, got %d .. %d" % (PMF_MAX_BLOCK, kmin, kmax))
+    return kmin, kmax
+
+
+def _predict_inputs(eta, var, aux, family):
+    """(family code, eta, var as contiguous float64 [n], aux as contiguous float32 [n] or None), on the device"""
+    fam = _family(family)
+    if fam == 1 and aux is None:
+        raise ValueError("the binomial family needs the trials in aux")
+    _lib.require_device(eta, var, aux)
+    eta = eta.reshape(-1).to(torch.float64).contiguous()
+    var = var.reshape(-1).to(torch.float64).contiguous()
+    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
+    for name, t in (("var", var), ("aux", aux)):
+        if t is not None and t.shape[0] != eta.shape[0]:
+            raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], eta.shape[0]))
+    return fam, eta, var, aux
+
+
+def count_predict_pmf(eta, var, aux, family, kmin, kmax, points=PMF_POINTS, log=False):
+    """The predictive pmf of the counts kmin .. kmax at every node: [n, kmax - kmin + 1] float64 (mgp_count_predict_pmf), its
+    log with log=True.  eta [n]: the linear predictor at the mode without the exposure, var [n]: the latent marginal variance
+    (both taken as float64; var <= 2^-76, negative entries included: the plain pmf at eta); aux [n] as count_site takes it:
+    the log-exposure (family "poisson"; None: zeros) or the trials (family "binomial").  At most 65536 counts per call."""
+    points = _pmf_points(points)
+    kmin, kmax = _count_range(kmin, kmax)
+    fam, eta, var, aux = _predict_inputs(eta, var, aux, family)
+    n, K = eta.shape[0], kmax - kmin + 1
+    out = torch.empty((n, K), dtype=torch.float64, device=eta.device)
+    check(lib().mgp_count_predict_pmf(ptr(eta), ptr(var), ptr(aux), n, fam, kmin, K, points, int(bool(log)), ptr(out), stream()),
+          "mgp_count_predict_pmf")
+    return out
+
+
+def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS):
+    """The log predictive probability of the one count y_i per node: [n] float64 (mgp_count_predict_logpmf), NaN outside the
+    bool mask at [n] (None: every node).  y [n] integers in [0, 2^24] (taken as float32; not read outside at, NaN allowed
+    there); eta, var, aux as count_predict_pmf."""
+    points = _pmf_points(points)
+    if at is not None and (not torch.is_tensor(at) or at.dtype != torch.bool):
+        raise ValueError("at must be a bool tensor [n]")
+    fam, eta, var, aux = _predict_inputs(eta, var, aux, family)
+    _lib.require_device(y, at)
+    n = eta.shape[0]
+    y = _lib.f32c(y.reshape(-1))
+    at = None if at is None else at.reshape(-1).contiguous()
+    for name, t in (("y", y), ("at", at)):
+        if t is not None and t.shape[0] != n:
+            raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], n))
+    out = torch.empty(n, dtype=torch.float64, device=eta.device)
+    check(lib().mgp_count_predict_logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, fam, points, ptr(out), stream()),
+          "mgp_count_predict_logpmf")
+    return out
 
 
 def _node_vector(t, n, name):
@@ -227,6 +303,110 @@ class CountLaplaceFit(LaplaceFit):
             return m, m + m * m * torch.expm1(v), v
         p = bernoulli_predict(self.eta().float(), v, points)
         return self.trials * p, self.trials * p * (1.0 - p), v
+
+    # -------------------------------------------------------------------------- the predictive distribution of a new count
+    def _variance(self, variance, S, seed):
+        """the latent marginal variance a predict_* call uses: the caller's (a latent_variance result) or latent_variance(S, seed)[0]"""
+        if variance is None:
+            return self.latent_variance(S, seed)[0]
+        n = self.mean.shape[0]
+        if not torch.is_tensor(variance) or variance.numel() != n or variance.dtype == torch.bool:
+            raise ValueError("variance must be a tensor of %d latent marginal variances" % n)
+        _lib.require_device(variance)
+        return variance.reshape(-1).to(torch.float64)
+
+    def _predict_args(self):
+        """(eta, aux) of the predict kernels.  Poisson: the log-exposure is added to eta in float64 and aux is None -- the
+        kernel's float32 log-exposure would cost 1e-7 of the rate, and the pmf would miss predict_mean's mean by as much.
+        Binomial: eta and the trials as float32 (integers: exact)."""
+        if self.family == "poisson":
+            return self.eta() + self.exposure.log(), None
+        return self.eta(), self.trials.float()
+
+    def predict_pmf(self, kmax, S=64, seed=None, points=PMF_POINTS, kmin=0, variance=None, log=False):
+        """(pmf, latent_var): P(y_new = k) for k = kmin .. kmax at every node under the Laplace posterior, [n, kmax - kmin + 1]
+        float64 (its log with log=True), and the latent marginal variance it used [n]: `variance` (a latent_variance result) or
+        latent_variance(S, seed)[0] as predict_mean.  Exposure and trials are the fit's own, 1 where none was given at an
+        unobserved node.  A quadrature of its own per (node, k) with `points` nodes (docs/kernels/count_predict.md)."""
+        points = _pmf_points(points)
+        kmin, kmax = _count_range(kmin, kmax)
+        v = self._variance(variance, S, seed)
+        eta, aux = self._predict_args()
+        return count_predict_pmf(eta, v, aux, self.family, kmin, kmax, points, log), v
+
+    def predict_log_density(self, y, at=None, S=64, seed=None, points=PMF_POINTS, variance=None):
+        """log P(y_new = y_i) at the nodes of the bool mask at [n] (None: every node) under the Laplace posterior, float64 [n], NaN
+        elsewhere: the log predictive density of held-out counts.  y [n]: integers in [0, 2^24] at those nodes, at most the fit's
+        trials there for the binomial family; not read elsewhere (NaN allowed)."""
+        points = _pmf_points(points)
+        n = self.mean.shape[0]
+        y = _node_vector(y, n, "y")
+        if at is not None:
+            if not torch.is_tensor(at) or at.dtype != torch.bool or at.dim() != 1 or at.shape[0] != n:
+                raise ValueError("at must be a bool tensor [%d]" % n)
+            if not bool(at.any()):
+                raise ValueError("at selects no node")
+        pick = (lambda t: t) if at is None else (lambda t: t[at.to(t.device)])
+        asked = pick(y)
+        if not bool(((asked >= 0) & (asked <= MAX_COUNT) & (asked == asked.round())).all()):
+            raise ValueError("counts at the nodes asked for must all be integers in [0, 2^24]")
+        if self.family == "binomial" and not bool((asked.to(self.trials.device) <= pick(self.trials)).all()):
+            raise ValueError("counts must be at most the fit's trials at the nodes asked for")
+        v = self._variance(variance, S, seed)
+        _lib.require_device(y, at)
+        eta, aux = self._predict_args()
+        return count_predict_logpmf(eta, v, aux, y, at, self.family, points)
+
+    def predict_exceedance(self, threshold, S=64, seed=None, points=PMF_POINTS, variance=None):
+        """P(y_new > threshold) at every node, float64 [n]: 1 - sum_{k <= threshold} pmf(k) on the pmf block 0 .. max threshold
+        (clamped at 0).  threshold: an int or an integer tensor [n], 0 .. 65535 (one block of predict_pmf)."""
+        points = _pmf_points(points)
+        n = self.mean.shape[0]
+        if torch.is_tensor(threshold):
+            if (threshold.dtype == torch.bool or threshold.is_floating_point() or threshold.is_complex()
+                    or threshold.numel() != n):
+                raise ValueError("threshold must be an int or an integer tensor of %d values" % n)
+            thr = threshold.reshape(-1).to(torch.int64)
+            top, low = int(thr.max()), int(thr.min())
+        else:
+            top = low = _int(threshold, "threshold")
+            thr = None
+        if low < 0 or top >= PMF_MAX_BLOCK:
+            raise ValueError("threshold must lie in 0 .. %d, got %d .. %d" % (PMF_MAX_BLOCK - 1, low, top))
+        _lib.require_device(thr)
+        pmf, _ = self.predict_pmf(top, S, seed, points, variance=variance)
+        if thr is not None:
+            keep = torch.arange(top + 1, device=pmf.device)[None, :] <= thr.to(pmf.device)[:, None]
+            pmf = torch.where(keep, pmf, torch.zeros((), dtype=pmf.dtype, device=pmf.device))
+        return (1.0 - pmf.sum(1)).clamp_min(0.0)
+
+    def predict_interval(self, level=0.9, kmax=None, S=64, seed=None, points=PMF_POINTS, variance=None):
+        """(lo, hi, reached): the equal-tailed predictive interval of a new count at every node -- the quantiles (1 - level) / 2
+        and (1 + level) / 2 of the predictive cdf (the least k whose cdf is at least the level), int64 [n] -- from cumulative sums
+        of the pmf block 0 .. kmax.  reached [n] bool: False where the upper quantile lies beyond kmax; hi = -1 there (and lo = -1
+        where the lower one does).  kmax defaults to the largest predict_mean mean plus 8 of its standard deviations (Poisson) or
+        the largest number of trials (binomial), capped at 65535."""
+        points = _pmf_points(points)
+        level = _real(level, "level")
+        if not 0.0 < level < 1.0:
+            raise ValueError("level must lie in (0, 1), got %r" % (level,))
+        if kmax is not None:
+            _, kmax = _count_range(0, kmax)
+        v = self._variance(variance, S, seed)
+        if kmax is None:
+            if self.family == "poisson":
+                m = self.exposure * torch.exp(self.eta() + 0.5 * v)
+                top = float((m + 8.0 * (m + m * m * torch.expm1(v)).sqrt()).max())
+            else:
+                top = float(self.trials.max())
+            kmax = int(min(math.ceil(top), PMF_MAX_BLOCK - 1)) if math.isfinite(top) else PMF_MAX_BLOCK - 1
+        pmf, _ = self.predict_pmf(kmax, points=points, variance=v)
+        cdf = pmf.cumsum(1)
+        lo = (cdf < (1.0 - level) / 2.0).sum(1)
+        hi = (cdf < (1.0 + level) / 2.0).sum(1)
+        reached = hi <= kmax
+        gone = torch.full_like(hi, -1)
+        return torch.where(lo <= kmax, lo, gone), torch.where(reached, hi, gone), reached
 
 
 def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, trials=None, mean=None, step_tol=1e-3,

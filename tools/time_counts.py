@@ -1,7 +1,9 @@
 """Time the count fits (manifold_gp_amd/counts.py) on the 60k manifold_784 graph (k = 50, random walk, nu = 2; 10 % of the
 nodes observed; Poisson counts with exposures in [0.5, 20] and binomial counts out of 1 .. 39 trials, both from 1.2 x the
 standardised targets) at two output scales: the wall time of laplace_fit_counts with its Newton and CG iteration counts, the
-event time of the count_site call next to bernoulli_site in the same process, and the wall time of predict_mean at S = 64.
+event time of the count_site call next to bernoulli_site in the same process, the wall time of predict_mean at S = 64, and the
+event times of the predictive pmf of the counts 0 .. 512 at every node (60k x 513 quadratures, P = 65 and 129) and of the log
+density of the node's own count, both with predict_mean's latent variance.
 Prints one JSON line.  Nothing here is an acceptance bar.
 
     python tools/time_counts.py [--reps 5]
@@ -66,6 +68,10 @@ def main():
             r["bernoulli_site_us"] = round(_events_ms(lambda: cl.bernoulli_site(f, qf, labels, obs), args.reps) * 1e3, 2)
             mean, var, lv = fit.predict_mean(64, seed=3)
             r["predict_mean_wall_ms"] = round(_wall_ms(lambda: fit.predict_mean(64, seed=3), args.reps), 3)
+            for points in (65, 129):
+                r["predict_pmf_513_counts_p%d_ms" % points] = round(_events_ms(
+                    lambda: fit.predict_pmf(512, points=points, variance=lv), args.reps), 3)
+            r["predict_log_density_us"] = round(_events_ms(lambda: fit.predict_log_density(y, variance=lv), args.reps) * 1e3, 2)
             truth = E * np.exp(1.0 + ftrue) if family == "poisson" else N / (1.0 + np.exp(-ftrue))
             # (exposure and trials are given at every node.)  The Poisson predictive mean carries exp(v / 2): at a prior variance
             # of 100 it is far above the median of the predictive rate, which is what map_mean follows
