@@ -245,6 +245,9 @@ typedef struct {
 /* workgroups that write dot partials for this CSR (format aware; use this one to size dot_partials) */
 int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C);
 int mgp_spmm_set_tile_mode(int on);          /* C == 1: use the tile dictionaries when present (default 1) */
+/* C == 1 tile kernel, lab: 1 = run the tile-loop form of the kernel even where every workgroup owns one tile (default 0: such
+ * graphs, up to 4096 row tiles, run the single-tile form).  Both forms give the same bits (tests/test_gpu_tile_head.py). */
+int mgp_spmm_set_tile_loop_mode(int on);
 int mgp_spmm_set_tile_small_mode(int on);    /* C in {4,8,12,16}: LDS-dictionary multi-column kernel on 64-row tiles
                                                 (default 1; 0 = the per-entry gather kernel) */
 /* 16 < C <= 256 with C % 4 == 0 on 64-row tiles: LDS-dictionary kernel in 16-column chunks where it wins (an X block of

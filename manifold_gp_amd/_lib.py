@@ -89,6 +89,7 @@ SIGNATURES = {
     "mgp_graph_bfs_order": (c_int, [c_int64, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_spmm_dot_blocks_csr": (c_int, [POINTER(CsrT), c_int]),
     "mgp_spmm_set_tile_mode": (c_int, [c_int]),
+    "mgp_spmm_set_tile_loop_mode": (c_int, [c_int]),
     "mgp_spmm_set_tile_small_mode": (c_int, [c_int]),
     "mgp_spmm_set_tile_wide_mode": (c_int, [c_int]),
     "mgp_spmm_set_dict_mode": (c_int, [c_int]),

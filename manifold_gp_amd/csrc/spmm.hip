@@ -240,6 +240,7 @@ struct TileArgs {
 };
 
 typedef unsigned short mgp_v4h __attribute__((ext_vector_type(4)));
+typedef int mgp_v8i __attribute__((ext_vector_type(8)));
 
 // The body serves three kernels through its MODE (an epilogue policy resolved at compile time: the code of a mode holds nothing
 // of the others):
@@ -249,28 +250,89 @@ typedef unsigned short mgp_v4h __attribute__((ext_vector_type(4)));
 enum { kTilePlain = 0, kTileSelfDot = 1, kTileCgStep = 2 };
 struct NoCgStep {};
 
-template <bool PRE, int BS, bool CBV, int MODE, bool DECIDE, int DS, class CS>
-__device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs t, const CS cs) {
+// The view of SpmmArgs the body reads.  The step kernel's launch (mgp_spmm_cgstep) leaves Y, pre, base, cbv, the dot hooks, skip,
+// tick, the row offset and the init-free hooks unset: in that mode they are constants here and never reach a register (the step
+// instantiation carries SpmmArgs + TileArgs + MgpCgStep, 648 bytes of arguments, and sat at 100 SGPRs with spills in its head).
+template <bool STEP>
+struct TileView {
+  int64_t n, goff;
+  const int32_t* rowptr;
+  const float *vals, *diag, *X, *pre, *post, *base, *dotw, *cbv;
+  float *Y, *dot_partials, *copy_x, *dot2_partials;
+  float a, b, cb, co;
+  const int* skip;
+  int* tick;
+  int tick_reset;
+  __device__ __forceinline__ explicit TileView(const SpmmArgs& p)
+      : n(p.n), goff(STEP ? 0 : p.goff), rowptr(p.rowptr), vals(p.vals), diag(p.diag), X(p.X), pre(STEP ? nullptr : p.pre),
+        post(p.post), base(STEP ? nullptr : p.base), dotw(STEP ? nullptr : p.dotw), cbv(STEP ? nullptr : p.cbv),
+        Y(STEP ? nullptr : p.Y), dot_partials(STEP ? nullptr : p.dot_partials), copy_x(STEP ? nullptr : p.copy_x),
+        dot2_partials(STEP ? nullptr : p.dot2_partials), a(p.a), b(p.b), cb(p.cb), co(p.co), skip(STEP ? nullptr : p.skip),
+        tick(STEP ? nullptr : p.tick), tick_reset(STEP ? 0 : p.tick_reset) {}
+};
+
+// ---- The head of a launch, as emitted (docs/kernels/spmm.md, round 7; tests/test_tile_head_isa_cpu.py reads it in the .s).
+// What a workgroup waits for before its tile is requested is a chain of dependent round trips, 0.2-0.3 us each, so the chain is kept
+// at two links in front of the ids:
+//   1. ONE batch of kernel-argument loads and one s_waitcnt lgkmcnt(0).  Left to itself the compiler fetches the arguments where
+//      they are first used, four to five batches with a wait each, all in front of the first vector load; the empty asm below names
+//      every uniform argument the body reads, which puts their loads in front of it.
+//   2. ONE round trip for what the ids' and the stream's addresses are made of: rowptr[r0], rowptr[r1], tile_ptr[t], tile_ptr[t + 1]
+//      (scalar loads: nothing has been stored yet, so the uniform addresses go to the scalar cache) together with, MODE by MODE,
+//      the skip flag and the tick (vector path, see below) or the step's 32-byte scalar block (one s_load_dwordx8).
+//   then the ids, the first half of the stream, the gathers, the second half, the row operands, and last the step's partials
+//   (12 per lane; they are waited for and summed behind the tile's first barrier, the step's coefficients are formed behind the
+//   second: alpha and beta are not needed before the row epilogue).
+// ONE (tiles_per_block == 1: every graph of up to 4096 row tiles): no tile loop, so nothing is loop-invariant and nothing moves
+// into a preheader in front of the tile's loads.  The loop form (larger graphs; mgp_spmm_set_tile_loop_mode) has the same source
+// order; there the offsets of the tiles come through the vector path, because the loop stores.
+template <bool PRE, int BS, bool CBV, int MODE, bool DECIDE, int DS, bool ONE, class CS>
+__device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs t, const CS cs) {
   extern __shared__ __attribute__((aligned(16))) float tile_lds[];
-  // the CG graph's skip flag / iteration tick: loaded here, consumed only after the first tile's
-  // metadata loads have been issued, so that the flag costs no round trip of its own
-  // The CG graph's skip flag / iteration tick are fetched through the VECTOR memory path, at the top of the tile loop, and
+  constexpr bool STEP = MODE == kTileCgStep;
+  const TileView<STEP> p(pa);
+  // The batch: a zero the compiler cannot see through, an s_mov whose inputs are the uniform arguments; the workgroup's tile
+  // index below is made of it, so every argument named here is in its register before the first address is formed.  ONE asm
+  // per mode (two of them came out as two batches), and the raw row pointers are named, not the selected ones (a select in
+  // front of the asm split the batch as well).  It is not volatile and has no memory clobber: a volatile one counts as a store,
+  // and every uniform load behind it (the tile offsets, the scalar block) would leave the scalar path.  An "s" OUTPUT must not
+  // carry a pointer either: the compiler loses its address space and every load through it becomes a flat load.  Arguments a
+  // mode does not read are not named (a null stands in).
+  int zero;
+  const unsigned grid_x = gridDim.x;
+#define MGP_TILE_HEAD_ARGS                                                                                                     \
+  "s"(p.n), "s"(p.rowptr), "s"(t.rowptr_t), "s"(p.vals), "s"(t.vals_t), "s"(p.diag), "s"(p.X), "s"(p.post), "s"(p.a), "s"(p.b),   \
+      "s"(p.cb), "s"(p.co), "s"(t.tile_ptr), "s"(t.tile_cols), "s"(t.lid), "s"(t.max_cols), "s"(t.rowid), "s"(grid_x),           \
+      "s"(PRE ? p.pre : nullptr), "s"(CBV ? p.cbv : nullptr), "s"(ONE ? (int64_t)0 : t.ntiles), "s"(ONE ? 0 : t.tiles_per_block)
+  if constexpr (!STEP) {
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : MGP_TILE_HEAD_ARGS, "s"(p.goff), "s"(p.base), "s"(p.dotw), "s"(p.Y), "s"(p.dot_partials),
+        "s"(p.copy_x), "s"(p.dot2_partials), "s"(p.skip), "s"(p.tick), "s"(p.tick_reset));
+  } else {
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : MGP_TILE_HEAD_ARGS, "s"(cs.r), "s"(cs.x), "s"(cs.p), "s"(cs.s), "s"(cs.us), "s"(cs.pre),
+        "s"(cs.pd_rr), "s"(cs.pd_delta), "s"(cs.nbs), "s"(cs.blk), "s"(cs.state), "s"(cs.host_state), "s"(cs.host_resid),
+        "s"(cs.arrive), "s"(cs.tol), "s"(cs.max_iter), "s"(cs.min_iter), "s"(cs.stop_mode), "s"(cs.dcoef), "s"(cs.dgamma));
+  }
+#undef MGP_TILE_HEAD_ARGS
+  // restrict-qualified read-only views: wave-uniform addresses become scalar (s_load) reads
+  const int32_t* __restrict__ rowptr = t.rowptr_t ? t.rowptr_t : p.rowptr;   // CSR in tile order
+  const float* __restrict__ vals = t.vals_t ? t.vals_t : p.vals;
+  // The CG graph's skip flag / iteration tick are fetched through the VECTOR memory path, at the top of the tile pass, and
   // tested when the tile's own loads have all been issued.  As scalar loads at the head of the kernel (rounds 1-3) they cost
   // every launch a round trip beyond L2 (~0.5 us) in front of everything else: scalar loads return out of order, so the
   // first use of ANY later scalar -- the kernel arguments -- waits for lgkmcnt(0), flag included (s_load_dword +
   // s_waitcnt lgkmcnt(0) at the top of the .s).  `lane0` is a zero the compiler cannot see through (mbcnt is a divergent
   // source): a uniform address would be selected back to the scalar cache, and a provably uniform VALUE is moved to an SGPR
-  // (v_readfirstlane behind s_waitcnt) in the loop preheader.
-  const int lane0 = __builtin_amdgcn_mbcnt_lo(0u, 0u);
-  const int* __restrict__ skip_ptr = (p.skip ? p.skip : reinterpret_cast<const int*>(p.rowptr)) + lane0;
-  const int* __restrict__ tick_ptr = (p.tick ? p.tick : reinterpret_cast<const int*>(p.rowptr)) + lane0;
+  // (v_readfirstlane behind s_waitcnt).  The step kernel has neither word: its flag and iteration come with the scalar block.
+  const int lane0 = __builtin_amdgcn_mbcnt_lo(0u, 0u) + zero;       // (+ zero: behind the argument batch, not in the middle of it)
+  const int* __restrict__ skip_ptr = (p.skip ? p.skip : reinterpret_cast<const int*>(rowptr)) + lane0;
+  const int* __restrict__ tick_ptr = (p.tick ? p.tick : reinterpret_cast<const int*>(rowptr)) + lane0;
   int skipl = 0, tickl = 0;
   constexpr int TR = BS / 4;
   constexpr int NQ = 4;
-  const int lb = mgp_xcd_block(blockIdx.x, gridDim.x);
+  const int lb = mgp_xcd_block(blockIdx.x, grid_x) + zero;
   const int tid = threadIdx.x, sub = tid & 3;
 #ifdef MGP_STAMP   // lab build (tools/lab/stamp_solve.py): block 0 leaves its start / end time behind the CG state words
-  int* st_base = !p.stamp_on ? nullptr : (p.skip ? const_cast<int*>(p.skip) - 1 : p.tick);
+  int* st_base = !pa.stamp_on ? nullptr : (p.skip ? const_cast<int*>(p.skip) - 1 : p.tick);
   if (st_base && blockIdx.x == 0 && tid == 0) {
     const int si = atomicAdd(st_base + 8, 1);
     reinterpret_cast<unsigned long long*>(st_base + 16)[si & 255] = wall_clock64() * 8 + 0;
@@ -279,52 +341,98 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs 
 #endif
   float* __restrict__ xl = tile_lds;
   float* __restrict__ part = tile_lds + t.max_cols;
-  // restrict-qualified read-only views: wave-uniform addresses become scalar (s_load) reads
   const float* __restrict__ x = p.X;
   const float* __restrict__ prev = p.pre;
-  const int32_t* __restrict__ rowptr = t.rowptr_t ? t.rowptr_t : p.rowptr;   // CSR in tile order
-  const float* __restrict__ vals = t.vals_t ? t.vals_t : p.vals;
   const int32_t* __restrict__ tile_ptr = t.tile_ptr;
   const uint32_t* __restrict__ tile_cols = reinterpret_cast<const uint32_t*>(t.tile_cols);
   const uint16_t* __restrict__ lid = t.lid;
   float dsum = 0.f, dsum2 = 0.f;
-  const int64_t t0 = (int64_t)lb * t.tiles_per_block;
-  const int64_t t1 = t0 + t.tiles_per_block < t.ntiles ? t0 + t.tiles_per_block : t.ntiles;
-  // ---- kTileCgStep, prologue: everything the step's scalars are made of is requested here, in front of the first tile's own
-  // loads (loads retire in issue order: what the tile waits for anyway covers them) -- the scalar block in one load, both
-  // parities of the ||r||^2 partials and the |t|^2 partials of the first SpMV, DS slots of BS per lane on clamped addresses
+  // ONE: the grid is the tile count (tile_grid), workgroup lb owns tile lb, and the "loop" below is one pass the compiler
+  // flattens (its trip count is the constant 1)
+  const int64_t t0 = ONE ? (int64_t)lb : (int64_t)lb * t.tiles_per_block;
+  const int64_t t1 = ONE ? t0 + 1 : (t0 + t.tiles_per_block < t.ntiles ? t0 + t.tiles_per_block : t.ntiles);
+  // ---- kTileCgStep, prologue: the scalar block, one 32-byte scalar load in the round trip of the first tile's offsets.  What
+  // else the step's scalars are made of -- both parities of the ||r||^2 partials and the |t|^2 partials of the first SpMV, DS
+  // slots of BS per lane on clamped addresses -- is requested BEHIND the first tile's row operands and summed behind the tile's
+  // first barrier (alpha and beta are not needed before the row epilogue).  Round 6 requested the partials here and meant to
+  // sum them under cover of the tile's loads; the sums were invariant in the tile loop, moved into its preheader, and the
+  // emitted code waited for all twelve partials before it requested the tile.
   __shared__ float cg_sh_w[MODE == kTileCgStep ? BS / MGP_WAVE : 1][3];
   __shared__ float cg_sh_o[MODE == kTileCgStep ? BS / MGP_WAVE : 1];
   __shared__ int cg_sh_state[MODE == kTileCgStep ? 2 : 1];
   __shared__ int cg_sh_last[1];
-  [[maybe_unused]] float cg_rv[2][DS], cg_dv[DS];
+  // DS == 4 (up to 1024 partials, what the default folds): 12 values per lane, held from behind the row operands to behind the
+  // tile's first barrier.  DS == 16 (lab knob fold_update = 2): 48 values per lane held that long cost 80-120 VGPRs and half the
+  // occupancy, so that instantiation keeps what round 6's emitted code did -- requested and summed here, in front of the tile
+  constexpr bool CG_LATE = DS <= 4;
+  [[maybe_unused]] float cg_rv[2][DS], cg_dv[DS], cg_s3[3] = {0.f, 0.f, 0.f};
+  [[maybe_unused]] auto cg_request_partials = [&]() {
+    if constexpr (STEP) {
+#pragma unroll
+      for (int q = 0; q < DS; ++q) {
+        const int b = tid + q * BS;
+        const int bc = b < cs.nbs ? b : cs.nbs - 1;
+        cg_rv[0][q] = cs.pd_rr[bc];
+        cg_rv[1][q] = cs.pd_rr[cs.nbs + bc];
+        cg_dv[q] = cs.pd_delta[bc];
+      }
+    }
+  };
+  // fixed order: lane slots in order, the wave sum, then (w0 + w1) + (w2 + w3) behind the tile's second barrier
+  [[maybe_unused]] auto cg_sum_partials = [&]() {
+    if constexpr (STEP) {
+#pragma unroll
+      for (int q = 0; q < DS; ++q) {
+        const bool on = tid + q * BS < cs.nbs;
+        cg_s3[0] += on ? cg_rv[0][q] : 0.f; cg_s3[1] += on ? cg_rv[1][q] : 0.f; cg_s3[2] += on ? cg_dv[q] : 0.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) cg_s3[k] = mgp_wave_sum(cg_s3[k]);
+    }
+  };
   [[maybe_unused]] float cg_go0 = 0.f, cg_go1 = 0.f, cg_ao0 = 0.f, cg_ao1 = 0.f, cg_bb_old = 0.f;
   [[maybe_unused]] int cg_st_it = 0, cg_st_done = 0;
+  // The block as ONE scalar load (a struct copy is fetched field by field where each field is first used: three loads, three
+  // waits): the eight words pass through an empty asm where the tile's offsets are waited for anyway, which keeps the load whole
+  // and in front of that wait.  The words are data, not addresses, so nothing is lost by hiding them from the compiler.
+  [[maybe_unused]] mgp_v8i cg_blk;
+  [[maybe_unused]] auto take_blk = [&]() {
+    asm("" : "+s"(cg_blk));
+    const CgScalars sc = __builtin_bit_cast(CgScalars, cg_blk);
+    cg_go0 = sc.go0; cg_go1 = sc.go1; cg_ao0 = sc.ao0; cg_ao1 = sc.ao1; cg_bb_old = sc.bb; cg_st_it = sc.it; cg_st_done = sc.done;
+  };
   [[maybe_unused]] float cg_alpha = 0.f, cg_beta = 0.f, cg_bb = 0.f, cg_nrr = 0.f;
   [[maybe_unused]] int cg_it = 0;
   [[maybe_unused]] bool cg_fresh = false;
   if constexpr (MODE == kTileCgStep) {
     static_assert(BS == 256, "the step's sums are written for four waves");
-    const CgScalars sc = *reinterpret_cast<const CgScalars*>(cs.blk);
-    cg_go0 = sc.go0; cg_go1 = sc.go1; cg_ao0 = sc.ao0; cg_ao1 = sc.ao1; cg_bb_old = sc.bb; cg_st_it = sc.it; cg_st_done = sc.done;
-#pragma unroll
-    for (int q = 0; q < DS; ++q) {
-      const int b = tid + q * BS;
-      const int bc = b < cs.nbs ? b : cs.nbs - 1;
-      cg_rv[0][q] = cs.pd_rr[bc];
-      cg_rv[1][q] = cs.pd_rr[cs.nbs + bc];
-      cg_dv[q] = cs.pd_delta[bc];
-    }
+    static_assert(sizeof(CgScalars) == sizeof(mgp_v8i) && alignof(CgScalars) == alignof(mgp_v8i), "the scalar block is one load");
+    cg_blk = *reinterpret_cast<const mgp_v8i*>(cs.blk);
+    if constexpr (!ONE) take_blk();
+    if constexpr (!CG_LATE) { cg_request_partials(); cg_sum_partials(); }
   }
+  // kTileCgStep: x of this workgroup's rows, which nobody has initialised when the solve ends before its first update
+  [[maybe_unused]] auto zero_x = [&]() {
+    if constexpr (STEP) {
+      for (int64_t tl = t0; tl < t1; ++tl) {
+        const int64_t pos = tl * TR + tid;
+        if (tid < TR && pos < p.n) cs.x[t.rowid ? (int64_t)t.rowid[pos] : pos] = 0.f;
+      }
+    }
+  };
   for (int64_t tile = t0; tile < t1; ++tile) {
-    skipl = *skip_ptr;
-    tickl = *tick_ptr;
+    if constexpr (!STEP) {
+      skipl = *skip_ptr;
+      tickl = *tick_ptr;
+    }
     const int64_t r0 = tile * TR;
     const int64_t r1 = r0 + TR < p.n ? r0 + TR : p.n;
     const int e0 = rowptr[r0], e1 = rowptr[r1];
     const int dp = tile_ptr[tile];
     const int D = tile_ptr[tile + 1] - dp;
     const int qb = e0 >> 2, Q = (e1 - e0) >> 2;
+    __builtin_amdgcn_sched_barrier(0);    // one round trip: every request above is out before the first of them is waited for
+    if constexpr (STEP && ONE) take_blk();
     // phase 0 (loads are retired in issue order, so the order below is the order they are needed in):
     // dictionary ids first, then the matrix stream, then the row-phase operands -- all unconditional on
     // clamped addresses, all in flight before the first wait
@@ -392,19 +500,9 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs 
     if (p.skip && skipl) return;          // CG converged: every load above went to a valid address, nothing is written
     if constexpr (MODE == kTileCgStep) {
       if (tile == t0) {
-        // fixed order: lane slots in order, the wave sum, then (w0 + w1) + (w2 + w3) behind the barrier below
-        float s3[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-        for (int q = 0; q < DS; ++q) {
-          const bool on = tid + q * BS < cs.nbs;
-          s3[0] += on ? cg_rv[0][q] : 0.f; s3[1] += on ? cg_rv[1][q] : 0.f; s3[2] += on ? cg_dv[q] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) s3[k] = mgp_wave_sum(s3[k]);
-        if ((tid & 63) == 0) {
-#pragma unroll
-          for (int k = 0; k < 3; ++k) cg_sh_w[tid >> 6][k] = s3[k];
-        }
+        // the partials, last in the queue: nbs hot lines that every workgroup of the launch reads stay off the front of it
+        if constexpr (CG_LATE) cg_request_partials();
+        __builtin_amdgcn_sched_barrier(0);
         // workgroup 0 may raise the done flag while this launch runs: one lane's view of the state is published, so that all
         // waves of a workgroup take the same branch (the tile's first barrier carries it)
         if (tid == 0) { cg_sh_state[0] = cg_st_it; cg_sh_state[1] = cg_st_done; }
@@ -424,50 +522,20 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs 
     __syncthreads();
     if constexpr (MODE == kTileCgStep) {
       if (tile == t0) {
-        // every lane derives alpha, beta and the decision redundantly through cg_rule.h, as cg_update_c1_kernel does
-        const int it = cg_sh_state[0];
-        const bool fresh = it == 1;             // a folded plan starts init-free: r = b, p = s = x = 0 whatever the buffers hold
-        // x of this workgroup's rows, which nobody has initialised when the solve ends before its first update
-        auto zero_x = [&]() {
-          for (int64_t tl = t0; tl < t1; ++tl) {
-            const int64_t pos = tl * TR + tid;
-            if (tid < TR && pos < p.n) cs.x[t.rowid ? (int64_t)t.rowid[pos] : pos] = 0.f;
-          }
-        };
+        cg_it = cg_sh_state[0];
+        cg_fresh = cg_it == 1;                  // a folded plan starts init-free: r = b, p = s = x = 0 whatever the buffers hold
         if (cg_sh_state[1]) {
           // flag already up.  At iteration 1 the first SpMV reset it, so workgroup 0 raised it in THIS launch (b = 0 or not finite)
-          if (fresh) zero_x();
+          if (cg_fresh) zero_x();
           if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(cs.state, cs.host_state);    // nobody arrives
           return;
         }
-        const int par = it & 1, prev = par ^ 1;
-        float tt3[3];
+        // the partials are waited for here, behind the barrier
+        if constexpr (CG_LATE) cg_sum_partials();
+        if ((tid & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) tt3[k] = (cg_sh_w[0][k] + cg_sh_w[1][k]) + (cg_sh_w[2][k] + cg_sh_w[3][k]);
-        const float rr2 = prev ? tt3[1] : tt3[0];        // = gamma: u = r.  Iteration 1: ||b||^2, left in parity 0 by the first SpMV
-        const float gamma = rr2;
-        const float delta = (cs.dgamma ? gamma : 0.f) + cs.dcoef * tt3[2];      // u . A u = [gamma +] c |B P u|^2
-        const float bb = (it == 1) ? rr2 : cg_bb_old;
-        const float rel = cg_rel(rr2, bb);
-        const CgCoef kc = cg_coef(it == 1, cg_frozen(cs.stop_mode, cs.tol, rel), gamma, delta, prev ? cg_go1 : cg_go0,
-                                  prev ? cg_ao1 : cg_ao0);
-        const CgStop st = cg_stop(cs.stop_mode, cs.min_iter, cs.max_iter, cs.tol, it, rel);
-        if (blockIdx.x == 0 && tid == 0) {
-          float* gamma_old = cs.blk;
-          float* alpha_old = cs.blk + 2;
-          gamma_old[par] = gamma;
-          alpha_old[par] = kc.alpha;
-          if (it == 1) cs.blk[4] = bb;
-          // DECIDE and not done: the last arriver of this launch writes the residual of step it + 1 to the same word
-          if (!DECIDE || st.done) cs.blk[5] = rel;
-          if (st.done) cg_publish(cs.state, cs.host_state, cs.host_resid, &rel, 1, it, st.status);
+          for (int k = 0; k < 3; ++k) cg_sh_w[tid >> 6][k] = cg_s3[k];
         }
-        if (st.done) {
-          if (fresh) zero_x();
-          if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(cs.state, cs.host_state);    // every workgroup leaves here
-          return;
-        }
-        cg_alpha = kc.alpha; cg_beta = kc.beta; cg_bb = bb; cg_it = it; cg_fresh = fresh;
       }
     }
     // phase 2: quad products
@@ -492,6 +560,40 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs 
       part[q] = s;
     }
     __syncthreads();
+    if constexpr (MODE == kTileCgStep) {
+      if (tile == t0) {
+        // every lane derives alpha, beta and the decision redundantly through cg_rule.h, as cg_update_c1_kernel does
+        const int it = cg_it;
+        const int par = it & 1, prev = par ^ 1;
+        float tt3[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tt3[k] = (cg_sh_w[0][k] + cg_sh_w[1][k]) + (cg_sh_w[2][k] + cg_sh_w[3][k]);
+        const float rr2 = prev ? tt3[1] : tt3[0];        // = gamma: u = r.  Iteration 1: ||b||^2, left in parity 0 by the first SpMV
+        const float gamma = rr2;
+        const float delta = (cs.dgamma ? gamma : 0.f) + cs.dcoef * tt3[2];      // u . A u = [gamma +] c |B P u|^2
+        const float bb = (it == 1) ? rr2 : cg_bb_old;
+        const float rel = cg_rel(rr2, bb);
+        const CgCoef kc = cg_coef(it == 1, cg_frozen(cs.stop_mode, cs.tol, rel), gamma, delta, prev ? cg_go1 : cg_go0,
+                                  prev ? cg_ao1 : cg_ao0);
+        const CgStop st = cg_stop(cs.stop_mode, cs.min_iter, cs.max_iter, cs.tol, it, rel);
+        if (blockIdx.x == 0 && tid == 0) {
+          float* gamma_old = cs.blk;
+          float* alpha_old = cs.blk + 2;
+          gamma_old[par] = gamma;
+          alpha_old[par] = kc.alpha;
+          if (it == 1) cs.blk[4] = bb;
+          // DECIDE and not done: the last arriver of this launch writes the residual of step it + 1 to the same word
+          if (!DECIDE || st.done) cs.blk[5] = rel;
+          if (st.done) cg_publish(cs.state, cs.host_state, cs.host_resid, &rel, 1, it, st.status);
+        }
+        if (st.done) {
+          if (cg_fresh) zero_x();
+          if (DECIDE && blockIdx.x == 0 && tid == 0) cg_mark_end_of_graph(cs.state, cs.host_state);    // every workgroup leaves here
+          return;
+        }
+        cg_alpha = kc.alpha; cg_beta = kc.beta; cg_bb = bb;
+      }
+    }
     // phase 3: rows
     float acc = 0.f;
     {
@@ -578,9 +680,10 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs p, const TileArgs 
 }
 
 // SELF: the self dot of MgpSpmmOpts (partials of y . y and of the raw input squared instead of the weighted ones)
-template <bool PRE, int BS, bool CBV, bool SELF>
+// ONE: the single-tile form (one tile per workgroup, no tile loop; spmv_tile_body)
+template <bool PRE, int BS, bool CBV, bool SELF, bool ONE>
 __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
-  spmv_tile_body<PRE, BS, CBV, SELF ? kTileSelfDot : kTilePlain, false, 1>(p, t, NoCgStep{});
+  spmv_tile_body<PRE, BS, CBV, SELF ? kTileSelfDot : kTilePlain, false, 1, ONE>(p, t, NoCgStep{});
 }
 
 // ---- The CG step of a nu = 2 solve in the epilogue of the apply's second SpMV (docs/kernels/cg.md, round 6).  With
@@ -592,9 +695,9 @@ __global__ __launch_bounds__(BS) void spmv_tile_kernel(SpmmArgs p, TileArgs t) {
 // step, x zeroed when the solve ends at step 1, the workgroup that sees the flag raised during the launch, workgroup 0 writing
 // gamma_old / alpha_old / bb / resid and publishing, DECIDE through the same hand-off (cg_handoff.h).
 // DS: slots of 256 partials a lane sums (4 for nbs <= 1024, else 16), as cg_update_c1_kernel<*, DS>.
-template <int BS, int DS, bool DECIDE>
+template <int BS, int DS, bool DECIDE, bool ONE>
 __global__ __launch_bounds__(BS) void spmv_tile_cgstep_kernel(SpmmArgs p, TileArgs t, MgpCgStep cs) {
-  spmv_tile_body<false, BS, false, kTileCgStep, DECIDE, DS>(p, t, cs);
+  spmv_tile_body<false, BS, false, kTileCgStep, DECIDE, DS, ONE>(p, t, cs);
 }
 
 // ---------------------------------------------------------------- C > 1
@@ -1701,6 +1804,7 @@ std::atomic<int> g_rows_in_flight{1};
 // the helpers of one call cannot see two settings.  (Two CALLS -- sizing the dot partials, then launching -- can still see
 // different settings: the header says the switches are not to be flipped while another thread is inside this family of calls.)
 std::atomic<int> g_tile_mode{1};
+std::atomic<int> g_tile_loop_mode{0};
 std::atomic<int> g_tile_small_mode{1};
 std::atomic<int> g_tile_wide_mode{1};
 std::atomic<int> g_spmm_v4_mode{1};
@@ -1730,6 +1834,11 @@ extern "C" int mgp_stamp_enable(int on) { g_stamp_enable = on ? 1 : 0; return 0;
 
 extern "C" int mgp_spmm_set_tile_mode(int on) {
   g_tile_mode = on ? 1 : 0;
+  return MGP_OK;
+}
+
+extern "C" int mgp_spmm_set_tile_loop_mode(int on) {
+  g_tile_loop_mode = on ? 1 : 0;
   return MGP_OK;
 }
 
@@ -1896,6 +2005,7 @@ struct SpmmPlan {
   int lanes, rows_in_flight;    // RowGroups
   bool v4_ok;               // Gather: switch and shape allow the float4 member (the launch adds the alignment test)
   int tiles_per_block;      // TileC1, TileSmall, TileWide (Dict: 1)
+  bool one_tile;            // TileC1: the single-tile form of the kernel (tiles_per_block == 1 and the loop form not forced)
   int window;               // TileSmall: quads of partial sums staged per window
   int slots, stream_cap;    // Dict
   int wide_cap;             // TileWide
@@ -1919,6 +2029,7 @@ static SpmmPlan spmm_plan(const mgp_csr_t* L, int C, int64_t row_offset, bool wi
   if (C == 1 && dicts && (L->tile_rows == 32 || L->tile_rows == 64 || L->tile_rows == 128) && tile_lds_bytes(L) <= 65536 - 64) {
     pl.family = SpmmFamily::TileC1;
     pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
+    pl.one_tile = pl.tiles_per_block == 1 && !g_tile_loop_mode;
     pl.lds = tile_lds_bytes(L);
     return pl;
   }
@@ -2129,18 +2240,20 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
       TileLaunchRecord rec{p, ta};
       memcpy(record_to, &rec, sizeof(rec));
     }
-    auto tiles = [&](auto bs) { with_pre(pre, [&](auto P) {
+    auto tiles = [&](auto bs, auto one) { with_pre(pre, [&](auto P) {
       constexpr int BS = decltype(bs)::value;
-      const auto kernel = self_dot ? &spmv_tile_kernel<decltype(P)::value, BS, CB, true> : &spmv_tile_kernel<decltype(P)::value, BS, CB, false>;
+      constexpr bool ONE = decltype(one)::value;
+      const auto kernel = self_dot ? &spmv_tile_kernel<decltype(P)::value, BS, CB, true, ONE> : &spmv_tile_kernel<decltype(P)::value, BS, CB, false, ONE>;
       if (g_spmv_timer.on && 2 * g_spmv_timer.used + 1 < (int)g_spmv_timer.ev.size()) {
         hipEvent_t e0 = g_spmv_timer.ev[2 * g_spmv_timer.used], e1 = g_spmv_timer.ev[2 * g_spmv_timer.used + 1];
         ++g_spmv_timer.used;
         hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BS), lds, st, e0, e1, 0, p, ta);
       } else hipLaunchKernelGGL(kernel, dim3(grid), dim3(BS), lds, st, p, ta);
     }); };
-    if (L->tile_rows == 32) tiles(IntC<128>{});
-    else if (L->tile_rows == 64) tiles(IntC<256>{});
-    else tiles(IntC<512>{});
+    auto forms = [&](auto bs) { if (pl.one_tile) tiles(bs, std::true_type{}); else tiles(bs, std::false_type{}); };
+    if (L->tile_rows == 32) forms(IntC<128>{});
+    else if (L->tile_rows == 64) forms(IntC<256>{});
+    else forms(IntC<512>{});
   } break;
   case SpmmFamily::TileSmall: {
     TileArgs ta = tile_args(L, pl.tiles_per_block, pl.window);
@@ -2277,19 +2390,22 @@ int mgp_spmm_cgstep(const mgp_csr_t* L, const float* T, float a, float b, const 
   if (pl.family != SpmmFamily::TileC1 || L->tile_rows != 64 || pl.lds + kCgStepStaticLds > 65536) return MGP_ERR_UNSUPPORTED;
   if (cs.nbs != pl.dot_blocks || cs.nbs < 1 || cs.nbs > 16 * 256) return MGP_ERR_ARG;
   // X = t; base = r enters through cs (form 2: dgamma), cb = 1; Y, the dot hooks, skip and tick are not used by this kernel:
-  // the done flag and the iteration come with the scalar block, and the first SpMV of the step has ticked
+  // the done flag and the iteration come with the scalar block, and the first SpMV of the step has ticked.  The kernel does not
+  // even load them (TileView<true> in spmv_tile_body holds them as constants): a caller that sets one here must change that view
   SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, T, nullptr, 1, a, b, nullptr, post, nullptr, 1.f, co,
              nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
   const TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
   const dim3 grid(pl.grid), block(256);
   hipStream_t st = mgp_stream(stream);
-  if (cs.nbs <= 4 * 256) {
-    if (decide) hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 4, true>), grid, block, pl.lds, st, p, ta, cs);
-    else hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 4, false>), grid, block, pl.lds, st, p, ta, cs);
-  } else {
-    if (decide) hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 16, true>), grid, block, pl.lds, st, p, ta, cs);
-    else hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, 16, false>), grid, block, pl.lds, st, p, ta, cs);
-  }
+  auto step = [&](auto ds, auto one) {
+    constexpr int DS = decltype(ds)::value;
+    constexpr bool ONE = decltype(one)::value;
+    if (decide) hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, DS, true, ONE>), grid, block, pl.lds, st, p, ta, cs);
+    else hipLaunchKernelGGL((spmv_tile_cgstep_kernel<256, DS, false, ONE>), grid, block, pl.lds, st, p, ta, cs);
+  };
+  // 16 slots: more than 1024 partials, i.e. more than 1024 tiles; the single-tile form serves up to 4096 of them
+  if (cs.nbs <= 4 * 256) { if (pl.one_tile) step(IntC<4>{}, std::true_type{}); else step(IntC<4>{}, std::false_type{}); }
+  else { if (pl.one_tile) step(IntC<16>{}, std::true_type{}); else step(IntC<16>{}, std::false_type{}); }
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }
