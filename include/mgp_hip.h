@@ -601,6 +601,43 @@ int mgp_count_site(const float* f, const float* qf, const float* y, const float*
                    double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work, size_t work_bytes,
                    void* stream);
 
+/* Ordered categories at the nodes (csrc/laplace.hip, docs/kernels/ordinal.md): the likelihood stage of one Newton step of
+ * ordinal.laplace_fit_ordinal, a cumulative-logit model with one latent function, with the contract of mgp_bernoulli_site.
+ * f, qf (NULL: zeros), obs (NULL: every node) as there; lo [n] and hi [n] are the float32 ends of the node's interval of
+ * cutpoints, lo < hi, -inf and +inf allowed (the end categories); read at observed nodes only (NaN allowed elsewhere).  The
+ * kernel sees intervals, never labels: no table is indexed.  Per observed node in float64 from the float32 inputs, with
+ * u = hi - f, l = lo - f, logsig(x) = -(max(-x, 0) + log1p(exp(-|x|))) and sigma(x) = 1 / (1 + e) (x >= 0), e / (1 + e) (x < 0),
+ * e = exp(-|x|):
+ *   P(y | f) = sigma(u) - sigma(l) = sigma(u) sigma(-l) (1 - exp(-(hi - lo)))                  (no cancellation)
+ *   log p = logsig(u) + logsig(-l)            (log(-expm1(-(hi - lo))) does not depend on f and is left to the caller)
+ *   g = sigma(l) - sigma(-u),   h = e_u / (1 + e_u)^2 + e_l / (1 + e_l)^2,   0 < h <= 1/2
+ * (g = h = 0 at unobserved nodes), and
+ *   w_i = (float)(s_ref h_i),   rhs_i = (float)(s_ref (g_i - qf_i)),
+ *   sums [4] float64 (device) = { sum_obs log p,  sum_i f_i qf_i,  max_i |g_i - qf_i|,  sum_i (g_i - qf_i)^2 }.
+ * Finite for any finite f and any lo < hi, infinite ends included.  One partial per workgroup and the second launch of
+ * mgp_bernoulli_site: fixed order, no atomics, repeated calls are bitwise equal.  `work`: mgp_ordinal_site_workspace_bytes(n)
+ * bytes, 8-byte aligned.  float4 / uchar4 accesses where f, qf, lo, hi, w, rhs are 16-byte and obs 4-byte aligned, scalar ones
+ * otherwise.  MGP_ERR_ARG for null f, lo, hi, w, rhs or sums and n < 1; MGP_ERR_WORKSPACE for a null, misaligned or short `work`.
+ * The checks precede every launch. */
+size_t mgp_ordinal_site_workspace_bytes(int64_t n);
+int mgp_ordinal_site(const float* f, const float* qf, const float* lo, const float* hi, const uint8_t* obs, int64_t n,
+                     double s_ref, float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream);
+/* The predictive probabilities of the K ordered categories, 2 <= K <= 64, under a Gaussian latent marginal:
+ *   out [n, K] row-major,   out_ik = int P(y = k | f) N(f; eta_i, var_i) df,
+ * by the `points`-point trapezoid rule of mgp_bernoulli_predict, u_j = -8 + j D, D = 16 / (points - 1), f_j = eta_i + sqrt(var_i) u_j,
+ * weights D phi(u_j), j ascending, all in float64, with the integrand in the product form
+ *   c_k sigma(b_{k+1} - f_j) sigma(f_j - b_k),   c_k = -expm1(-(b_{k+1} - b_k)),
+ * one factor and c = 1 for an end category (b_0 = -inf, b_K = +inf): every term is positive, so a tail category keeps its
+ * relative accuracy.  The sum is divided by the sum of the weights, so a row sums to 1 up to rounding at every `points` (the
+ * weights of 9 points sum to 1.014, those of 65 and more to 1 - 1.3e-15).  cuts [K - 1] float64 on the device, strictly
+ * increasing (not validated here); eta, var [n] float64.  var <= 2^-76 (zero and negative variances included) gives the plain
+ * probability at eta; NaN in eta or var gives a row of NaN.  log_out non-zero: the logarithm of the same number (-inf where it
+ * underflows).  A group of TK lanes (the least power of two >= K) per node, lane k its category.  No workspace, no atomics:
+ * repeated calls are bitwise equal.  Element alignment only.  MGP_ERR_ARG for null eta, var, cuts or out, n < 1, K outside
+ * 2 .. 64 and points even or outside 9 .. 1025.  The checks precede the launch. */
+int mgp_ordinal_predict(const double* eta, const double* var, const double* cuts, int64_t n, int K, int points, int log_out,
+                        double* out, void* stream);
+
 /* The predictive pmf of a count fit (csrc/count_predict.hip, docs/kernels/count_predict.md): per node and count k,
  *   pmf(k) = (2 pi v)^-1/2 int exp(g(x)) dx,   Poisson   g = k (x + a) - exp(x + a) - lgamma(k + 1) - (x - m)^2 / 2v,
  *                                              binomial  g = log C(N, k) - k softplus(-x) - (N - k) softplus(x) - (x - m)^2 / 2v,

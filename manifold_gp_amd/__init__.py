@@ -20,6 +20,7 @@ from . import sampling  # noqa: F401
 from . import classification  # noqa: F401
 from . import counts  # noqa: F401
 from . import evidence  # noqa: F401
+from . import ordinal  # noqa: F401
 
 __version__ = "0.1.0"
 

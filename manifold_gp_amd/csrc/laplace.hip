@@ -36,6 +36,16 @@
 //
 // 6. mgp_scale_rows: out = s_i V_ij or fmaf(s_i, X_ij, V_ij) on row-major [n, P] blocks: the two row scalings around the solve in a
 //    product with B = I + S Q2^-1 S.  Both are bandwidth-trivial and launch-bound at 60k nodes.
+//
+// 7. mgp_ordinal_site: the likelihood stage of an ordered-category fit (ordinal.laplace_fit_ordinal, docs/kernels/ordinal.md), the
+//    layout and the sums of kernel 4 with the node's interval of cutpoints (lo, hi] in the place of (y, aux): u = hi - f,
+//    l = lo - f, log p = log sigma(u) + log sigma(-l) (the product form of sigma(u) - sigma(l), its f-independent factor left
+//    to the caller), g = sigma(l) - sigma(-u), h = sigma(u) sigma(-u) + sigma(l) sigma(-l) in (0, 1/2].  The ends may be infinite.
+//
+// 8. mgp_ordinal_predict: out_ik = int P(y = k | f) N(f; eta_i, var_i) df for the K ordered categories by the trapezoid rule of
+//    kernel 2, the integrand in the product form (every term positive: a tail category keeps its relative accuracy), the sum
+//    divided by the sum of the weights (rows sum to 1).  A group of TK lanes per node as kernel 3, lane k its category: one exp
+//    per lane and point, the lower cut's factor from lane k - 1 by a shuffle.
 #include <cfloat>
 
 #include "mgp_common.h"
@@ -297,6 +307,131 @@ __global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restr
   }
 }
 
+// one node of mgp_ordinal_site: the category is the interval (lo32, hi32] of cutpoints, -inf / +inf at the end categories.
+// exp(-|x|) is 0 at an infinite end, so sigma, log sigma and sigma (1 - sigma) need no special case there
+__device__ __forceinline__ void ordinal_node(float f32, float qf32, float lo32, float hi32, bool obs, double s_ref, float& w,
+                                             float& rhs, SiteAcc& acc) {
+  const double f = (double)f32, qf = (double)qf32;
+  double g = 0.0, h = 0.0;
+  if (obs) {
+    const double u = (double)hi32 - f, l = (double)lo32 - f;
+    const double eu = exp(-fabs(u)), el = exp(-fabs(l));
+    const double du = 1.0 + eu, dl = 1.0 + el;
+    acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu)) - ((l > 0.0 ? l : 0.0) + log1p(el));   // log sigma(u) + log sigma(-l)
+    g = (l >= 0.0 ? 1.0 / dl : el / dl) - (u >= 0.0 ? eu / du : 1.0 / du);               // sigma(l) - sigma(-u)
+    h = eu / (du * du) + el / (dl * dl);
+  }
+  const double r = g - qf;
+  w = (float)(s_ref * h);
+  rhs = (float)(s_ref * r);
+  acc.fq += f * qf;
+  const double ar = fabs(r);
+  acc.mx = ar > acc.mx ? ar : acc.mx;
+  acc.sq += r * r;
+}
+
+// the layout of count_site_kernel: lo and hi in the place of y and aux, read where a node of the quad is observed
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void ordinal_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
+                                                              const float* __restrict__ lo, const float* __restrict__ hi,
+                                                              const uint8_t* __restrict__ obs, int64_t n, double s_ref,
+                                                              float* __restrict__ w, float* __restrict__ rhs,
+                                                              double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : zero;
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 lv = any ? *reinterpret_cast<const float4*>(lo + i0) : zero;
+      const float4 hv = any ? *reinterpret_cast<const float4*>(hi + i0) : zero;
+      float4 wv, rv;
+      ordinal_node(fv.x, qv.x, lv.x, hv.x, ov.x != 0, s_ref, wv.x, rv.x, acc);
+      ordinal_node(fv.y, qv.y, lv.y, hv.y, ov.y != 0, s_ref, wv.y, rv.y, acc);
+      ordinal_node(fv.z, qv.z, lv.z, hv.z, ov.z != 0, s_ref, wv.z, rv.z, acc);
+      ordinal_node(fv.w, qv.w, lv.w, hv.w, ov.w != 0, s_ref, wv.w, rv.w, acc);
+      *reinterpret_cast<float4*>(w + i0) = wv;
+      *reinterpret_cast<float4*>(rhs + i0) = rv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float wi, ri;
+        ordinal_node(f[i], qf ? qf[i] : 0.f, o ? lo[i] : 0.f, o ? hi[i] : 0.f, o, s_ref, wi, ri, acc);
+        w[i] = wi;
+        rhs[i] = ri;
+      }
+    }
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
+constexpr double kOrdinalVMin = 0x1p-76;  // below it the rule and the plain probability at eta agree to 2^-77 relative
+
+// sigma(up - f) sigma(f - b_k) of lane k's category at the latent value f: the lane forms e = exp(-|up - f|) once, keeps
+// sigma(up - f) and hands sigma(f - up), the lower factor of category k + 1, to the next lane of its group.  up = +inf (the last
+// category, idle lanes) gives the factor 1; lane 0 has no lower cut.  Every lane of the wave calls it.
+template <int TK>
+__device__ __forceinline__ double ordinal_term(double up, double f, int k) {
+  const double x = up - f;
+  const double e = exp(-fabs(x));
+  const double d = 1.0 + e;
+  const double below = x >= 0.0 ? 1.0 / d : e / d;                     // sigma(up - f)
+  const double above = x >= 0.0 ? e / d : 1.0 / d;                     // sigma(f - up)
+  const double lower = __shfl_up(above, 1, TK);
+  return k == 0 ? below : below * lower;
+}
+
+// a group of TK lanes per node, lane k its category (softmax_rows.h); the weight table as bernoulli_predict_kernel fills it
+template <int TK>
+__global__ __launch_bounds__(kBlock) void ordinal_predict_kernel(const double* __restrict__ eta, const double* __restrict__ var,
+                                                                 const double* __restrict__ cuts, int64_t n, int K, int points,
+                                                                 int log_out, double* __restrict__ out) {
+  __shared__ double s_u[kMaxPoints];
+  __shared__ double s_wt[kMaxPoints];
+  const double step = 16.0 / (double)(points - 1);
+  for (int j = threadIdx.x; j < points; j += kBlock) {
+    const double u = -8.0 + (double)j * step;
+    s_u[j] = u;
+    s_wt[j] = step * (0.3989422804014327 * exp(-0.5 * u * u));         // D phi(u_j), 1 / sqrt(2 pi)
+  }
+  __syncthreads();
+  double total = 0.0;                                                  // the sum of the weights, j ascending
+  for (int j = 0; j < points; ++j) total += s_wt[j];
+  constexpr int kRows = kBlock / TK;                                   // nodes a workgroup takes per step
+  const int k = threadIdx.x & (TK - 1), g = threadIdx.x / TK;
+  const double up = k < K - 1 ? cuts[k] : INFINITY;
+  const double c = (k >= 1 && k < K - 1) ? -expm1(-(up - cuts[k - 1])) : 1.0;
+  const int64_t stride = (int64_t)gridDim.x * kRows;
+  const int64_t steps = (n + stride - 1) / stride;                     // the same for every lane: the shuffles stay convergent
+  for (int64_t s = 0; s < steps; ++s) {
+    const int64_t i = s * stride + (int64_t)blockIdx.x * kRows + g;
+    const bool node = i < n;
+    const double m = node ? eta[i] : 0.0;
+    const double v = node ? var[i] : 0.0;
+    const bool plain = v <= kOrdinalVMin;                              // (a NaN variance is not: sqrt keeps it)
+    const double sd = plain ? 0.0 : sqrt(v);
+    double p = 0.0;
+    for (int j = 0; j < points; ++j) p += s_wt[j] * ordinal_term<TK>(up, m + sd * s_u[j], k);
+    const double at_eta = ordinal_term<TK>(up, m, k);
+    if (!node || k >= K) continue;                                     // (after the group's shuffles)
+    const double r = c * (plain ? at_eta : p / total);
+    out[i * (int64_t)K + k] = log_out ? log(r) : r;
+  }
+}
+
 // one node of mgp_laplace_evidence_site at the mode.  FAMILY 0: Poisson (a32 the log-exposure), 1: binomial (a32 the trials),
 // 2: Bernoulli-logit (one trial, y the label).  acc: lp = sum l, fq = nodes kept, sq = sum corr, mx = max |corr|
 template <int FAMILY>
@@ -541,6 +676,42 @@ extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, c
   }
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_ordinal_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_ordinal_site(const float* f, const float* qf, const float* lo, const float* hi, const uint8_t* obs, int64_t n,
+                                double s_ref, float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream) {
+  if (!f || !lo || !hi || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_ordinal_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(lo, 16) && aligned_to(hi, 16) && aligned_to(obs, 4) &&
+                    aligned_to(w, 16) && aligned_to(rhs, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (vec4)
+    hipLaunchKernelGGL(ordinal_site_kernel<true>, grid, block, 0, st, f, qf, lo, hi, obs, n, s_ref, w, rhs, partials);
+  else
+    hipLaunchKernelGGL(ordinal_site_kernel<false>, grid, block, 0, st, f, qf, lo, hi, obs, n, s_ref, w, rhs, partials);
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" int mgp_ordinal_predict(const double* eta, const double* var, const double* cuts, int64_t n, int K, int points,
+                                   int log_out, double* out, void* stream) {
+  if (!eta || !var || !cuts || !out || n < 1 || K < 2 || K > 64) return MGP_ERR_ARG;
+  if (points < 9 || points > kMaxPoints || (points & 1) == 0) return MGP_ERR_ARG;
+  const int blocks = mgp_softmax_blocks(n, K, kBlock, kPredictMaxBlocks);
+  hipStream_t st = mgp_stream(stream);
+  mgp_softmax_dispatch(K, [&](auto tk) {
+    hipLaunchKernelGGL(ordinal_predict_kernel<decltype(tk)::value>, dim3((unsigned)blocks), dim3(kBlock), 0, st, eta, var, cuts, n,
+                       K, points, log_out, out);
+  });
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

@@ -178,6 +178,16 @@ class RiemannGP(torch.nn.Module):
         desc, _, y = self._sampling_args()
         return laplace_fit_counts(desc, y, observed, **kw)
 
+    def laplace_posterior_ordinal(self, num_categories, cutpoints=None, observed=None, **kw):
+        """Ordered categories at the graph nodes: train_targets are categories in [0, num_categories), read at `observed`
+        (bool [N]; None: every node; NaN allowed elsewhere).  The Laplace approximation of the latent posterior under a
+        cumulative-logit likelihood with the fixed cutpoints (None: ordinal.ordinal_cutpoints of the observed labels), an
+        ordinal.OrdinalLaplaceFit (mode, latent variances and samples, category probabilities); kw as
+        ordinal.laplace_fit_ordinal.  The Gaussian likelihood's noise is not used."""
+        from ..ordinal import laplace_fit_ordinal
+        desc, _, y = self._sampling_args()
+        return laplace_fit_ordinal(desc, y, num_categories, cutpoints, observed, **kw)
+
     def _laplace_fit(self, observed, family, **kw):
         """The binary fit (family "bernoulli") or the count fit ("poisson", "binomial") of train_targets."""
         if family == "bernoulli":
