@@ -514,7 +514,8 @@ int mgp_cg_solve(const mgp_operator_t* op, const float* B, int C, float* X, cons
                  const mgp_cg_params_t* params, int32_t* iters, float* resid, void* work,
                  size_t work_bytes, void* stream);
 /* cheap Jacobi preconditioner: minv_i = 1 / A_ii with the polynomial's off-diagonal
- * contributions to the diagonal ignored for nu > 2 (exact for nu <= 2) */
+ * contributions to the diagonal ignored for nu > 2 (exact for nu <= 2, forms 0 / 2 / 3; entries with col == row, the self
+ * edges of a graph with coincident points, count as part of the row's diagonal: A_ii = tau + diag_i - sum S_ii) */
 int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* stream);
 
 /* The operator in float64 from the float32 matrix: Y = A X for X, Y [n,C] float64 (device, X != Y), every product and sum of

@@ -344,21 +344,28 @@ extern "C" int mgp_operator_apply_dot(const mgp_operator_t* op, const float* X, 
   return mgp_operator_apply_ex(op, X, C, Y, dotw, dot_partials, nullptr, nullptr, work, work_bytes, stream);
 }
 
-// Jacobi: diag(A).  For the chain B = tau I + L_sym: diag(B) = tau + diag_i; diag(B^2)_i =
-// (tau + diag_i)^2 + sum_j S_ij^2 (exact); for nu > 2 the pure diagonal power is used.
-__global__ void jacobi_kernel(int64_t n, const int32_t* __restrict__ rowptr, const float* __restrict__ vals,
-                              const float* __restrict__ diag, const float* __restrict__ pre,
-                              const float* __restrict__ post, int nu, float tau, float scale, int form,
-                              float noise, const float* __restrict__ obs_w, float* __restrict__ minv) {
+// Jacobi: diag(A).  For the chain B = tau I + L_sym, L_sym = diag - S with S the stored entries: the entries of row i
+// with col == row are the row's own diagonal part (a self edge of a graph with coincident points sits there twice, with
+// its value; padding sits there with value 0), so b_i = tau + diag_i - sum_{col == i} S_ii.  diag(B)_i = b_i; diag(B^2)_i =
+// b_i^2 + sum_{j != i} S_ij^2: both exact.  For nu > 2 the pure diagonal power b_i^nu is used.
+__global__ void jacobi_kernel(int64_t n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                              const float* __restrict__ vals, const float* __restrict__ diag,
+                              const float* __restrict__ pre, const float* __restrict__ post, int nu, float tau,
+                              float scale, int form, float noise, const float* __restrict__ obs_w,
+                              float* __restrict__ minv) {
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < n;
        r += (int64_t)gridDim.x * blockDim.x) {
-    const float b = tau + diag[r];
+    float own = 0.f, s2 = 0.f;
+    for (int i = rowptr[r]; i < rowptr[r + 1]; ++i) {
+      const float v = vals[i];
+      if (col[i] == (int)r) own += v;
+      else s2 = fmaf(v, v, s2);
+    }
+    const float b = tau + diag[r] - own;
     float q;
     if (nu == 1) {
       q = b;
     } else if (nu == 2) {
-      float s2 = 0.f;
-      for (int i = rowptr[r]; i < rowptr[r + 1]; ++i) s2 = fmaf(vals[i], vals[i], s2);
       q = b * b + s2;
     } else {
       q = powf(b, (float)nu);
@@ -382,7 +389,7 @@ extern "C" int mgp_operator_jacobi(const mgp_operator_t* op, float* minv, void* 
   int64_t grid = mgp_cdiv(op->L.n, 256);
   if (grid > 4096) grid = 4096;
   hipLaunchKernelGGL(jacobi_kernel, dim3((int)grid), dim3(256), 0, mgp_stream(stream), op->L.n, op->L.rowptr,
-                     op->L.vals, op->L.diag, op->pre, op->post, op->nu, tau, op->scale, op->form, op->noise,
+                     op->L.col, op->L.vals, op->L.diag, op->pre, op->post, op->nu, tau, op->scale, op->form, op->noise,
                      op->form == 3 ? op->obs_w : nullptr, minv);
   MGP_LAUNCH_CHECK();
   return MGP_OK;

@@ -69,6 +69,17 @@ def build_tiles(n, rowptr, col, nnz, tile_rows=None, order=None):
     return None
 
 
+def require_no_self_edges(graph, stage):
+    """ValueError for a stage that reads the matrix entry by entry and takes col == row for padding: on a graph with self edges
+    it would compute from another matrix than the one the products and solves apply (diag - S - S^T, whose diagonal is
+    diag_i - 2 S_ii).  Raised on the host, before any launch."""
+    count = int(getattr(graph, "self_edges", 0))
+    if count:
+        raise ValueError("%s is not defined on a graph with self edges: %d coincident node%s (a repeated point whose k-NN list "
+                         "does not start with itself, or an edge (i, i) of the caller's list); remove the repeated points first"
+                         % (stage, count, "" if count == 1 else "s"))
+
+
 WIDE_CHAIN = [True]         # wide products on the chain-relabelled matrix where it pays (KnnGraph.wide_relabelled)
 WIDE_CHAIN_MIN_NODES = 4096
 WIDE_CHAIN_MAX_NODES = 400000
@@ -157,6 +168,10 @@ class KnnGraph:
         self.rowptr, self.col, self.d2, self.eid = rowptr, col, d2, eid
         self.M = int(tri_val.shape[0])
         self.nnz = int(col.shape[0])
+        # edges (i, i): coincident points, whose own index is not first in their k-NN list (the reference drops column 0 whoever
+        # it names), or a caller's edge list.  Each sits twice in row i of the CSR with col == row and a non-zero value; the
+        # stages that cannot tell such an entry from padding refuse the graph by this count (require_no_self_edges)
+        self.self_edges = int((tri_row == tri_col).sum()) if self.M else 0
         self._edge_index = None
         if isinstance(tiles, str):          # "auto": build on the device the CSR lives on (host tensors: none)
             tiles = build_tiles_auto(self.n, rowptr, col, self.nnz, points) if col.is_cuda else None
@@ -172,6 +187,12 @@ class KnnGraph:
     @property
     def device(self):
         return self.tri_val.device
+
+    def self_edge_index(self):
+        """Positions in the edge list of the edges (i, i): int64 [self_edges] on the graph's device (cached)."""
+        if getattr(self, "_self_edge_index", None) is None:
+            self._self_edge_index = torch.nonzero(self.tri_row == self.tri_col).view(-1)
+        return self._self_edge_index
 
     def csr_with(self, vals, diag, tile_vals=None, mt=None):
         """mgp_csr_t over this graph's structure with the given entry values / diagonal (tile_vals: the
@@ -299,6 +320,7 @@ class RelabelledGraph:
         t = g.tiles if tiles is None else tiles         # (tiles: an ordered 64-row tile view of g over another order, see wide_relabelled)
         dev = g.device
         self.n, self.nnz, self.M, self.spmv_lanes = g.n, g.nnz, g.M, g.spmv_lanes
+        self.self_edges = g.self_edges
         self.device = dev
         self.order = t["rowid"].long()                                  # new position -> caller's node id
         self.inv = torch.empty_like(self.order)

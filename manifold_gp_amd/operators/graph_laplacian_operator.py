@@ -72,6 +72,8 @@ class GraphLaplacianOperator(LinearOperator):
 
     @property
     def laplacian_diag(self):
+        """The reference's `laplacian_diag` ARRAY (graph_laplacian_operator.py:92-97), the `diag` of `diag v - S v - S^T v`.  On a
+        graph with self edges it is not the diagonal of the applied matrix: that is diagonal()."""
         return self.data.diag
 
     @property
@@ -79,7 +81,13 @@ class GraphLaplacianOperator(LinearOperator):
         return self.data.edge_values(2)
 
     def _diagonal(self):
-        return self.laplacian_diag
+        """The diagonal of the applied matrix diag - S - S^T (the same for both normalisations): the `diag` array, less 2 S_ii
+        at the nodes with a self edge (i, i)."""
+        d, g = self.data, self.graph
+        if not g.self_edges:
+            return d.diag
+        e = g.self_edge_index()
+        return d.diag.index_add(0, g.tri_row.index_select(0, e).long(), -2.0 * d.edge_values(2).index_select(0, e))
 
     # ---- hooks
     def _mode(self):

@@ -29,6 +29,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream
+from .graph import require_no_self_edges
 
 CHUNK = 256          # columns per noise launch / solve (the operator and CG paths take at most 256)
 NODE_TAGS = (0, 2, 3)
@@ -67,6 +68,9 @@ def gmrf_noise(data, S, seed, offset=0, node_coef=1.0, tag=0, edges=False):
     if tag not in NODE_TAGS:
         raise ValueError("tag must be one of %s (tag 1 is the edge stream), got %r" % (NODE_TAGS, tag))
     g = data.graph
+    if edges:
+        # the factor G = [sqrt(tau) I | E] is that of diag - S - S^T over edges between two nodes
+        require_no_self_edges(g, "the edge factor of the GMRF noise (samples at odd nu)")
     csr = _lib.csr_struct(g.n, g.rowptr, g.col, data.vals, data.diag, lanes=g.spmv_lanes)
     Y = torch.empty(g.n, S, dtype=torch.float32, device=g.device)
     check(lib().mgp_gmrf_noise(ctypes.byref(csr), ptr(data.dsqrt), float(node_coef), int(tag), int(bool(edges)),
@@ -87,6 +91,15 @@ def _check_desc(desc):
             or desc.post.data_ptr() != sq.data_ptr()):
         raise NotImplementedError("sampling of masked (Schur-complement) descriptors is not supported")
     return sq
+
+
+def _check_draws(desc):
+    """_check_desc for a caller that draws z ~ N(0, Q2): at odd nu that needs the edge factor, refused on a graph with self
+    edges here, ahead of everything else, as gmrf_noise refuses it."""
+    P = _check_desc(desc)
+    if int(desc.nu) % 2:
+        require_no_self_edges(desc.data.graph, "the edge factor of the GMRF noise (samples at odd nu)")
+    return P
 
 
 def _tau(desc):
@@ -124,7 +137,7 @@ def _solve_kw(tol, refine, max_iter):
 
 def precision_samples(desc, S, seed=None):
     """z ~ N(0, Q2): [S, n] float32."""
-    P = _check_desc(desc)
+    P = _check_draws(desc)
     S, seed = _count(S), _seed(seed)
     out = torch.empty(S, desc.n, dtype=torch.float32, device=desc.data.graph.device)
     with torch.no_grad():
@@ -137,7 +150,7 @@ def precision_samples(desc, S, seed=None):
 def prior_samples(desc, S, seed=None, tol=1e-5, refine=0, max_iter=5000):
     """f ~ N(0, Q2^-1): [S, n] float32 (CG solves with A^k to `tol`, true relative residual per column)."""
     from .solvers import cg_solve
-    P = _check_desc(desc)
+    P = _check_draws(desc)
     S, seed = _count(S), _seed(seed)
     nu = int(desc.nu)
     k = (nu + 1) // 2 if nu % 2 else nu // 2
@@ -230,7 +243,7 @@ def _observed_rhs(desc, P, ob, yv, C, seed, offset):
 def posterior_rhs(desc, y, noise, C, seed, offset=0, observed=None):
     """y + s z + sqrt(s) w2 for the columns offset .. offset + C - 1 (the perturbed right-hand side of posterior_samples).
     With observed= or a per-node noise [n]: W y + s_ref z + sqrt(s_ref) W^1/2 w2, the right-hand side of form 3."""
-    P = _check_desc(desc)
+    P = _check_draws(desc)
     one = observed is None and not (torch.is_tensor(noise) and noise.numel() != 1)
     ob = None if one else _observation(desc, noise, observed)         # (one noise, every node: unchecked, as before)
     if ob is not None:
@@ -249,7 +262,7 @@ def posterior_samples(desc, y, noise, S, seed=None, noisy=False, tol=1e-5, refin
     observed (bool [n]) and / or noise as a tensor [n] of per-node variances: f | y_observed ~ N(A3^-1 W y, (Q2 + W / s_ref)^-1)
     at every node (form 3); targets at unobserved nodes are not read (NaN allowed); noisy=True adds sigma_i w3 at every node."""
     from .solvers import cg_solve
-    P = _check_desc(desc)
+    P = _check_draws(desc)
     S, seed = _count(S), _seed(seed)
     ob = _observation(desc, noise, observed)
     kw = _solve_kw(tol, refine, max_iter)
@@ -298,7 +311,9 @@ RB_MAX_NU = 3        # mgp_operator_diag_exact: the exact diagonal of A3 exists 
 
 
 def operator_diag_exact(desc):
-    """The exact diagonal of a form 0 / 2 / 3 descriptor (nu <= 3): [n] float64 on the graph's device."""
+    """The exact diagonal of a form 0 / 2 / 3 descriptor (nu <= 3): [n] float64 on the graph's device.  ValueError on a graph
+    with self edges (the kernel reads col == row as padding)."""
+    require_no_self_edges(desc.data.graph, "the exact operator diagonal (Rao-Blackwell variances)")
     op = desc.struct()
     dev = desc.data.graph.device
     d = torch.empty(desc.n, dtype=torch.float64, device=dev)
@@ -338,12 +353,14 @@ def posterior_variance(desc, noise, S=64, seed=None, observed=None, method="rao-
     "samples", the plain mean_s delta_is^2 (any nu).  se_i = sqrt((mean e^4 - (mean e^2)^2) / S) of the averaged term.
     noise / observed as in posterior_samples; noisy=True adds the noise variance sigma_i^2 (the variance of y*)."""
     from .solvers import cg_solve
-    P = _check_desc(desc)
+    P = _check_draws(desc)
     S, seed = _count(S), _seed(seed)
     if method not in ("rao-blackwell", "samples"):
         raise ValueError("method must be 'rao-blackwell' or 'samples', got %r" % (method,))
-    ob = _observation(desc, noise, observed)
     rb = method == "rao-blackwell"
+    if rb and int(desc.nu) <= RB_MAX_NU:
+        require_no_self_edges(desc.data.graph, "the exact operator diagonal (Rao-Blackwell variances)")
+    ob = _observation(desc, noise, observed)
     if rb and int(desc.nu) > RB_MAX_NU:
         raise NotImplementedError("method='rao-blackwell' needs the exact diagonal of the system, which exists for nu <= %d "
                                   "(nu = %d): use method='samples'" % (RB_MAX_NU, int(desc.nu)))
