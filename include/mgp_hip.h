@@ -601,6 +601,28 @@ size_t mgp_count_site_workspace_bytes(int64_t n);
 int mgp_count_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
                    double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work, size_t work_bytes,
                    void* stream);
+/* Overdispersed counts (csrc/laplace.hip, docs/kernels/counts.md): the likelihood stage of one Newton step of
+ * counts.laplace_fit_counts(family="negative_binomial"), y_i ~ NB(mean mu_i = E_i exp(f_i + mean), dispersion r),
+ * Var y = mu + mu^2 / r, with the contract of mgp_count_site.  f, qf (NULL: zeros), obs (NULL: every node) as there; y [n] counts
+ * and aux [n], the float32 log-exposure (NULL: zeros), are read at observed nodes only (NaN allowed elsewhere).  dispersion: one
+ * finite scalar in [2^-10, 2^20].  Per observed node in float64 from the float32 inputs, z = f + mean + aux - log r (so that
+ * pi = sigma(z) = mu / (r + mu)), e = exp(-|z|), d = 1 + e:
+ *     pi = z >= 0 ? 1 / d : e / d,   1 - pi = z >= 0 ? e / d : 1 / d,
+ *     l = -r (max(z, 0) + log1p(e)) - y (max(-z, 0) + log1p(e)),   g = y (1 - pi) - r pi,   h = (y + r) e / d^2,
+ *     0 < h <= (y + r) / 4      (c(y, r) = lgamma(y + r) - lgamma(r) - lgamma(y + 1) is left to the caller)
+ * the binomial arithmetic of mgp_count_site with y + r trials and r failures at a shifted predictor: no exp of an unclamped
+ * argument, nothing saturates for finite inputs.  (g = h = 0 at unobserved nodes), and
+ *   w_i = (float)(s_ref h_i),   rhs_i = (float)(s_ref (g_i - qf_i)),   both saturated at +-FLT_MAX,
+ *   sums [4] float64 (device) = { sum_obs l,  sum_i f_i qf_i,  max_i |g_i - qf_i|,  sum_i (g_i - qf_i)^2 }.
+ * For finite inputs with |f| <= 1e4 and counts <= 2^24 the first three sums are finite term by term; the fourth may be +inf.
+ * One partial per workgroup and a second launch that adds them: fixed order, no atomics, repeated calls are bitwise equal.
+ * `work`: mgp_nb_site_workspace_bytes(n) bytes, 8-byte aligned.  float4 / uchar4 accesses where f, qf, y, aux, w, rhs
+ * are 16-byte and obs 4-byte aligned, scalar ones otherwise.  MGP_ERR_ARG for null f, y, w, rhs or sums, n < 1 and a dispersion
+ * outside [2^-10, 2^20] (NaN included); MGP_ERR_WORKSPACE for a null, misaligned or short `work`.  The checks precede every
+ * launch. */
+size_t mgp_nb_site_workspace_bytes(int64_t n);
+int mgp_nb_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n, double s_ref,
+                double mean, double dispersion, float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream);
 
 /* Ordered categories at the nodes (csrc/laplace.hip, docs/kernels/ordinal.md): the likelihood stage of one Newton step of
  * ordinal.laplace_fit_ordinal, a cumulative-logit model with one latent function, with the contract of mgp_bernoulli_site.
@@ -661,6 +683,31 @@ int mgp_count_predict_pmf(const double* eta, const double* var, const float* aux
                           int points, int log_out, double* out, void* stream);
 int mgp_count_predict_logpmf(const double* eta, const double* var, const float* aux, const float* y, const uint8_t* at,
                              int64_t n, int family, int points, double* out, void* stream);
+/* The predictive pmf of a negative-binomial fit (csrc/count_predict.hip, docs/kernels/count_predict.md): per node and count k,
+ *   pmf(k) = (2 pi v)^-1/2 int exp(g(x)) dx,   g = c(k, r) - k softplus(-z) - r softplus(z) - (x - m)^2 / 2v,   z = x + a - log r,
+ *   c(k, r) = lgamma(k + r) - lgamma(r) - lgamma(k + 1),
+ * with m = eta_i (the linear predictor at the mode WITHOUT the exposure, float64), v = var_i (float64), a the float32
+ * log-exposure aux_i (NULL: zeros) and r = dispersion, one finite scalar in [2^-10, 2^20].  In the variable z this is the binomial
+ * integrand of mgp_count_predict_pmf with k + r in the place of N, r in the place of N - k and m + a - log r in the place of m, and
+ * the same rule runs on it, all in float64: the mode x* by the safeguarded Newton iteration (bracket: m and log k - a for k > 0,
+ * m - v r and m for k = 0; a step that leaves the bracket or does not halve the last one is a bisection), the window at whose ends
+ * g has dropped by 40, and the `points`-point trapezoid rule of exp(g(x* + t) - g(x*)), t ascending, the difference formed
+ * without cancellation; log pmf = g(x*) + log(h sum / sqrt(2 pi v)).  There is no upper end of the count range.  c(k, r) is formed
+ * from terms of the size of the result: sum_{j < k} log((r + j) / (j + 1)) for k < 32, beyond it Stirling's formula with the two
+ * leading terms of lgamma(k + r) and of the larger of lgamma(r), lgamma(k + 1) combined through log1p (count_predict.md has the
+ * error).  v <= 2^-76 (zero and negative variances included) is the plain log pmf at x = m; NaN in eta, var or y gives NaN.
+ * mgp_nb_predict_pmf writes the counts k0 .. k0 + K - 1 of every node to out [n, K] row-major: the pmf, or its log when
+ * log_out is non-zero; 1 <= K <= 65536, 0 <= k0, k0 + K - 1 <= 2^24.  A wave per (node, 64 counts).
+ * mgp_nb_predict_logpmf writes the log pmf of the one count y_i (a float32 integer in [0, 2^24], not validated) per node to
+ * out [n]; y is read only where `at` [n] bytes is non-zero (NULL: every node), out is NaN at the other nodes.  It is bitwise
+ * the matching entry of mgp_nb_predict_pmf with log_out.
+ * points: odd, 17 .. 257.  No workspace, no atomics: repeated calls are bitwise equal.  Element alignment only.
+ * MGP_ERR_ARG for null eta, var, out (y), n < 1, K, k0 or points out of range and a dispersion outside [2^-10, 2^20] (NaN
+ * included).  The checks precede every launch. */
+int mgp_nb_predict_pmf(const double* eta, const double* var, const float* aux, int64_t n, double dispersion, int64_t k0, int K,
+                       int points, int log_out, double* out, void* stream);
+int mgp_nb_predict_logpmf(const double* eta, const double* var, const float* aux, const float* y, const uint8_t* at, int64_t n,
+                          double dispersion, int points, double* out, void* stream);
 
 /* The Laplace evidence at the mode (csrc/laplace.hip, docs/kernels/evidence.md): the per-node stage of
  * evidence.laplace_evidence.  f [n] the mode, y, aux, obs as mgp_count_site (read in quads that hold an observed node only; NaN
@@ -681,6 +728,22 @@ size_t mgp_laplace_evidence_site_workspace_bytes(int64_t n);
 int mgp_laplace_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var, int64_t n,
                               double mean, int family, double h_floor, float* root_h, float* corr, double* sums, void* work,
                               size_t work_bytes, void* stream);
+/* The same stage for a negative-binomial fit with the dispersion r in [2^-10, 2^20] (mgp_nb_site): f, y, aux (the float32
+ * log-exposure, NULL: zeros), obs, var as above.  Per observed node in float64, z, pi, l and h as mgp_nb_site, and
+ *   h' = dh / df = h ((1 - pi) - pi),  (1 - pi) - pi = -+(-expm1(-|z|)) / (1 + e)  (- for z >= 0),
+ * and, on the observed nodes with h >= h_floor (0 at every other node),
+ *   root_h_i = (float) sqrt(h_i),   corr_i = (float)(var_i h'_i),   both saturated at +-FLT_MAX;
+ *   sums [4] float64 (device) = { sum_obs l,  m = nodes kept,  sum_i corr_i,  max_i |corr_i| }   (corr before the float cast).
+ * corr is not written, and sums 2 and 3 are 0, when var or corr is NULL.  One partial per workgroup and the second launch of
+ * mgp_bernoulli_site: fixed order, no atomics, repeated calls are bitwise equal.  `work`:
+ * mgp_nb_evidence_site_workspace_bytes(n) bytes, 8-byte aligned.  float4 / uchar4 / double2 accesses where f, y, aux, var,
+ * root_h, corr are 16-byte and obs 4-byte aligned, scalar ones otherwise.  MGP_ERR_ARG for null f, y, root_h or sums, n < 1,
+ * h_floor negative or NaN and a dispersion outside [2^-10, 2^20] (NaN included); MGP_ERR_WORKSPACE for a null, misaligned or
+ * short `work`.  The checks precede every launch. */
+size_t mgp_nb_evidence_site_workspace_bytes(int64_t n);
+int mgp_nb_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var, int64_t n,
+                         double mean, double dispersion, double h_floor, float* root_h, float* corr, double* sums, void* work,
+                         size_t work_bytes, void* stream);
 /* Row scaling of a row-major [n, P] float32 block, 1 <= P <= 256:  out_ij = s_i V_ij  (X NULL)  or  fmaf(s_i, X_ij, V_ij).
  * out may be V or X.  float4 accesses where P % 4 == 0 and V, X, out are 16-byte aligned.  MGP_ERR_ARG for null s, V or out,
  * n < 1 and P outside 1 .. 256. */

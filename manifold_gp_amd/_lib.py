@@ -152,13 +152,19 @@ SIGNATURES = {
     "mgp_bernoulli_predict": (c_int, [_P, _P, c_int64, c_int, _P, _P]),
     "mgp_count_site_workspace_bytes": (c_size_t, [c_int64]),
     "mgp_count_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_double, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "mgp_nb_site_workspace_bytes": (c_size_t, [c_int64]),
+    "mgp_nb_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_double, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_ordinal_site_workspace_bytes": (c_size_t, [c_int64]),
     "mgp_ordinal_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_ordinal_predict": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P]),
     "mgp_count_predict_pmf": (c_int, [_P, _P, _P, c_int64, c_int, c_int64, c_int, c_int, c_int, _P, _P]),
     "mgp_count_predict_logpmf": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int, c_int, _P, _P]),
+    "mgp_nb_predict_pmf": (c_int, [_P, _P, _P, c_int64, c_double, c_int64, c_int, c_int, c_int, _P, _P]),
+    "mgp_nb_predict_logpmf": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_int, _P, _P]),
     "mgp_laplace_evidence_site_workspace_bytes": (c_size_t, [c_int64]),
     "mgp_laplace_evidence_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_int, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "mgp_nb_evidence_site_workspace_bytes": (c_size_t, [c_int64]),
+    "mgp_nb_evidence_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_double, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_scale_rows": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P]),
     "mgp_softmax_site_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "mgp_softmax_site": (c_int, [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P, _P, c_size_t, _P]),

@@ -1,10 +1,12 @@
-"""Count data at the graph nodes: the Laplace approximation of a graph Matern GP with a Poisson or a binomial likelihood
-(docs/kernels/counts.md).
+"""Count data at the graph nodes: the Laplace approximation of a graph Matern GP with a Poisson, a binomial or a negative-binomial
+likelihood (docs/kernels/counts.md).
 
 With Q2 the form-0 precision of sampling.py, f the latent function and eta_i = f_i + mean (+ log E_i) the linear predictor,
 
     poisson:   y_i ~ Poisson(E_i exp(eta_i))            l = y eta - mu,                    g = y - mu,               h = mu
     binomial:  y_i ~ Binomial(N_i, sigma(eta_i))        l = y log pi + (N - y) log(1 - pi),  g = y (1 - pi) - (N - y) pi,  h = N pi (1 - pi)
+    negative_binomial:  y_i ~ NB(mean mu_i = E_i exp(eta_i), dispersion r), Var y = mu + mu^2 / r: with pi = mu / (r + mu)
+                                                        l = y log pi + r log(1 - pi),      g = y (1 - pi) - r pi,    h = (y + r) pi (1 - pi)
 
 at the observed nodes (g = h = 0 elsewhere), the mode of psi(f) = sum_obs l_i - 1/2 f^T Q2 f is found by the Newton loop of
 classification.py (_newton): a step solves (H + Q2) delta = g - Q2 f, which multiplied by s_ref is operator form 3 with
@@ -14,7 +16,9 @@ obs_w = s_ref h and noise = s_ref.  The per-node stage is one kernel (mgp_count_
 s_ref is a power of two fixed once per fit from the data, so one CG plan serves every step and (float)(s_ref h) is the scaled
 correctly rounded h: 2^-ceil(log2 max(1, max y)) for Poisson (h = mu is about y at the mode; at a trial point w may exceed
 1, which nothing in form 3 depends on: the operator, its Jacobi diagonal and the CG take any w >= 0) and 4 * 2^-ceil(log2 max N)
-for the binomial (h <= N / 4, so w <= 1; at N = 1 this is the Bernoulli fit's 4).
+for the binomial (h <= N / 4, so w <= 1; at N = 1 this is the Bernoulli fit's 4), and 4 * 2^-ceil(log2 ceil(max y + r)) for the
+negative binomial (h <= (y + r) / 4).  Its dispersion r is one scalar per fit, fixed by the caller: dispersion_profile fits a list
+of candidates and compares their Laplace evidence.
 
 The iteration stops by the size of an accepted full Newton step (step_tol), not by the gradient relative to max |g(0)|:
 for counts max |g(0)| is the size of the largest count, and a gradient rule relative to it stops hundreds of times further
@@ -35,7 +39,9 @@ from . import _lib, sampling
 from ._lib import check, lib, ptr, stream
 from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2, bernoulli_predict
 
-FAMILIES = {"poisson": 0, "binomial": 1}
+FAMILIES = {"poisson": 0, "binomial": 1, "negative_binomial": 2}
+NB = 2                       # the family with entry points of its own (mgp_nb_*): mgp_count_* refuse every code but 0 and 1
+DISPERSION_MIN, DISPERSION_MAX = 2.0 ** -10, 2.0 ** 20
 MAX_COUNT = 2 ** 24          # counts and trials are float32 on the device: integers are exact up to here
 ETA_MAX = 700.0              # mu = exp(min(eta, ETA_MAX)) stays finite in float64
 PMF_POINTS = 65              # the default rule of the predictive pmf (docs/kernels/count_predict.md)
@@ -48,12 +54,28 @@ def _family(family):
     return FAMILIES[family]
 
 
-def count_site(f, qf, y, aux, observed, s_ref, mean, family):
-    """(w, rhs, sums) of mgp_count_site: w = s_ref h and rhs = s_ref (g - qf) as fresh float32 [n] tensors (saturated at
+def _dispersion(fam, dispersion):
+    """float(dispersion) for the negative binomial (required: a finite scalar in [2^-10, 2^20]); None for the other families, which
+    take none"""
+    if fam != NB:
+        if dispersion is not None:
+            raise ValueError("dispersion belongs to the negative_binomial family")
+        return None
+    if dispersion is None:
+        raise ValueError("the negative_binomial family needs dispersion=")
+    r = _real(dispersion, "dispersion")
+    if not DISPERSION_MIN <= r <= DISPERSION_MAX:            # (NaN fails the comparison)
+        raise ValueError("dispersion must be a finite scalar in [2^-10, 2^20], got %r" % (dispersion,))
+    return r
+
+
+def count_site(f, qf, y, aux, observed, s_ref, mean, family, dispersion=None):
+    """(w, rhs, sums) of mgp_count_site (mgp_nb_site for family "negative_binomial", with its dispersion): w = s_ref h and rhs = s_ref (g - qf) as fresh float32 [n] tensors (saturated at
     +-FLT_MAX), sums [4] float64 on the device (sum_obs l without the f-independent constant, sum f qf, max |g - qf|,
     sum (g - qf)^2).  f, y [n] float32; qf [n] or None (zeros); aux [n]: the log-exposure (family "poisson"; None: zeros) or the
     trials (family "binomial"); observed [n] bool or None (every node); mean: the constant added to f in the linear predictor."""
     fam = _family(family)
+    r = _dispersion(fam, dispersion)
     if fam == 1 and aux is None:
         raise ValueError("the binomial family needs the trials in aux")
     _lib.require_device(f, qf, y, aux, observed)
@@ -70,8 +92,12 @@ def count_site(f, qf, y, aux, observed, s_ref, mean, family):
             raise ValueError("%s has %d entries, f %d" % (name, t.shape[0], n))
     w, rhs = torch.empty_like(f), torch.empty_like(f)
     sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_count_site_workspace_bytes(n)
+    wb = lib().mgp_nb_site_workspace_bytes(n) if fam == NB else lib().mgp_count_site_workspace_bytes(n)
     work = _lib.workspace(wb, "count_site", f.device)
+    if fam == NB:
+        check(lib().mgp_nb_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), r, ptr(w), ptr(rhs),
+                                ptr(sums), ptr(work), work.numel(), stream()), "mgp_nb_site")
+        return w, rhs, sums
     check(lib().mgp_count_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), fam, ptr(w),
                                ptr(rhs), ptr(sums), ptr(work), work.numel(), stream()), "mgp_count_site")
     return w, rhs, sums
@@ -96,9 +122,11 @@ def _count_range(kmin, kmax):
     return kmin, kmax
 
 
-def _predict_inputs(eta, var, aux, family):
-    """(family code, eta, var as contiguous float64 [n], aux as contiguous float32 [n] or None), on the device"""
+def _predict_inputs(eta, var, aux, family, dispersion=None):
+    """(family code, eta, var as contiguous float64 [n], aux as contiguous float32 [n] or None, the dispersion or None), on the
+    device"""
     fam = _family(family)
+    r = _dispersion(fam, dispersion)
     if fam == 1 and aux is None:
         raise ValueError("the binomial family needs the trials in aux")
     _lib.require_device(eta, var, aux)
@@ -108,32 +136,37 @@ def _predict_inputs(eta, var, aux, family):
     for name, t in (("var", var), ("aux", aux)):
         if t is not None and t.shape[0] != eta.shape[0]:
             raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], eta.shape[0]))
-    return fam, eta, var, aux
+    return fam, eta, var, aux, r
 
 
-def count_predict_pmf(eta, var, aux, family, kmin, kmax, points=PMF_POINTS, log=False):
+def count_predict_pmf(eta, var, aux, family, kmin, kmax, points=PMF_POINTS, log=False, dispersion=None):
     """The predictive pmf of the counts kmin .. kmax at every node: [n, kmax - kmin + 1] float64 (mgp_count_predict_pmf), its
     log with log=True.  eta [n]: the linear predictor at the mode without the exposure, var [n]: the latent marginal variance
     (both taken as float64; var <= 2^-76, negative entries included: the plain pmf at eta); aux [n] as count_site takes it:
-    the log-exposure (family "poisson"; None: zeros) or the trials (family "binomial").  At most 65536 counts per call."""
+    the log-exposure (family "poisson" and "negative_binomial", the latter with its dispersion, mgp_nb_predict_pmf; None: zeros)
+    or the trials (family "binomial").  At most 65536 counts per call."""
     points = _pmf_points(points)
     kmin, kmax = _count_range(kmin, kmax)
-    fam, eta, var, aux = _predict_inputs(eta, var, aux, family)
+    fam, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
     n, K = eta.shape[0], kmax - kmin + 1
     out = torch.empty((n, K), dtype=torch.float64, device=eta.device)
+    if fam == NB:
+        check(lib().mgp_nb_predict_pmf(ptr(eta), ptr(var), ptr(aux), n, r, kmin, K, points, int(bool(log)), ptr(out), stream()),
+              "mgp_nb_predict_pmf")
+        return out
     check(lib().mgp_count_predict_pmf(ptr(eta), ptr(var), ptr(aux), n, fam, kmin, K, points, int(bool(log)), ptr(out), stream()),
           "mgp_count_predict_pmf")
     return out
 
 
-def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS):
+def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS, dispersion=None):
     """The log predictive probability of the one count y_i per node: [n] float64 (mgp_count_predict_logpmf), NaN outside the
     bool mask at [n] (None: every node).  y [n] integers in [0, 2^24] (taken as float32; not read outside at, NaN allowed
-    there); eta, var, aux as count_predict_pmf."""
+    there); eta, var, aux, dispersion as count_predict_pmf."""
     points = _pmf_points(points)
     if at is not None and (not torch.is_tensor(at) or at.dtype != torch.bool):
         raise ValueError("at must be a bool tensor [n]")
-    fam, eta, var, aux = _predict_inputs(eta, var, aux, family)
+    fam, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
     _lib.require_device(y, at)
     n = eta.shape[0]
     y = _lib.f32c(y.reshape(-1))
@@ -142,6 +175,10 @@ def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS):
         if t is not None and t.shape[0] != n:
             raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], n))
     out = torch.empty(n, dtype=torch.float64, device=eta.device)
+    if fam == NB:
+        check(lib().mgp_nb_predict_logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, r, points, ptr(out), stream()),
+              "mgp_nb_predict_logpmf")
+        return out
     check(lib().mgp_count_predict_logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, fam, points, ptr(out), stream()),
           "mgp_count_predict_logpmf")
     return out
@@ -168,9 +205,10 @@ def _ceil_log2(m):
     return (int(m) - 1).bit_length()
 
 
-def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0):
-    """The host-side argument checks of laplace_fit_counts, before any device call.  Returns (y, observed, extra, mean, s_ref)
-    with y and extra (exposure or trials; None: ones) float64 [n] on the device they came on."""
+def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, dispersion=None):
+    """The host-side argument checks of laplace_fit_counts / laplace_fit_negative_binomial, before any device call.  Returns
+    (y, observed, extra, mean, s_ref) with y and extra (exposure or trials; None: ones) float64 [n] on the device they came on.
+    dispersion: the negative binomial's, already checked (_dispersion); it enters s_ref."""
     sampling._check_desc(desc)
     fam = _family(family)
     n = desc.n
@@ -187,9 +225,10 @@ def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0):
     seen = pick(y)
     if not bool(((seen >= 0) & (seen <= MAX_COUNT) & (seen == seen.round())).all()):
         raise ValueError("counts at the observed nodes must all be integers in [0, 2^24]")
-    if fam == 0:
+    if fam != 1:
         if trials is not None:
-            raise ValueError("trials belong to the binomial family; the Poisson family takes exposure")
+            raise ValueError("trials belong to the binomial family; the Poisson %s exposure"
+                             % ("family takes" if fam == 0 else "and negative_binomial families take"))
         extra = None if exposure is None else _node_vector(exposure, n, "exposure")
         if extra is not None and not bool((torch.isfinite(pick(extra)) & (pick(extra) > 0)).all()):
             raise ValueError("exposure at the observed nodes must be finite and positive")
@@ -212,29 +251,37 @@ def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0):
         raise ValueError("step_tol must be positive, got %r" % (step_tol,))
     if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != n):
         raise ValueError("f0 must be a tensor of %d latent values" % n)
-    if fam == 0:
+    if fam != 1:
         total = float(seen.sum())
         if mean is None:
             if total == 0.0:
                 raise ValueError("every observed count is 0: the intercept-only estimate of the mean is -inf; pass mean=")
             mean = math.log(total / (float(seen.numel()) if extra is None else float(pick(extra).sum())))
-        s_ref = 2.0 ** -_ceil_log2(max(1.0, float(seen.max())))
+        if fam == 0:
+            s_ref = 2.0 ** -_ceil_log2(max(1.0, float(seen.max())))
+        else:                                             # h <= (y + r) / 4: w <= 1 as for the binomial
+            s_ref = 4.0 * 2.0 ** -_ceil_log2(math.ceil(float(seen.max()) + dispersion))
     else:
         mean = 0.0 if mean is None else mean
         s_ref = 4.0 * 2.0 ** -_ceil_log2(float(pick(extra).max()))
     return y, observed, extra, float(mean), s_ref
 
 
-def _site64(family, eta, y, extra):
-    """(g, h) in float64 with the formulas of mgp_count_site; eta already holds the mean (and the log-exposure)."""
+def _site64(family, eta, y, extra, dispersion=None):
+    """(g, h) in float64 with the formulas of mgp_count_site / mgp_nb_site; eta already holds the mean (and the log-exposure)."""
     if family == "poisson":
         mu = torch.exp(eta.clamp_max(ETA_MAX))
         return y - mu, mu
+    if family == "negative_binomial":                     # y + r trials, r failures at z = eta - log r
+        eta, extra = eta - math.log(dispersion), y + dispersion
+        fail = dispersion
+    else:
+        fail = extra - y
     e = torch.exp(-eta.abs())
     d = 1.0 + e
     pi = torch.where(eta >= 0, 1.0 / d, e / d)
     pib = torch.where(eta >= 0, e / d, 1.0 / d)
-    return y * pib - (extra - y) * pi, extra * e / (d * d)
+    return y * pib - fail * pi, extra * e / (d * d)
 
 
 class CountLaplaceFit(LaplaceFit):
@@ -242,15 +289,16 @@ class CountLaplaceFit(LaplaceFit):
     mean [n] float32: the mode f_hat of the latent function (the linear predictor is eta_hat = f_hat + prior_mean, plus the
     log-exposure inside the Poisson rate); converged, iterations; history: one (psi, relative gradient, step, CG iterations)
     per Newton step, psi without the likelihood's constant; log_likelihood: sum_obs log p(y_i | eta_hat_i) with the constant
-    (-lgamma(y + 1) or log C(N, y)); family, prior_mean, s_ref; exposure / trials: float64 [n], 1 where none was given
-    (prediction at unobserved nodes is per unit exposure / per trial there)."""
+    (-lgamma(y + 1), log C(N, y) or lgamma(y + r) - lgamma(r) - lgamma(y + 1)); family, prior_mean, s_ref; dispersion: r of the
+    negative binomial, None otherwise; exposure / trials: float64 [n], 1 where none was given (prediction at unobserved nodes
+    is per unit exposure / per trial there)."""
 
     def __init__(self, desc, y, observed, mean, converged, iterations, history, log_likelihood, family, prior_mean, s_ref,
-                 aux, extra):
+                 aux, extra, dispersion=None):
         super().__init__(desc, y, observed, mean, converged, iterations, history, log_likelihood)
-        self.family, self.prior_mean, self.s_ref = family, prior_mean, s_ref
+        self.family, self.prior_mean, self.s_ref, self.dispersion = family, prior_mean, s_ref, dispersion
         self._aux = aux                       # what the kernel read: float32 log-exposure (or None) / float32 trials
-        if family == "poisson":
+        if family != "binomial":
             self.exposure, self.trials = extra, None
         else:
             self.exposure, self.trials = None, extra
@@ -265,8 +313,9 @@ class CountLaplaceFit(LaplaceFit):
         f = self.mean.double()
         obs = torch.ones_like(f, dtype=torch.bool) if self.observed is None else self.observed
         y = torch.where(obs, self.y.double(), torch.zeros_like(f))
-        if self.family == "poisson":                      # (_aux is finite at every node: laplace_fit_counts)
-            g, h = _site64(self.family, self.eta() if self._aux is None else self.eta() + self._aux.double(), y, None)
+        if self.family != "binomial":                     # (_aux is finite at every node: laplace_fit_counts)
+            g, h = _site64(self.family, self.eta() if self._aux is None else self.eta() + self._aux.double(), y, None,
+                           self.dispersion)
         else:
             g, h = _site64(self.family, self.eta(), y, self._aux.double())
         eff = obs & (h >= H_FLOOR)
@@ -284,9 +333,9 @@ class CountLaplaceFit(LaplaceFit):
         raise NotImplementedError("a count fit has no class probability: see map_mean and predict_mean")
 
     def map_mean(self):
-        """E exp(eta_hat) (Poisson) or N sigma(eta_hat) (binomial): the expected count at the mode, [n] float64 (ignores the
-        latent variance)."""
-        if self.family == "poisson":
+        """E exp(eta_hat) (Poisson, negative binomial) or N sigma(eta_hat) (binomial): the expected count at the mode, [n] float64
+        (ignores the latent variance)."""
+        if self.family != "binomial":
             return self.exposure * torch.exp(self.eta())
         return self.trials * torch.sigmoid(self.eta())
 
@@ -294,6 +343,7 @@ class CountLaplaceFit(LaplaceFit):
         """(mean, var, latent_var): the mean and the variance of a new count at every node under the Laplace posterior, and the
         latent marginal variance v they used (latent_variance(S, seed)[0]); float64 [n] each.
         Poisson, in closed form (the rate is log-normal): m = E exp(eta_hat + v / 2), var = m + m^2 (e^v - 1).
+        Negative binomial, in closed form as well: the same m, var = m + m^2 (e^v - 1) + m^2 e^v / r (E[mu^2] / r on top).
         Binomial: p = int sigma(eta) N(eta; eta_hat, v) d eta by the trapezoid rule of bernoulli_predict (eta_hat as float32, the
         kernel's input format), mean = N p, var = N p (1 - p): the variance of a draw with the success probability p."""
         points = _points(points)
@@ -301,6 +351,9 @@ class CountLaplaceFit(LaplaceFit):
         if self.family == "poisson":
             m = self.exposure * torch.exp(self.eta() + 0.5 * v)
             return m, m + m * m * torch.expm1(v), v
+        if self.family == "negative_binomial":
+            m = self.exposure * torch.exp(self.eta() + 0.5 * v)
+            return m, m + m * m * torch.expm1(v) + m * m * torch.exp(v) / self.dispersion, v
         p = bernoulli_predict(self.eta().float(), v, points)
         return self.trials * p, self.trials * p * (1.0 - p), v
 
@@ -316,10 +369,10 @@ class CountLaplaceFit(LaplaceFit):
         return variance.reshape(-1).to(torch.float64)
 
     def _predict_args(self):
-        """(eta, aux) of the predict kernels.  Poisson: the log-exposure is added to eta in float64 and aux is None -- the
+        """(eta, aux) of the predict kernels.  Poisson and negative binomial: the log-exposure is added to eta in float64 and aux is None -- the
         kernel's float32 log-exposure would cost 1e-7 of the rate, and the pmf would miss predict_mean's mean by as much.
         Binomial: eta and the trials as float32 (integers: exact)."""
-        if self.family == "poisson":
+        if self.family != "binomial":
             return self.eta() + self.exposure.log(), None
         return self.eta(), self.trials.float()
 
@@ -332,7 +385,7 @@ class CountLaplaceFit(LaplaceFit):
         kmin, kmax = _count_range(kmin, kmax)
         v = self._variance(variance, S, seed)
         eta, aux = self._predict_args()
-        return count_predict_pmf(eta, v, aux, self.family, kmin, kmax, points, log), v
+        return count_predict_pmf(eta, v, aux, self.family, kmin, kmax, points, log, self.dispersion), v
 
     def predict_log_density(self, y, at=None, S=64, seed=None, points=PMF_POINTS, variance=None):
         """log P(y_new = y_i) at the nodes of the bool mask at [n] (None: every node) under the Laplace posterior, float64 [n], NaN
@@ -355,7 +408,7 @@ class CountLaplaceFit(LaplaceFit):
         v = self._variance(variance, S, seed)
         _lib.require_device(y, at)
         eta, aux = self._predict_args()
-        return count_predict_logpmf(eta, v, aux, y, at, self.family, points)
+        return count_predict_logpmf(eta, v, aux, y, at, self.family, points, self.dispersion)
 
     def predict_exceedance(self, threshold, S=64, seed=None, points=PMF_POINTS, variance=None):
         """P(y_new > threshold) at every node, float64 [n]: 1 - sum_{k <= threshold} pmf(k) on the pmf block 0 .. max threshold
@@ -384,8 +437,8 @@ class CountLaplaceFit(LaplaceFit):
         """(lo, hi, reached): the equal-tailed predictive interval of a new count at every node -- the quantiles (1 - level) / 2
         and (1 + level) / 2 of the predictive cdf (the least k whose cdf is at least the level), int64 [n] -- from cumulative sums
         of the pmf block 0 .. kmax.  reached [n] bool: False where the upper quantile lies beyond kmax; hi = -1 there (and lo = -1
-        where the lower one does).  kmax defaults to the largest predict_mean mean plus 8 of its standard deviations (Poisson) or
-        the largest number of trials (binomial), capped at 65535."""
+        where the lower one does).  kmax defaults to the largest predict_mean mean plus 8 of its standard deviations (Poisson,
+        negative binomial) or the largest number of trials (binomial), capped at 65535."""
         points = _pmf_points(points)
         level = _real(level, "level")
         if not 0.0 < level < 1.0:
@@ -394,9 +447,12 @@ class CountLaplaceFit(LaplaceFit):
             _, kmax = _count_range(0, kmax)
         v = self._variance(variance, S, seed)
         if kmax is None:
-            if self.family == "poisson":
+            if self.family != "binomial":
                 m = self.exposure * torch.exp(self.eta() + 0.5 * v)
-                top = float((m + 8.0 * (m + m * m * torch.expm1(v)).sqrt()).max())
+                var = m + m * m * torch.expm1(v)
+                if self.family == "negative_binomial":
+                    var = var + m * m * torch.exp(v) / self.dispersion
+                top = float((m + 8.0 * var.sqrt()).max())
             else:
                 top = float(self.trials.max())
             kmax = int(min(math.ceil(top), PMF_MAX_BLOCK - 1)) if math.isfinite(top) else PMF_MAX_BLOCK - 1
@@ -417,11 +473,42 @@ def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, 
     ones); mean: the constant prior mean of the linear predictor, default log(sum_obs y / sum_obs exposure), the
     intercept-only maximum-likelihood estimate.  family "binomial": y_i ~ Binomial(trials_i, sigma(f_i + mean)); trials [n]
     integers >= max(1, y_i) at the observed nodes; mean defaults to 0.  Counts and trials are integers up to 2^24.
+    The negative binomial needs its dispersion and has a front of its own, laplace_fit_negative_binomial; fit_counts takes every
+    family with dispersion=.
     Exposure / trials at unobserved nodes are used by predict_mean where they are valid and count as 1 elsewhere.
     desc: a form-0 precision descriptor as the samplers take.  Stops after an accepted full Newton step with
     max |delta| <= step_tol; every step is a form-3 CG solve to the relative residual cg_tol.  f0 [n]: the start (default 0)."""
+    if _family(family) == NB:
+        raise ValueError("the negative_binomial family needs dispersion=: laplace_fit_negative_binomial(desc, y, dispersion, ...) "
+                         "or fit_counts(..., family=, dispersion=)")
+    return _fit(desc, y, observed, family, exposure, trials, mean, step_tol, max_newton, cg_tol, max_iter, f0, None)
+
+
+def laplace_fit_negative_binomial(desc, y, dispersion, observed=None, exposure=None, mean=None, step_tol=1e-3, max_newton=30,
+                                  cg_tol=1e-3, max_iter=5000, f0=None):
+    """Overdispersed counts: laplace_fit_counts with y_i ~ NB(mean exposure_i exp(f_i + mean), dispersion), variance
+    mean + mean^2 / dispersion.  dispersion: one finite scalar in [2^-10, 2^20], fixed (the Poisson family is its limit
+    dispersion -> inf, 1 is the geometric distribution; dispersion_profile compares candidates by their evidence); exposure, the
+    default mean log(sum_obs y / sum_obs exposure) and every other argument as laplace_fit_counts takes them for Poisson."""
+    return _fit(desc, y, observed, "negative_binomial", exposure, None, mean, step_tol, max_newton, cg_tol, max_iter, f0, dispersion)
+
+
+def fit_counts(desc, y, observed=None, family="poisson", dispersion=None, **kw):
+    """The count fit of any family: family "negative_binomial" with dispersion= (required there, refused elsewhere) goes to
+    laplace_fit_negative_binomial, "poisson" and "binomial" to laplace_fit_counts; kw as those take them."""
+    if _dispersion(_family(family), dispersion) is None:
+        return laplace_fit_counts(desc, y, observed, family, **kw)
+    if kw.get("trials") is not None:
+        raise ValueError("trials belong to the binomial family; the Poisson and negative_binomial families take exposure")
+    kw.pop("trials", None)
+    return laplace_fit_negative_binomial(desc, y, dispersion, observed, **kw)
+
+
+def _fit(desc, y, observed, family, exposure, trials, mean, step_tol, max_newton, cg_tol, max_iter, f0, dispersion):
+    """laplace_fit_counts and laplace_fit_negative_binomial: the checks, the constant of the likelihood and the Newton loop"""
     from .solvers import cg_solve
-    y, observed, extra, mean, s_ref = _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0)
+    r = _dispersion(_family(family), dispersion)
+    y, observed, extra, mean, s_ref = _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, r)
     _lib.require_device(y, f0, extra)
     dev = desc.data.graph.device
     n = desc.n
@@ -434,18 +521,20 @@ def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, 
         extra, aux = torch.ones(n, dtype=torch.float64, device=dev), None
     else:
         extra = extra.to(dev)
-        valid = torch.isfinite(extra) & (extra > 0) if family == "poisson" else (extra >= 1) & (extra == extra.round())
+        valid = torch.isfinite(extra) & (extra > 0) if family != "binomial" else (extra >= 1) & (extra == extra.round())
         extra = torch.where(seen | valid, extra, one)
-        aux = (extra.log() if family == "poisson" else extra).float().contiguous()
+        aux = (extra.log() if family != "binomial" else extra).float().contiguous()
     if family == "poisson":
         const = -float(torch.lgamma(y[seen] + 1.0).sum())
+    elif family == "negative_binomial":
+        const = float(nb_log_constant(y[seen], r).sum())
     else:
         N = extra[seen]
         const = float((torch.lgamma(N + 1.0) - torch.lgamma(y[seen] + 1.0) - torch.lgamma(N - y[seen] + 1.0)).sum())
     y32 = y.float().contiguous()
 
     def site(f, qf):
-        w, rhs, sums = count_site(f, qf, y32, aux, obs, s_ref, mean, family)
+        w, rhs, sums = count_site(f, qf, y32, aux, obs, s_ref, mean, family, r)
         return w, rhs, sums.tolist()                      # the one host read of an evaluation
 
     def solve(w, rhs):
@@ -459,4 +548,65 @@ def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, 
         f, _, sums, converged, its, history = _newton("laplace_fit_counts", site, lambda v: _q2(desc, v), solve,
                                                       torch.zeros(n, dtype=torch.float32, device=dev), start, 0.0, max_newton,
                                                       step_tol=float(step_tol))
-    return CountLaplaceFit(desc, y32, obs, f, converged, its, history, sums[0] + const, family, mean, s_ref, aux, extra)
+    return CountLaplaceFit(desc, y32, obs, f, converged, its, history, sums[0] + const, family, mean, s_ref, aux, extra, r)
+
+
+_STIRLING = (1.0 / 12, -1.0 / 360, 1.0 / 1260, -1.0 / 1680, 1.0 / 1188, -691.0 / 360360)
+
+
+def _stirling_s(x):
+    zi = 1.0 / x
+    z2 = zi * zi
+    s = _STIRLING[5]
+    for c in _STIRLING[4::-1]:
+        s = c + z2 * s
+    return zi * s
+
+
+def nb_log_constant(k, r):
+    """c(k, r) = lgamma(k + r) - lgamma(r) - lgamma(k + 1) of a float64 tensor of counts k and the scalar dispersion r, in the
+    form of the device's nb_const (csrc/count_predict.hip): sum_{j < k} log((r + j) / (j + 1)) for k < 32, Stirling differences
+    beyond it -- no term is larger than the result's scale, where lgamma(k + r) and lgamma(r) are 1.3e7 each at r = 2^20."""
+    k = k.to(torch.float64)
+    r = float(r)
+    small = torch.zeros_like(k)
+    for j in range(31):
+        small = small + torch.where(k > j, torch.full_like(k, math.log((r + j) / (j + 1.0))), torch.zeros_like(k))
+    kk = k.clamp_min(32.0)                                # (the branch not taken stays finite)
+    x = kk + r
+    if r >= 33.0:
+        big_r = (x - 0.5) * torch.log1p(kk / r) + kk * math.log(r) - kk + (_stirling_s(x) - _stirling_s(r)) - torch.lgamma(kk + 1.0)
+    else:
+        big_r = torch.zeros_like(k)
+    y, d = kk + 1.0, r - 1.0
+    big_k = (x - 0.5) * torch.log1p(d / y) + d * torch.log(y) - d + (_stirling_s(x) - _stirling_s(y)) - math.lgamma(r)
+    return torch.where(k < 32.0, small, torch.where(kk + 1.0 <= r, big_r, big_k))
+
+
+def dispersion_profile(desc, y, dispersions, observed=None, exposure=None, mean=None, **kw):
+    """Negative-binomial fits over a list of candidate dispersions and their Laplace evidence: (results, best) with results the
+    list of (r, CountLaplaceFit, LaplaceEvidence) in the order given and best the index of the largest evidence value.  Every fit
+    starts from the mode of the one before it (f0=), and every evidence is taken with the same keyword arguments -- the same
+    seed and probes, so that the Lanczos error of the log-determinant is common to the candidates (up to 512 effective nodes
+    the log-determinant is exact).  kw: keyword arguments of laplace_fit_counts (step_tol, max_newton, cg_tol, max_iter, f0: the
+    first start) and of evidence.laplace_evidence (the others).  Host code only."""
+    from .evidence import laplace_evidence
+    fit_names = ("step_tol", "max_newton", "cg_tol", "max_iter", "f0")
+    fit_kw = {k: v for k, v in kw.items() if k in fit_names}
+    ev_kw = {k: v for k, v in kw.items() if k not in fit_names}
+    for bad in ("family", "dispersion", "trials", "operator"):
+        if bad in ev_kw:
+            raise ValueError("dispersion_profile takes no %s=" % bad)
+    try:
+        candidates = [_dispersion(NB, r) for r in dispersions]
+    except TypeError:
+        raise ValueError("dispersions must be a sequence of scalars")
+    if not candidates:
+        raise ValueError("dispersions is empty")
+    results, f0 = [], fit_kw.pop("f0", None)
+    for r in candidates:
+        fit = laplace_fit_negative_binomial(desc, y, r, observed, exposure, mean, f0=f0, **fit_kw)
+        results.append((r, fit, laplace_evidence(fit, **ev_kw)))
+        f0 = fit.mean
+    values = [float(e.value) for _, _, e in results]
+    return results, max(range(len(values)), key=values.__getitem__)

@@ -28,11 +28,14 @@
 //    the sums of kernel 1 with one more input array.  eta = f + mean (+ log-exposure); Poisson: mu = exp(min(eta, 700)),
 //    l = y eta - mu, g = y - mu, h = mu; binomial with N trials: e = exp(-|eta|), l = -(N - y)(max(eta, 0) + log1p(e))
 //    - y (max(-eta, 0) + log1p(e)), g = y (1 - pi) - (N - y) pi with 1 - pi formed without the subtraction, h = N e / (1 + e)^2.
-//    h is unbounded here: w and rhs saturate at +-FLT_MAX instead of leaving as inf.
+//    h is unbounded here: w and rhs saturate at +-FLT_MAX instead of leaving as inf.  mgp_nb_site is the same kernel's third
+//    family, the negative binomial with dispersion r: the binomial arithmetic with y + r trials and r failures at
+//    z = f + mean + log-exposure - log r, so 0 < h <= (y + r) / 4 and nothing saturates.
 //
 // 5. mgp_laplace_evidence_site: the per-node stage of the Laplace evidence at the mode (evidence.laplace_evidence,
 //    docs/kernels/evidence.md), the layout of kernel 4 for the three families: sqrt(h) and var h' (h' = dh / df) on the observed
 //    nodes with h >= h_floor, 0 elsewhere, and the sums { sum_obs l, nodes kept, sum corr, max |corr| } through the same partials.
+//    mgp_nb_evidence_site: the same kernel's negative-binomial family.
 //
 // 6. mgp_scale_rows: out = s_i V_ij or fmaf(s_i, X_ij, V_ij) on row-major [n, P] blocks: the two row scalings around the solve in a
 //    product with B = I + S Q2^-1 S.  Both are bandwidth-trivial and launch-bound at 60k nodes.
@@ -47,6 +50,7 @@
 //    divided by the sum of the weights (rows sum to 1).  A group of TK lanes per node as kernel 3, lane k its category: one exp
 //    per lane and point, the lower cut's factor from lane k - 1 by a shuffle.
 #include <cfloat>
+#include <cmath>
 
 #include "mgp_common.h"
 #include "mgp_internal.h"
@@ -222,10 +226,12 @@ __device__ __forceinline__ float sat_f32(double v) {
   return (float)(v > m ? m : (v < -m ? -m : v));
 }
 
-// one node of mgp_count_site.  FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials
+// one node of mgp_count_site / mgp_nb_site.  FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials;
+// FAMILY 2: negative binomial with the dispersion r (log_r = log r), a32 the log-exposure: the binomial arithmetic with y + r
+// "trials" and r "failures" at the predictor z = f + mean + a - log r (pi = mu / (r + mu))
 template <int FAMILY>
 __device__ __forceinline__ void count_node(float f32, float qf32, float y32, float a32, bool obs, double s_ref, double mean,
-                                           float& w, float& rhs, SiteAcc& acc) {
+                                           double r_nb, double log_r, float& w, float& rhs, SiteAcc& acc) {
   const double f = (double)f32, qf = (double)qf32;
   double g = 0.0, h = 0.0;
   if (obs) {
@@ -237,9 +243,9 @@ __device__ __forceinline__ void count_node(float f32, float qf32, float y32, flo
       g = y - mu;
       h = mu;
     } else {
-      const double eta = f + mean;
-      const double N = (double)a32;
-      const double m = N - y;                                          // failures: exact, both are integers <= 2^24
+      const double eta = FAMILY == 1 ? f + mean : f + mean + (double)a32 - log_r;
+      const double N = FAMILY == 1 ? (double)a32 : y + r_nb;
+      const double m = FAMILY == 1 ? N - y : r_nb;                     // failures (binomial: exact, both are integers <= 2^24)
       const double e = exp(-fabs(eta));
       const double d = 1.0 + e;
       const double l1 = log1p(e);
@@ -264,7 +270,8 @@ template <bool VEC4, int FAMILY>
 __global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
                                                             const float* __restrict__ y, const float* __restrict__ aux,
                                                             const uint8_t* __restrict__ obs, int64_t n, double s_ref,
-                                                            double mean, float* __restrict__ w, float* __restrict__ rhs,
+                                                            double mean, double r_nb, double log_r,
+                                                            float* __restrict__ w, float* __restrict__ rhs,
                                                             double* __restrict__ partials) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
@@ -280,10 +287,10 @@ __global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restr
       const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : zero;
       const float4 av = (any && aux) ? *reinterpret_cast<const float4*>(aux + i0) : zero;
       float4 wv, rv;
-      count_node<FAMILY>(fv.x, qv.x, yv.x, av.x, ov.x != 0, s_ref, mean, wv.x, rv.x, acc);
-      count_node<FAMILY>(fv.y, qv.y, yv.y, av.y, ov.y != 0, s_ref, mean, wv.y, rv.y, acc);
-      count_node<FAMILY>(fv.z, qv.z, yv.z, av.z, ov.z != 0, s_ref, mean, wv.z, rv.z, acc);
-      count_node<FAMILY>(fv.w, qv.w, yv.w, av.w, ov.w != 0, s_ref, mean, wv.w, rv.w, acc);
+      count_node<FAMILY>(fv.x, qv.x, yv.x, av.x, ov.x != 0, s_ref, mean, r_nb, log_r, wv.x, rv.x, acc);
+      count_node<FAMILY>(fv.y, qv.y, yv.y, av.y, ov.y != 0, s_ref, mean, r_nb, log_r, wv.y, rv.y, acc);
+      count_node<FAMILY>(fv.z, qv.z, yv.z, av.z, ov.z != 0, s_ref, mean, r_nb, log_r, wv.z, rv.z, acc);
+      count_node<FAMILY>(fv.w, qv.w, yv.w, av.w, ov.w != 0, s_ref, mean, r_nb, log_r, wv.w, rv.w, acc);
       *reinterpret_cast<float4*>(w + i0) = wv;
       *reinterpret_cast<float4*>(rhs + i0) = rv;
     } else {
@@ -291,7 +298,8 @@ __global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restr
       for (int64_t i = i0; i < i1; ++i) {
         const bool o = obs ? obs[i] != 0 : true;
         float wi, ri;
-        count_node<FAMILY>(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, s_ref, mean, wi, ri, acc);
+        count_node<FAMILY>(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, s_ref, mean, r_nb, log_r, wi,
+                           ri, acc);
         w[i] = wi;
         rhs[i] = ri;
       }
@@ -433,10 +441,12 @@ __global__ __launch_bounds__(kBlock) void ordinal_predict_kernel(const double* _
 }
 
 // one node of mgp_laplace_evidence_site at the mode.  FAMILY 0: Poisson (a32 the log-exposure), 1: binomial (a32 the trials),
-// 2: Bernoulli-logit (one trial, y the label).  acc: lp = sum l, fq = nodes kept, sq = sum corr, mx = max |corr|
+// 2: Bernoulli-logit (one trial, y the label), 3: negative binomial (a32 the log-exposure, r_nb the dispersion, log_r its log:
+// y + r trials and r failures at z = f + mean + a - log r, as count_node).  acc: lp = sum l, fq = nodes kept, sq = sum corr,
+// mx = max |corr|
 template <int FAMILY>
 __device__ __forceinline__ void evidence_node(float f32, float y32, float a32, bool obs, double var, bool has_var, double mean,
-                                              double h_floor, float& root, float& corr, SiteAcc& acc) {
+                                              double r_nb, double log_r, double h_floor, float& root, float& corr, SiteAcc& acc) {
   root = 0.f;
   corr = 0.f;
   if (!obs) return;
@@ -449,10 +459,10 @@ __device__ __forceinline__ void evidence_node(float f32, float y32, float a32, b
     h = mu;
     hp = mu;
   } else {
-    const double eta = (double)f32 + mean;
-    const double N = FAMILY == 1 ? (double)a32 : 1.0;
-    const double y = FAMILY == 1 ? (double)y32 : (y32 > 0.5f ? 1.0 : 0.0);
-    const double m = N - y;
+    const double eta = FAMILY == 3 ? (double)f32 + mean + (double)a32 - log_r : (double)f32 + mean;
+    const double y = FAMILY == 2 ? (y32 > 0.5f ? 1.0 : 0.0) : (double)y32;
+    const double N = FAMILY == 1 ? (double)a32 : (FAMILY == 3 ? y + r_nb : 1.0);
+    const double m = FAMILY == 3 ? r_nb : N - y;
     const double e = exp(-fabs(eta));
     const double d = 1.0 + e;
     const double l1 = log1p(e);
@@ -480,7 +490,8 @@ template <bool VEC4, int FAMILY>
 __global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __restrict__ f, const float* __restrict__ y,
                                                                const float* __restrict__ aux, const uint8_t* __restrict__ obs,
                                                                const double* __restrict__ var, int64_t n, double mean,
-                                                               double h_floor, float* __restrict__ root_h,
+                                                               double r_nb, double log_r, double h_floor,
+                                                               float* __restrict__ root_h,
                                                                float* __restrict__ corr, double* __restrict__ partials) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   const bool has_var = var != nullptr && corr != nullptr;
@@ -501,10 +512,10 @@ __global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __re
         v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
       }
       float4 rv, cv;
-      evidence_node<FAMILY>(fv.x, yv.x, av.x, ov.x != 0, v0.x, has_var, mean, h_floor, rv.x, cv.x, acc);
-      evidence_node<FAMILY>(fv.y, yv.y, av.y, ov.y != 0, v0.y, has_var, mean, h_floor, rv.y, cv.y, acc);
-      evidence_node<FAMILY>(fv.z, yv.z, av.z, ov.z != 0, v1.x, has_var, mean, h_floor, rv.z, cv.z, acc);
-      evidence_node<FAMILY>(fv.w, yv.w, av.w, ov.w != 0, v1.y, has_var, mean, h_floor, rv.w, cv.w, acc);
+      evidence_node<FAMILY>(fv.x, yv.x, av.x, ov.x != 0, v0.x, has_var, mean, r_nb, log_r, h_floor, rv.x, cv.x, acc);
+      evidence_node<FAMILY>(fv.y, yv.y, av.y, ov.y != 0, v0.y, has_var, mean, r_nb, log_r, h_floor, rv.y, cv.y, acc);
+      evidence_node<FAMILY>(fv.z, yv.z, av.z, ov.z != 0, v1.x, has_var, mean, r_nb, log_r, h_floor, rv.z, cv.z, acc);
+      evidence_node<FAMILY>(fv.w, yv.w, av.w, ov.w != 0, v1.y, has_var, mean, r_nb, log_r, h_floor, rv.w, cv.w, acc);
       *reinterpret_cast<float4*>(root_h + i0) = rv;
       if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
     } else {
@@ -513,7 +524,7 @@ __global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __re
         const bool o = obs ? obs[i] != 0 : true;
         float ri, ci;
         evidence_node<FAMILY>(f[i], o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, (o && has_var) ? var[i] : 0.0, has_var, mean,
-                              h_floor, ri, ci, acc);
+                              r_nb, log_r, h_floor, ri, ci, acc);
         root_h[i] = ri;
         if (has_var) corr[i] = ci;
       }
@@ -665,15 +676,48 @@ extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, c
   hipStream_t st = mgp_stream(stream);
   if (family == 0) {
     if (vec4)
-      hipLaunchKernelGGL((count_site_kernel<true, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+      hipLaunchKernelGGL((count_site_kernel<true, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
+                         partials);
     else
-      hipLaunchKernelGGL((count_site_kernel<false, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+      hipLaunchKernelGGL((count_site_kernel<false, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
+                         partials);
   } else {
     if (vec4)
-      hipLaunchKernelGGL((count_site_kernel<true, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+      hipLaunchKernelGGL((count_site_kernel<true, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
+                         partials);
     else
-      hipLaunchKernelGGL((count_site_kernel<false, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, w, rhs, partials);
+      hipLaunchKernelGGL((count_site_kernel<false, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
+                         partials);
   }
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+// the dispersion of the negative-binomial entry points: one finite scalar in [2^-10, 2^20] (NaN fails the comparison)
+bool nb_dispersion_ok(double r) { return r >= 0x1p-10 && r <= 0x1p20; }
+
+extern "C" size_t mgp_nb_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_nb_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
+                           double s_ref, double mean, double dispersion, float* w, float* rhs, double* sums, void* work,
+                           size_t work_bytes, void* stream) {
+  if (!f || !y || !w || !rhs || !sums || n < 1 || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_nb_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) &&
+                    aligned_to(w, 16) && aligned_to(rhs, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  const double log_r = std::log(dispersion);
+  if (vec4)
+    hipLaunchKernelGGL((count_site_kernel<true, 2>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, dispersion, log_r, w,
+                       rhs, partials);
+  else
+    hipLaunchKernelGGL((count_site_kernel<false, 2>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, dispersion, log_r, w,
+                       rhs, partials);
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
   MGP_LAUNCH_CHECK();
@@ -733,8 +777,9 @@ extern "C" int mgp_laplace_evidence_site(const float* f, const float* y, const f
                     aligned_to(root_h, 16) && aligned_to(corr, 16);
   const dim3 grid((unsigned)blocks), block(kBlock);
   hipStream_t st = mgp_stream(stream);
-#define MGP_EVIDENCE_LAUNCH(V, F) \
-  hipLaunchKernelGGL((evidence_site_kernel<V, F>), grid, block, 0, st, f, y, aux, obs, var, n, mean, h_floor, root_h, corr, partials)
+#define MGP_EVIDENCE_LAUNCH(V, F)                                                                                             \
+  hipLaunchKernelGGL((evidence_site_kernel<V, F>), grid, block, 0, st, f, y, aux, obs, var, n, mean, 0.0, 0.0, h_floor, root_h, \
+                     corr, partials)
   if (family == 0) {
     if (vec4) MGP_EVIDENCE_LAUNCH(true, 0); else MGP_EVIDENCE_LAUNCH(false, 0);
   } else if (family == 1) {
@@ -743,6 +788,33 @@ extern "C" int mgp_laplace_evidence_site(const float* f, const float* y, const f
     if (vec4) MGP_EVIDENCE_LAUNCH(true, 2); else MGP_EVIDENCE_LAUNCH(false, 2);
   }
 #undef MGP_EVIDENCE_LAUNCH
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_nb_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_nb_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
+                                    int64_t n, double mean, double dispersion, double h_floor, float* root_h, float* corr,
+                                    double* sums, void* work, size_t work_bytes, void* stream) {
+  if (!f || !y || !root_h || !sums || n < 1 || !(h_floor >= 0.0) || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_nb_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  if (!var || !corr) var = nullptr, corr = nullptr;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
+                    aligned_to(root_h, 16) && aligned_to(corr, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  const double log_r = std::log(dispersion);
+  if (vec4)
+    hipLaunchKernelGGL((evidence_site_kernel<true, 3>), grid, block, 0, st, f, y, aux, obs, var, n, mean, dispersion, log_r, h_floor,
+                       root_h, corr, partials);
+  else
+    hipLaunchKernelGGL((evidence_site_kernel<false, 3>), grid, block, 0, st, f, y, aux, obs, var, n, mean, dispersion, log_r, h_floor,
+                       root_h, corr, partials);
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
   MGP_LAUNCH_CHECK();

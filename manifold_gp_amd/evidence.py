@@ -27,24 +27,29 @@ from ._lib import check, lib, ptr, stream
 from .classification import H_FLOOR, S_REF
 
 FAMILIES = {"poisson": 0, "binomial": 1, "bernoulli": 2}
+NB_FAMILY, NB = "negative_binomial", 3     # the family with an entry point of its own (mgp_nb_evidence_site)
 DENSE_MAX = 512           # method "auto": the m x m Cholesky up to here
 MAX_COLUMNS = sampling.CHUNK
 
 
 def _family(family):
+    if family == NB_FAMILY:
+        return NB
     if family not in FAMILIES:
-        raise ValueError("family must be one of %s, got %r" % (sorted(FAMILIES), family))
+        raise ValueError("family must be one of %s, got %r" % (sorted(list(FAMILIES) + [NB_FAMILY]), family))
     return FAMILIES[family]
 
 
-def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR):
+def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR, dispersion=None):
     """(root_h, corr, sums) of mgp_laplace_evidence_site at the mode f [n] float32: root_h = sqrt(h) and corr = variance h' as
     fresh float32 [n] tensors (0 off the observed nodes with h >= h_floor; corr None when variance is None), sums [4] float64 on
     the device (sum_obs l without the f-independent constant, m = nodes kept, sum corr, max |corr|).  y [n]; aux [n]: the
-    log-exposure (family "poisson"; None: zeros) or the trials ("binomial"); family "bernoulli" reads y as labels and takes no
-    aux; observed [n] bool or None (every node); variance [n] (taken as float64) or None; mean: the constant of the linear
+    log-exposure (family "poisson" and "negative_binomial", the latter with its dispersion, mgp_nb_evidence_site; None: zeros) or
+    the trials ("binomial"); family "bernoulli" reads y as labels and takes no aux; observed [n] bool or None (every node); variance [n] (taken as float64) or None; mean: the constant of the linear
     predictor."""
     fam = _family(family)
+    from .counts import NB as COUNT_NB, _dispersion
+    r = _dispersion(COUNT_NB if fam == NB else -1, dispersion)       # (the codes differ: 2 is Bernoulli here)
     if fam == 1 and aux is None:
         raise ValueError("the binomial family needs the trials in aux")
     if fam == 2 and aux is not None:
@@ -70,8 +75,13 @@ def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR):
     root_h = torch.empty_like(f)
     corr = None if variance is None else torch.empty_like(f)
     sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_laplace_evidence_site_workspace_bytes(n)
+    wb = lib().mgp_nb_evidence_site_workspace_bytes(n) if fam == NB else lib().mgp_laplace_evidence_site_workspace_bytes(n)
     work = _lib.workspace(wb, "evidence_site", f.device)
+    if fam == NB:
+        check(lib().mgp_nb_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), r, float(h_floor),
+                                         ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),
+              "mgp_nb_evidence_site")
+        return root_h, corr, sums
     check(lib().mgp_laplace_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), fam,
                                           float(h_floor), ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),
           "mgp_laplace_evidence_site")
@@ -221,20 +231,20 @@ class LaplaceEvidence:
 
 
 def _site_of(fit):
-    """(family, mean, aux, s_ref) of a binary or a count fit."""
+    """(family, mean, aux, s_ref, dispersion) of a binary or a count fit."""
     family = getattr(fit, "family", None)
     if family is None:
-        return "bernoulli", 0.0, None, S_REF
-    return family, fit.prior_mean, fit._aux, fit.s_ref
+        return "bernoulli", 0.0, None, S_REF, None
+    return family, fit.prior_mean, fit._aux, fit.s_ref, getattr(fit, "dispersion", None)
 
 
-def _weights(fit, family, mean, aux, s_ref):
+def _weights(fit, family, mean, aux, s_ref, dispersion=None):
     """obs_w = (float)(s_ref h) of the fit's own form-3 system at the mode, from the kernel its Newton steps used."""
     if family == "bernoulli":
         from .classification import bernoulli_site
         return bernoulli_site(fit.mean, None, fit.y, fit.observed, s_ref)[0]
     from .counts import count_site
-    return count_site(fit.mean, None, fit.y, aux, fit.observed, s_ref, mean, family)[0]
+    return count_site(fit.mean, None, fit.y, aux, fit.observed, s_ref, mean, family, dispersion)[0]
 
 
 REFINE_ROUNDS = 4         # refinement rounds of the float64 solves of the gradient (they stop at a true residual of 2 tol)
@@ -268,13 +278,14 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
     if not hasattr(fit, "_pseudo") or fit.mean.dim() != 1:
         raise NotImplementedError("laplace_evidence takes a binary or a count fit")
     desc = fit.desc
-    family, mean, aux, s_ref = _site_of(fit)
+    family, mean, aux, s_ref, dispersion = _site_of(fit)
     grad = operator is not None and needs_grad(*getattr(operator, "_hyper_tensors", lambda: [])())
     with torch.no_grad():
         f = fit.mean
         if grad and variance is None:
             variance = fit.latent_variance(var_samples)[0]
-        root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family)
+        root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family,
+                                          dispersion=dispersion)
         sums = sums.tolist()                              # the one host read of the site stage
         m = int(sums[1])
         if m < 1:
@@ -298,7 +309,7 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
             # 2.4e-6 on the 1546-node dumbbell, cond Q = 1e3; the unrefined factorised solve of the Lanczos products 4.8e-6).
             # Y goes through the float32 operator chain and stays float32 (refined as sampling.posterior_variance solves form 3).
             kw = dict(tol=float(solve_tol), stop_mode=1, max_iter=int(max_iter))
-            w = _weights(fit, family, mean, aux, s_ref)
+            w = _weights(fit, family, mean, aux, s_ref, dispersion)
             d3 = desc.with_(form=3, noise=s_ref, obs_w=w)
             kw3 = dict(kw, jacobi=sampling.OBSERVED_JACOBI[0])
             SZ = scale_rows(root_h, Z)

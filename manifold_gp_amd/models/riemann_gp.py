@@ -170,13 +170,14 @@ class RiemannGP(torch.nn.Module):
 
     def laplace_posterior_counts(self, observed=None, **kw):
         """Counts at the graph nodes: train_targets are counts, read at `observed` (bool [N]; None: every node; NaN allowed
-        elsewhere).  The Laplace approximation of the latent posterior under a Poisson (with exposure=) or a binomial (with
-        trials=) likelihood, a counts.CountLaplaceFit (mode, latent variances and samples, predicted counts); kw as
-        counts.laplace_fit_counts (family, exposure, trials, mean, step_tol, ...).  The Gaussian likelihood's noise is not
+        elsewhere).  The Laplace approximation of the latent posterior under a Poisson (with exposure=), a binomial (with
+        trials=) or a negative-binomial (family="negative_binomial" with dispersion= and exposure=) likelihood, a
+        counts.CountLaplaceFit (mode, latent variances and samples, predicted counts); kw as counts.laplace_fit_counts (family,
+        dispersion, exposure, trials, mean, step_tol, ...).  The Gaussian likelihood's noise is not
         used."""
-        from ..counts import laplace_fit_counts
+        from ..counts import fit_counts
         desc, _, y = self._sampling_args()
-        return laplace_fit_counts(desc, y, observed, **kw)
+        return fit_counts(desc, y, observed, **kw)
 
     def laplace_posterior_ordinal(self, num_categories, cutpoints=None, observed=None, **kw):
         """Ordered categories at the graph nodes: train_targets are categories in [0, num_categories), read at `observed`
@@ -189,15 +190,15 @@ class RiemannGP(torch.nn.Module):
         return laplace_fit_ordinal(desc, y, num_categories, cutpoints, observed, **kw)
 
     def _laplace_fit(self, observed, family, **kw):
-        """The binary fit (family "bernoulli") or the count fit ("poisson", "binomial") of train_targets."""
+        """The binary fit (family "bernoulli") or the count fit ("poisson", "binomial", "negative_binomial") of train_targets."""
         if family == "bernoulli":
             return self.laplace_posterior(observed, **kw)
         return self.laplace_posterior_counts(observed, family=family, **kw)
 
     def laplace_evidence(self, observed=None, family="bernoulli", **kw):
-        """Fit the nodes (family "bernoulli": laplace_posterior; "poisson" / "binomial": laplace_posterior_counts) and return the
-        Laplace approximation of log p(train_targets[observed]), an evidence.LaplaceEvidence.  kw: the arguments of the fit
-        (exposure, trials, mean, f0, tolerances) go to it, the others to evidence.laplace_evidence (num_probes, steps, seed,
+        """Fit the nodes (family "bernoulli": laplace_posterior; "poisson" / "binomial" / "negative_binomial": laplace_posterior_counts) and
+        return the Laplace approximation of log p(train_targets[observed]), an evidence.LaplaceEvidence.  kw: the arguments of the
+        fit (dispersion, exposure, trials, mean, f0, tolerances) go to it, the others to evidence.laplace_evidence (num_probes, steps, seed,
         method, ...).  max_iter is an argument of both and goes to the FIT; fit_kw= and evidence_kw= (dicts, as
         utils.laplace_train takes them) name the receiver explicitly and win over the split: evidence_kw=dict(max_iter=...)
         caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta."""
@@ -209,6 +210,8 @@ class RiemannGP(torch.nn.Module):
         kw = dict(kw)
         fit_kw, evidence_kw = dict(kw.pop("fit_kw", None) or {}), dict(kw.pop("evidence_kw", None) or {})
         names = set(inspect.signature(laplace_fit if family == "bernoulli" else laplace_fit_counts).parameters)
+        if family != "bernoulli":
+            names.add("dispersion")                       # (counts.fit_counts: the negative binomial's, refused elsewhere)
         fit_kw = dict({k: v for k, v in kw.items() if k in names}, **fit_kw)
         evidence_kw = dict({k: v for k, v in kw.items() if k not in names}, **evidence_kw)
         fit = self._laplace_fit(observed, family, **fit_kw)

@@ -99,7 +99,8 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
                   verbose=False):
     """Train the kernel hyper-parameters of `model` (a RiemannGP) on the Laplace evidence of its node fit: the loss is
     -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
-    model.train_targets), "poisson" or "binomial" (counts; fit_kw carries exposure / trials / mean).  Every epoch refits the mode
+    model.train_targets), "poisson", "binomial" or "negative_binomial" (counts; fit_kw carries exposure / trials / mean, and the negative binomial's
+    fixed dispersion).  Every epoch refits the mode
     from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
     the last loss."""
     from ..evidence import _family, laplace_evidence
