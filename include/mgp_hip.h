@@ -744,6 +744,41 @@ size_t mgp_nb_evidence_site_workspace_bytes(int64_t n);
 int mgp_nb_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var, int64_t n,
                          double mean, double dispersion, double h_floor, float* root_h, float* corr, double* sums, void* work,
                          size_t work_bytes, void* stream);
+/* The same stage for an ordered-category fit (ordinal.laplace_fit_ordinal, docs/kernels/ordinal.md) with the contract of
+ * mgp_laplace_evidence_site: lo [n] and hi [n], the float32 ends of the node's interval of cutpoints as mgp_ordinal_site reads
+ * them (lo < hi, -inf / +inf at the end categories), in the place of (y, aux); read only in quads that hold an observed node (NaN
+ * allowed elsewhere), as var.  Per observed node in float64, with u = hi - f, l = lo - f, e_x = exp(-|x|), a_x = e_x / (1 + e_x)^2
+ * and gap_x = sigma(-x) - sigma(x) = -+(-expm1(-|x|)) / (1 + e_x) (- for x >= 0; an infinite end has a = 0 and adds nothing),
+ *   l = log sigma(u) + log sigma(-l),   h = a_u + a_l in (0, 1/2],   h' = dh / df = -(a_u gap_u + a_l gap_l);
+ * at the observed nodes with h >= h_floor (the m nodes kept; 0 elsewhere)
+ *   root_h_i = (float) sqrt(h_i),   corr_i = (float)(var_i h'_i),
+ *   sums [4] float64 (device) = { sum_obs l,  m,  sum_i corr_i,  max_i |corr_i| }.
+ * corr is not written, and sums 2 and 3 are 0, when var or corr is NULL.  Partials, second launch, vector accesses and `work`
+ * (mgp_ordinal_evidence_site_workspace_bytes(n) bytes, 8-byte aligned) as mgp_laplace_evidence_site: repeated calls are bitwise
+ * equal.  MGP_ERR_ARG for null f, lo, hi, root_h or sums, n < 1, h_floor negative or NaN; MGP_ERR_WORKSPACE for a null, misaligned
+ * or short `work`.  The checks precede every launch. */
+size_t mgp_ordinal_evidence_site_workspace_bytes(int64_t n);
+int mgp_ordinal_evidence_site(const float* f, const float* lo, const float* hi, const uint8_t* obs, const double* var, int64_t n,
+                              double h_floor, float* root_h, float* corr, double* sums, void* work, size_t work_bytes,
+                              void* stream);
+/* The derivative of the ordinal Laplace evidence with respect to the K - 1 cutpoints, 2 <= K <= 64, as three rows of sums over the
+ * observed nodes (docs/kernels/ordinal.md): out [3, K - 1] float64 row-major (device), column k - 1 the cutpoint b_k.  f, lo, hi,
+ * obs (NULL: every node) as above; cat [n] uint8: the node's category c (lo = b_c, hi = b_{c+1}); var [n] float64 (NULL: row 1 is
+ * 0): diag(A^-1); u [n] float64 (NULL: row 2 is 0): A^-1 (var o h').  lo, hi, cat, var and u are read at observed nodes only; a
+ * node with cat >= K adds nothing, and cat is compared, never used as an index.  With w = hi - lo and the notation above, a node
+ * of category c adds to column c (its upper cut, c <= K - 2) and to column c - 1 (its lower cut, c >= 1)
+ *   row 0:   sigma(-u) + 1 / expm1(w)              -(sigma(l) + 1 / expm1(w))           the likelihood (1 / expm1(inf) = 0)
+ *   row 1:   -1/2 var a_u gap_u                     -1/2 var a_l gap_l                    the curvature at fixed f
+ *   row 2:   -1/2 u a_u                             -1/2 u a_l                            through the mode
+ * rows 1 and 2 only where h >= h_floor.  One partial [3, K - 1] per workgroup, every entry summed in node order by one lane, and
+ * a second launch that adds the partials in workgroup order: no atomics, repeated calls are bitwise equal.  `work`:
+ * mgp_ordinal_cut_sums_workspace_bytes(n, K) bytes (0 for n < 1 or K outside 2 .. 64), 8-byte aligned.  Element alignment only.
+ * MGP_ERR_ARG for null f, lo, hi, cat or out, n < 1, K outside 2 .. 64, h_floor negative or NaN; MGP_ERR_WORKSPACE for a null,
+ * misaligned or short `work`.  The checks precede every launch. */
+size_t mgp_ordinal_cut_sums_workspace_bytes(int64_t n, int K);
+int mgp_ordinal_cut_sums(const float* f, const float* lo, const float* hi, const uint8_t* cat, const uint8_t* obs,
+                         const double* var, const double* u, int64_t n, int K, double h_floor, double* out, void* work,
+                         size_t work_bytes, void* stream);
 /* Row scaling of a row-major [n, P] float32 block, 1 <= P <= 256:  out_ij = s_i V_ij  (X NULL)  or  fmaf(s_i, X_ij, V_ij).
  * out may be V or X.  float4 accesses where P % 4 == 0 and V, X, out are 16-byte aligned.  MGP_ERR_ARG for null s, V or out,
  * n < 1 and P outside 1 .. 256. */

@@ -49,6 +49,15 @@
 //    kernel 2, the integrand in the product form (every term positive: a tail category keeps its relative accuracy), the sum
 //    divided by the sum of the weights (rows sum to 1).  A group of TK lanes per node as kernel 3, lane k its category: one exp
 //    per lane and point, the lower cut's factor from lane k - 1 by a shuffle.
+//
+// 9. mgp_ordinal_evidence_site: kernel 5 for the ordered-category fit, the interval (lo, hi] in the place of (y, aux): sqrt(h) and
+//    var h' with h' = -(a_u (sigma(-u) - sigma(u)) + a_l (sigma(-l) - sigma(l))), a_x = sigma(x) sigma(-x), the differences formed as
+//    -+(1 - e) / (1 + e) from e = exp(-|x|).
+//
+// 10. mgp_ordinal_cut_sums: the three rows of d log Z / d b_k for the K - 1 cutpoints (likelihood, curvature at fixed f, through
+//    the mode), a per-cutpoint float64 reduction over the nodes: a node of category c adds to its upper cut b_{c+1} and to its lower
+//    cut b_c.  A workgroup stages a step's contributions in LDS and one lane per (row, cut) adds them in node order; one partial
+//    [3, K - 1] per workgroup, a second launch adds the partials in workgroup order.  No atomics, no shuffles.
 #include <cfloat>
 #include <cmath>
 
@@ -540,6 +549,195 @@ __global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __re
   }
 }
 
+// sigma(x), sigma(-x), a = sigma(x) sigma(-x) and gap = sigma(-x) - sigma(x) = -+ (1 - e) / (1 + e) from one e = exp(-|x|): the gap
+// as evidence_node forms (1 - pi) - pi, no cancellation near 0.  x = +-inf: e = 0, a = 0, gap = -+1, every product with a is 0
+struct OrdinalEnd {
+  double e, sig, sigm, a, gap;
+};
+
+__device__ __forceinline__ OrdinalEnd ordinal_end(double x) {
+  const double ax = fabs(x);
+  const double e = exp(-ax);
+  const double d = 1.0 + e;
+  const double big = 1.0 / d, small = e / d;
+  const double gap = -expm1(-ax) / d;
+  OrdinalEnd r;
+  r.e = e;
+  r.sig = x >= 0.0 ? big : small;
+  r.sigm = x >= 0.0 ? small : big;
+  r.a = e / (d * d);
+  r.gap = x >= 0.0 ? -gap : gap;
+  return r;
+}
+
+// one node of mgp_ordinal_evidence_site at the mode: the interval of ordinal_node, h' = -(a_u gap_u + a_l gap_l); acc as
+// evidence_node fills it
+__device__ __forceinline__ void ordinal_evidence_node(float f32, float lo32, float hi32, bool obs, double var, bool has_var,
+                                                      double h_floor, float& root, float& corr, SiteAcc& acc) {
+  root = 0.f;
+  corr = 0.f;
+  if (!obs) return;
+  const double f = (double)f32;
+  const double u = (double)hi32 - f, l = (double)lo32 - f;
+  const OrdinalEnd eu = ordinal_end(u), el = ordinal_end(l);
+  acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu.e)) - ((l > 0.0 ? l : 0.0) + log1p(el.e));   // log sigma(u) + log sigma(-l), as ordinal_node
+  const double h = eu.a + el.a;
+  const double hp = -(eu.a * eu.gap + el.a * el.gap);
+  if (!(h >= h_floor)) return;
+  acc.fq += 1.0;
+  root = (float)sqrt(h);                                               // h <= 1/2
+  if (has_var) {
+    const double m = (double)FLT_MAX;
+    double c = var * hp;
+    c = c > m ? m : (c < -m ? -m : c);
+    corr = (float)c;
+    acc.sq += c;
+    const double ac = fabs(c);
+    acc.mx = ac > acc.mx ? ac : acc.mx;
+  }
+}
+
+// the layout of evidence_site_kernel with lo and hi in the place of y and aux
+template <bool VEC4>
+__global__ __launch_bounds__(kBlock) void ordinal_evidence_site_kernel(const float* __restrict__ f, const float* __restrict__ lo,
+                                                                       const float* __restrict__ hi,
+                                                                       const uint8_t* __restrict__ obs,
+                                                                       const double* __restrict__ var, int64_t n, double h_floor,
+                                                                       float* __restrict__ root_h, float* __restrict__ corr,
+                                                                       double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const bool has_var = var != nullptr && corr != nullptr;
+  const int64_t nq = (n + 3) >> 2;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 lv = any ? *reinterpret_cast<const float4*>(lo + i0) : zero;
+      const float4 hv = any ? *reinterpret_cast<const float4*>(hi + i0) : zero;
+      double2 v0 = make_double2(0.0, 0.0), v1 = v0;
+      if (has_var && any) {
+        v0 = *reinterpret_cast<const double2*>(var + i0);
+        v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
+      }
+      float4 rv, cv;
+      ordinal_evidence_node(fv.x, lv.x, hv.x, ov.x != 0, v0.x, has_var, h_floor, rv.x, cv.x, acc);
+      ordinal_evidence_node(fv.y, lv.y, hv.y, ov.y != 0, v0.y, has_var, h_floor, rv.y, cv.y, acc);
+      ordinal_evidence_node(fv.z, lv.z, hv.z, ov.z != 0, v1.x, has_var, h_floor, rv.z, cv.z, acc);
+      ordinal_evidence_node(fv.w, lv.w, hv.w, ov.w != 0, v1.y, has_var, h_floor, rv.w, cv.w, acc);
+      *reinterpret_cast<float4*>(root_h + i0) = rv;
+      if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float ri, ci;
+        ordinal_evidence_node(f[i], o ? lo[i] : 0.f, o ? hi[i] : 0.f, o, (o && has_var) ? var[i] : 0.0, has_var, h_floor, ri, ci,
+                              acc);
+        root_h[i] = ri;
+        if (has_var) corr[i] = ci;
+      }
+    }
+  }
+  const SiteAcc r = block_reduce(acc);
+  if (threadIdx.x == 0) {
+    double* p = partials + 4 * (int64_t)blockIdx.x;
+    p[0] = r.lp;
+    p[1] = r.fq;
+    p[2] = r.mx;
+    p[3] = r.sq;
+  }
+}
+
+constexpr int kCutMaxBlocks = 1024;       // grid cap of mgp_ordinal_cut_sums: 1024 x 256 threads x 1 node per step
+constexpr int kCutRows = 3;               // likelihood, curvature, through the mode
+
+// The three rows of d log Z / d b_k, k = 1 .. K - 1, as one partial [3, K - 1] per workgroup.  A step: thread t stages the six
+// contributions of its node in LDS -- three to its upper cut b_{c+1} and three to its lower cut b_c -- with its category c (-1: no
+// contribution), then lane t < 3 (K - 1), the owner of (row, cut) = (t / (K - 1), 1 + t % (K - 1)), scans the 256 staged nodes in
+// thread order (every lane reads the same address: a broadcast) and adds the ones that touch its cut.  The sum of a (row, cut) is
+// therefore taken in node order inside the workgroup's stripe, by one lane: no shuffles, no atomics, the same trip count for
+// every thread (the barriers stay convergent).
+__global__ __launch_bounds__(kBlock) void ordinal_cut_sums_kernel(const float* __restrict__ f, const float* __restrict__ lo,
+                                                                  const float* __restrict__ hi, const uint8_t* __restrict__ cat,
+                                                                  const uint8_t* __restrict__ obs, const double* __restrict__ var,
+                                                                  const double* __restrict__ usol, int64_t n, int K, double h_floor,
+                                                                  double* __restrict__ partials) {
+  __shared__ double s_val[kBlock][2 * kCutRows];
+  __shared__ int s_cat[kBlock];
+  const int cuts = K - 1;
+  const int t = threadIdx.x;
+  const bool owner = t < kCutRows * cuts;
+  const int row = owner ? t / cuts : 0;
+  const int cut = owner ? 1 + t % cuts : 0;
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t steps = (n + stride - 1) / stride;                     // the same for every thread of the grid
+  for (int64_t s = 0; s < steps; ++s) {
+    const int64_t i = s * stride + (int64_t)blockIdx.x * kBlock + t;
+    int c = -1;
+    double up0 = 0.0, up1 = 0.0, up2 = 0.0, dn0 = 0.0, dn1 = 0.0, dn2 = 0.0;
+    if (i < n && (obs ? obs[i] != 0 : true)) {
+      const int ci = (int)cat[i];
+      if (ci < K) {                                                    // compared before it selects a cut: no table is indexed
+        c = ci;
+        const double fi = (double)f[i];
+        const double lo_i = (double)lo[i], hi_i = (double)hi[i];
+        const OrdinalEnd eu = ordinal_end(hi_i - fi), el = ordinal_end(lo_i - fi);
+        const double width = 1.0 / expm1(hi_i - lo_i);                 // 0 at an infinite end
+        up0 = eu.sigm + width;
+        dn0 = -(el.sig + width);
+        if (eu.a + el.a >= h_floor) {
+          if (var) {
+            const double v = var[i];
+            up1 = -0.5 * (v * (eu.a * eu.gap));
+            dn1 = -0.5 * (v * (el.a * el.gap));
+          }
+          if (usol) {
+            const double ui = usol[i];
+            up2 = -0.5 * (ui * eu.a);
+            dn2 = -0.5 * (ui * el.a);
+          }
+        }
+      }
+    }
+    s_cat[t] = c;
+    s_val[t][0] = up0;
+    s_val[t][1] = up1;
+    s_val[t][2] = up2;
+    s_val[t][3] = dn0;
+    s_val[t][4] = dn1;
+    s_val[t][5] = dn2;
+    __syncthreads();
+    if (owner) {
+      // both candidates are read whatever the category, so the reads of the next nodes do not wait for a branch; a node that does
+      // not touch the cut adds 0.0, which changes nothing
+#pragma unroll 8
+      for (int j = 0; j < kBlock; ++j) {
+        const int cj = s_cat[j];
+        const double up = s_val[j][row], dn = s_val[j][kCutRows + row];    // the node's upper cut, its lower cut
+        acc += cj == cut - 1 ? up : (cj == cut ? dn : 0.0);
+      }
+    }
+    __syncthreads();
+  }
+  if (owner) partials[(int64_t)blockIdx.x * (kCutRows * cuts) + t] = acc;
+}
+
+// out [3, K - 1] from the partials of `nblk` workgroups: lane t adds its entry over the workgroups in order
+__global__ __launch_bounds__(kBlock) void ordinal_cut_sums_add_kernel(const double* __restrict__ partials, int nblk, int entries,
+                                                                      double* __restrict__ out) {
+  const int t = threadIdx.x;
+  if (t >= entries) return;
+  double acc = 0.0;
+#pragma unroll 8
+  for (int b = 0; b < nblk; ++b) acc += partials[(int64_t)b * entries + t];          // (the loads run ahead, the adds stay in order)
+  out[t] = acc;
+}
+
 constexpr int kScaleMaxBlocks = 2048;     // grid cap of mgp_scale_rows: 2048 x 256 threads x 4 (or 1) entries per step
 
 // out = s_i V_ij, or fmaf(s_i, X_ij, V_ij): one entry (or one float4 inside a row, P % 4 == 0) per thread and step.  out may be
@@ -817,6 +1015,57 @@ extern "C" int mgp_nb_evidence_site(const float* f, const float* y, const float*
                        root_h, corr, partials);
   MGP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" size_t mgp_ordinal_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+
+extern "C" int mgp_ordinal_evidence_site(const float* f, const float* lo, const float* hi, const uint8_t* obs, const double* var,
+                                         int64_t n, double h_floor, float* root_h, float* corr, double* sums, void* work,
+                                         size_t work_bytes, void* stream) {
+  if (!f || !lo || !hi || !root_h || !sums || n < 1 || !(h_floor >= 0.0)) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_ordinal_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  if (!var || !corr) var = nullptr, corr = nullptr;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(lo, 16) && aligned_to(hi, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
+                    aligned_to(root_h, 16) && aligned_to(corr, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (vec4)
+    hipLaunchKernelGGL(ordinal_evidence_site_kernel<true>, grid, block, 0, st, f, lo, hi, obs, var, n, h_floor, root_h, corr,
+                       partials);
+  else
+    hipLaunchKernelGGL(ordinal_evidence_site_kernel<false>, grid, block, 0, st, f, lo, hi, obs, var, n, h_floor, root_h, corr,
+                       partials);
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+int cut_blocks(int64_t n) {
+  const int64_t b = mgp_cdiv(n, (int64_t)kBlock);
+  return (int)(b > kCutMaxBlocks ? kCutMaxBlocks : b);
+}
+
+extern "C" size_t mgp_ordinal_cut_sums_workspace_bytes(int64_t n, int K) {
+  return (n < 1 || K < 2 || K > 64) ? 0 : (size_t)cut_blocks(n) * kCutRows * (size_t)(K - 1) * sizeof(double);
+}
+
+extern "C" int mgp_ordinal_cut_sums(const float* f, const float* lo, const float* hi, const uint8_t* cat, const uint8_t* obs,
+                                    const double* var, const double* u, int64_t n, int K, double h_floor, double* out, void* work,
+                                    size_t work_bytes, void* stream) {
+  if (!f || !lo || !hi || !cat || !out || n < 1 || K < 2 || K > 64 || !(h_floor >= 0.0)) return MGP_ERR_ARG;
+  if (!work || !aligned_to(work, 8) || work_bytes < mgp_ordinal_cut_sums_workspace_bytes(n, K)) return MGP_ERR_WORKSPACE;
+  const int blocks = cut_blocks(n);
+  double* partials = static_cast<double*>(work);
+  hipStream_t st = mgp_stream(stream);
+  hipLaunchKernelGGL(ordinal_cut_sums_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, st, f, lo, hi, cat, obs, var, u, n, K,
+                     h_floor, partials);
+  MGP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ordinal_cut_sums_add_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, kCutRows * (K - 1), out);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

@@ -16,6 +16,11 @@ For a kernel hyper-parameter theta with Q' = dQ / d theta (the likelihood's mean
 
 every term a bilinear form in Q(theta) between detached vectors: one differentiable operator.matmul of the block [f | Y],
 added to the value as sur - sur.detach() the way solvers.inv_quad_logdet does.
+
+The ordered-category fit (ordinal.OrdinalLaplaceFit) has the same evidence with its own site stage (mgp_ordinal_evidence_site: the
+node's interval of cutpoints in the place of the observation) and one more set of parameters, the cutpoints b: d log Z / d b_k
+is three per-cutpoint sums over the nodes (mgp_ordinal_cut_sums, docs/kernels/ordinal.md) of the same v and u, with no trace
+estimate, and enters the value as the surrogate (G . b).
 """
 import math
 
@@ -28,6 +33,7 @@ from .classification import H_FLOOR, S_REF
 
 FAMILIES = {"poisson": 0, "binomial": 1, "bernoulli": 2}
 NB_FAMILY, NB = "negative_binomial", 3     # the family with an entry point of its own (mgp_nb_evidence_site)
+ORDINAL_FAMILY = "ordinal"                 # the ordered-category fit: intervals of cutpoints, not (y, aux) (mgp_ordinal_evidence_site)
 DENSE_MAX = 512           # method "auto": the m x m Cholesky up to here
 MAX_COLUMNS = sampling.CHUNK
 
@@ -218,20 +224,26 @@ class LaplaceEvidence:
     gradient surrogate when it was asked for; se: its standard error (logdet_se / 2); log_likelihood: sum_obs log p(y_i | f_i)
     with the constants; quad: f^T Q f / 2; logdet: logdet B with logdet_se; method: "slq" or "dense"; m: the effective observed
     nodes; per_probe: the probes' estimates of logdet B (slq); solves: None, or with the gradient the dict of what it was made
-    of (Z, root_h, corr, w, s_ref, Y float32; u, X float64); site_sums: the four sums of mgp_laplace_evidence_site (sum_obs l
-    without the families' constants, m, sum corr, max |corr|)."""
+    of (Z, root_h, corr, w, s_ref, Y float32; u, X float64; with the cutpoints' gradient alone: root_h, corr, w, s_ref, u);
+    site_sums: the four sums of mgp_laplace_evidence_site (sum_obs l without the families' constants, m, sum corr, max |corr|);
+    cutpoint_grad: None, or for an ordinal fit asked for the cutpoints' gradient the three rows [3, K - 1] float64 of
+    mgp_ordinal_cut_sums on the device, whose column sum is d log Z / d b."""
 
-    def __init__(self, value, se, log_likelihood, quad, logdet, logdet_se, method, m, per_probe, solves, site_sums=None):
+    def __init__(self, value, se, log_likelihood, quad, logdet, logdet_se, method, m, per_probe, solves, site_sums=None,
+                 cutpoint_grad=None):
         self.value, self.se, self.log_likelihood, self.quad = value, se, log_likelihood, quad
         self.logdet, self.logdet_se, self.method, self.m = logdet, logdet_se, method, m
-        self.per_probe, self.solves, self.site_sums = per_probe, solves, site_sums
+        self.per_probe, self.solves, self.site_sums, self.cutpoint_grad = per_probe, solves, site_sums, cutpoint_grad
 
     def __repr__(self):
         return "LaplaceEvidence(value=%.6f, se=%.3g, method=%r, m=%d)" % (float(self.value), self.se, self.method, self.m)
 
 
 def _site_of(fit):
-    """(family, mean, aux, s_ref, dispersion) of a binary or a count fit."""
+    """(family, mean, aux, s_ref, dispersion) of a binary, a count or an ordinal fit."""
+    from . import ordinal
+    if isinstance(fit, ordinal.OrdinalLaplaceFit):
+        return ORDINAL_FAMILY, 0.0, None, ordinal.S_REF, None
     family = getattr(fit, "family", None)
     if family is None:
         return "bernoulli", 0.0, None, S_REF, None
@@ -240,6 +252,9 @@ def _site_of(fit):
 
 def _weights(fit, family, mean, aux, s_ref, dispersion=None):
     """obs_w = (float)(s_ref h) of the fit's own form-3 system at the mode, from the kernel its Newton steps used."""
+    if family == ORDINAL_FAMILY:
+        from .ordinal import ordinal_site
+        return ordinal_site(fit.mean, None, fit._lo, fit._hi, fit.observed, s_ref)[0]
     if family == "bernoulli":
         from .classification import bernoulli_site
         return bernoulli_site(fit.mean, None, fit.y, fit.observed, s_ref)[0]
@@ -265,27 +280,52 @@ def _solve64(desc, B, kw):
     return plan.solution64_view().clone()
 
 
+def _check_cutpoints(fit, family, cutpoints):
+    """True when the cutpoints' gradient is asked for: cutpoints a float64 [K - 1] tensor that requires grad and rounds to the
+    fit's own cutpoints in float32."""
+    if cutpoints is None:
+        return False
+    if family != ORDINAL_FAMILY:
+        raise ValueError("cutpoints belong to an ordinal fit, this is a %s fit" % family)
+    K = fit.num_categories
+    if not torch.is_tensor(cutpoints) or cutpoints.dtype != torch.float64 or cutpoints.shape != (K - 1,):
+        raise ValueError("cutpoints must be a float64 tensor of %d values" % (K - 1))
+    if not torch.equal(cutpoints.detach().float().double().cpu(), fit.cutpoints.cpu()):
+        raise ValueError("cutpoints are not the fit's: rounded to float32 they must equal fit.cutpoints")
+    return bool(cutpoints.requires_grad)
+
+
 def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_probes=16, steps=12, seed=1337, solve_tol=1e-6,
-                     method="auto", probes=None, max_iter=5000):
-    """log Z of a LaplaceFit or a CountLaplaceFit: a LaplaceEvidence.  logdet B by logdet_b(num_probes, steps, seed, solve_tol,
+                     method="auto", probes=None, max_iter=5000, cutpoints=None):
+    """log Z of a LaplaceFit, a CountLaplaceFit or an OrdinalLaplaceFit: a LaplaceEvidence.
+    logdet B by logdet_b(num_probes, steps, seed, solve_tol,
     method, probes).  operator: the model's precision(noise=False), the operator fit.desc describes; when one of its
     _hyper_tensors() requires grad, value carries d log Z / d theta of the module docstring: corr = variance h' from variance
     [n] (default fit.latent_variance(var_samples)[0]), X by one form-0 solve and Y, u by form-3 solves with the fit's s_ref and
     weights, all refined to solve_tol on the true residual (X and u kept as the float64 solutions, _solve64), the probes those
-    of logdet B (drawn from num_probes and seed also when method is "dense")."""
+    of logdet B (drawn from num_probes and seed also when method is "dense").
+    cutpoints (ordinal fits only): a float64 tensor [K - 1] whose float32 rounding is fit.cutpoints, for example the output of an
+    ordinal.CutpointParameter; when it requires grad, value carries d log Z / d b as the surrogate (G . cutpoints) with G the
+    column sum of mgp_ordinal_cut_sums (LaplaceEvidence.cutpoint_grad holds the three rows): it needs the variance and the u solve
+    of the hyper-parameter gradient, and neither probes nor X and Y."""
     from .autograd import needs_grad
     from .solvers import cg_solve
     if not hasattr(fit, "_pseudo") or fit.mean.dim() != 1:
-        raise NotImplementedError("laplace_evidence takes a binary or a count fit")
+        raise NotImplementedError("laplace_evidence takes a binary, a count or an ordinal fit")
     desc = fit.desc
     family, mean, aux, s_ref, dispersion = _site_of(fit)
     grad = operator is not None and needs_grad(*getattr(operator, "_hyper_tensors", lambda: [])())
+    cut_grad = _check_cutpoints(fit, family, cutpoints)
     with torch.no_grad():
         f = fit.mean
-        if grad and variance is None:
+        if (grad or cut_grad) and variance is None:
             variance = fit.latent_variance(var_samples)[0]
-        root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family,
-                                          dispersion=dispersion)
+        if family == ORDINAL_FAMILY:
+            from .ordinal import ordinal_cut_sums, ordinal_evidence_site
+            root_h, corr, sums = ordinal_evidence_site(f, fit._lo, fit._hi, fit.observed, variance if grad or cut_grad else None)
+        else:
+            root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family,
+                                              dispersion=dispersion)
         sums = sums.tolist()                              # the one host read of the site stage
         m = int(sums[1])
         if m < 1:
@@ -300,10 +340,9 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
                                           max_iter)
     ll = float(fit.log_likelihood)
     value = torch.tensor(ll - quad - 0.5 * logdet, dtype=torch.float64, device=f.device)
-    solves = None
-    if grad:
+    solves = G = None
+    if grad or cut_grad:
         with torch.no_grad():
-            P = Z.shape[1]
             # X and u only weight the operator's output, so they enter the bilinear forms as the float64 solutions the refined
             # solves accumulate: a float32 X cannot hold a true residual of 2 solve_tol on Q itself (its rounding alone leaves
             # 2.4e-6 on the 1546-node dumbbell, cond Q = 1e3; the unrefined factorised solve of the Lanczos products 4.8e-6).
@@ -312,13 +351,24 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
             w = _weights(fit, family, mean, aux, s_ref, dispersion)
             d3 = desc.with_(form=3, noise=s_ref, obs_w=w)
             kw3 = dict(kw, jacobi=sampling.OBSERVED_JACOBI[0])
-            SZ = scale_rows(root_h, Z)
-            X = _solve64(desc, SZ, dict(kw, refine=REFINE_ROUNDS))
-            Y = cg_solve(d3, SZ * s_ref, **dict(kw3, refine=1))[0]
+            if grad:
+                SZ = scale_rows(root_h, Z)
+                X = _solve64(desc, SZ, dict(kw, refine=REFINE_ROUNDS))
+                Y = cg_solve(d3, SZ * s_ref, **dict(kw3, refine=1))[0]
+            # u = A^-1 (v o h') serves both gradients: one solve
             u = _solve64(d3, (corr * s_ref).view(-1, 1), dict(kw3, refine=REFINE_ROUNDS)).view(-1)
-            V = torch.cat([f.view(-1, 1), Y], 1).contiguous()
-            W = torch.cat([0.5 * (u - f.double()).view(-1, 1), X * (0.5 / P)], 1)
-            solves = dict(Z=Z, root_h=root_h, corr=corr, w=w, s_ref=s_ref, u=u, X=X, Y=Y)
+            solves = dict(root_h=root_h, corr=corr, w=w, s_ref=s_ref, u=u)
+            if cut_grad:
+                G = ordinal_cut_sums(f, fit._lo, fit._hi, fit.y, fit.observed, variance, u, fit.num_categories)
+            if grad:
+                P = Z.shape[1]
+                V = torch.cat([f.view(-1, 1), Y], 1).contiguous()
+                W = torch.cat([0.5 * (u - f.double()).view(-1, 1), X * (0.5 / P)], 1)
+                solves = dict(Z=Z, root_h=root_h, corr=corr, w=w, s_ref=s_ref, u=u, X=X, Y=Y)
+    if grad:
         sur = (W * operator.matmul(V).double()).sum()
         value = value + (sur - sur.detach())
-    return LaplaceEvidence(value, 0.5 * logdet_se, ll, quad, logdet, logdet_se, method, m, per, solves, sums)
+    if cut_grad:
+        sur = (G.sum(0).to(cutpoints.device) * cutpoints).sum()
+        value = value + (sur - sur.detach()).to(value.device)
+    return LaplaceEvidence(value, 0.5 * logdet_se, ll, quad, logdet, logdet_se, method, m, per, solves, sums, G)

@@ -190,9 +190,15 @@ class RiemannGP(torch.nn.Module):
         return laplace_fit_ordinal(desc, y, num_categories, cutpoints, observed, **kw)
 
     def _laplace_fit(self, observed, family, **kw):
-        """The binary fit (family "bernoulli") or the count fit ("poisson", "binomial", "negative_binomial") of train_targets."""
+        """The binary fit (family "bernoulli"), the count fit ("poisson", "binomial", "negative_binomial") or the ordered-category
+        fit ("ordinal", with num_categories= and cutpoints= in kw) of train_targets."""
         if family == "bernoulli":
             return self.laplace_posterior(observed, **kw)
+        if family == "ordinal":
+            if "num_categories" not in kw:
+                raise ValueError("family 'ordinal' needs num_categories")
+            kw = dict(kw)
+            return self.laplace_posterior_ordinal(kw.pop("num_categories"), kw.pop("cutpoints", None), observed, **kw)
         return self.laplace_posterior_counts(observed, family=family, **kw)
 
     def laplace_evidence(self, observed=None, family="bernoulli", **kw):
@@ -201,19 +207,29 @@ class RiemannGP(torch.nn.Module):
         fit (dispersion, exposure, trials, mean, f0, tolerances) go to it, the others to evidence.laplace_evidence (num_probes, steps, seed,
         method, ...).  max_iter is an argument of both and goes to the FIT; fit_kw= and evidence_kw= (dicts, as
         utils.laplace_train takes them) name the receiver explicitly and win over the split: evidence_kw=dict(max_iter=...)
-        caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta."""
+        caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta.
+        family "ordinal" (laplace_posterior_ordinal) takes num_categories= and cutpoints=; cutpoints may be an
+        ordinal.CutpointParameter or a float64 tensor that requires grad: the fit runs at their detached values and value carries
+        d log Z / d cutpoints as well."""
         import inspect
         from ..classification import laplace_fit
         from ..counts import laplace_fit_counts
-        from ..evidence import _family, laplace_evidence
-        _family(family)
+        from ..evidence import ORDINAL_FAMILY, _family, laplace_evidence
+        from ..ordinal import _live_cutpoints, laplace_fit_ordinal
+        if family != ORDINAL_FAMILY:
+            _family(family)
         kw = dict(kw)
         fit_kw, evidence_kw = dict(kw.pop("fit_kw", None) or {}), dict(kw.pop("evidence_kw", None) or {})
-        names = set(inspect.signature(laplace_fit if family == "bernoulli" else laplace_fit_counts).parameters)
-        if family != "bernoulli":
+        fitter = {"bernoulli": laplace_fit, ORDINAL_FAMILY: laplace_fit_ordinal}.get(family, laplace_fit_counts)
+        names = set(inspect.signature(fitter).parameters)
+        if fitter is laplace_fit_counts:
             names.add("dispersion")                       # (counts.fit_counts: the negative binomial's, refused elsewhere)
         fit_kw = dict({k: v for k, v in kw.items() if k in names}, **fit_kw)
         evidence_kw = dict({k: v for k, v in kw.items() if k not in names}, **evidence_kw)
+        if family == ORDINAL_FAMILY:
+            fit_kw, live = _live_cutpoints(fit_kw)
+            if live is not None:
+                evidence_kw.setdefault("cutpoints", live)
         fit = self._laplace_fit(observed, family, **fit_kw)
         return laplace_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
 

@@ -21,6 +21,11 @@ labels (ordinal_cutpoints).  They are rounded to float32, the format the kernel 
 The Laplace posterior N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets
 f_hat + g / h: OrdinalLaplaceFit restates _pseudo() and inherits latent_variance / latent_samples.  The predictive probabilities
 of the K categories come from one quadrature per (node, category) in float64 (mgp_ordinal_predict).
+
+The Laplace evidence of the fit is evidence.laplace_evidence (OrdinalLaplaceFit.laplace_evidence) with the per-node stage
+mgp_ordinal_evidence_site; its derivative with respect to the cutpoints is three per-cutpoint sums over the nodes
+(mgp_ordinal_cut_sums).  CutpointParameter states strictly increasing cutpoints in unconstrained parameters and learn_cutpoints
+runs Adam on them, one warm-started fit per step: the frequency logits are the right cutpoints for a flat latent function only.
 """
 import torch
 
@@ -145,6 +150,145 @@ def ordinal_site(f, qf, lo, hi, observed=None, s_ref=S_REF):
     return w, rhs, sums
 
 
+def _site_args(f, lo, hi, observed, variance, h_floor, extra=()):
+    """The host-side checks the two evidence kernels share: f, lo, hi tensors of one length n >= 1, observed bool [n] or None,
+    variance and the `extra` (name, tensor) pairs [n] or None, h_floor >= 0.  Returns n."""
+    if not float(h_floor) >= 0.0:
+        raise ValueError("h_floor must be >= 0, got %r" % (h_floor,))
+    for name, t in (("f", f), ("lo", lo), ("hi", hi)):
+        if not torch.is_tensor(t):
+            raise ValueError("%s must be a tensor [n]" % name)
+    n = f.numel()
+    if observed is not None and (not torch.is_tensor(observed) or observed.dtype != torch.bool):
+        raise ValueError("observed must be a bool tensor [n]")
+    for name, t in (("lo", lo), ("hi", hi), ("observed", observed), ("variance", variance)) + tuple(extra):
+        if t is not None and (not torch.is_tensor(t) or t.numel() != n):
+            raise ValueError("%s has %s entries, f %d" % (name, t.numel() if torch.is_tensor(t) else type(t), n))
+    if n < 1:
+        raise ValueError("f has no entries")
+    return n
+
+
+def ordinal_evidence_site(f, lo, hi, observed=None, variance=None, h_floor=H_FLOOR):
+    """(root_h, corr, sums) of mgp_ordinal_evidence_site at the mode f [n] float32, the contract of evidence.evidence_site with the
+    intervals (lo, hi] of ordinal_site in the place of the observations: root_h = sqrt(h) and corr = variance h' as fresh float32
+    [n] tensors (0 off the observed nodes with h >= h_floor; corr None when variance is None), sums [4] float64 on the device
+    (sum_obs (log sigma(hi - f) + log sigma(f - lo)), m = nodes kept, sum corr, max |corr|).  variance [n] (taken as float64)."""
+    n = _site_args(f, lo, hi, observed, variance, h_floor)
+    _lib.require_device(f, lo, hi, observed, variance)
+    f, lo, hi = _lib.f32c(f.reshape(-1)), _lib.f32c(lo.reshape(-1)), _lib.f32c(hi.reshape(-1))
+    observed = None if observed is None else observed.reshape(-1).contiguous()
+    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
+    root_h = torch.empty_like(f)
+    corr = None if variance is None else torch.empty_like(f)
+    sums = torch.empty(4, dtype=torch.float64, device=f.device)
+    work = _lib.workspace(lib().mgp_ordinal_evidence_site_workspace_bytes(n), "evidence_site", f.device)
+    check(lib().mgp_ordinal_evidence_site(ptr(f), ptr(lo), ptr(hi), ptr(observed), ptr(variance), n, float(h_floor), ptr(root_h),
+                                          ptr(corr), ptr(sums), ptr(work), work.numel(), stream()), "mgp_ordinal_evidence_site")
+    return root_h, corr, sums
+
+
+def ordinal_cut_sums(f, lo, hi, cat, observed, variance, u, K, h_floor=H_FLOOR):
+    """The three rows of d log Z / d b_k, k = 1 .. K - 1 (mgp_ordinal_cut_sums): [3, K - 1] float64 on the device -- the
+    likelihood's term, the curvature's at fixed f (zeros when variance is None) and the one through the mode (zeros when u is
+    None); their column sum is the derivative.  f [n] float32: the mode; lo, hi [n] as ordinal_site; cat [n]: the category of
+    every node, an integer tensor (uint8 as it is, any other integer type with values outside 0 .. 255 set to 255), read at
+    observed nodes only, a value >= K adds nothing; observed [n] bool or None; variance [n]: diag(A^-1) and u [n]:
+    A^-1 (variance o h'), taken as float64."""
+    K = _categories(K)
+    if not torch.is_tensor(cat) or cat.dtype == torch.bool or cat.is_floating_point() or cat.is_complex():
+        raise ValueError("cat must be an integer tensor [n] of categories")
+    n = _site_args(f, lo, hi, observed, variance, h_floor, (("cat", cat), ("u", u)))
+    _lib.require_device(f, lo, hi, cat, observed, variance, u)
+    f, lo, hi = _lib.f32c(f.reshape(-1)), _lib.f32c(lo.reshape(-1)), _lib.f32c(hi.reshape(-1))
+    cat = cat.reshape(-1)
+    if cat.dtype != torch.uint8:
+        cat = torch.where((cat < 0) | (cat > 255), torch.full_like(cat, 255), cat).to(torch.uint8)
+    cat = cat.contiguous()
+    observed = None if observed is None else observed.reshape(-1).contiguous()
+    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
+    u = None if u is None else u.reshape(-1).to(torch.float64).contiguous()
+    out = torch.empty((3, K - 1), dtype=torch.float64, device=f.device)
+    work = _lib.workspace(lib().mgp_ordinal_cut_sums_workspace_bytes(n, K), "ordinal_cut_sums", f.device)
+    check(lib().mgp_ordinal_cut_sums(ptr(f), ptr(lo), ptr(hi), ptr(cat), ptr(observed), ptr(variance), ptr(u), n, K, float(h_floor),
+                                     ptr(out), ptr(work), work.numel(), stream()), "mgp_ordinal_cut_sums")
+    return out
+
+
+GAP_FLOOR = 2.0 ** -10   # the least gap of a CutpointParameter: distinct after the fit's float32 rounding for |b| < 2^12
+
+
+class CutpointParameter(torch.nn.Module):
+    """K - 1 strictly increasing cutpoints as a differentiable function of unconstrained float64 parameters
+    raw = (b_1, rho_2 .. rho_{K-1}):  forward() = b_1, b_1 + sum_{j <= k} (2^-10 + softplus(rho_j)).  init [K - 1]: the start, for
+    example ordinal_cutpoints(...), reproduced up to rounding; its gaps must exceed 2^-10."""
+
+    def __init__(self, num_categories, init):
+        super().__init__()
+        K = _categories(num_categories)
+        b = _cutpoints(init, K)
+        x = b[1:] - b[:-1] - GAP_FLOOR
+        if not bool((x > 0.0).all()):
+            raise ValueError("the cutpoints of a CutpointParameter must lie more than 2^-10 apart, got a gap of %g"
+                             % float((b[1:] - b[:-1]).min()))
+        rho = x + torch.log(-torch.expm1(-x))                 # the inverse of softplus: log(expm1(x)), no overflow
+        self.num_categories = K
+        self.raw = torch.nn.Parameter(torch.cat([b[:1], rho]))
+
+    def forward(self):
+        gaps = GAP_FLOOR + torch.nn.functional.softplus(self.raw[1:])
+        return self.raw[0] + torch.cat([torch.zeros_like(self.raw[:1]), gaps.cumsum(0)])
+
+
+def _live_cutpoints(fit_kw):
+    """(fit_kw with cutpoints detached, the live tensor or None): cutpoints given as a CutpointParameter are evaluated now; a
+    tensor that requires grad, theirs or the caller's, is what laplace_evidence differentiates."""
+    fit_kw = dict(fit_kw)
+    c = fit_kw.get("cutpoints")
+    if isinstance(c, torch.nn.Module):
+        c = c()
+    if not torch.is_tensor(c):
+        return fit_kw, None
+    fit_kw["cutpoints"] = c.detach()
+    return fit_kw, (c if c.requires_grad else None)
+
+
+def learn_cutpoints(desc, y, num_categories, observed=None, cutpoints0=None, steps=30, lr=0.1, var_samples=64, variance=None,
+                    fit_kw=None, evidence_kw=None):
+    """Learn the cutpoints on the Laplace evidence with the kernel hyper-parameters fixed: Adam(lr) for `steps` steps on a
+    CutpointParameter started at cutpoints0 (None: ordinal_cutpoints of the observed labels), loss -log Z / m, every fit
+    warm-started from the previous mode, the gradient that of evidence.laplace_evidence(cutpoints=).  variance: None (every
+    step draws fit.latent_variance(var_samples)[0]), or a callable fit -> diag(A^-1) [n].  fit_kw as laplace_fit_ordinal takes,
+    evidence_kw as laplace_evidence.  Returns (cutpoints float64 [K - 1] on the device, as float32 holds them; the
+    OrdinalLaplaceFit at them; history: one (log Z, se) per step, taken before the step's update)."""
+    from .evidence import laplace_evidence
+    K = _categories(num_categories)
+    steps = _int(steps, "steps")
+    if steps < 1 or not float(lr) > 0.0:
+        raise ValueError("steps must be >= 1 and lr positive, got %r and %r" % (steps, lr))
+    if variance is not None and not callable(variance):
+        raise ValueError("variance must be None or a callable fit -> tensor [n]")
+    fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
+    if cutpoints0 is None:
+        labels, mask, _ = _validate(desc, y, K, None, observed, None)
+        cutpoints0 = ordinal_cutpoints(labels, K, None if mask is None else mask.to(labels.device))
+    cut = CutpointParameter(K, cutpoints0)
+    opt = torch.optim.Adam(cut.parameters(), lr=float(lr))
+    f0, history = fit_kw.pop("f0", None), []
+    for _ in range(steps):
+        opt.zero_grad()
+        b = cut()
+        fit = laplace_fit_ordinal(desc, y, K, b.detach(), observed, f0=f0, **fit_kw)
+        f0 = fit.mean
+        ev = laplace_evidence(fit, variance=None if variance is None else variance(fit), var_samples=var_samples, cutpoints=b,
+                              **evidence_kw)
+        history.append((float(ev.value.detach()), ev.se))
+        (-ev.value / ev.m).backward()
+        opt.step()
+    fit = laplace_fit_ordinal(desc, y, K, cut().detach(), observed, f0=f0, **fit_kw)
+    return fit.cutpoints.clone(), fit, history
+
+
 def ordinal_predict(eta, var, cutpoints, points=129, log=False):
     """P(y = k) = int P(y = k | f) N(f; eta_i, var_i) df for the K = len(cutpoints) + 1 categories at every node: [n, K] float64
     (mgp_ordinal_predict), its log with log=True.  eta, var [n] (taken as float64; var <= 2^-76, negative entries included: the
@@ -215,7 +359,14 @@ class OrdinalLaplaceFit(LaplaceFit):
         return targets, noise, eff
 
     def evidence(self, **kw):
-        raise NotImplementedError("the Laplace evidence of the ordinal fit is not built: see docs/scope.md")
+        raise NotImplementedError("the evidence of the ordinal fit is OrdinalLaplaceFit.laplace_evidence(...) or "
+                                  "evidence.laplace_evidence(fit, ...): see docs/kernels/ordinal.md")
+
+    def laplace_evidence(self, **kw):
+        """The Laplace approximation of log p(y) at this mode, an evidence.LaplaceEvidence; kw as evidence.laplace_evidence
+        (operator= for the hyper-parameter gradient, cutpoints= for the cutpoints', num_probes, steps, seed, method, ...)."""
+        from .evidence import laplace_evidence
+        return laplace_evidence(self, **kw)
 
     def map_proba(self):
         """P(y = k | f_hat) in the product form: the category probabilities at the mode, [n, K] float64 (ignores the latent

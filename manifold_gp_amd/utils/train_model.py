@@ -100,11 +100,14 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     """Train the kernel hyper-parameters of `model` (a RiemannGP) on the Laplace evidence of its node fit: the loss is
     -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
     model.train_targets), "poisson", "binomial" or "negative_binomial" (counts; fit_kw carries exposure / trials / mean, and the negative binomial's
-    fixed dispersion).  Every epoch refits the mode
+    fixed dispersion); "ordinal" (ordered categories; fit_kw carries num_categories and cutpoints: an ordinal.CutpointParameter is
+    evaluated every epoch and its parameters, held by the same optimizer, are trained along).  Every epoch refits the mode
     from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
     the last loss."""
-    from ..evidence import _family, laplace_evidence
-    _family(family)
+    from ..evidence import ORDINAL_FAMILY, _family, laplace_evidence
+    from ..ordinal import _live_cutpoints
+    if family != ORDINAL_FAMILY:
+        _family(family)
     model.train()
     fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
     graph = getattr(getattr(model.base_kernel, "knn", None), "knn_graph", None)
@@ -114,9 +117,11 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     loss = torch.zeros(())
     while epoch <= max_iter:
         optimizer.zero_grad()
-        fit = model._laplace_fit(observed, family, f0=f0, **fit_kw)
+        epoch_kw, live = _live_cutpoints(fit_kw) if family == ORDINAL_FAMILY else (fit_kw, None)
+        fit = model._laplace_fit(observed, family, f0=f0, **epoch_kw)
         f0 = fit.mean
-        ev = laplace_evidence(fit, operator=model.precision(noise=False), **evidence_kw)
+        epoch_ev = evidence_kw if live is None else dict(evidence_kw, cutpoints=live)
+        ev = laplace_evidence(fit, operator=model.precision(noise=False), **epoch_ev)
         loss = -ev.value
         for _, module, prior, closure, _ in _named_priors(model):
             loss = loss - prior.log_prob(closure(module)).sum().to(loss)
