@@ -847,6 +847,29 @@ int mgp_softmax_cg_block(const mgp_operator_t* op, const float* pi, int C, int S
 size_t mgp_softmax_hessian_add_block_workspace_bytes(int64_t n, int C, int S);
 int mgp_softmax_hessian_add_block(const float* pi, const float* X, int64_t n, int C, int S, float* Y, double* sums, void* work,
                                   size_t work_bytes, void* stream);
+/* The symmetric factor of the softmax Hessian (csrc/laplace.hip, docs/kernels/evidence.md "The softmax family"): with
+ * s_i = sqrt(pi_i),  R_i = diag(s_i)(I - s_i s_i^T),  R_i R_i^T = H_i = diag(pi_i) - pi_i pi_i^T  where the row sums to 1.
+ *   transpose == 0:  out = R V          (R v)_c   = s_c v_c - pi_c sum_k s_k v_k               (X must be NULL)
+ *   transpose != 0:  out = V + R^T X    (R^T x)_c = s_c (x_c - sum_k pi_k x_k)                 (V NULL: out = R^T X)
+ * on S vectors of [n, C] float32, 2 <= C <= 64, S >= 1, C S <= 256: entry (i, c, s) of V, X and out lies at
+ * i C S + c class_stride + s sample_stride, so (S, 1) is the layout [n, C, S] of a block of Lanczos vectors and (1, C) the
+ * [n, S, C] of mgp_softmax_cg_block.  pi [n, C] is shared by the samples.  A group of lanes owns a (node, sample) row; sqrt(pi), the
+ * row's dot product and the combination are float64 from the float32 inputs, rounded once at the store.  Where pi_ic = 0 the
+ * entry is exactly 0 (forward) or exactly V (0 without V) whatever V and X hold there, NaN included.  out may be V or X.  No
+ * atomics, no workspace: repeated calls are bitwise equal.  Element alignment only.
+ * MGP_ERR_ARG for null pi or out, null V (forward) or X (transposed), X given forward, n < 1, C outside 2 .. 64, S < 1, C S > 256,
+ * and strides that are not positive, let two entries of a row overlap or reach beyond its C S floats.  The checks precede the
+ * launch. */
+int mgp_softmax_root_apply(const float* pi, const float* V, const float* X, int64_t n, int C, int S, int64_t class_stride,
+                           int64_t sample_stride, int transpose, float* out, void* stream);
+/* The curvature term of the softmax evidence's gradient from latent deviations: for delta [n, S, C] float32 (the solution of
+ * mgp_softmax_cg_block for S perturb-and-MAP right-hand sides: delta_s ~ N(0, A^-1)) and pi [n, C],
+ *   d = delta_is - (pi_i . delta_is),   g_s = pi_ic (d_c^2 - sum_a pi_ia d_a^2),   acc_ic += sum_s g_s,   acc2_ic += sum_s g_s^2
+ * in float64 from the float32 inputs, the samples added in the order s = 0 .. S - 1 and then to the entry: E g_s =
+ * tr(V_i dH_i / df_ic) with V_i the C x C diagonal block of A^-1.  acc, acc2 [n, C] float64, distinct.  A row of zeros in pi is not
+ * written.  One writer per entry, no atomics: a second run over the same blocks is bitwise equal.
+ * MGP_ERR_ARG for null pointers, acc == acc2, n < 1, C outside 2 .. 64, S < 1, C S > 256. */
+int mgp_softmax_curvature(const float* pi, const float* delta, int64_t n, int C, int S, double* acc, double* acc2, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Eigensolve: the m smallest eigenpairs of L_sym by a Chebyshev-filtered block Krylov iteration

@@ -181,6 +181,8 @@ SIGNATURES = {
                                      POINTER(c_float), POINTER(c_int32), _P, c_size_t, _P]),
     "mgp_softmax_hessian_add_block_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mgp_softmax_hessian_add_block": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mgp_softmax_root_apply": (c_int, [_P, _P, _P, c_int64, c_int, c_int, c_int64, c_int64, c_int, _P, _P]),
+    "mgp_softmax_curvature": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P]),
     "mgp_cg_workspace_bytes": (c_size_t, [POINTER(OperatorT), c_int]),
     "mgp_cg_solve": (c_int, [POINTER(OperatorT), _P, c_int, _P, _P, POINTER(CgParamsT), POINTER(c_int32),
                              POINTER(c_float), _P, c_size_t, _P]),

@@ -510,7 +510,30 @@ class MulticlassLaplaceFit:
         return torch.softmax(self.mean.double(), dim=-1)
 
     def evidence(self, **kw):
-        raise NotImplementedError("the Laplace evidence of the softmax fit is not built: see docs/scope.md")
+        raise NotImplementedError("the evidence of the softmax fit has its own entry point: MulticlassLaplaceFit.laplace_evidence "
+                                  "(evidence.softmax_evidence)")
+
+    def laplace_evidence(self, **kw):
+        """log Z of this fit and, with operator=, its hyper-parameter gradient: evidence.softmax_evidence(self, **kw)."""
+        from .evidence import softmax_evidence
+        return softmax_evidence(self, **kw)
+
+    def _delta_blocks(self, S, seed, tol, max_iter, b):
+        """The deviations delta_s = A^-1 (z_s + R eps_s) ~ N(0, A^-1) of the samples s = 0 .. S - 1, `b` per solve: (delta
+        [n, b, C] float32, the number of live samples in it) per block; the samples beyond S - 1 of the last block are zeros."""
+        desc, C = self.desc, self.num_classes
+        P = sampling._check_desc(desc)
+        _lib.require_device(self.mean, self.pi)
+        n, pi = desc.n, self.pi[:, None, :]
+        with torch.no_grad():
+            for s0 in range(0, S, b):
+                # every block has width b, the last one too: sample s then depends on (seed, s, b) alone, not on S
+                z = sampling._precision_chunk(desc, P, b * C, seed, s0 * C).view(n, b, C)
+                eps = sampling.gmrf_noise(desc.data, b * C, seed, s0 * C, tag=2).view(n, b, C)
+                rhs = z + softmax_noise_factor(pi, eps)
+                if s0 + b > S:
+                    rhs[:, S - s0:] = 0.0
+                yield softmax_cg_solve_block(desc, self.pi, rhs, tol=tol, max_iter=max_iter)[0], min(b, S - s0)
 
     def _samples(self, S, seed, tol, max_iter, block=None):
         """Sample s = 0 .. S - 1 as [n, C] float32: one at a time (block None), or drawn `block` per solve (views into the
@@ -527,17 +550,9 @@ class MulticlassLaplaceFit:
                     delta = softmax_cg_solve(desc, self.pi, z + softmax_noise_factor(self.pi, eps), tol=tol, max_iter=max_iter)[0]
                     yield self.mean + delta
                 return
-            _lib.require_device(self.mean, self.pi)
-            n, pi = desc.n, self.pi[:, None, :]
-            for s0 in range(0, S, b):
-                # every block has width b, the last one too: sample s then depends on (seed, s, b) alone, not on S
-                z = sampling._precision_chunk(desc, P, b * C, seed, s0 * C).view(n, b, C)
-                eps = sampling.gmrf_noise(desc.data, b * C, seed, s0 * C, tag=2).view(n, b, C)
-                rhs = z + softmax_noise_factor(pi, eps)
-                if s0 + b > S:
-                    rhs[:, S - s0:] = 0.0
-                x = self.mean[:, None, :] + softmax_cg_solve_block(desc, self.pi, rhs, tol=tol, max_iter=max_iter)[0]
-                for k in range(min(b, S - s0)):
+            for delta, live in self._delta_blocks(S, seed, tol, max_iter, b):
+                x = self.mean[:, None, :] + delta
+                for k in range(live):
                     yield x[:, k]
 
     def latent_samples(self, S, seed=None, tol=1e-5, max_iter=5000, block=None):

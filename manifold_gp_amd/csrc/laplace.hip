@@ -58,8 +58,18 @@
 //    the mode), a per-cutpoint float64 reduction over the nodes: a node of category c adds to its upper cut b_{c+1} and to its lower
 //    cut b_c.  A workgroup stages a step's contributions in LDS and one lane per (row, cut) adds them in node order; one partial
 //    [3, K - 1] per workgroup, a second launch adds the partials in workgroup order.  No atomics, no shuffles.
+//
+// 11. mgp_softmax_root_apply: the factor R of the softmax Hessian, R_i = diag(s_i)(I - s_i s_i^T) with s_i = sqrt(pi_i), so that
+//    R_i R_i^T = H_i: out = R V or out = V + R^T X on S vectors of [n, C] in either order of class and sample inside a row (the
+//    strides are arguments), the row layout of kernel 3 with a row per (node, sample).  The two launches around the solve in a
+//    product with B = I + R^T (Q2^-1 (x) I) R (docs/kernels/evidence.md, "The softmax family").
+//
+// 12. mgp_softmax_curvature: g_ic = tr(V_i dH_i / df_ic) of the same evidence as an expectation over latent deviations,
+//    accumulated block by block in float64 with its sum of squares: a group per node adds its S samples in order, one writer per
+//    entry.
 #include <cfloat>
 #include <cmath>
+#include <utility>
 
 #include "mgp_common.h"
 #include "mgp_internal.h"
@@ -820,6 +830,83 @@ __global__ __launch_bounds__(kBlock) void softmax_site_kernel(const float* __res
   }
 }
 
+// out = R V (forward) or V + R^T X (transposed; V nullable) on S vectors of [n, C]: entry (i, c, s) lies at i C S + c cstride +
+// s sstride.  A group of TC lanes owns the row q = i S + s, lane c its class.  sqrt(pi), the row's dot product (an xor tree over
+// the group) and the combination in float64, one rounding at the store.  Where pi_ic = 0 the lane's terms are exactly 0 whatever
+// V and X hold.  out may be V or X: every lane loads its entry before the group's shuffles and stores after them.
+template <int TC>
+__global__ __launch_bounds__(kBlock) void softmax_root_kernel(const float* __restrict__ pi, const float* V, const float* X,
+                                                              int64_t n, int C, int S, int64_t cstride, int64_t sstride,
+                                                              bool transpose, float* out) {
+  constexpr int kRows = kBlock / TC;
+  const int c = threadIdx.x & (TC - 1), g = threadIdx.x / TC;
+  const int64_t rows = n * S;
+  const int64_t stride = (int64_t)gridDim.x * kRows;
+  const int64_t steps = (rows + stride - 1) / stride;                   // the same for every lane: the shuffles stay convergent
+  for (int64_t k = 0; k < steps; ++k) {
+    const int64_t q = k * stride + (int64_t)blockIdx.x * kRows + g;
+    const bool live = q < rows && c < C;
+    const int64_t i = q / S;
+    const int64_t at = i * C * S + c * cstride + (q - i * S) * sstride;
+    const double p = live ? (double)pi[i * C + c] : 0.0;
+    const bool on = p > 0.0;
+    const double root = on ? sqrt(p) : 0.0;
+    double r;
+    if (!transpose) {
+      const double t = on ? root * (double)V[at] : 0.0;
+      const double dot = mgp_group_sum_d<TC>(t);
+      r = on ? t - p * dot : 0.0;
+    } else {
+      const double x = on ? (double)X[at] : 0.0;
+      const double dot = mgp_group_sum_d<TC>(p * x);
+      const double v = (live && V) ? (double)V[at] : 0.0;
+      r = on ? v + root * (x - dot) : v;
+    }
+    if (live) out[at] = (float)r;
+  }
+}
+
+// acc_ic += sum_s g_s, acc2_ic += sum_s g_s^2 with g_s = pi_c (d_c^2 - sum_a pi_a d_a^2), d = delta_s - (pi . delta_s), over the
+// S deviations delta [n, S, C] of a block: a group of TC lanes owns node i for all its samples, which it adds in the order
+// s = 0 .. S - 1.  float64 from the float32 inputs; one writer per entry.  A row of zeros in pi is not written.
+template <int TC>
+__global__ __launch_bounds__(kBlock) void softmax_curvature_kernel(const float* __restrict__ pi, const float* __restrict__ delta,
+                                                                   int64_t n, int C, int S, double* __restrict__ acc,
+                                                                   double* __restrict__ acc2) {
+  constexpr int kRows = kBlock / TC;
+  const int c = threadIdx.x & (TC - 1), g = threadIdx.x / TC;
+  const int64_t stride = (int64_t)gridDim.x * kRows;
+  const int64_t steps = (n + stride - 1) / stride;
+  for (int64_t k = 0; k < steps; ++k) {
+    const int64_t i = k * stride + (int64_t)blockIdx.x * kRows + g;
+    const bool live = i < n && c < C;
+    const double p = live ? (double)pi[i * C + c] : 0.0;
+    const bool row_on = mgp_group_max_d<TC>(p) > 0.0;                    // (no early exit: the groups of a wave stay in step)
+    double sum = 0.0, sum2 = 0.0;
+    for (int s = 0; s < S; ++s) {
+      const double x = p > 0.0 ? (double)delta[(i * S + s) * C + c] : 0.0;
+      const double d = x - mgp_group_sum_d<TC>(p * x);
+      const double d2 = d * d;
+      const double gs = p * (d2 - mgp_group_sum_d<TC>(p * d2));
+      sum += gs;
+      sum2 += gs * gs;
+    }
+    if (live && row_on) {
+      acc[i * C + c] += sum;
+      acc2[i * C + c] += sum2;
+    }
+  }
+}
+
+// the strides of a dense [C, S] or [S, C] image of a row: positive, no two entries at one offset, every offset below C S
+bool root_strides_ok(int C, int S, int64_t cstride, int64_t sstride) {
+  if (cstride < 1 || sstride < 1) return false;
+  int64_t s1 = cstride, e1 = C, s2 = sstride, e2 = S;
+  if (s1 > s2 || (s1 == s2 && e1 < e2)) { std::swap(s1, s2); std::swap(e1, e2); }     // (s1, e1): the inner dimension
+  if (e2 > 1 && s2 < s1 * e1) return false;                                            // the outer dimension steps over the inner
+  return (e1 - 1) * s1 + (e2 - 1) * s2 < (int64_t)C * S;
+}
+
 int softmax_site_blocks(int64_t n, int C) { return mgp_softmax_blocks(n, C, kBlock, kSiteMaxBlocks); }
 
 int site_blocks(int64_t n) {
@@ -1080,6 +1167,35 @@ extern "C" int mgp_scale_rows(const float* s, const float* V, const float* X, in
     hipLaunchKernelGGL(scale_rows_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), s, V, X, n, P, out);
   else
     hipLaunchKernelGGL(scale_rows_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), s, V, X, n, P, out);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" int mgp_softmax_root_apply(const float* pi, const float* V, const float* X, int64_t n, int C, int S,
+                                      int64_t class_stride, int64_t sample_stride, int transpose, float* out, void* stream) {
+  if (!pi || !out || n < 1 || C < 2 || C > 64 || S < 1 || (int64_t)C * S > 256) return MGP_ERR_ARG;
+  if (transpose ? !X : (!V || X)) return MGP_ERR_ARG;
+  if (!root_strides_ok(C, S, class_stride, sample_stride)) return MGP_ERR_ARG;
+  const int blocks = mgp_softmax_blocks(n * S, C, kBlock, kSiteMaxBlocks);
+  hipStream_t st = mgp_stream(stream);
+  mgp_softmax_dispatch(C, [&](auto tc) {
+    hipLaunchKernelGGL(softmax_root_kernel<decltype(tc)::value>, dim3((unsigned)blocks), dim3(kBlock), 0, st, pi, V, X, n, C, S,
+                       class_stride, sample_stride, transpose != 0, out);
+  });
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+extern "C" int mgp_softmax_curvature(const float* pi, const float* delta, int64_t n, int C, int S, double* acc, double* acc2,
+                                     void* stream) {
+  if (!pi || !delta || !acc || !acc2 || acc == acc2 || n < 1 || C < 2 || C > 64 || S < 1 || (int64_t)C * S > 256)
+    return MGP_ERR_ARG;
+  const int blocks = softmax_site_blocks(n, C);
+  hipStream_t st = mgp_stream(stream);
+  mgp_softmax_dispatch(C, [&](auto tc) {
+    hipLaunchKernelGGL(softmax_curvature_kernel<decltype(tc)::value>, dim3((unsigned)blocks), dim3(kBlock), 0, st, pi, delta, n,
+                       C, S, acc, acc2);
+  });
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }

@@ -190,10 +190,16 @@ class RiemannGP(torch.nn.Module):
         return laplace_fit_ordinal(desc, y, num_categories, cutpoints, observed, **kw)
 
     def _laplace_fit(self, observed, family, **kw):
-        """The binary fit (family "bernoulli"), the count fit ("poisson", "binomial", "negative_binomial") or the ordered-category
-        fit ("ordinal", with num_categories= and cutpoints= in kw) of train_targets."""
+        """The binary fit (family "bernoulli"), the count fit ("poisson", "binomial", "negative_binomial"), the ordered-category
+        fit ("ordinal", with num_categories= and cutpoints= in kw) or the C-class fit ("multiclass", with num_classes= in kw) of
+        train_targets."""
         if family == "bernoulli":
             return self.laplace_posterior(observed, **kw)
+        if family == "multiclass":
+            if "num_classes" not in kw:
+                raise ValueError("family 'multiclass' needs num_classes")
+            kw = dict(kw)
+            return self.laplace_posterior_multiclass(kw.pop("num_classes"), observed, **kw)
         if family == "ordinal":
             if "num_categories" not in kw:
                 raise ValueError("family 'ordinal' needs num_categories")
@@ -210,17 +216,20 @@ class RiemannGP(torch.nn.Module):
         caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta.
         family "ordinal" (laplace_posterior_ordinal) takes num_categories= and cutpoints=; cutpoints may be an
         ordinal.CutpointParameter or a float64 tensor that requires grad: the fit runs at their detached values and value carries
-        d log Z / d cutpoints as well."""
+        d log Z / d cutpoints as well.
+        family "multiclass" (laplace_posterior_multiclass) takes num_classes=; the other arguments go to
+        evidence.softmax_evidence (curvature, var_samples, block, num_probes, ...)."""
         import inspect
-        from ..classification import laplace_fit
+        from ..classification import laplace_fit, laplace_fit_multiclass
         from ..counts import laplace_fit_counts
-        from ..evidence import ORDINAL_FAMILY, _family, laplace_evidence
+        from ..evidence import MULTICLASS_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
         from ..ordinal import _live_cutpoints, laplace_fit_ordinal
-        if family != ORDINAL_FAMILY:
+        if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
             _family(family)
         kw = dict(kw)
         fit_kw, evidence_kw = dict(kw.pop("fit_kw", None) or {}), dict(kw.pop("evidence_kw", None) or {})
-        fitter = {"bernoulli": laplace_fit, ORDINAL_FAMILY: laplace_fit_ordinal}.get(family, laplace_fit_counts)
+        fitter = {"bernoulli": laplace_fit, ORDINAL_FAMILY: laplace_fit_ordinal,
+                  MULTICLASS_FAMILY: laplace_fit_multiclass}.get(family, laplace_fit_counts)
         names = set(inspect.signature(fitter).parameters)
         if fitter is laplace_fit_counts:
             names.add("dispersion")                       # (counts.fit_counts: the negative binomial's, refused elsewhere)
@@ -231,6 +240,8 @@ class RiemannGP(torch.nn.Module):
             if live is not None:
                 evidence_kw.setdefault("cutpoints", live)
         fit = self._laplace_fit(observed, family, **fit_kw)
+        if family == MULTICLASS_FAMILY:
+            return softmax_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
         return laplace_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
 
     # ------------------------------------------------------------------ riemann_gp.py:41-43

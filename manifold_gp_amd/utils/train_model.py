@@ -101,13 +101,15 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
     model.train_targets), "poisson", "binomial" or "negative_binomial" (counts; fit_kw carries exposure / trials / mean, and the negative binomial's
     fixed dispersion); "ordinal" (ordered categories; fit_kw carries num_categories and cutpoints: an ordinal.CutpointParameter is
-    evaluated every epoch and its parameters, held by the same optimizer, are trained along).  Every epoch refits the mode
+    evaluated every epoch and its parameters, held by the same optimizer, are trained along); "multiclass" (class indices; fit_kw
+    carries num_classes, the evidence is evidence.softmax_evidence).  Every epoch refits the mode
     from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
     the last loss."""
-    from ..evidence import ORDINAL_FAMILY, _family, laplace_evidence
+    from ..evidence import MULTICLASS_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
     from ..ordinal import _live_cutpoints
-    if family != ORDINAL_FAMILY:
+    if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
         _family(family)
+    evidence_of = softmax_evidence if family == MULTICLASS_FAMILY else laplace_evidence
     model.train()
     fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
     graph = getattr(getattr(model.base_kernel, "knn", None), "knn_graph", None)
@@ -121,7 +123,7 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
         fit = model._laplace_fit(observed, family, f0=f0, **epoch_kw)
         f0 = fit.mean
         epoch_ev = evidence_kw if live is None else dict(evidence_kw, cutpoints=live)
-        ev = laplace_evidence(fit, operator=model.precision(noise=False), **epoch_ev)
+        ev = evidence_of(fit, operator=model.precision(noise=False), **epoch_ev)
         loss = -ev.value
         for _, module, prior, closure, _ in _named_priors(model):
             loss = loss - prior.log_prob(closure(module)).sum().to(loss)

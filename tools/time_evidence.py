@@ -1,11 +1,12 @@
 """Time the Laplace evidence (manifold_gp_amd/evidence.py) on the 60k manifold_784 workload of tools/time_counts.py (k = 50,
-random walk, nu = 2; 10 % of the nodes observed; 0/1 labels, Poisson and binomial counts): the wall time of the evidence value
+random walk, nu = 2; 10 % of the nodes observed; 0/1 labels, Poisson and binomial counts, and three classes for the softmax fit,
+whose evidence is evidence.softmax_evidence): the wall time of the evidence value
 with 16 probes (method "slq": m = 6000 is above the dense threshold), of the value with its hyper-parameter gradient (backward
 included), and of one laplace_train epoch, each the median of --reps in one warmed process, and the share of each spent inside
 cg_solve (a second, instrumented pass that synchronises around every solve).  Prints one JSON line.  Nothing here is an
 acceptance bar.
 
-    python tools/time_evidence.py [--reps 5]
+    python tools/time_evidence.py [--reps 5] [--families bernoulli,poisson,binomial,multiclass]
 """
 import argparse
 import json
@@ -25,12 +26,14 @@ from tools.time_sampling import _wall_ms  # noqa: E402
 
 
 class _SolveClock:
-    """Replaces solvers.cg_solve and evidence._solve64 (the float64 solves of the gradient, which go to their plan directly) by
-    wrappers that add up the synchronised wall time of the solves."""
+    """Replaces solvers.cg_solve, evidence._solve64 (the float64 solves of the gradient, which go to their plan directly) and
+    classification.softmax_cg_solve_block (the coupled solves of the softmax family) by wrappers that add up the synchronised
+    wall time of the solves."""
 
     def __init__(self):
-        from manifold_gp_amd import evidence, solvers
-        self.targets = [(solvers, "cg_solve", solvers.cg_solve), (evidence, "_solve64", evidence._solve64)]
+        from manifold_gp_amd import classification, evidence, solvers
+        self.targets = [(solvers, "cg_solve", solvers.cg_solve), (evidence, "_solve64", evidence._solve64),
+                        (classification, "softmax_cg_solve_block", classification.softmax_cg_solve_block)]
         self.ms, self.calls = 0.0, 0
 
     def _timed(self, inner):
@@ -73,6 +76,7 @@ def _timed(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--families", default="bernoulli,poisson,binomial,multiclass")
     args = ap.parse_args()
     import manifold_gp_amd as mgp
     from manifold_gp_amd.models import GaussianLikelihood, RiemannGP, ScaleKernel
@@ -93,7 +97,10 @@ def main():
     trials = torch.from_numpy(N.astype(np.float32)).to(dev)
     data = {"bernoulli": ((torch.from_numpy(y_bin).to(dev) * 2 > trials).float(), {}),
             "poisson": (torch.from_numpy(y_pois).to(dev), dict(exposure=torch.from_numpy(E).to(dev))),
-            "binomial": (torch.from_numpy(y_bin).to(dev), dict(trials=trials))}
+            "binomial": (torch.from_numpy(y_bin).to(dev), dict(trials=trials)),
+            "multiclass": (torch.from_numpy(np.searchsorted(np.quantile(ftrue, [1 / 3, 2 / 3]), ftrue).astype(np.float32)).to(dev),
+                           dict(num_classes=3))}
+    data = {k: v for k, v in data.items() if k in args.families.split(",")}
     res = dict(tool="time_evidence", n=n, observed=int(obs_np.sum()), probes=16, steps=12)
     for family, (y, kw) in data.items():
         kern = mgp.kernels.RiemannMaternKernel(nu=2, x=x, nearest_neighbors=50, laplacian_normalization="randomwalk",
@@ -101,18 +108,19 @@ def main():
         kern.initialize(graphbandwidth=0.3, lengthscale=3.0)
         model = RiemannGP(x, y, GaussianLikelihood(1e-2).to(dev), ScaleKernel(kern, 1.0).to(dev)).to(dev)
         fit = model._laplace_fit(obs, family, **kw)
-        ev = fit.evidence()
+        evidence = fit.laplace_evidence if family == "multiclass" else fit.evidence
+        ev = evidence()
         r = dict(m=ev.m, method=ev.method, log_z=round(float(ev.value), 3), se=round(ev.se, 3), logdet_b=round(ev.logdet, 3),
                  fit_newton_steps=fit.iterations)
 
         def with_gradient():
             model.zero_grad()
-            fit.evidence(operator=model.precision(noise=False)).value.backward()
+            evidence(operator=model.precision(noise=False)).value.backward()
 
         def epoch():
             opt = torch.optim.Adam(model.parameters(), lr=0.0)          # the hyper-parameters stay where they are
             laplace_train(model, opt, observed=obs, family=family, max_iter=0, fit_kw=dict(kw, f0=fit.mean))
-        for name, fn in (("value", lambda: fit.evidence()), ("value_and_gradient", with_gradient), ("train_epoch", epoch)):
+        for name, fn in (("value", lambda: evidence()), ("value_and_gradient", with_gradient), ("train_epoch", epoch)):
             r[name + "_wall_ms"], r[name + "_solve_share"], r[name + "_solves"] = _timed(fn, args.reps)
         res[family] = r
     print(json.dumps(res))
