@@ -33,7 +33,7 @@ import warnings
 
 import torch
 
-from . import _lib, sampling
+from . import _lib, _sites, sampling
 from ._lib import check, lib, ptr, stream
 
 S_REF = 4.0              # obs_w = S_REF h <= 1
@@ -72,21 +72,8 @@ def bernoulli_site(f, qf, y, observed=None, s_ref=S_REF, link="logit"):
     (zeros); observed [n] bool or None (every node)."""
     if link not in LINKS:
         raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    _lib.require_device(f, qf, y, observed)
-    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
-    n = f.shape[0]
-    qf = None if qf is None else _lib.f32c(qf.reshape(-1))
-    if observed is not None:
-        if observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        observed = observed.reshape(-1).contiguous()
-    for name, t in (("qf", qf), ("y", y), ("observed", observed)):
-        if t is not None and t.shape[0] != n:
-            raise ValueError("%s has %d entries, f %d" % (name, t.shape[0], n))
-    w, rhs = torch.empty_like(f), torch.empty_like(f)
-    sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_bernoulli_site_workspace_bytes(n)
-    work = _lib.workspace(wb, "bernoulli_site", f.device)
+    f, qf, (y,), observed, n, w, rhs, sums, work = _sites.newton_args(
+        f, qf, (("y", y),), (), observed, "bernoulli_site", lib().mgp_bernoulli_site_workspace_bytes)
     check(lib().mgp_bernoulli_site(ptr(f), ptr(qf), ptr(y), ptr(observed), n, float(s_ref), LINKS[link], ptr(w), ptr(rhs),
                                    ptr(sums), ptr(work), work.numel(), stream()), "mgp_bernoulli_site")
     return w, rhs, sums

@@ -35,7 +35,7 @@ import math
 
 import torch
 
-from . import _lib, sampling
+from . import _lib, _sites, sampling
 from ._lib import check, lib, ptr, stream
 from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2, bernoulli_predict
 
@@ -78,22 +78,9 @@ def count_site(f, qf, y, aux, observed, s_ref, mean, family, dispersion=None):
     r = _dispersion(fam, dispersion)
     if fam == 1 and aux is None:
         raise ValueError("the binomial family needs the trials in aux")
-    _lib.require_device(f, qf, y, aux, observed)
-    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
-    n = f.shape[0]
-    qf = None if qf is None else _lib.f32c(qf.reshape(-1))
-    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
-    if observed is not None:
-        if observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        observed = observed.reshape(-1).contiguous()
-    for name, t in (("qf", qf), ("y", y), ("aux", aux), ("observed", observed)):
-        if t is not None and t.shape[0] != n:
-            raise ValueError("%s has %d entries, f %d" % (name, t.shape[0], n))
-    w, rhs = torch.empty_like(f), torch.empty_like(f)
-    sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_nb_site_workspace_bytes(n) if fam == NB else lib().mgp_count_site_workspace_bytes(n)
-    work = _lib.workspace(wb, "count_site", f.device)
+    f, qf, (y, aux), observed, n, w, rhs, sums, work = _sites.newton_args(
+        f, qf, (("y", y),), (("aux", aux),), observed, "count_site",
+        lib().mgp_nb_site_workspace_bytes if fam == NB else lib().mgp_count_site_workspace_bytes)
     if fam == NB:
         check(lib().mgp_nb_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), r, ptr(w), ptr(rhs),
                                 ptr(sums), ptr(work), work.numel(), stream()), "mgp_nb_site")

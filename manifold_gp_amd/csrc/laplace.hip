@@ -1,72 +1,64 @@
-// Laplace approximation for a Bernoulli-logit likelihood on the graph nodes (docs/kernels/classification.md): the two
-// per-node kernels that classification.laplace_fit adds to the form-3 solver.
+// The per-node kernels of the Laplace fits on the graph nodes: Bernoulli-logit and softmax (docs/kernels/classification.md),
+// Poisson / binomial / negative binomial (docs/kernels/counts.md), ordered categories (docs/kernels/ordinal.md), and of their
+// evidence (docs/kernels/evidence.md).  All float64 arithmetic from float32 inputs, one rounding at the store.
 //
-// 1. mgp_bernoulli_site: the likelihood stage of one Newton step.  Per node, in float64 from the float32 inputs, with
-//    t = (y > 0.5), a = (2 t - 1) f and e = exp(-|f|):
-//      log p = min(a, 0) - log1p(e)          pi = f >= 0 ? 1 / (1 + e) : e / (1 + e)
-//      g = t - pi                            h = e / (1 + e)^2                          (no overflow, h without cancellation)
-//    w = s_ref h (0 at unobserved nodes) and rhs = s_ref (g - qf) (g = 0 at unobserved nodes) leave as float32, and four
-//    float64 sums -- sum_obs log p, sum f qf, max |g - qf|, sum (g - qf)^2 -- through per-workgroup partials: a thread adds
-//    its nodes in index order, xor tree over the wave, the waves in order, and a second single-workgroup launch adds the
-//    partials in a fixed order.  No atomics: repeated calls are bitwise equal.  18 bytes per node (f, qf, y, obs in; w, rhs
-//    out): a float4 / uchar4 per lane and step where the arrays are 16-byte (obs 4-byte) aligned, scalar otherwise and
-//    for the last n % 4 nodes.
+// The node loop (site_kernel, evidence_kernel).  Every family of the two per-node stages runs one loop: a thread takes quads of
+// nodes at a grid stride (256 threads, at most 1024 workgroups), a float4 / uchar4 (var: two double2) per array and step where
+// every array is 16-byte (obs 4-byte) aligned, scalar otherwise and for the last n % 4 nodes.  The family -- a struct passed by
+// value, its scalars as members and operator() the formulas of one node -- is the template argument.  Its two input
+// arrays (a, b) are (y, -) for Bernoulli, (y, aux) for the counts and (lo, hi) for ordinal; they are read only where a node of
+// the quad is observed (they may be NaN elsewhere) and b may be NULL (zeros).  qf NULL: zeros; obs NULL: every node.
 //
-// 2. mgp_bernoulli_predict: p_i = sum_k D phi(u_k) sigma(m_i + sqrt(v_i) u_k), u_k = -8 + k D, D = 16 / (K - 1): the K-point
-//    trapezoid rule on [-8, 8] in float64.  The workgroup fills (u_k, D phi(u_k)) in LDS once; a thread per node sums k in
-//    ascending order.
+// The sums.  A thread adds its nodes in index order into a SiteAcc {lp, fq, mx, sq}; block_reduce takes an xor tree over each
+// wave and the waves in order; store_partials leaves the workgroup's four float64 numbers in the workspace (32 bytes per
+// workgroup) and a second single-workgroup launch, site_sum_kernel, adds the partials in a fixed order into sums[4].  No atomics:
+// repeated calls are bitwise equal.  Newton stage: sums = { sum_obs log p, sum f qf, max |g - qf|, sum (g - qf)^2 }; evidence
+// stage: { sum_obs log p, nodes kept, sum corr, max |corr| } (sum_first: the sum slot leaves before the max slot).
 //
-// 3. mgp_softmax_site: the likelihood stage of a C-class fit (classification.laplace_fit_multiclass).  F, Q2 F, pi and rhs are
-//    row-major [n, C]; a group of TC lanes (the least power of two >= C) owns a row, lane c its class: consecutive lanes read
-//    consecutive floats of the block.  Per row in float64: m = max_c f_c, e_c = exp(f_c - m), Z = sum e_c (xor trees inside
-//    the group), pi_c = e_c / Z, log p = f_t - m - log Z; G = onehot(t) - pi on observed rows (G_t = sum_{c != t} e_c / Z, a second
-//    xor tree: 1 - pi_t cancels where pi_t -> 1), 0 elsewhere, rhs = G - qf.  The
-//    label is only compared with the lane's class, never used as an index.  The four sums leave through SiteAcc, block_reduce
-//    and bernoulli_site_sum_kernel as above.
+// Newton stage (mgp_bernoulli_site, mgp_count_site, mgp_nb_site, mgp_ordinal_site): from the family's log p, g = d log p / df and
+// h = -d g / df on observed nodes (g = h = 0 elsewhere), w = s_ref h and rhs = s_ref (g - qf) leave as float32.
+//   Bernoulli, t = (y > 0.5), a = (2 t - 1) f, e = exp(-|f|):  log p = min(a, 0) - log1p(e), pi = f >= 0 ? 1 / (1 + e) : e / (1 + e),
+//     g = t - pi, h = e / (1 + e)^2  (no overflow, h without cancellation).
+//   Poisson, eta = f + mean + log-exposure:  mu = exp(min(eta, 700)), log p = y eta - mu, g = y - mu, h = mu.
+//   Binomial with N trials, eta = f + mean, e = exp(-|eta|):  log p = -(N - y)(max(eta, 0) + log1p(e)) - y (max(-eta, 0) + log1p(e)),
+//     g = y (1 - pi) - (N - y) pi with 1 - pi formed without the subtraction, h = N e / (1 + e)^2.
+//   Negative binomial with dispersion r:  the binomial arithmetic with y + r trials and r failures at eta = f + mean +
+//     log-exposure - log r, so 0 < h <= (y + r) / 4.
+//   h of the counts is unbounded: their w and rhs saturate at +-FLT_MAX instead of leaving as inf (site_tail<true>).
+//   Ordinal, the node's interval of cutpoints (lo, hi], u = hi - f, l = lo - f:  log p = log sigma(u) + log sigma(-l) (the product
+//     form of sigma(u) - sigma(l), its f-independent factor left to the caller), g = sigma(l) - sigma(-u),
+//     h = sigma(u) sigma(-u) + sigma(l) sigma(-l) in (0, 1/2].  The ends may be infinite.
 //
-// 4. mgp_count_site: the likelihood stage of a count fit (counts.laplace_fit_counts, docs/kernels/counts.md), the layout and
-//    the sums of kernel 1 with one more input array.  eta = f + mean (+ log-exposure); Poisson: mu = exp(min(eta, 700)),
-//    l = y eta - mu, g = y - mu, h = mu; binomial with N trials: e = exp(-|eta|), l = -(N - y)(max(eta, 0) + log1p(e))
-//    - y (max(-eta, 0) + log1p(e)), g = y (1 - pi) - (N - y) pi with 1 - pi formed without the subtraction, h = N e / (1 + e)^2.
-//    h is unbounded here: w and rhs saturate at +-FLT_MAX instead of leaving as inf.  mgp_nb_site is the same kernel's third
-//    family, the negative binomial with dispersion r: the binomial arithmetic with y + r trials and r failures at
-//    z = f + mean + log-exposure - log r, so 0 < h <= (y + r) / 4 and nothing saturates.
+// Evidence stage at the mode (mgp_laplace_evidence_site, mgp_nb_evidence_site, mgp_ordinal_evidence_site): root_h = sqrt(h) and
+// corr = var h' (h' = dh / df; var NULL: no corr) on the observed nodes with h >= h_floor, 0 elsewhere.  h as above (Bernoulli:
+// the binomial with one trial); h' = mu (Poisson), h (1 - 2 pi) (binomial kind), -(a_u (sigma(-u) - sigma(u)) + a_l (sigma(-l) -
+// sigma(l))) with a_x = sigma(x) sigma(-x) (ordinal), the differences formed as -+(1 - e) / (1 + e) from e = exp(-|x|).
 //
-// 5. mgp_laplace_evidence_site: the per-node stage of the Laplace evidence at the mode (evidence.laplace_evidence,
-//    docs/kernels/evidence.md), the layout of kernel 4 for the three families: sqrt(h) and var h' (h' = dh / df) on the observed
-//    nodes with h >= h_floor, 0 elsewhere, and the sums { sum_obs l, nodes kept, sum corr, max |corr| } through the same partials.
-//    mgp_nb_evidence_site: the same kernel's negative-binomial family.
-//
-// 6. mgp_scale_rows: out = s_i V_ij or fmaf(s_i, X_ij, V_ij) on row-major [n, P] blocks: the two row scalings around the solve in a
-//    product with B = I + S Q2^-1 S.  Both are bandwidth-trivial and launch-bound at 60k nodes.
-//
-// 7. mgp_ordinal_site: the likelihood stage of an ordered-category fit (ordinal.laplace_fit_ordinal, docs/kernels/ordinal.md), the
-//    layout and the sums of kernel 4 with the node's interval of cutpoints (lo, hi] in the place of (y, aux): u = hi - f,
-//    l = lo - f, log p = log sigma(u) + log sigma(-l) (the product form of sigma(u) - sigma(l), its f-independent factor left
-//    to the caller), g = sigma(l) - sigma(-u), h = sigma(u) sigma(-u) + sigma(l) sigma(-l) in (0, 1/2].  The ends may be infinite.
-//
-// 8. mgp_ordinal_predict: out_ik = int P(y = k | f) N(f; eta_i, var_i) df for the K ordered categories by the trapezoid rule of
-//    kernel 2, the integrand in the product form (every term positive: a tail category keeps its relative accuracy), the sum
-//    divided by the sum of the weights (rows sum to 1).  A group of TK lanes per node as kernel 3, lane k its category: one exp
-//    per lane and point, the lower cut's factor from lane k - 1 by a shuffle.
-//
-// 9. mgp_ordinal_evidence_site: kernel 5 for the ordered-category fit, the interval (lo, hi] in the place of (y, aux): sqrt(h) and
-//    var h' with h' = -(a_u (sigma(-u) - sigma(u)) + a_l (sigma(-l) - sigma(l))), a_x = sigma(x) sigma(-x), the differences formed as
-//    -+(1 - e) / (1 + e) from e = exp(-|x|).
-//
-// 10. mgp_ordinal_cut_sums: the three rows of d log Z / d b_k for the K - 1 cutpoints (likelihood, curvature at fixed f, through
-//    the mode), a per-cutpoint float64 reduction over the nodes: a node of category c adds to its upper cut b_{c+1} and to its lower
-//    cut b_c.  A workgroup stages a step's contributions in LDS and one lane per (row, cut) adds them in node order; one partial
-//    [3, K - 1] per workgroup, a second launch adds the partials in workgroup order.  No atomics, no shuffles.
-//
-// 11. mgp_softmax_root_apply: the factor R of the softmax Hessian, R_i = diag(s_i)(I - s_i s_i^T) with s_i = sqrt(pi_i), so that
-//    R_i R_i^T = H_i: out = R V or out = V + R^T X on S vectors of [n, C] in either order of class and sample inside a row (the
-//    strides are arguments), the row layout of kernel 3 with a row per (node, sample).  The two launches around the solve in a
-//    product with B = I + R^T (Q2^-1 (x) I) R (docs/kernels/evidence.md, "The softmax family").
-//
-// 12. mgp_softmax_curvature: g_ic = tr(V_i dH_i / df_ic) of the same evidence as an expectation over latent deviations,
-//    accumulated block by block in float64 with its sum of squares: a group per node adds its S samples in order, one writer per
-//    entry.
+// The other kernels:
+//   mgp_softmax_site: the Newton stage of a C-class fit.  F, Q2 F, pi and rhs are row-major [n, C]; a group of TC lanes owns a row
+//     (softmax_rows.h).  Per row: m = max_c f_c, e_c = exp(f_c - m), Z = sum e_c (xor trees inside the group), pi_c = e_c / Z,
+//     log p = f_t - m - log Z; G = onehot(t) - pi on observed rows (G_t = sum_{c != t} e_c / Z, a second xor tree: 1 - pi_t cancels
+//     where pi_t -> 1), 0 elsewhere, rhs = G - qf.  The label is only compared with the lane's class, never used as an index.
+//     The four sums leave as above.
+//   mgp_bernoulli_predict: p_i = sum_k D phi(u_k) sigma(m_i + sqrt(v_i) u_k), u_k = -8 + k D, D = 16 / (K - 1): the K-point
+//     trapezoid rule on [-8, 8].  The workgroup fills (u_k, D phi(u_k)) in LDS once (trapezoid_table); a thread per node sums k in
+//     ascending order.
+//   mgp_ordinal_predict: out_ik = int P(y = k | f) N(f; eta_i, var_i) df for the K ordered categories by the same rule, the
+//     integrand in the product form (every term positive: a tail category keeps its relative accuracy), the sum divided by the
+//     sum of the weights (rows sum to 1).  A group of TK lanes per node, lane k its category: one exp per lane and point, the
+//     lower cut's factor from lane k - 1 by a shuffle.
+//   mgp_ordinal_cut_sums: the three rows of d log Z / d b_k for the K - 1 cutpoints (likelihood, curvature at fixed f, through the
+//     mode), a per-cutpoint float64 reduction over the nodes: a node of category c adds to its upper cut b_{c+1} and to its lower
+//     cut b_c.  A workgroup stages a step's contributions in LDS and one lane per (row, cut) adds them in node order; one partial
+//     [3, K - 1] per workgroup, a second launch adds the partials in workgroup order.  No atomics, no shuffles.
+//   mgp_scale_rows: out = s_i V_ij or fmaf(s_i, X_ij, V_ij) on row-major [n, P] blocks: the two row scalings around the solve in a
+//     product with B = I + S Q2^-1 S.  Bandwidth-trivial and launch-bound at 60k nodes.
+//   mgp_softmax_root_apply: the factor R of the softmax Hessian, R_i = diag(s_i)(I - s_i s_i^T) with s_i = sqrt(pi_i), so that
+//     R_i R_i^T = H_i: out = R V or out = V + R^T X on S vectors of [n, C] in either order of class and sample inside a row (the
+//     strides are arguments), a row per (node, sample).  The two launches around the solve in a product with
+//     B = I + R^T (Q2^-1 (x) I) R (docs/kernels/evidence.md, "The softmax family").
+//   mgp_softmax_curvature: g_ic = tr(V_i dH_i / df_ic) of the same evidence as an expectation over latent deviations, accumulated
+//     block by block in float64 with its sum of squares: a group per node adds its S samples in order, one writer per entry.
 #include <cfloat>
 #include <cmath>
 #include <utility>
@@ -79,7 +71,7 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / MGP_WAVE;
-constexpr int kSiteMaxBlocks = 1024;      // grid cap of the site kernels: 1024 x 256 threads x 4 nodes per step (Bernoulli),
+constexpr int kSiteMaxBlocks = 1024;      // grid cap of the site kernels: 1024 x 256 threads x 4 nodes per step (the node loop),
                                           // 1024 x 256 / TC rows per step (softmax)
 constexpr int kPredictMaxBlocks = 2048;   // grid cap of the predict kernel: 2048 x 256 threads x 1 node per step
 constexpr int kMaxPoints = 1025;
@@ -87,29 +79,6 @@ constexpr int kMaxPoints = 1025;
 struct SiteAcc {
   double lp, fq, mx, sq;
 };
-
-__device__ __forceinline__ void site_node(float f32, float qf32, float y32, bool obs, double s_ref, float& w, float& rhs,
-                                          SiteAcc& acc) {
-  const double f = (double)f32, qf = (double)qf32;
-  double g = 0.0, h = 0.0;
-  if (obs) {
-    const bool t = y32 > 0.5f;
-    const double a = t ? f : -f;
-    const double e = exp(-fabs(f));
-    const double d = 1.0 + e;
-    const double pi = f >= 0.0 ? 1.0 / d : e / d;
-    acc.lp += (a < 0.0 ? a : 0.0) - log1p(e);
-    g = (t ? 1.0 : 0.0) - pi;
-    h = e / (d * d);
-  }
-  const double r = g - qf;
-  w = (float)(s_ref * h);
-  rhs = (float)(s_ref * r);
-  acc.fq += f * qf;
-  const double ar = fabs(r);
-  acc.mx = ar > acc.mx ? ar : acc.mx;
-  acc.sq += r * r;
-}
 
 __device__ __forceinline__ double wave_max_d(double v) {
 #pragma unroll
@@ -145,42 +114,8 @@ __device__ __forceinline__ SiteAcc block_reduce(SiteAcc a) {
   return r;
 }
 
-template <bool VEC4>
-__global__ __launch_bounds__(kBlock) void bernoulli_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
-                                                                const float* __restrict__ y,
-                                                                const uint8_t* __restrict__ obs, int64_t n, double s_ref,
-                                                                float* __restrict__ w, float* __restrict__ rhs,
-                                                                double* __restrict__ partials) {
-  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
-  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
-    const int64_t i0 = q << 2;
-    if (VEC4 && i0 + 4 <= n) {
-      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
-      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
-      // labels are read where a node of the quad is observed (they may be NaN elsewhere: never compared)
-      const bool any = ov.x | ov.y | ov.z | ov.w;
-      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-      float4 wv, rv;
-      site_node(fv.x, qv.x, yv.x, ov.x != 0, s_ref, wv.x, rv.x, acc);
-      site_node(fv.y, qv.y, yv.y, ov.y != 0, s_ref, wv.y, rv.y, acc);
-      site_node(fv.z, qv.z, yv.z, ov.z != 0, s_ref, wv.z, rv.z, acc);
-      site_node(fv.w, qv.w, yv.w, ov.w != 0, s_ref, wv.w, rv.w, acc);
-      *reinterpret_cast<float4*>(w + i0) = wv;
-      *reinterpret_cast<float4*>(rhs + i0) = rv;
-    } else {
-      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
-      for (int64_t i = i0; i < i1; ++i) {
-        const bool o = obs ? obs[i] != 0 : true;
-        float wi, ri;
-        site_node(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, o, s_ref, wi, ri, acc);
-        w[i] = wi;
-        rhs[i] = ri;
-      }
-    }
-  }
+// the workgroup's partial {lp, fq, mx, sq} from its threads' sums; every thread of the workgroup calls it
+__device__ __forceinline__ void store_partials(const SiteAcc& acc, double* __restrict__ partials) {
   const SiteAcc r = block_reduce(acc);
   if (threadIdx.x == 0) {
     double* p = partials + 4 * (int64_t)blockIdx.x;
@@ -192,9 +127,9 @@ __global__ __launch_bounds__(kBlock) void bernoulli_site_kernel(const float* __r
 }
 
 // sums[4] from the partials of `nblk` workgroups: thread t takes partials t, t + 256, ... in order, then the same tree.
-// sum_first: the sum slot leaves before the max slot (mgp_laplace_evidence_site: { .., sum corr, max |corr| })
-__global__ __launch_bounds__(kBlock) void bernoulli_site_sum_kernel(const double* __restrict__ partials, int nblk,
-                                                                    double* __restrict__ sums, bool sum_first = false) {
+// sum_first: the sum slot leaves before the max slot (the evidence stage: { .., sum corr, max |corr| })
+__global__ __launch_bounds__(kBlock) void site_sum_kernel(const double* __restrict__ partials, int nblk,
+                                                          double* __restrict__ sums, bool sum_first = false) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nblk; b += kBlock) {
     const double* p = partials + 4 * (int64_t)b;
@@ -212,11 +147,151 @@ __global__ __launch_bounds__(kBlock) void bernoulli_site_sum_kernel(const double
   }
 }
 
-__global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* __restrict__ mean,
-                                                                   const double* __restrict__ var, int64_t n, int K,
-                                                                   double* __restrict__ prob) {
-  __shared__ double s_u[kMaxPoints];
-  __shared__ double s_wt[kMaxPoints];
+// a float64 result as float32, +-FLT_MAX where the cast would leave as inf (NaN stays NaN)
+__device__ __forceinline__ float sat_f32(double v) {
+  const double m = (double)FLT_MAX;
+  return (float)(v > m ? m : (v < -m ? -m : v));
+}
+
+// ---- Newton stage.  A family: its scalars, kReadsB (it reads the second array) and operator(): one node, observed or not --
+// log p into acc.lp, g and h, then site_tail.
+
+// w, rhs and the three sums of a node from its g and h (0 at an unobserved node).  SATURATE: the counts, whose h is unbounded
+template <bool SATURATE>
+__device__ __forceinline__ void site_tail(double s_ref, double f, double qf, double g, double h, float& w, float& rhs,
+                                          SiteAcc& acc) {
+  const double r = g - qf;
+  w = SATURATE ? sat_f32(s_ref * h) : (float)(s_ref * h);
+  rhs = SATURATE ? sat_f32(s_ref * r) : (float)(s_ref * r);
+  acc.fq += f * qf;
+  const double ar = fabs(r);
+  acc.mx = ar > acc.mx ? ar : acc.mx;
+  acc.sq += r * r;
+}
+
+struct BernoulliSite {
+  static constexpr bool kReadsB = false;
+  double s_ref;
+  __device__ __forceinline__ void operator()(float f32, float qf32, float y32, float, bool obs, float& w, float& rhs,
+                                             SiteAcc& acc) const {
+    const double f = (double)f32;
+    double g = 0.0, h = 0.0;
+    if (obs) {
+      const bool t = y32 > 0.5f;
+      const double a = t ? f : -f;
+      const double e = exp(-fabs(f));
+      const double d = 1.0 + e;
+      const double pi = f >= 0.0 ? 1.0 / d : e / d;
+      acc.lp += (a < 0.0 ? a : 0.0) - log1p(e);
+      g = (t ? 1.0 : 0.0) - pi;
+      h = e / (d * d);
+    }
+    site_tail<false>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
+  }
+};
+
+// FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials; FAMILY 2: negative binomial with the dispersion
+// r_nb (log_r = log r), a32 the log-exposure: the binomial arithmetic with y + r "trials" and r "failures" at the predictor
+// z = f + mean + a - log r (pi = mu / (r + mu))
+template <int FAMILY>
+struct CountSite {
+  static constexpr bool kReadsB = true;
+  double s_ref, mean, r_nb, log_r;
+  __device__ __forceinline__ void operator()(float f32, float qf32, float y32, float a32, bool obs, float& w, float& rhs,
+                                             SiteAcc& acc) const {
+    const double f = (double)f32;
+    double g = 0.0, h = 0.0;
+    if (obs) {
+      const double y = (double)y32;
+      if (FAMILY == 0) {
+        const double eta = f + mean + (double)a32;
+        const double mu = exp(eta < 700.0 ? eta : 700.0);
+        acc.lp += y * eta - mu;
+        g = y - mu;
+        h = mu;
+      } else {
+        const double eta = FAMILY == 1 ? f + mean : f + mean + (double)a32 - log_r;
+        const double N = FAMILY == 1 ? (double)a32 : y + r_nb;
+        const double m = FAMILY == 1 ? N - y : r_nb;                     // failures (binomial: exact, both are integers <= 2^24)
+        const double e = exp(-fabs(eta));
+        const double d = 1.0 + e;
+        const double l1 = log1p(e);
+        const double pi = eta >= 0.0 ? 1.0 / d : e / d;
+        const double pib = eta >= 0.0 ? e / d : 1.0 / d;                 // 1 - pi without the subtraction
+        acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
+        g = y * pib - m * pi;
+        h = N * e / (d * d);
+      }
+    }
+    site_tail<true>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
+  }
+};
+
+// the category is the interval (lo32, hi32] of cutpoints, -inf / +inf at the end categories.  exp(-|x|) is 0 at an infinite end,
+// so sigma, log sigma and sigma (1 - sigma) need no special case there
+struct OrdinalSite {
+  static constexpr bool kReadsB = true;
+  double s_ref;
+  __device__ __forceinline__ void operator()(float f32, float qf32, float lo32, float hi32, bool obs, float& w, float& rhs,
+                                             SiteAcc& acc) const {
+    const double f = (double)f32;
+    double g = 0.0, h = 0.0;
+    if (obs) {
+      const double u = (double)hi32 - f, l = (double)lo32 - f;
+      const double eu = exp(-fabs(u)), el = exp(-fabs(l));
+      const double du = 1.0 + eu, dl = 1.0 + el;
+      acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu)) - ((l > 0.0 ? l : 0.0) + log1p(el));   // log sigma(u) + log sigma(-l)
+      g = (l >= 0.0 ? 1.0 / dl : el / dl) - (u >= 0.0 ? eu / du : 1.0 / du);               // sigma(l) - sigma(-u)
+      h = eu / (du * du) + el / (dl * dl);
+    }
+    site_tail<false>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
+  }
+};
+
+template <bool VEC4, typename Family>
+__global__ __launch_bounds__(kBlock) void site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
+                                                      const float* __restrict__ a, const float* __restrict__ b,
+                                                      const uint8_t* __restrict__ obs, int64_t n, Family fam,
+                                                      float* __restrict__ w, float* __restrict__ rhs,
+                                                      double* __restrict__ partials) {
+  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
+  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
+    const int64_t i0 = q << 2;
+    if (VEC4 && i0 + 4 <= n) {
+      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
+      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
+      // a and b are read where a node of the quad is observed (they may be NaN elsewhere: never compared).  The zeros are written
+      // out at each use: with one named float4 the compiler splits these float4 loads into four dependent dword loads
+      const bool any = ov.x | ov.y | ov.z | ov.w;
+      const float4 av = any ? *reinterpret_cast<const float4*>(a + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 bv =
+          (Family::kReadsB && any && b) ? *reinterpret_cast<const float4*>(b + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 wv, rv;
+      fam(fv.x, qv.x, av.x, bv.x, ov.x != 0, wv.x, rv.x, acc);
+      fam(fv.y, qv.y, av.y, bv.y, ov.y != 0, wv.y, rv.y, acc);
+      fam(fv.z, qv.z, av.z, bv.z, ov.z != 0, wv.z, rv.z, acc);
+      fam(fv.w, qv.w, av.w, bv.w, ov.w != 0, wv.w, rv.w, acc);
+      *reinterpret_cast<float4*>(w + i0) = wv;
+      *reinterpret_cast<float4*>(rhs + i0) = rv;
+    } else {
+      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
+      for (int64_t i = i0; i < i1; ++i) {
+        const bool o = obs ? obs[i] != 0 : true;
+        float wi, ri;
+        fam(f[i], qf ? qf[i] : 0.f, o ? a[i] : 0.f, (Family::kReadsB && o && b) ? b[i] : 0.f, o, wi, ri, acc);
+        w[i] = wi;
+        rhs[i] = ri;
+      }
+    }
+  }
+  store_partials(acc, partials);
+}
+
+// (u_k, D phi(u_k)), k < K, of the K-point trapezoid rule on [-8, 8] in the workgroup's LDS, ready after the call
+__device__ __forceinline__ void trapezoid_table(int K, double* s_u, double* s_wt) {
   const double step = 16.0 / (double)(K - 1);
   for (int k = threadIdx.x; k < K; k += kBlock) {
     const double u = -8.0 + (double)k * step;
@@ -224,6 +299,14 @@ __global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* 
     s_wt[k] = step * (0.3989422804014327 * exp(-0.5 * u * u));        // D phi(u_k), 1 / sqrt(2 pi)
   }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* __restrict__ mean,
+                                                                   const double* __restrict__ var, int64_t n, int K,
+                                                                   double* __restrict__ prob) {
+  __shared__ double s_u[kMaxPoints];
+  __shared__ double s_wt[kMaxPoints];
+  trapezoid_table(K, s_u, s_wt);
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
     const double m = (double)mean[i];
@@ -236,172 +319,6 @@ __global__ __launch_bounds__(kBlock) void bernoulli_predict_kernel(const float* 
       p += s_wt[k] * (x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e));
     }
     prob[i] = p > 1.0 ? 1.0 : p;                                       // the weights sum to 1 up to rounding
-  }
-}
-
-// a float64 result as float32, +-FLT_MAX where the cast would leave as inf (NaN stays NaN)
-__device__ __forceinline__ float sat_f32(double v) {
-  const double m = (double)FLT_MAX;
-  return (float)(v > m ? m : (v < -m ? -m : v));
-}
-
-// one node of mgp_count_site / mgp_nb_site.  FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials;
-// FAMILY 2: negative binomial with the dispersion r (log_r = log r), a32 the log-exposure: the binomial arithmetic with y + r
-// "trials" and r "failures" at the predictor z = f + mean + a - log r (pi = mu / (r + mu))
-template <int FAMILY>
-__device__ __forceinline__ void count_node(float f32, float qf32, float y32, float a32, bool obs, double s_ref, double mean,
-                                           double r_nb, double log_r, float& w, float& rhs, SiteAcc& acc) {
-  const double f = (double)f32, qf = (double)qf32;
-  double g = 0.0, h = 0.0;
-  if (obs) {
-    const double y = (double)y32;
-    if (FAMILY == 0) {
-      const double eta = f + mean + (double)a32;
-      const double mu = exp(eta < 700.0 ? eta : 700.0);
-      acc.lp += y * eta - mu;
-      g = y - mu;
-      h = mu;
-    } else {
-      const double eta = FAMILY == 1 ? f + mean : f + mean + (double)a32 - log_r;
-      const double N = FAMILY == 1 ? (double)a32 : y + r_nb;
-      const double m = FAMILY == 1 ? N - y : r_nb;                     // failures (binomial: exact, both are integers <= 2^24)
-      const double e = exp(-fabs(eta));
-      const double d = 1.0 + e;
-      const double l1 = log1p(e);
-      const double pi = eta >= 0.0 ? 1.0 / d : e / d;
-      const double pib = eta >= 0.0 ? e / d : 1.0 / d;                 // 1 - pi without the subtraction
-      acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
-      g = y * pib - m * pi;
-      h = N * e / (d * d);
-    }
-  }
-  const double r = g - qf;
-  w = sat_f32(s_ref * h);
-  rhs = sat_f32(s_ref * r);
-  acc.fq += f * qf;
-  const double ar = fabs(r);
-  acc.mx = ar > acc.mx ? ar : acc.mx;
-  acc.sq += r * r;
-}
-
-// the layout of bernoulli_site_kernel with one more input: aux (NULL: zeros), read like y where a node of the quad is observed
-template <bool VEC4, int FAMILY>
-__global__ __launch_bounds__(kBlock) void count_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
-                                                            const float* __restrict__ y, const float* __restrict__ aux,
-                                                            const uint8_t* __restrict__ obs, int64_t n, double s_ref,
-                                                            double mean, double r_nb, double log_r,
-                                                            float* __restrict__ w, float* __restrict__ rhs,
-                                                            double* __restrict__ partials) {
-  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
-  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
-    const int64_t i0 = q << 2;
-    if (VEC4 && i0 + 4 <= n) {
-      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
-      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : zero;
-      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
-      const bool any = ov.x | ov.y | ov.z | ov.w;
-      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : zero;
-      const float4 av = (any && aux) ? *reinterpret_cast<const float4*>(aux + i0) : zero;
-      float4 wv, rv;
-      count_node<FAMILY>(fv.x, qv.x, yv.x, av.x, ov.x != 0, s_ref, mean, r_nb, log_r, wv.x, rv.x, acc);
-      count_node<FAMILY>(fv.y, qv.y, yv.y, av.y, ov.y != 0, s_ref, mean, r_nb, log_r, wv.y, rv.y, acc);
-      count_node<FAMILY>(fv.z, qv.z, yv.z, av.z, ov.z != 0, s_ref, mean, r_nb, log_r, wv.z, rv.z, acc);
-      count_node<FAMILY>(fv.w, qv.w, yv.w, av.w, ov.w != 0, s_ref, mean, r_nb, log_r, wv.w, rv.w, acc);
-      *reinterpret_cast<float4*>(w + i0) = wv;
-      *reinterpret_cast<float4*>(rhs + i0) = rv;
-    } else {
-      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
-      for (int64_t i = i0; i < i1; ++i) {
-        const bool o = obs ? obs[i] != 0 : true;
-        float wi, ri;
-        count_node<FAMILY>(f[i], qf ? qf[i] : 0.f, o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, s_ref, mean, r_nb, log_r, wi,
-                           ri, acc);
-        w[i] = wi;
-        rhs[i] = ri;
-      }
-    }
-  }
-  const SiteAcc r = block_reduce(acc);
-  if (threadIdx.x == 0) {
-    double* p = partials + 4 * (int64_t)blockIdx.x;
-    p[0] = r.lp;
-    p[1] = r.fq;
-    p[2] = r.mx;
-    p[3] = r.sq;
-  }
-}
-
-// one node of mgp_ordinal_site: the category is the interval (lo32, hi32] of cutpoints, -inf / +inf at the end categories.
-// exp(-|x|) is 0 at an infinite end, so sigma, log sigma and sigma (1 - sigma) need no special case there
-__device__ __forceinline__ void ordinal_node(float f32, float qf32, float lo32, float hi32, bool obs, double s_ref, float& w,
-                                             float& rhs, SiteAcc& acc) {
-  const double f = (double)f32, qf = (double)qf32;
-  double g = 0.0, h = 0.0;
-  if (obs) {
-    const double u = (double)hi32 - f, l = (double)lo32 - f;
-    const double eu = exp(-fabs(u)), el = exp(-fabs(l));
-    const double du = 1.0 + eu, dl = 1.0 + el;
-    acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu)) - ((l > 0.0 ? l : 0.0) + log1p(el));   // log sigma(u) + log sigma(-l)
-    g = (l >= 0.0 ? 1.0 / dl : el / dl) - (u >= 0.0 ? eu / du : 1.0 / du);               // sigma(l) - sigma(-u)
-    h = eu / (du * du) + el / (dl * dl);
-  }
-  const double r = g - qf;
-  w = (float)(s_ref * h);
-  rhs = (float)(s_ref * r);
-  acc.fq += f * qf;
-  const double ar = fabs(r);
-  acc.mx = ar > acc.mx ? ar : acc.mx;
-  acc.sq += r * r;
-}
-
-// the layout of count_site_kernel: lo and hi in the place of y and aux, read where a node of the quad is observed
-template <bool VEC4>
-__global__ __launch_bounds__(kBlock) void ordinal_site_kernel(const float* __restrict__ f, const float* __restrict__ qf,
-                                                              const float* __restrict__ lo, const float* __restrict__ hi,
-                                                              const uint8_t* __restrict__ obs, int64_t n, double s_ref,
-                                                              float* __restrict__ w, float* __restrict__ rhs,
-                                                              double* __restrict__ partials) {
-  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
-  const int64_t nq = (n + 3) >> 2;                                     // quads of nodes, the last one may be short
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
-    const int64_t i0 = q << 2;
-    if (VEC4 && i0 + 4 <= n) {
-      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
-      const float4 qv = qf ? *reinterpret_cast<const float4*>(qf + i0) : zero;
-      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
-      const bool any = ov.x | ov.y | ov.z | ov.w;
-      const float4 lv = any ? *reinterpret_cast<const float4*>(lo + i0) : zero;
-      const float4 hv = any ? *reinterpret_cast<const float4*>(hi + i0) : zero;
-      float4 wv, rv;
-      ordinal_node(fv.x, qv.x, lv.x, hv.x, ov.x != 0, s_ref, wv.x, rv.x, acc);
-      ordinal_node(fv.y, qv.y, lv.y, hv.y, ov.y != 0, s_ref, wv.y, rv.y, acc);
-      ordinal_node(fv.z, qv.z, lv.z, hv.z, ov.z != 0, s_ref, wv.z, rv.z, acc);
-      ordinal_node(fv.w, qv.w, lv.w, hv.w, ov.w != 0, s_ref, wv.w, rv.w, acc);
-      *reinterpret_cast<float4*>(w + i0) = wv;
-      *reinterpret_cast<float4*>(rhs + i0) = rv;
-    } else {
-      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
-      for (int64_t i = i0; i < i1; ++i) {
-        const bool o = obs ? obs[i] != 0 : true;
-        float wi, ri;
-        ordinal_node(f[i], qf ? qf[i] : 0.f, o ? lo[i] : 0.f, o ? hi[i] : 0.f, o, s_ref, wi, ri, acc);
-        w[i] = wi;
-        rhs[i] = ri;
-      }
-    }
-  }
-  const SiteAcc r = block_reduce(acc);
-  if (threadIdx.x == 0) {
-    double* p = partials + 4 * (int64_t)blockIdx.x;
-    p[0] = r.lp;
-    p[1] = r.fq;
-    p[2] = r.mx;
-    p[3] = r.sq;
   }
 }
 
@@ -421,20 +338,14 @@ __device__ __forceinline__ double ordinal_term(double up, double f, int k) {
   return k == 0 ? below : below * lower;
 }
 
-// a group of TK lanes per node, lane k its category (softmax_rows.h); the weight table as bernoulli_predict_kernel fills it
+// a group of TK lanes per node, lane k its category (softmax_rows.h)
 template <int TK>
 __global__ __launch_bounds__(kBlock) void ordinal_predict_kernel(const double* __restrict__ eta, const double* __restrict__ var,
                                                                  const double* __restrict__ cuts, int64_t n, int K, int points,
                                                                  int log_out, double* __restrict__ out) {
   __shared__ double s_u[kMaxPoints];
   __shared__ double s_wt[kMaxPoints];
-  const double step = 16.0 / (double)(points - 1);
-  for (int j = threadIdx.x; j < points; j += kBlock) {
-    const double u = -8.0 + (double)j * step;
-    s_u[j] = u;
-    s_wt[j] = step * (0.3989422804014327 * exp(-0.5 * u * u));         // D phi(u_j), 1 / sqrt(2 pi)
-  }
-  __syncthreads();
+  trapezoid_table(points, s_u, s_wt);
   double total = 0.0;                                                  // the sum of the weights, j ascending
   for (int j = 0; j < points; ++j) total += s_wt[j];
   constexpr int kRows = kBlock / TK;                                   // nodes a workgroup takes per step
@@ -459,108 +370,41 @@ __global__ __launch_bounds__(kBlock) void ordinal_predict_kernel(const double* _
   }
 }
 
-// one node of mgp_laplace_evidence_site at the mode.  FAMILY 0: Poisson (a32 the log-exposure), 1: binomial (a32 the trials),
-// 2: Bernoulli-logit (one trial, y the label), 3: negative binomial (a32 the log-exposure, r_nb the dispersion, log_r its log:
-// y + r trials and r failures at z = f + mean + a - log r, as count_node).  acc: lp = sum l, fq = nodes kept, sq = sum corr,
-// mx = max |corr|
+// ---- Evidence stage.  A family: its scalars, kReadsB, kSaturate (sqrt(h) may leave the float32 range) and
+// operator()(f, a, b, h, hp): h and h' = dh / df of one observed node at the mode, its log p returned.
+
+// FAMILY 0: Poisson (a32 the log-exposure), 1: binomial (a32 the trials), 2: Bernoulli-logit (one trial, y the label), 3: negative
+// binomial (a32 the log-exposure, r_nb the dispersion, log_r its log: y + r trials and r failures at z = f + mean + a - log r, as
+// CountSite)
 template <int FAMILY>
-__device__ __forceinline__ void evidence_node(float f32, float y32, float a32, bool obs, double var, bool has_var, double mean,
-                                              double r_nb, double log_r, double h_floor, float& root, float& corr, SiteAcc& acc) {
-  root = 0.f;
-  corr = 0.f;
-  if (!obs) return;
-  double h, hp;
-  if (FAMILY == 0) {
-    const double y = (double)y32;
-    const double eta = (double)f32 + mean + (double)a32;
-    const double mu = exp(eta < 700.0 ? eta : 700.0);
-    acc.lp += y * eta - mu;
-    h = mu;
-    hp = mu;
-  } else {
-    const double eta = FAMILY == 3 ? (double)f32 + mean + (double)a32 - log_r : (double)f32 + mean;
+struct CountEvidence {
+  static constexpr bool kReadsB = FAMILY != 2, kSaturate = true;
+  double mean, r_nb, log_r;
+  __device__ __forceinline__ double operator()(double f, float y32, float a32, double& h, double& hp) const {
+    if (FAMILY == 0) {
+      const double y = (double)y32;
+      const double eta = f + mean + (double)a32;
+      const double mu = exp(eta < 700.0 ? eta : 700.0);
+      h = mu;
+      hp = mu;
+      return y * eta - mu;
+    }
+    const double eta = FAMILY == 3 ? f + mean + (double)a32 - log_r : f + mean;
     const double y = FAMILY == 2 ? (y32 > 0.5f ? 1.0 : 0.0) : (double)y32;
     const double N = FAMILY == 1 ? (double)a32 : (FAMILY == 3 ? y + r_nb : 1.0);
     const double m = FAMILY == 3 ? r_nb : N - y;
     const double e = exp(-fabs(eta));
     const double d = 1.0 + e;
     const double l1 = log1p(e);
-    acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
     h = N * e / (d * d);
     const double gap = -expm1(-fabs(eta)) / d;                         // |(1 - pi) - pi| = (1 - e) / (1 + e), no cancellation
     hp = h * (eta >= 0.0 ? -gap : gap);
+    return -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
   }
-  if (!(h >= h_floor)) return;
-  acc.fq += 1.0;
-  root = sat_f32(sqrt(h));
-  if (has_var) {
-    const double m = (double)FLT_MAX;
-    double c = var * hp;
-    c = c > m ? m : (c < -m ? -m : c);
-    corr = (float)c;
-    acc.sq += c;
-    const double ac = fabs(c);
-    acc.mx = ac > acc.mx ? ac : acc.mx;
-  }
-}
-
-// the layout of count_site_kernel; var (NULL: no corr) is float64, two double2 per quad on the vector path
-template <bool VEC4, int FAMILY>
-__global__ __launch_bounds__(kBlock) void evidence_site_kernel(const float* __restrict__ f, const float* __restrict__ y,
-                                                               const float* __restrict__ aux, const uint8_t* __restrict__ obs,
-                                                               const double* __restrict__ var, int64_t n, double mean,
-                                                               double r_nb, double log_r, double h_floor,
-                                                               float* __restrict__ root_h,
-                                                               float* __restrict__ corr, double* __restrict__ partials) {
-  SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
-  const bool has_var = var != nullptr && corr != nullptr;
-  const int64_t nq = (n + 3) >> 2;
-  const int64_t stride = (int64_t)gridDim.x * kBlock;
-  for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
-    const int64_t i0 = q << 2;
-    if (VEC4 && i0 + 4 <= n) {
-      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 fv = *reinterpret_cast<const float4*>(f + i0);
-      const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
-      const bool any = ov.x | ov.y | ov.z | ov.w;
-      const float4 yv = any ? *reinterpret_cast<const float4*>(y + i0) : zero;
-      const float4 av = (any && aux) ? *reinterpret_cast<const float4*>(aux + i0) : zero;
-      double2 v0 = make_double2(0.0, 0.0), v1 = v0;
-      if (has_var && any) {
-        v0 = *reinterpret_cast<const double2*>(var + i0);
-        v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
-      }
-      float4 rv, cv;
-      evidence_node<FAMILY>(fv.x, yv.x, av.x, ov.x != 0, v0.x, has_var, mean, r_nb, log_r, h_floor, rv.x, cv.x, acc);
-      evidence_node<FAMILY>(fv.y, yv.y, av.y, ov.y != 0, v0.y, has_var, mean, r_nb, log_r, h_floor, rv.y, cv.y, acc);
-      evidence_node<FAMILY>(fv.z, yv.z, av.z, ov.z != 0, v1.x, has_var, mean, r_nb, log_r, h_floor, rv.z, cv.z, acc);
-      evidence_node<FAMILY>(fv.w, yv.w, av.w, ov.w != 0, v1.y, has_var, mean, r_nb, log_r, h_floor, rv.w, cv.w, acc);
-      *reinterpret_cast<float4*>(root_h + i0) = rv;
-      if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
-    } else {
-      const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
-      for (int64_t i = i0; i < i1; ++i) {
-        const bool o = obs ? obs[i] != 0 : true;
-        float ri, ci;
-        evidence_node<FAMILY>(f[i], o ? y[i] : 0.f, (o && aux) ? aux[i] : 0.f, o, (o && has_var) ? var[i] : 0.0, has_var, mean,
-                              r_nb, log_r, h_floor, ri, ci, acc);
-        root_h[i] = ri;
-        if (has_var) corr[i] = ci;
-      }
-    }
-  }
-  const SiteAcc r = block_reduce(acc);
-  if (threadIdx.x == 0) {
-    double* p = partials + 4 * (int64_t)blockIdx.x;
-    p[0] = r.lp;
-    p[1] = r.fq;
-    p[2] = r.mx;
-    p[3] = r.sq;
-  }
-}
+};
 
 // sigma(x), sigma(-x), a = sigma(x) sigma(-x) and gap = sigma(-x) - sigma(x) = -+ (1 - e) / (1 + e) from one e = exp(-|x|): the gap
-// as evidence_node forms (1 - pi) - pi, no cancellation near 0.  x = +-inf: e = 0, a = 0, gap = -+1, every product with a is 0
+// as CountEvidence forms (1 - pi) - pi, no cancellation near 0.  x = +-inf: e = 0, a = 0, gap = -+1, every product with a is 0
 struct OrdinalEnd {
   double e, sig, sigm, a, gap;
 };
@@ -580,22 +424,25 @@ __device__ __forceinline__ OrdinalEnd ordinal_end(double x) {
   return r;
 }
 
-// one node of mgp_ordinal_evidence_site at the mode: the interval of ordinal_node, h' = -(a_u gap_u + a_l gap_l); acc as
-// evidence_node fills it
-__device__ __forceinline__ void ordinal_evidence_node(float f32, float lo32, float hi32, bool obs, double var, bool has_var,
-                                                      double h_floor, float& root, float& corr, SiteAcc& acc) {
-  root = 0.f;
-  corr = 0.f;
-  if (!obs) return;
-  const double f = (double)f32;
-  const double u = (double)hi32 - f, l = (double)lo32 - f;
-  const OrdinalEnd eu = ordinal_end(u), el = ordinal_end(l);
-  acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu.e)) - ((l > 0.0 ? l : 0.0) + log1p(el.e));   // log sigma(u) + log sigma(-l), as ordinal_node
-  const double h = eu.a + el.a;
-  const double hp = -(eu.a * eu.gap + el.a * el.gap);
+// the interval of OrdinalSite, h' = -(a_u gap_u + a_l gap_l)
+struct OrdinalEvidence {
+  static constexpr bool kReadsB = true, kSaturate = false;                             // h <= 1/2
+  __device__ __forceinline__ double operator()(double f, float lo32, float hi32, double& h, double& hp) const {
+    const double u = (double)hi32 - f, l = (double)lo32 - f;
+    const OrdinalEnd eu = ordinal_end(u), el = ordinal_end(l);
+    h = eu.a + el.a;
+    hp = -(eu.a * eu.gap + el.a * el.gap);
+    return -((u < 0.0 ? -u : 0.0) + log1p(eu.e)) - ((l > 0.0 ? l : 0.0) + log1p(el.e));   // log p as OrdinalSite forms it
+  }
+};
+
+// root and corr of an observed node from its h and h'; acc: fq = nodes kept, sq = sum corr, mx = max |corr|
+template <bool SATURATE>
+__device__ __forceinline__ void evidence_tail(double h, double hp, double var, bool has_var, double h_floor, float& root,
+                                              float& corr, SiteAcc& acc) {
   if (!(h >= h_floor)) return;
   acc.fq += 1.0;
-  root = (float)sqrt(h);                                               // h <= 1/2
+  root = SATURATE ? sat_f32(sqrt(h)) : (float)sqrt(h);
   if (has_var) {
     const double m = (double)FLT_MAX;
     double c = var * hp;
@@ -607,14 +454,24 @@ __device__ __forceinline__ void ordinal_evidence_node(float f32, float lo32, flo
   }
 }
 
-// the layout of evidence_site_kernel with lo and hi in the place of y and aux
-template <bool VEC4>
-__global__ __launch_bounds__(kBlock) void ordinal_evidence_site_kernel(const float* __restrict__ f, const float* __restrict__ lo,
-                                                                       const float* __restrict__ hi,
-                                                                       const uint8_t* __restrict__ obs,
-                                                                       const double* __restrict__ var, int64_t n, double h_floor,
-                                                                       float* __restrict__ root_h, float* __restrict__ corr,
-                                                                       double* __restrict__ partials) {
+template <typename Family>
+__device__ __forceinline__ void evidence_node(const Family& fam, float f32, float a32, float b32, bool obs, double var,
+                                              bool has_var, double h_floor, float& root, float& corr, SiteAcc& acc) {
+  root = 0.f;
+  corr = 0.f;
+  if (!obs) return;
+  double h, hp;
+  acc.lp += fam((double)f32, a32, b32, h, hp);
+  evidence_tail<Family::kSaturate>(h, hp, var, has_var, h_floor, root, corr, acc);
+}
+
+// the node loop of site_kernel; var (NULL: no corr) is float64, two double2 per quad on the vector path
+template <bool VEC4, typename Family>
+__global__ __launch_bounds__(kBlock) void evidence_kernel(const float* __restrict__ f, const float* __restrict__ a,
+                                                          const float* __restrict__ b, const uint8_t* __restrict__ obs,
+                                                          const double* __restrict__ var, int64_t n, Family fam, double h_floor,
+                                                          float* __restrict__ root_h, float* __restrict__ corr,
+                                                          double* __restrict__ partials) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   const bool has_var = var != nullptr && corr != nullptr;
   const int64_t nq = (n + 3) >> 2;
@@ -622,22 +479,22 @@ __global__ __launch_bounds__(kBlock) void ordinal_evidence_site_kernel(const flo
   for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
     const int64_t i0 = q << 2;
     if (VEC4 && i0 + 4 <= n) {
-      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 fv = *reinterpret_cast<const float4*>(f + i0);
       const uchar4 ov = obs ? *reinterpret_cast<const uchar4*>(obs + i0) : make_uchar4(1, 1, 1, 1);
       const bool any = ov.x | ov.y | ov.z | ov.w;
-      const float4 lv = any ? *reinterpret_cast<const float4*>(lo + i0) : zero;
-      const float4 hv = any ? *reinterpret_cast<const float4*>(hi + i0) : zero;
+      const float4 av = any ? *reinterpret_cast<const float4*>(a + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 bv =
+          (Family::kReadsB && any && b) ? *reinterpret_cast<const float4*>(b + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
       double2 v0 = make_double2(0.0, 0.0), v1 = v0;
       if (has_var && any) {
         v0 = *reinterpret_cast<const double2*>(var + i0);
         v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
       }
       float4 rv, cv;
-      ordinal_evidence_node(fv.x, lv.x, hv.x, ov.x != 0, v0.x, has_var, h_floor, rv.x, cv.x, acc);
-      ordinal_evidence_node(fv.y, lv.y, hv.y, ov.y != 0, v0.y, has_var, h_floor, rv.y, cv.y, acc);
-      ordinal_evidence_node(fv.z, lv.z, hv.z, ov.z != 0, v1.x, has_var, h_floor, rv.z, cv.z, acc);
-      ordinal_evidence_node(fv.w, lv.w, hv.w, ov.w != 0, v1.y, has_var, h_floor, rv.w, cv.w, acc);
+      evidence_node(fam, fv.x, av.x, bv.x, ov.x != 0, v0.x, has_var, h_floor, rv.x, cv.x, acc);
+      evidence_node(fam, fv.y, av.y, bv.y, ov.y != 0, v0.y, has_var, h_floor, rv.y, cv.y, acc);
+      evidence_node(fam, fv.z, av.z, bv.z, ov.z != 0, v1.x, has_var, h_floor, rv.z, cv.z, acc);
+      evidence_node(fam, fv.w, av.w, bv.w, ov.w != 0, v1.y, has_var, h_floor, rv.w, cv.w, acc);
       *reinterpret_cast<float4*>(root_h + i0) = rv;
       if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
     } else {
@@ -645,21 +502,14 @@ __global__ __launch_bounds__(kBlock) void ordinal_evidence_site_kernel(const flo
       for (int64_t i = i0; i < i1; ++i) {
         const bool o = obs ? obs[i] != 0 : true;
         float ri, ci;
-        ordinal_evidence_node(f[i], o ? lo[i] : 0.f, o ? hi[i] : 0.f, o, (o && has_var) ? var[i] : 0.0, has_var, h_floor, ri, ci,
-                              acc);
+        evidence_node(fam, f[i], o ? a[i] : 0.f, (Family::kReadsB && o && b) ? b[i] : 0.f, o, (o && has_var) ? var[i] : 0.0,
+                      has_var, h_floor, ri, ci, acc);
         root_h[i] = ri;
         if (has_var) corr[i] = ci;
       }
     }
   }
-  const SiteAcc r = block_reduce(acc);
-  if (threadIdx.x == 0) {
-    double* p = partials + 4 * (int64_t)blockIdx.x;
-    p[0] = r.lp;
-    p[1] = r.fq;
-    p[2] = r.mx;
-    p[3] = r.sq;
-  }
+  store_partials(acc, partials);
 }
 
 constexpr int kCutMaxBlocks = 1024;       // grid cap of mgp_ordinal_cut_sums: 1024 x 256 threads x 1 node per step
@@ -820,14 +670,7 @@ __global__ __launch_bounds__(kBlock) void softmax_site_kernel(const float* __res
     acc.mx = ar > acc.mx ? ar : acc.mx;
     acc.sq += r * r;
   }
-  const SiteAcc r = block_reduce(acc);
-  if (threadIdx.x == 0) {
-    double* p = partials + 4 * (int64_t)blockIdx.x;
-    p[0] = r.lp;
-    p[1] = r.fq;
-    p[2] = r.mx;
-    p[3] = r.sq;
-  }
+  store_partials(acc, partials);
 }
 
 // out = R V (forward) or V + R^T X (transposed; V nullable) on S vectors of [n, C]: entry (i, c, s) lies at i C S + c cstride +
@@ -914,37 +757,82 @@ int site_blocks(int64_t n) {
   return (int)(b > kSiteMaxBlocks ? kSiteMaxBlocks : b);
 }
 
+int cut_blocks(int64_t n) {
+  const int64_t b = mgp_cdiv(n, (int64_t)kBlock);
+  return (int)(b > kCutMaxBlocks ? kCutMaxBlocks : b);
+}
+
+// the workspace of the node loop's entry points: one partial per workgroup
+size_t site_workspace_bytes(int64_t n) { return n < 1 ? 0 : (size_t)site_blocks(n) * 4 * sizeof(double); }
+
 bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// the second launch of every site entry point: sums[4] from the partials of `blocks` workgroups
+int sum_partials(const double* partials, int blocks, double* sums, bool sum_first, hipStream_t st) {
+  hipLaunchKernelGGL(site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, sum_first);
+  MGP_LAUNCH_CHECK();
+  return MGP_OK;
+}
+
+// The Newton stage of one family on validated arguments: the workspace check, the vector instantiation where every array
+// allows it (a NULL pointer does), the sums.
+template <typename Family>
+int launch_site(const float* f, const float* qf, const float* a, const float* b, const uint8_t* obs, int64_t n, const Family& fam,
+                float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream) {
+  if (!work || !aligned_to(work, 8) || work_bytes < site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(obs, 4) &&
+                    aligned_to(w, 16) && aligned_to(rhs, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (vec4)
+    hipLaunchKernelGGL((site_kernel<true, Family>), grid, block, 0, st, f, qf, a, b, obs, n, fam, w, rhs, partials);
+  else
+    hipLaunchKernelGGL((site_kernel<false, Family>), grid, block, 0, st, f, qf, a, b, obs, n, fam, w, rhs, partials);
+  MGP_LAUNCH_CHECK();
+  return sum_partials(partials, blocks, sums, false, st);
+}
+
+// The evidence stage of one family, as launch_site.  corr is written only where var is given too.
+template <typename Family>
+int launch_evidence(const float* f, const float* a, const float* b, const uint8_t* obs, const double* var, int64_t n,
+                    const Family& fam, double h_floor, float* root_h, float* corr, double* sums, void* work, size_t work_bytes,
+                    void* stream) {
+  if (!work || !aligned_to(work, 8) || work_bytes < site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  if (!var || !corr) var = nullptr, corr = nullptr;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
+                    aligned_to(root_h, 16) && aligned_to(corr, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (vec4)
+    hipLaunchKernelGGL((evidence_kernel<true, Family>), grid, block, 0, st, f, a, b, obs, var, n, fam, h_floor, root_h, corr,
+                       partials);
+  else
+    hipLaunchKernelGGL((evidence_kernel<false, Family>), grid, block, 0, st, f, a, b, obs, var, n, fam, h_floor, root_h, corr,
+                       partials);
+  MGP_LAUNCH_CHECK();
+  return sum_partials(partials, blocks, sums, true, st);
+}
+
+// the dispersion of the negative-binomial entry points: one finite scalar in [2^-10, 2^20] (NaN fails the comparison)
+bool nb_dispersion_ok(double r) { return r >= 0x1p-10 && r <= 0x1p20; }
 
 }  // namespace
 
-extern "C" size_t mgp_bernoulli_site_workspace_bytes(int64_t n) {
-  return n < 1 ? 0 : (size_t)site_blocks(n) * 4 * sizeof(double);
-}
+extern "C" size_t mgp_bernoulli_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_bernoulli_site(const float* f, const float* qf, const float* y, const uint8_t* obs, int64_t n,
                                   double s_ref, int link, float* w, float* rhs, double* sums, void* work,
                                   size_t work_bytes, void* stream) {
   if (!f || !y || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
   if (link != 0) return MGP_ERR_UNSUPPORTED;
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_bernoulli_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(obs, 4) && aligned_to(w, 16) &&
-                    aligned_to(rhs, 16);
-  if (vec4)
-    hipLaunchKernelGGL(bernoulli_site_kernel<true>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), f, qf, y,
-                       obs, n, s_ref, w, rhs, partials);
-  else
-    hipLaunchKernelGGL(bernoulli_site_kernel<false>, dim3((unsigned)blocks), dim3(kBlock), 0, mgp_stream(stream), f, qf, y,
-                       obs, n, s_ref, w, rhs, partials);
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, mgp_stream(stream), partials, blocks, sums, false);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  return launch_site(f, qf, y, nullptr, obs, n, BernoulliSite{s_ref}, w, rhs, sums, work, work_bytes, stream);
 }
 
-extern "C" size_t mgp_count_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_count_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
                               double s_ref, double mean, int family, float* w, float* rhs, double* sums, void* work,
@@ -952,83 +840,27 @@ extern "C" int mgp_count_site(const float* f, const float* qf, const float* y, c
   if (!f || !y || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
   if (family != 0 && family != 1) return MGP_ERR_UNSUPPORTED;
   if (family == 1 && !aux) return MGP_ERR_ARG;                         // the trials have no default
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_count_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) &&
-                    aligned_to(w, 16) && aligned_to(rhs, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  if (family == 0) {
-    if (vec4)
-      hipLaunchKernelGGL((count_site_kernel<true, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
-                         partials);
-    else
-      hipLaunchKernelGGL((count_site_kernel<false, 0>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
-                         partials);
-  } else {
-    if (vec4)
-      hipLaunchKernelGGL((count_site_kernel<true, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
-                         partials);
-    else
-      hipLaunchKernelGGL((count_site_kernel<false, 1>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, 0.0, 0.0, w, rhs,
-                         partials);
-  }
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  if (family == 0)
+    return launch_site(f, qf, y, aux, obs, n, CountSite<0>{s_ref, mean, 0.0, 0.0}, w, rhs, sums, work, work_bytes, stream);
+  return launch_site(f, qf, y, aux, obs, n, CountSite<1>{s_ref, mean, 0.0, 0.0}, w, rhs, sums, work, work_bytes, stream);
 }
 
-// the dispersion of the negative-binomial entry points: one finite scalar in [2^-10, 2^20] (NaN fails the comparison)
-bool nb_dispersion_ok(double r) { return r >= 0x1p-10 && r <= 0x1p20; }
-
-extern "C" size_t mgp_nb_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_nb_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_nb_site(const float* f, const float* qf, const float* y, const float* aux, const uint8_t* obs, int64_t n,
                            double s_ref, double mean, double dispersion, float* w, float* rhs, double* sums, void* work,
                            size_t work_bytes, void* stream) {
   if (!f || !y || !w || !rhs || !sums || n < 1 || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_nb_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) &&
-                    aligned_to(w, 16) && aligned_to(rhs, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  const double log_r = std::log(dispersion);
-  if (vec4)
-    hipLaunchKernelGGL((count_site_kernel<true, 2>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, dispersion, log_r, w,
-                       rhs, partials);
-  else
-    hipLaunchKernelGGL((count_site_kernel<false, 2>), grid, block, 0, st, f, qf, y, aux, obs, n, s_ref, mean, dispersion, log_r, w,
-                       rhs, partials);
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  return launch_site(f, qf, y, aux, obs, n, CountSite<2>{s_ref, mean, dispersion, std::log(dispersion)}, w, rhs, sums, work,
+                     work_bytes, stream);
 }
 
-extern "C" size_t mgp_ordinal_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_ordinal_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_ordinal_site(const float* f, const float* qf, const float* lo, const float* hi, const uint8_t* obs, int64_t n,
                                 double s_ref, float* w, float* rhs, double* sums, void* work, size_t work_bytes, void* stream) {
   if (!f || !lo || !hi || !w || !rhs || !sums || n < 1) return MGP_ERR_ARG;
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_ordinal_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(qf, 16) && aligned_to(lo, 16) && aligned_to(hi, 16) && aligned_to(obs, 4) &&
-                    aligned_to(w, 16) && aligned_to(rhs, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  if (vec4)
-    hipLaunchKernelGGL(ordinal_site_kernel<true>, grid, block, 0, st, f, qf, lo, hi, obs, n, s_ref, w, rhs, partials);
-  else
-    hipLaunchKernelGGL(ordinal_site_kernel<false>, grid, block, 0, st, f, qf, lo, hi, obs, n, s_ref, w, rhs, partials);
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  return launch_site(f, qf, lo, hi, obs, n, OrdinalSite{s_ref}, w, rhs, sums, work, work_bytes, stream);
 }
 
 extern "C" int mgp_ordinal_predict(const double* eta, const double* var, const double* cuts, int64_t n, int K, int points,
@@ -1045,7 +877,7 @@ extern "C" int mgp_ordinal_predict(const double* eta, const double* var, const d
   return MGP_OK;
 }
 
-extern "C" size_t mgp_laplace_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_laplace_evidence_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_laplace_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
                                          int64_t n, double mean, int family, double h_floor, float* root_h, float* corr,
@@ -1053,88 +885,33 @@ extern "C" int mgp_laplace_evidence_site(const float* f, const float* y, const f
   if (!f || !y || !root_h || !sums || n < 1 || !(h_floor >= 0.0)) return MGP_ERR_ARG;
   if (family < 0 || family > 2) return MGP_ERR_UNSUPPORTED;
   if (family == 1 && !aux) return MGP_ERR_ARG;                         // the trials have no default
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_laplace_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  if (family == 2) aux = nullptr;                                      // the Bernoulli family takes none
-  if (!var || !corr) var = nullptr, corr = nullptr;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
-                    aligned_to(root_h, 16) && aligned_to(corr, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-#define MGP_EVIDENCE_LAUNCH(V, F)                                                                                             \
-  hipLaunchKernelGGL((evidence_site_kernel<V, F>), grid, block, 0, st, f, y, aux, obs, var, n, mean, 0.0, 0.0, h_floor, root_h, \
-                     corr, partials)
-  if (family == 0) {
-    if (vec4) MGP_EVIDENCE_LAUNCH(true, 0); else MGP_EVIDENCE_LAUNCH(false, 0);
-  } else if (family == 1) {
-    if (vec4) MGP_EVIDENCE_LAUNCH(true, 1); else MGP_EVIDENCE_LAUNCH(false, 1);
-  } else {
-    if (vec4) MGP_EVIDENCE_LAUNCH(true, 2); else MGP_EVIDENCE_LAUNCH(false, 2);
-  }
-#undef MGP_EVIDENCE_LAUNCH
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  if (family == 0)
+    return launch_evidence(f, y, aux, obs, var, n, CountEvidence<0>{mean, 0.0, 0.0}, h_floor, root_h, corr, sums, work, work_bytes,
+                           stream);
+  if (family == 1)
+    return launch_evidence(f, y, aux, obs, var, n, CountEvidence<1>{mean, 0.0, 0.0}, h_floor, root_h, corr, sums, work, work_bytes,
+                           stream);
+  return launch_evidence(f, y, nullptr, obs, var, n, CountEvidence<2>{mean, 0.0, 0.0}, h_floor, root_h, corr, sums, work,
+                         work_bytes, stream);                          // the Bernoulli family takes no aux
 }
 
-extern "C" size_t mgp_nb_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_nb_evidence_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_nb_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
                                     int64_t n, double mean, double dispersion, double h_floor, float* root_h, float* corr,
                                     double* sums, void* work, size_t work_bytes, void* stream) {
   if (!f || !y || !root_h || !sums || n < 1 || !(h_floor >= 0.0) || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_nb_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  if (!var || !corr) var = nullptr, corr = nullptr;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(y, 16) && aligned_to(aux, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
-                    aligned_to(root_h, 16) && aligned_to(corr, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  const double log_r = std::log(dispersion);
-  if (vec4)
-    hipLaunchKernelGGL((evidence_site_kernel<true, 3>), grid, block, 0, st, f, y, aux, obs, var, n, mean, dispersion, log_r, h_floor,
-                       root_h, corr, partials);
-  else
-    hipLaunchKernelGGL((evidence_site_kernel<false, 3>), grid, block, 0, st, f, y, aux, obs, var, n, mean, dispersion, log_r, h_floor,
-                       root_h, corr, partials);
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  return launch_evidence(f, y, aux, obs, var, n, CountEvidence<3>{mean, dispersion, std::log(dispersion)}, h_floor, root_h, corr,
+                         sums, work, work_bytes, stream);
 }
 
-extern "C" size_t mgp_ordinal_evidence_site_workspace_bytes(int64_t n) { return mgp_bernoulli_site_workspace_bytes(n); }
+extern "C" size_t mgp_ordinal_evidence_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
 
 extern "C" int mgp_ordinal_evidence_site(const float* f, const float* lo, const float* hi, const uint8_t* obs, const double* var,
                                          int64_t n, double h_floor, float* root_h, float* corr, double* sums, void* work,
                                          size_t work_bytes, void* stream) {
   if (!f || !lo || !hi || !root_h || !sums || n < 1 || !(h_floor >= 0.0)) return MGP_ERR_ARG;
-  if (!work || !aligned_to(work, 8) || work_bytes < mgp_ordinal_evidence_site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
-  if (!var || !corr) var = nullptr, corr = nullptr;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(lo, 16) && aligned_to(hi, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
-                    aligned_to(root_h, 16) && aligned_to(corr, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  if (vec4)
-    hipLaunchKernelGGL(ordinal_evidence_site_kernel<true>, grid, block, 0, st, f, lo, hi, obs, var, n, h_floor, root_h, corr,
-                       partials);
-  else
-    hipLaunchKernelGGL(ordinal_evidence_site_kernel<false>, grid, block, 0, st, f, lo, hi, obs, var, n, h_floor, root_h, corr,
-                       partials);
-  MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, true);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
-}
-
-int cut_blocks(int64_t n) {
-  const int64_t b = mgp_cdiv(n, (int64_t)kBlock);
-  return (int)(b > kCutMaxBlocks ? kCutMaxBlocks : b);
+  return launch_evidence(f, lo, hi, obs, var, n, OrdinalEvidence{}, h_floor, root_h, corr, sums, work, work_bytes, stream);
 }
 
 extern "C" size_t mgp_ordinal_cut_sums_workspace_bytes(int64_t n, int K) {
@@ -1216,9 +993,7 @@ extern "C" int mgp_softmax_site(const float* f, const float* qf, const int32_t* 
                        n, C, pi, rhs, partials);
   });
   MGP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bernoulli_site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, false);
-  MGP_LAUNCH_CHECK();
-  return MGP_OK;
+  return sum_partials(partials, blocks, sums, false, st);
 }
 
 extern "C" int mgp_bernoulli_predict(const float* mean, const double* var, int64_t n, int points, double* prob,

@@ -31,7 +31,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, sampling
+from . import _lib, _sites, sampling
 from ._lib import check, lib, ptr, stream
 from .classification import H_FLOOR, S_REF
 
@@ -64,29 +64,9 @@ def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR, 
         raise ValueError("the binomial family needs the trials in aux")
     if fam == 2 and aux is not None:
         raise ValueError("the bernoulli family takes no aux")
-    if not float(h_floor) >= 0.0:
-        raise ValueError("h_floor must be >= 0, got %r" % (h_floor,))
-    for name, t in (("f", f), ("y", y)):
-        if not torch.is_tensor(t):
-            raise ValueError("%s must be a tensor [n]" % name)
-    n = f.numel()
-    if observed is not None and (not torch.is_tensor(observed) or observed.dtype != torch.bool):
-        raise ValueError("observed must be a bool tensor [n]")
-    for name, t in (("y", y), ("aux", aux), ("observed", observed), ("variance", variance)):
-        if t is not None and (not torch.is_tensor(t) or t.numel() != n):
-            raise ValueError("%s has %s entries, f %d" % (name, t.numel() if torch.is_tensor(t) else type(t), n))
-    if n < 1:
-        raise ValueError("f has no entries")
-    _lib.require_device(f, y, aux, observed, variance)
-    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
-    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
-    observed = None if observed is None else observed.reshape(-1).contiguous()
-    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
-    root_h = torch.empty_like(f)
-    corr = None if variance is None else torch.empty_like(f)
-    sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_nb_evidence_site_workspace_bytes(n) if fam == NB else lib().mgp_laplace_evidence_site_workspace_bytes(n)
-    work = _lib.workspace(wb, "evidence_site", f.device)
+    f, (y, aux), observed, variance, n, root_h, corr, sums, work = _sites.evidence_args(
+        f, (("y", y),), (("aux", aux),), observed, variance, h_floor,
+        lib().mgp_nb_evidence_site_workspace_bytes if fam == NB else lib().mgp_laplace_evidence_site_workspace_bytes)
     if fam == NB:
         check(lib().mgp_nb_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), r, float(h_floor),
                                          ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),

@@ -29,7 +29,7 @@ runs Adam on them, one warm-started fit per step: the frequency logits are the r
 """
 import torch
 
-from . import _lib, sampling
+from . import _lib, _sites, sampling
 from ._lib import check, lib, ptr, stream
 from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2
 from .counts import CountLaplaceFit, _int
@@ -130,43 +130,11 @@ def ordinal_site(f, qf, lo, hi, observed=None, s_ref=S_REF):
     sum_obs log(1 - exp(-(hi - lo))) is the caller's).  f [n] float32; qf [n] or None (zeros); lo, hi [n] float32: the ends of
     every node's interval of cutpoints, lo < hi, -inf / +inf at the end categories, read at observed nodes only (NaN allowed
     elsewhere); observed [n] bool or None (every node)."""
-    _lib.require_device(f, qf, lo, hi, observed)
-    f, lo, hi = _lib.f32c(f.reshape(-1)), _lib.f32c(lo.reshape(-1)), _lib.f32c(hi.reshape(-1))
-    n = f.shape[0]
-    qf = None if qf is None else _lib.f32c(qf.reshape(-1))
-    if observed is not None:
-        if observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        observed = observed.reshape(-1).contiguous()
-    for name, t in (("qf", qf), ("lo", lo), ("hi", hi), ("observed", observed)):
-        if t is not None and t.shape[0] != n:
-            raise ValueError("%s has %d entries, f %d" % (name, t.shape[0], n))
-    w, rhs = torch.empty_like(f), torch.empty_like(f)
-    sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    wb = lib().mgp_ordinal_site_workspace_bytes(n)
-    work = _lib.workspace(wb, "ordinal_site", f.device)
+    f, qf, (lo, hi), observed, n, w, rhs, sums, work = _sites.newton_args(
+        f, qf, (("lo", lo), ("hi", hi)), (), observed, "ordinal_site", lib().mgp_ordinal_site_workspace_bytes)
     check(lib().mgp_ordinal_site(ptr(f), ptr(qf), ptr(lo), ptr(hi), ptr(observed), n, float(s_ref), ptr(w), ptr(rhs), ptr(sums),
                                  ptr(work), work.numel(), stream()), "mgp_ordinal_site")
     return w, rhs, sums
-
-
-def _site_args(f, lo, hi, observed, variance, h_floor, extra=()):
-    """The host-side checks the two evidence kernels share: f, lo, hi tensors of one length n >= 1, observed bool [n] or None,
-    variance and the `extra` (name, tensor) pairs [n] or None, h_floor >= 0.  Returns n."""
-    if not float(h_floor) >= 0.0:
-        raise ValueError("h_floor must be >= 0, got %r" % (h_floor,))
-    for name, t in (("f", f), ("lo", lo), ("hi", hi)):
-        if not torch.is_tensor(t):
-            raise ValueError("%s must be a tensor [n]" % name)
-    n = f.numel()
-    if observed is not None and (not torch.is_tensor(observed) or observed.dtype != torch.bool):
-        raise ValueError("observed must be a bool tensor [n]")
-    for name, t in (("lo", lo), ("hi", hi), ("observed", observed), ("variance", variance)) + tuple(extra):
-        if t is not None and (not torch.is_tensor(t) or t.numel() != n):
-            raise ValueError("%s has %s entries, f %d" % (name, t.numel() if torch.is_tensor(t) else type(t), n))
-    if n < 1:
-        raise ValueError("f has no entries")
-    return n
 
 
 def ordinal_evidence_site(f, lo, hi, observed=None, variance=None, h_floor=H_FLOOR):
@@ -174,15 +142,8 @@ def ordinal_evidence_site(f, lo, hi, observed=None, variance=None, h_floor=H_FLO
     intervals (lo, hi] of ordinal_site in the place of the observations: root_h = sqrt(h) and corr = variance h' as fresh float32
     [n] tensors (0 off the observed nodes with h >= h_floor; corr None when variance is None), sums [4] float64 on the device
     (sum_obs (log sigma(hi - f) + log sigma(f - lo)), m = nodes kept, sum corr, max |corr|).  variance [n] (taken as float64)."""
-    n = _site_args(f, lo, hi, observed, variance, h_floor)
-    _lib.require_device(f, lo, hi, observed, variance)
-    f, lo, hi = _lib.f32c(f.reshape(-1)), _lib.f32c(lo.reshape(-1)), _lib.f32c(hi.reshape(-1))
-    observed = None if observed is None else observed.reshape(-1).contiguous()
-    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
-    root_h = torch.empty_like(f)
-    corr = None if variance is None else torch.empty_like(f)
-    sums = torch.empty(4, dtype=torch.float64, device=f.device)
-    work = _lib.workspace(lib().mgp_ordinal_evidence_site_workspace_bytes(n), "evidence_site", f.device)
+    f, (lo, hi), observed, variance, n, root_h, corr, sums, work = _sites.evidence_args(
+        f, (("lo", lo), ("hi", hi)), (), observed, variance, h_floor, lib().mgp_ordinal_evidence_site_workspace_bytes)
     check(lib().mgp_ordinal_evidence_site(ptr(f), ptr(lo), ptr(hi), ptr(observed), ptr(variance), n, float(h_floor), ptr(root_h),
                                           ptr(corr), ptr(sums), ptr(work), work.numel(), stream()), "mgp_ordinal_evidence_site")
     return root_h, corr, sums
@@ -198,7 +159,7 @@ def ordinal_cut_sums(f, lo, hi, cat, observed, variance, u, K, h_floor=H_FLOOR):
     K = _categories(K)
     if not torch.is_tensor(cat) or cat.dtype == torch.bool or cat.is_floating_point() or cat.is_complex():
         raise ValueError("cat must be an integer tensor [n] of categories")
-    n = _site_args(f, lo, hi, observed, variance, h_floor, (("cat", cat), ("u", u)))
+    n = _sites.check_evidence_args(f, (("lo", lo), ("hi", hi)), (), observed, variance, h_floor, (("cat", cat), ("u", u)))
     _lib.require_device(f, lo, hi, cat, observed, variance, u)
     f, lo, hi = _lib.f32c(f.reshape(-1)), _lib.f32c(lo.reshape(-1)), _lib.f32c(hi.reshape(-1))
     cat = cat.reshape(-1)
