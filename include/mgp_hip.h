@@ -968,6 +968,11 @@ int mgp_lanczos_tridiag(const mgp_operator_t* op, const float* q0, int steps, fl
  *   via mgp_eigvec_postprocess.
  * mgp_features_oos: fused Nystrom extension (graph_laplacian_operator.py:146-157) + bump
  *   modulation (riemann_kernel.py:138-147, torch_utils.py:38-41) without the [T,k,m] temporary.
+ *   Limits (MGP_ERR_ARG beyond them, nothing written): m <= 1024 modes (mgp_features_insample too), k <= 1024 neighbours,
+ *   normalization 0 (symmetric) or 1 (random walk).  A test point with sqrt(knn_d2[t][0]) >= bump_scale * eps gets a row of
+ *   exact zeros, whatever its weights.  A test point INSIDE the support whose k weights exp(-d2 / (4 eps^2)) all underflow
+ *   float32 to zero (d2 > ~415 eps^2: inside the support only with a bump scale above 20) has test degree 0 and gets a row of NaN (0 / 0), as the reference's
+ *   float32 arithmetic does: tests/test_gpu_spectral_kernels.py pins the pattern against a float32 numpy restatement.
  * mgp_kernel_block: K = Z1 Z2^T on the fp32 MFMA (v_mfma_f32_32x32x2_f32)
  *   (MatmulLinearOperator / LowRankRootLinearOperator evaluation, riemann_kernel.py:92-100). */
 size_t mgp_eigvec_postprocess_work_floats(int m);   /* size of colnorm_work in floats */

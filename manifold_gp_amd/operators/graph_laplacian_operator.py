@@ -173,6 +173,10 @@ class GraphLaplacianOperator(LinearOperator):
         _lib.require_device(x, edge_value, edge_idx)
         T, k = edge_idx.shape
         m = x.shape[1]
+        if m > 1024:
+            # the kernel takes at most 1024 modes (include/mgp_hip.h); the reference takes any width: columns in chunks,
+            # each with the sqrt(N / width) factor of its own width undone
+            return torch.cat([self.out_of_sample(x[:, c0:c0 + 1024], edge_value, edge_idx) for c0 in range(0, m, 1024)], 1)
         ones = torch.zeros(m, device=x.device)          # eigenvalues 0 -> sqrt-density is a constant
         Z = torch.empty(T, m, device=x.device, dtype=torch.float32)
         d = self.data

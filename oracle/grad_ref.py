@@ -8,6 +8,7 @@ but sparse (gather / index_add: O(nnz C)), so that the same oracle runs on the 1
   laplacian_f64           the Laplacian's node vectors and per-edge values, differentiable in eps (real or complex eps)
   laplacian_tangent_f64   d/d eps of the same six arrays by forward-mode AD (torch.func.jvp) -- no hand-written derivative,
                           so it shares no derivation with the kernel -- plus a per-entry term scale that sizes tolerances
+  laplacian_value_scale_f64   the same per-entry term scale and floor for the VALUES of the build (and the per-edge W, A, S)
   model_apply_f64         L, Q, Q2 or Q3 = Noise(Scale(Precision(L))) applied to a block V, differentiable in everything
 """
 import torch
@@ -66,6 +67,57 @@ def _term_scale(val, idx, n, eps, self_loops, lap, wmag, constants):
         s_diag = torch.full((n,), 2.0 / (e2 * eps) if constants else 0.0, dtype=torch.float64)
     return dict(degree_unnorm=s_ddt, degree=s_dd, diag=s_diag, dsqrt=0.5 * s_dd / d_.sqrt(),
                 dinvsqrt=0.5 * s_dd / (d_ * d_.sqrt()), triu=s_ds)
+
+
+VALUE_NAMES = NAMES + ("w", "a")
+
+
+def _value_scale(val, idx, n, eps, self_loops, lap, wmag, constants):
+    """The counterpart of _term_scale for the VALUES of mgp_laplacian_build (lap_pass) and mgp_edge_values: per entry, the sum of
+    the magnitudes of the terms the entry is made of, each term counted with everything it is divided by -- a quantity q =
+    f(D~, D, W) is moved by a perturbation of its inputs by sum |df/dx| s_x, with s_x the term scale of x -- with |W| replaced
+    by `wmag` (per edge) and the W-free terms (the self loop's 1 in D~, D~^-2 in D, the two terms of diag) only when
+    `constants`.  Keys: NAMES plus "w" (the weights W) and "a" (A = W / (D~_i D~_j)), the two per-edge arrays mgp_edge_values
+    returns besides S."""
+    r, c = idx[0], idx[1]
+    dt_, d_ = lap["degree_unnorm"], lap["degree"]
+    e2 = eps * eps
+    base = 1.0 if (self_loops and constants) else 0.0
+    s_dt = torch.full((n,), base, dtype=torch.float64).index_add(0, r, wmag).index_add(0, c, wmag)
+    am = wmag / (dt_[r] * dt_[c])
+    s_a = am * (1.0 + s_dt[r] / dt_[r] + s_dt[c] / dt_[c])                     # A = W / (D~_i D~_j)
+    s_d = torch.zeros(n, dtype=torch.float64).index_add(0, r, s_a).index_add(0, c, s_a)
+    if self_loops:
+        s_d = s_d + dt_.pow(-2) * (base + 2.0 * s_dt / dt_)                    # D = D~^-2 + sum A
+    sq = torch.sqrt(d_[r] * d_[c])
+    s_s = (s_a + am * (0.5 * s_d[r] / d_[r] + 0.5 * s_d[c] / d_[c])) / (sq * e2)   # S = A / (sqrt(D_i D_j) eps^2)
+    if self_loops:
+        s_diag = (2.0 * dt_.pow(-3) * s_dt / d_ + dt_.pow(-2) * s_d / (d_ * d_)) / e2
+        if constants:
+            s_diag = s_diag + (1.0 + dt_.pow(-2) / d_) / e2                     # diag = (1 - D~^-2 / D) / eps^2
+    else:
+        s_diag = torch.full((n,), 1.0 / e2 if constants else 0.0, dtype=torch.float64)
+    return dict(degree_unnorm=s_dt, degree=s_d, diag=s_diag, dsqrt=0.5 * s_d / d_.sqrt(), dinvsqrt=0.5 * s_d / (d_ * d_.sqrt()),
+                triu=s_s, w=wmag, a=s_a)
+
+
+def laplacian_value_scale_f64(val, idx, n, eps, self_loops=True):
+    """(value, scale, floor) over VALUE_NAMES for the values of the Laplacian build, the way laplacian_tangent_f64 returns them for
+    its tangent: the float64 arrays of laplacian_f64 (plus the weights "w" and the adjacency "a"), the per-entry term scale with
+    a weight W = exp(-d2 / (4 eps^2)) counted as W (1 + d2 / (4 eps^2)), and the floor over the weights float32 holds only as
+    subnormals or zero (W < 2^-126), each counted at 2^-126 (1 + d2 / (4 eps^2)).  eps: python / numpy scalar."""
+    val, idx, _ = _edges(val, idx, torch.tensor(0.0, dtype=torch.float64))
+    e = torch.tensor(float(eps), dtype=torch.float64)
+    value = dict(laplacian_f64(val, idx, n, e, self_loops))
+    arg = val / (4.0 * e * e)
+    w = torch.exp(-arg)
+    value["w"] = w
+    value["a"] = w / (value["degree_unnorm"][idx[0]] * value["degree_unnorm"][idx[1]])
+    normal = w >= FLT_MIN
+    scale = _value_scale(val, idx, n, e, self_loops, value, torch.where(normal, w, torch.zeros_like(w)) * (1.0 + arg), True)
+    floor = _value_scale(val, idx, n, e, self_loops, value, torch.where(normal, torch.zeros_like(w), torch.full_like(w, FLT_MIN))
+                         * (1.0 + arg), False)
+    return value, scale, floor
 
 
 def laplacian_tangent_f64(val, idx, n, eps, self_loops=True):

@@ -2,7 +2,9 @@
 size runs on.
 
   a  mgp_laplacian_tangent (lap_tangent_pass) entry by entry, on the golden graphs, a star-plus-ring graph with one long row, and a
-     150k-node swiss roll past both grid caps (4096 x 16 rows of the tangent passes, 512 x 256 rows of the backward sums);
+     150k-node swiss roll past both grid caps (4096 x 16 rows of the tangent passes, 512 x 256 rows of the backward sums); on the
+     same graphs the VALUES it differentiates -- the six arrays of mgp_laplacian_build and the per-edge W, A, S of
+     mgp_edge_values -- entry by entry in the same form and at the same bar;
   b  one differentiable fused SpMM (autograd.fused_spmm) and all nine of its gradients, at C = 1 ... 300, natural and locality
      row order, with the fused backward reductions on and off;
   c  mgp_spmm_backward_sums called directly against float64 numpy, every legal null pattern, every illegal one refused;
@@ -72,7 +74,37 @@ def _star_ring(mgp, dev, n=12000, hub=3500, seed=11):
     return mgp.graph.KnnGraph.from_coo(T(idx, dev), T(val, dev), n)
 
 
-# ============================================================================= a. tangent kernel
+# ============================================================================= a. tangent kernel (and the values it differentiates)
+def _value_ratio(got, ref, s, f, what):
+    """The tangent's form for a value: |got - ref| / (2^-24 scale + floor / 64), which must not exceed 64."""
+    assert got.dtype == torch.float64 and bool(torch.isfinite(got).all()), what
+    ratio = (got - ref).abs() / (U * s + f / 64.0)
+    r = float(ratio.max())
+    assert r <= 64.0, (what, r, int(ratio.argmax()))
+    return r
+
+
+def _check_build(data, graph, value, eps32, loops, eid, pad):
+    """The six arrays of mgp_laplacian_build (lap_pass) entry by entry against the float64 values `value` that
+    laplacian_tangent_f64 returns next to the tangent, in the tangent's form and at its bar: |got - ref| / (2^-24 scale +
+    floor / 64) <= 64, scale and floor from oracle/grad_ref.py::laplacian_value_scale_f64.  `vals` is compared at the
+    non-padding entries through eid; its padding entries are exactly 0.  Returns the worst ratio."""
+    from oracle.grad_ref import laplacian_value_scale_f64
+    val, idx = graph.edge_value.double().cpu(), graph.edge_index.cpu()
+    value2, scale, floor = laplacian_value_scale_f64(val, idx, graph.n, eps32, loops)
+    vals = data.vals.double().cpu()
+    assert data.vals.dtype == torch.float32 and bool((vals[pad] == 0).all()), "padding entries of the CSR values must be exactly 0"
+    worst = 0.0
+    for name in NAMES:
+        assert torch.equal(value[name], value2[name])
+        if name == "triu":
+            got, ref, s, f = vals[~pad], value[name][eid[~pad]], scale[name][eid[~pad]], floor[name][eid[~pad]]
+        else:
+            got, ref, s, f = getattr(data, name).double().cpu(), value[name], scale[name], floor[name]
+        worst = max(worst, _value_ratio(got, ref, s, f, name))
+    return worst
+
+
 def _check_tangent(mgp, graph, eps, loops):
     """Worst ratio |got - ref| / (2^-24 scale + floor / 64) over the six tangent arrays (the bound is 64)."""
     from manifold_gp_amd.graph import LaplacianData
@@ -82,9 +114,11 @@ def _check_tangent(mgp, graph, eps, loops):
     n = graph.n
     val = graph.edge_value.double().cpu()
     idx = graph.edge_index.cpu()
-    _, tan, scale, floor = laplacian_tangent_f64(val, idx, n, eps32, loops)
+    value, tan, scale, floor = laplacian_tangent_f64(val, idx, n, eps32, loops)
     eid = graph.eid.long().cpu()
     pad = eid < 0
+    print("build values n=%d eps=%.4g loops=%s: worst ratio %.2f" % (n, eps32, loops, _check_build(data, graph, value, eps32, loops,
+                                                                                               eid, pad)))
     d_vals = t.d_vals.double().cpu()
     assert bool((d_vals[pad] == 0).all()), "padding entries of the tangent CSR must be exactly 0"
     # the CSR's squared distances are the edge list's (the oracle and the kernel read the same numbers)
@@ -113,7 +147,9 @@ def test_tangent_golden_graphs(mgp, golden, dev, case, loops, bw):
     """lap_tangent_pass on the 1,546-node fixtures: every tangent entry within 64 * 2^-24 of its float64 term scale (plus the
     contribution of weights float32 cannot hold as normal numbers).  Bandwidths: the fixture's, a quarter and four times of
     it, and one at which most weights are below 2^-126 (self loops on only: without them D~ could be 0).
-    Measured worst ratio: 5.9 of the 64 (x1, k50 fixture); 1.2-1.4 at the underflow bandwidth."""
+    Measured worst ratio: 5.9 of the 64 (x1, k50 fixture); 1.2-1.4 at the underflow bandwidth.
+    The values the tangent differentiates (the six arrays of mgp_laplacian_build, _check_build) are held to the same form and
+    bar on the same graphs: measured worst 1.90 of the 64 (x4, k10 fixture, no loops)."""
     g, graph = _golden_graph(mgp, golden, case, dev)
     if bw == "underflow":                  # (self loops only: without them an isolated D~ is 0 and the Laplacian undefined)
         eps = underflow_eps(graph.edge_value.double().cpu())
@@ -128,7 +164,9 @@ def test_tangent_golden_graphs(mgp, golden, dev, case, loops, bw):
 @pytest.mark.parametrize("bw", ["x0.25", "x1", "x4", "underflow"])
 def test_tangent_star_plus_ring(mgp, dev, bw):
     """One hub row of 3,500 entries (a 16-lane group walks it 219 times) next to rows of one and two entries.
-    Measured worst ratio: 14.6 of the 64 (eps x 4); 4.1 at x1, 1.0 at the underflow bandwidth."""
+    Measured worst ratio: 14.6 of the 64 (eps x 4); 4.1 at x1, 1.0 at the underflow bandwidth.
+    Build values (_check_build; the hub row is 219 steps of lap_pass's float4 / int4 row walk): worst 2.90 of the 64 (x4, no
+    loops)."""
     graph = _star_ring(mgp, dev)
     counts = (graph.rowptr[1:] - graph.rowptr[:-1]).cpu()
     nz = torch.bincount(graph.eid.cpu()[graph.eid.cpu() >= 0].long(), minlength=graph.M)
@@ -160,7 +198,9 @@ def test_tangent_past_the_grid_caps(mgp, dev, swiss150k, bw, loops):
     """150,001 rows: past the tangent passes' 65,536-row grid (grid-stride loop) and the backward sums' 131,072; the tiles
     follow a locality order (random point order), so the tile-order copy of the tangent values is checked too.  At a quarter of
     the bandwidth most weights underflow float32.
-    Measured worst ratio: 4.2 of the 64 (x4, no loops); 3.8 at x0.25."""
+    Measured worst ratio: 4.2 of the 64 (x4, no loops); 3.8 at x0.25.
+    Build values (_check_build; lap_pass's grid covers 65,536 rows, the rest come from its grid-stride loop): worst 2.17 of the
+    64 (x0.25)."""
     graph, eps0 = swiss150k
     assert graph.n > 131072 and graph.n > 4096 * 16
     assert graph.tiles is not None and graph.tiles.get("rowid") is not None
@@ -171,6 +211,44 @@ def test_tangent_past_the_grid_caps(mgp, dev, swiss150k, bw, loops):
         assert float((w < U).double().mean()) > 0.5 and float((w < 2.0 ** -126).double().mean()) > 0.1
     worst = _check_tangent(mgp, graph, eps, loops)
     print("tangent swiss150k %s loops=%s: worst ratio %.2f" % (bw, loops, worst))
+
+
+def _check_edge_values(graph, eps, loops):
+    """mgp_edge_values, which = 0 (W), 1 (A), 2 (S) in edge-list order against the float64 values, through the ratio of
+    _check_build (same scale, floor and bar).  Returns the worst ratio."""
+    from manifold_gp_amd.graph import LaplacianData
+    from oracle.grad_ref import laplacian_value_scale_f64
+    data = LaplacianData(graph, eps, loops)
+    value, scale, floor = laplacian_value_scale_f64(graph.edge_value.double().cpu(), graph.edge_index.cpu(), graph.n,
+                                                    float(np.float32(eps)), loops)
+    worst = 0.0
+    for which, name in enumerate(("w", "a", "triu")):
+        out = data.edge_values(which)
+        assert out.dtype == torch.float32 and tuple(out.shape) == (graph.M,)
+        worst = max(worst, _value_ratio(out.double().cpu(), value[name], scale[name], floor[name], name))
+    return worst
+
+
+@pytest.mark.parametrize("bw", ["x0.25", "x1", "x4", "underflow"])
+def test_edge_values_star_plus_ring(mgp, dev, bw):
+    """W, A and S per edge on the star-plus-ring graph (the hub's D~ and D are sums of 3,500 terms), with and without self
+    loops.  Measured worst ratio: 1.03 of the 64 (underflow bandwidth)."""
+    graph = _star_ring(mgp, dev)
+    eps = underflow_eps(graph.edge_value.double().cpu()) if bw == "underflow" else 0.5 * float(bw[1:])
+    worst = _check_edge_values(graph, eps, True)
+    worst = max(worst, _check_edge_values(graph, eps, False)) if bw != "underflow" else worst
+    print("edge values star+ring %s: worst ratio %.2f" % (bw, worst))
+
+
+@pytest.mark.parametrize("bw,loops", [("x1", True), ("x1", False), ("x0.25", True)])
+def test_edge_values_at_150k_rows(mgp, dev, swiss150k, bw, loops):
+    """The 150,001-row swiss roll: 773,027 edges (1.5 M CSR entries), still UNDER the 8192 x 256 = 2,097,152-thread grid of
+    edge_values_kernel (its grid-stride loop is not entered; a graph that enters it needs 2.1 M edges), but every D~ and D it
+    reads came from the grid-stride loop of lap_pass.  Measured worst ratio: 1.40 of the 64 (x1, no loops)."""
+    graph, eps0 = swiss150k
+    assert 700_000 < graph.M < 8192 * 256 and graph.n > 4096 * 16
+    worst = _check_edge_values(graph, eps0 * float(bw[1:]), loops)
+    print("edge values swiss150k %s loops=%s: worst ratio %.2f" % (bw, loops, worst))
 
 
 # ============================================================================= b. one fused SpMM, every gradient

@@ -95,6 +95,43 @@ def test_golden_eps_gradients(golden, case, norm):
     print("golden eps gradients %s %s: rel err %.1e, %.1e" % (case, norm, e_ltv, abs(got - ref) / abs(ref)))
 
 
+def test_value_term_scale_closed_form_and_bounds_the_values(golden):
+    """laplacian_value_scale_f64 on a two-node graph with one edge, against the closed form (a weight W = exp(-q), q = d2 / (4
+    eps^2), counts as m = W (1 + q); every node has D~ = 1 + W, so s_D~ = 1 + m, s_A = m / D~^2 (1 + 2 s_D~ / D~), s_D = s_A +
+    (1 + 2 s_D~ / D~) / D~^2, s_S = (s_A + A s_D / D) / (D eps^2) with A counted as m / D~^2); and on a golden graph: scale +
+    floor bounds every value, the floor is zero where no weight underflows float32 and positive where most do, and the values
+    are those of laplacian_tangent_f64."""
+    from oracle.grad_ref import VALUE_NAMES, laplacian_value_scale_f64
+    d2, eps = 0.3, 0.4
+    value, scale, floor = laplacian_value_scale_f64(torch.tensor([d2], dtype=torch.float64), torch.tensor([[0], [1]]), 2, eps, True)
+    q = d2 / (4 * eps * eps)
+    W = np.exp(-q)
+    m, dt = W * (1 + q), 1 + W
+    s_dt = 1 + m
+    s_a = m / dt ** 2 * (1 + 2 * s_dt / dt)
+    s_d = s_a + (1 + 2 * s_dt / dt) / dt ** 2
+    D = (1 + W) / dt ** 2
+    want = dict(w=m, degree_unnorm=s_dt, a=s_a, degree=s_d, dsqrt=0.5 * s_d / D ** 0.5, dinvsqrt=0.5 * s_d / D ** 1.5,
+                triu=(s_a + m / dt ** 2 * s_d / D) / (D * eps * eps),
+                diag=(2 * s_dt / (dt ** 3 * D) + s_d / (dt * D) ** 2 + 1 + 1 / (dt * dt * D)) / (eps * eps))
+    assert set(want) == set(VALUE_NAMES)
+    for k in VALUE_NAMES:
+        assert abs(float(scale[k][0]) - want[k]) <= 1e-14 * want[k], k
+        assert float(floor[k].abs().max()) == 0.0
+    assert abs(float(value["degree"][0]) - D) <= 1e-15 and abs(float(value["a"][0]) - W / dt ** 2) <= 1e-15
+    g, val, idx, n, loops = _graph(golden, "dumbbell_k10_loop")
+    for eps in (float(g["eps"]), underflow_eps(val)):
+        value, scale, floor = laplacian_value_scale_f64(val, idx, n, eps, loops)
+        ref = laplacian_tangent_f64(val, idx, n, eps, loops)[0]
+        for k in VALUE_NAMES:
+            assert bool(torch.isfinite(scale[k]).all()) and bool((scale[k] >= 0).all()) and bool((floor[k] >= 0).all())
+            half = 2.0 if k in ("dsqrt", "dinvsqrt") else 1.0       # D^(+-1/2) is moved by HALF the relative change of D
+            assert bool((value[k].abs() <= half * (scale[k] + floor[k]) * (1 + 1e-12)).all()), (eps, k)
+            if k in NAMES:
+                assert torch.equal(value[k], ref[k])
+        assert (float(floor["triu"].max()) == 0.0) == (eps == float(g["eps"]))
+
+
 def test_tangent_term_scale_bounds_the_tangent(golden):
     """The term scale is a sum of magnitudes of the terms that make up each tangent entry, so it bounds the entry; the
     floor is zero where no weight underflows float32 and positive where the bandwidth is small enough that some do."""
