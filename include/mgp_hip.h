@@ -744,6 +744,29 @@ size_t mgp_nb_evidence_site_workspace_bytes(int64_t n);
 int mgp_nb_evidence_site(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var, int64_t n,
                          double mean, double dispersion, double h_floor, float* root_h, float* corr, double* sums, void* work,
                          size_t work_bytes, void* stream);
+/* The derivative of the negative-binomial Laplace evidence with respect to the dispersion r in [2^-10, 2^20], the mean and the
+ * exposure held fixed, as three sums over the nodes (docs/kernels/counts.md, "Learning the dispersion"): out [3] float64 (device).
+ * f, y, aux (NULL: zeros), obs (NULL: every node) as mgp_nb_evidence_site; var [n] float64 (NULL: row 1 is 0): diag(A^-1); u [n]
+ * float64 (NULL: row 2 is 0): A^-1 (var o h').  y, aux, var and u are read only in quads that hold an observed node (NaN allowed
+ * elsewhere).  Per observed node in float64, with z, pi, 1 - pi, h and h' as mgp_nb_evidence_site forms them,
+ *   row 0:   psi(y + r) - psi(r) + log(1 - pi) + pi - y (1 - pi) / r     the likelihood with d c(y, r) / dr, every observed node
+ *   row 1:   -1/2 var (pi (1 - pi) - h' / r)                             the curvature at fixed f, dh / dr
+ *   row 2:   -1/2 u (h / r - pi)                                         through the mode, dg / dr = h / r - pi
+ * rows 1 and 2 only where h >= h_floor; their sum is d log Z / dr.  log(1 - pi) = -(max(z, 0) + log1p(e)).  The digamma
+ * difference is formed from positive terms no larger than itself: sum_{j < y} 1 / (r + j), j ascending, for y <= 32; beyond it,
+ * with k = 32 for r < 32 and 0 otherwise, b = r + k, a = y + r and t(x) = 1/12 x^-2 - 1/120 x^-4 + 1/252 x^-6 - 1/240 x^-8 +
+ * 1/132 x^-10 - 691/32760 x^-12,
+ *   sum_{j < k} 1 / (r + j) + log1p((y - k) / b) + (y - k) / (2 a b) + (t(b) - t(a));
+ * y = 0 gives exactly 0; the first sum depends on r alone and is formed once on the host.  The node loop, the partials (one per workgroup, at most 1024) and the second launch are those of
+ * mgp_nb_evidence_site: fixed order, no atomics, repeated calls are bitwise equal.  `work`:
+ * mgp_nb_dispersion_sums_workspace_bytes(n) bytes, 8-byte aligned.  float4 / uchar4 / double2 accesses where f, y, aux, var, u
+ * are 16-byte and obs 4-byte aligned, scalar ones otherwise.  MGP_ERR_ARG for null f, y or out, n < 1, h_floor negative or NaN
+ * and a dispersion outside [2^-10, 2^20] (NaN included); MGP_ERR_WORKSPACE for a null, misaligned or short `work`.  The checks
+ * precede every launch. */
+size_t mgp_nb_dispersion_sums_workspace_bytes(int64_t n);
+int mgp_nb_dispersion_sums(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
+                           const double* u, int64_t n, double mean, double dispersion, double h_floor, double* out, void* work,
+                           size_t work_bytes, void* stream);
 /* The same stage for an ordered-category fit (ordinal.laplace_fit_ordinal, docs/kernels/ordinal.md) with the contract of
  * mgp_laplace_evidence_site: lo [n] and hi [n], the float32 ends of the node's interval of cutpoints as mgp_ordinal_site reads
  * them (lo < hi, -inf / +inf at the end categories), in the place of (y, aux); read only in quads that hold an observed node (NaN

@@ -167,6 +167,8 @@ SIGNATURES = {
     "mgp_nb_evidence_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, c_double, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "mgp_ordinal_evidence_site_workspace_bytes": (c_size_t, [c_int64]),
     "mgp_ordinal_evidence_site": (c_int, [_P, _P, _P, _P, _P, c_int64, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "mgp_nb_dispersion_sums_workspace_bytes": (c_size_t, [c_int64]),
+    "mgp_nb_dispersion_sums": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
     "mgp_ordinal_cut_sums_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "mgp_ordinal_cut_sums": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_double, _P, _P, c_size_t, _P]),
     "mgp_scale_rows": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P]),

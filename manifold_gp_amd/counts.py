@@ -17,8 +17,10 @@ s_ref is a power of two fixed once per fit from the data, so one CG plan serves 
 correctly rounded h: 2^-ceil(log2 max(1, max y)) for Poisson (h = mu is about y at the mode; at a trial point w may exceed
 1, which nothing in form 3 depends on: the operator, its Jacobi diagonal and the CG take any w >= 0) and 4 * 2^-ceil(log2 max N)
 for the binomial (h <= N / 4, so w <= 1; at N = 1 this is the Bernoulli fit's 4), and 4 * 2^-ceil(log2 ceil(max y + r)) for the
-negative binomial (h <= (y + r) / 4).  Its dispersion r is one scalar per fit, fixed by the caller: dispersion_profile fits a list
-of candidates and compares their Laplace evidence.
+negative binomial (h <= (y + r) / 4).  Its dispersion r is one scalar per fit: dispersion_profile fits a list of candidates and
+compares their Laplace evidence; evidence.laplace_evidence(dispersion=) carries d log Z / dr (three sums over the nodes,
+mgp_nb_dispersion_sums / nb_dispersion_sums), DispersionParameter states r = exp(rho) and learn_dispersion runs Adam on it with
+the kernel fixed; utils.laplace_train takes a DispersionParameter in fit_kw and trains it with the kernel.
 
 The iteration stops by the size of an accepted full Newton step (step_tol), not by the gradient relative to max |g(0)|:
 for counts max |g(0)| is the size of the largest count, and a gradient rule relative to it stops hundreds of times further
@@ -88,6 +90,27 @@ def count_site(f, qf, y, aux, observed, s_ref, mean, family, dispersion=None):
     check(lib().mgp_count_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), fam, ptr(w),
                                ptr(rhs), ptr(sums), ptr(work), work.numel(), stream()), "mgp_count_site")
     return w, rhs, sums
+
+
+def nb_dispersion_sums(f, y, aux, observed, variance, u, mean, dispersion, h_floor=H_FLOOR):
+    """The three rows of d log Z / dr of a negative-binomial fit, r its dispersion (mgp_nb_dispersion_sums): [3] float64 on the
+    device -- the likelihood's term with d c(y, r) / dr, the curvature's at fixed f (0 when variance is None) and the one through
+    the mode (0 when u is None); their sum is the derivative, the mean and the exposure held fixed.  f [n] float32: the mode;
+    y [n] the counts and aux [n] the log-exposure (None: zeros), read at observed nodes only; observed [n] bool or None;
+    variance [n]: diag(A^-1) and u [n]: A^-1 (variance o h'), taken as float64; mean: the constant of the linear predictor."""
+    r = _dispersion(NB, dispersion)
+    n = _sites.check_evidence_args(f, (("y", y),), (("aux", aux),), observed, variance, h_floor, (("u", u),))
+    _lib.require_device(f, y, aux, observed, variance, u)
+    f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
+    aux = None if aux is None else _lib.f32c(aux.reshape(-1))
+    observed = None if observed is None else observed.reshape(-1).contiguous()
+    variance = None if variance is None else variance.reshape(-1).to(torch.float64).contiguous()
+    u = None if u is None else u.reshape(-1).to(torch.float64).contiguous()
+    out = torch.empty(3, dtype=torch.float64, device=f.device)
+    work = _lib.workspace(lib().mgp_nb_dispersion_sums_workspace_bytes(n), "evidence_site", f.device)
+    check(lib().mgp_nb_dispersion_sums(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), ptr(u), n, float(mean), r,
+                                       float(h_floor), ptr(out), ptr(work), work.numel(), stream()), "mgp_nb_dispersion_sums")
+    return out
 
 
 def _pmf_points(points):
@@ -568,6 +591,75 @@ def nb_log_constant(k, r):
     y, d = kk + 1.0, r - 1.0
     big_k = (x - 0.5) * torch.log1p(d / y) + d * torch.log(y) - d + (_stirling_s(x) - _stirling_s(y)) - math.lgamma(r)
     return torch.where(k < 32.0, small, torch.where(kk + 1.0 <= r, big_r, big_k))
+
+
+class DispersionParameter(torch.nn.Module):
+    """The negative binomial's dispersion as a differentiable function of one unconstrained float64 parameter raw = rho = log r:
+    forward() = exp(rho) with rho clamped to [log 2^-10, log 2^20], a 0-dim float64 tensor.  init: the start, a scalar in
+    [2^-10, 2^20], which forward() returns exactly until raw moves (the exponential is taken of rho - log init)."""
+
+    def __init__(self, init):
+        super().__init__()
+        r = _dispersion(NB, init)
+        self.register_buffer("init", torch.tensor(r, dtype=torch.float64))
+        self.register_buffer("rho0", torch.tensor(math.log(r), dtype=torch.float64))
+        self.raw = torch.nn.Parameter(self.rho0.clone())
+
+    def forward(self):
+        lo, hi = math.log(DISPERSION_MIN), math.log(DISPERSION_MAX)
+        r = (self.init * torch.exp(self.raw.clamp(lo, hi) - self.rho0)).clamp(DISPERSION_MIN, DISPERSION_MAX)
+        bound = torch.full_like(r, DISPERSION_MAX).where(self.raw > hi, torch.full_like(r, DISPERSION_MIN))
+        return torch.where((self.raw > hi) | (self.raw < lo), bound, r)                    # a clamped rho: the bound itself
+
+
+def _live_dispersion(fit_kw):
+    """(fit_kw with the dispersion as a float, the live tensor or None): a dispersion given as a DispersionParameter is evaluated
+    now; a tensor that requires grad, its or the caller's, is what laplace_evidence differentiates.  Anything else passes as it
+    is."""
+    r = fit_kw.get("dispersion")
+    if isinstance(r, torch.nn.Module):
+        r = r()
+        fit_kw = dict(fit_kw, dispersion=r.detach())
+    if not torch.is_tensor(r) or not r.requires_grad:
+        return fit_kw, None
+    if r.numel() != 1:
+        raise ValueError("dispersion must be a real scalar, got a tensor of shape %s" % (tuple(r.shape),))
+    return dict(fit_kw, dispersion=float(r.detach())), r
+
+
+def learn_dispersion(desc, y, dispersion0, observed=None, exposure=None, mean=None, steps=30, lr=0.1, var_samples=64, variance=None,
+                     fit_kw=None, evidence_kw=None):
+    """Learn the negative binomial's dispersion on the Laplace evidence with the kernel hyper-parameters fixed: Adam(lr) for
+    `steps` steps on a DispersionParameter started at dispersion0, loss -log Z / m, every fit warm-started from the previous
+    mode, the gradient that of evidence.laplace_evidence(dispersion=).  variance: None (every step draws
+    fit.latent_variance(var_samples)[0]), or a callable fit -> diag(A^-1) [n].  fit_kw as laplace_fit_negative_binomial takes,
+    evidence_kw as laplace_evidence.  Returns (r, the CountLaplaceFit at it, history: one (r, log Z, se) per step, taken before
+    the step's update).  Warns when r ends on a bound of [2^-10, 2^20]: 2^20 is the Poisson limit, which the data may prefer."""
+    import warnings
+    from .evidence import laplace_evidence
+    steps = _int(steps, "steps")
+    if steps < 1 or not float(lr) > 0.0:
+        raise ValueError("steps must be >= 1 and lr positive, got %r and %r" % (steps, lr))
+    if variance is not None and not callable(variance):
+        raise ValueError("variance must be None or a callable fit -> tensor [n]")
+    fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
+    param = DispersionParameter(dispersion0)
+    opt = torch.optim.Adam(param.parameters(), lr=float(lr))
+    f0, history = fit_kw.pop("f0", None), []
+    for _ in range(steps):
+        opt.zero_grad()
+        r = param()
+        fit = laplace_fit_negative_binomial(desc, y, float(r.detach()), observed, exposure, mean, f0=f0, **fit_kw)
+        f0 = fit.mean
+        ev = laplace_evidence(fit, variance=None if variance is None else variance(fit), var_samples=var_samples, dispersion=r,
+                              **evidence_kw)
+        history.append((fit.dispersion, float(ev.value.detach()), ev.se))
+        (-ev.value / ev.m).backward()
+        opt.step()
+    r = float(param().detach())
+    if r in (DISPERSION_MIN, DISPERSION_MAX):
+        warnings.warn("learn_dispersion ended on the bound r = %g%s" % (r, ": the Poisson limit" if r == DISPERSION_MAX else ""))
+    return r, laplace_fit_negative_binomial(desc, y, r, observed, exposure, mean, f0=f0, **fit_kw), history
 
 
 def dispersion_profile(desc, y, dispersions, observed=None, exposure=None, mean=None, **kw):

@@ -34,6 +34,13 @@
 // the binomial with one trial); h' = mu (Poisson), h (1 - 2 pi) (binomial kind), -(a_u (sigma(-u) - sigma(u)) + a_l (sigma(-l) -
 // sigma(l))) with a_x = sigma(x) sigma(-x) (ordinal), the differences formed as -+(1 - e) / (1 + e) from e = exp(-|x|).
 //
+// mgp_nb_dispersion_sums runs the same loop with another node (DispersionNode: nothing is stored, a second float64 array u is
+// read beside var): the three rows of d log Z / dr of a negative-binomial fit, r its dispersion (docs/kernels/counts.md,
+// "Learning the dispersion"), in the slots lp, fq and sq:
+//   row 0 = sum_obs psi(y + r) - psi(r) + log(1 - pi) + pi - y (1 - pi) / r,  log(1 - pi) = -softplus(z),
+//   row 1 = -1/2 sum_eff var (pi (1 - pi) - h' / r),   row 2 = -1/2 sum_eff u (h / r - pi),   eff: observed and h >= h_floor;
+// psi(y + r) - psi(r) from positive terms no larger than itself (psi_diff).
+//
 // The other kernels:
 //   mgp_softmax_site: the Newton stage of a C-class fit.  F, Q2 F, pi and rhs are row-major [n, C]; a group of TC lanes owns a row
 //     (softmax_rows.h).  Per row: m = max_c f_c, e_c = exp(f_c - m), Z = sum e_c (xor trees inside the group), pi_c = e_c / Z,
@@ -127,9 +134,10 @@ __device__ __forceinline__ void store_partials(const SiteAcc& acc, double* __res
 }
 
 // sums[4] from the partials of `nblk` workgroups: thread t takes partials t, t + 256, ... in order, then the same tree.
-// sum_first: the sum slot leaves before the max slot (the evidence stage: { .., sum corr, max |corr| })
+// sum_first: the sum slot leaves before the max slot (the evidence stage: { .., sum corr, max |corr| }); nout < 4: only the
+// first nout slots leave (mgp_nb_dispersion_sums: three sums, sums has three entries)
 __global__ __launch_bounds__(kBlock) void site_sum_kernel(const double* __restrict__ partials, int nblk,
-                                                          double* __restrict__ sums, bool sum_first = false) {
+                                                          double* __restrict__ sums, bool sum_first = false, int nout = 4) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
   for (int b = threadIdx.x; b < nblk; b += kBlock) {
     const double* p = partials + 4 * (int64_t)b;
@@ -143,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void site_sum_kernel(const double* __restri
     sums[0] = r.lp;
     sums[1] = r.fq;
     sums[2] = sum_first ? r.sq : r.mx;
-    sums[3] = sum_first ? r.mx : r.sq;
+    if (nout > 3) sums[3] = sum_first ? r.mx : r.sq;
   }
 }
 
@@ -454,26 +462,99 @@ __device__ __forceinline__ void evidence_tail(double h, double hp, double var, b
   }
 }
 
+// A node of the evidence stage's loop: kReadsB (it reads the second array), kReadsU (the second float64 array), kWrites (root_h
+// and corr leave) and operator(): one node, observed or not; var and u are 0 where they are not read.
 template <typename Family>
-__device__ __forceinline__ void evidence_node(const Family& fam, float f32, float a32, float b32, bool obs, double var,
-                                              bool has_var, double h_floor, float& root, float& corr, SiteAcc& acc) {
-  root = 0.f;
-  corr = 0.f;
-  if (!obs) return;
-  double h, hp;
-  acc.lp += fam((double)f32, a32, b32, h, hp);
-  evidence_tail<Family::kSaturate>(h, hp, var, has_var, h_floor, root, corr, acc);
+struct EvidenceNode {
+  static constexpr bool kReadsB = Family::kReadsB, kReadsU = false, kWrites = true;
+  Family fam;
+  double h_floor;
+  __device__ __forceinline__ void operator()(float f32, float a32, float b32, bool obs, double var, double, bool has_var, bool,
+                                             float& root, float& corr, SiteAcc& acc) const {
+    root = 0.f;
+    corr = 0.f;
+    if (!obs) return;
+    double h, hp;
+    acc.lp += fam((double)f32, a32, b32, h, hp);
+    evidence_tail<Family::kSaturate>(h, hp, var, has_var, h_floor, root, corr, acc);
+  }
+};
+
+constexpr int kPsiLift = 32;              // psi_diff: the sum of reciprocals up to here, the asymptotic series at arguments from here
+
+// psi(x) - (log x - 1 / (2 x)) = -(1/12 x^-2 - 1/120 x^-4 + 1/252 x^-6 - 1/240 x^-8 + 1/132 x^-10 - 691/32760 x^-12) for x >= 32
+// (the next term is below 2^-67), returned with the sign turned: t(x) > 0, decreasing
+__device__ __forceinline__ double psi_tail(double x) {
+  const double x2 = 1.0 / (x * x);
+  return x2 * (1.0 / 12 - x2 * (1.0 / 120 - x2 * (1.0 / 252 - x2 * (1.0 / 240 - x2 * (1.0 / 132 - x2 * (691.0 / 32760))))));
 }
 
-// the node loop of site_kernel; var (NULL: no corr) is float64, two double2 per quad on the vector path
-template <bool VEC4, typename Family>
+// sum_{j < 32} 1 / (r + j), j ascending: the recurrence that lifts psi(r) to psi(r + 32).  It depends on r alone: the entry point
+// forms it once on the host, in the arithmetic of the device (correctly rounded divisions and sums, no contraction)
+inline double psi_lift(double r) {
+  double s = 0.0;
+  for (int j = 0; j < kPsiLift; ++j) s += 1.0 / (r + (double)j);
+  return s;
+}
+
+// psi(y + r) - psi(r) for a count y (an integer 0 .. 2^24) and r in [2^-10, 2^20], every term positive and no larger than the
+// result: y <= 32: sum_{j < y} 1 / (r + j), j ascending.  Beyond it, with k = 32 for r < 32 and 0 otherwise, b = r + k, a = y + r:
+//   sum_{j < k} 1 / (r + j)  +  log1p((y - k) / b)  +  (y - k) / (2 a b)  +  (t(b) - t(a))
+// (the recurrence psi(r) = psi(r + k) - sum_{j < k} 1 / (r + j), then psi(a) - psi(b) from the asymptotic series with the
+// logarithms as one log1p of the ratio and the 1 / (2 x) terms as one quotient).  lift: psi_lift(r) for r < 32, 0 otherwise.
+// y = 0 gives exactly 0.
+__device__ __forceinline__ double psi_diff(double y, double r, double lift) {
+  if (y <= (double)kPsiLift) {
+    double s = 0.0;
+    for (int j = 0; j < kPsiLift && (double)j < y; ++j) s += 1.0 / (r + (double)j);
+    return s;
+  }
+  const bool lifted = r < (double)kPsiLift;
+  const double b = lifted ? r + (double)kPsiLift : r;
+  const double d = lifted ? y - (double)kPsiLift : y;
+  const double a = y + r;
+  return lift + log1p(d / b) + d / (2.0 * a * b) + (psi_tail(b) - psi_tail(a));
+}
+
+// The integrands of d log Z / dr of a negative-binomial fit at the mode (mgp_nb_dispersion_sums): acc.lp the likelihood's term
+// on every observed node, acc.fq the curvature's at fixed f and acc.sq the one through the mode on the nodes with h >= h_floor.
+// z, pi, 1 - pi, h and h' as CountEvidence<3> forms them.
+struct DispersionNode {
+  static constexpr bool kReadsB = true, kReadsU = true, kWrites = false;
+  double mean, r_nb, log_r, lift, h_floor;
+  __device__ __forceinline__ void operator()(float f32, float y32, float a32, bool obs, double var, double u, bool has_var,
+                                             bool has_u, float&, float&, SiteAcc& acc) const {
+    if (!obs) return;
+    const double y = (double)y32;
+    const double z = (double)f32 + mean + (double)a32 - log_r;
+    const double az = fabs(z);
+    const double e = exp(-az);
+    const double d = 1.0 + e;
+    const double pi = z >= 0.0 ? 1.0 / d : e / d;
+    const double pib = z >= 0.0 ? e / d : 1.0 / d;                     // 1 - pi without the subtraction
+    const double softplus = (z > 0.0 ? z : 0.0) + log1p(e);            // -log(1 - pi)
+    acc.lp += ((psi_diff(y, r_nb, lift) - softplus) + pi) - y * pib / r_nb;
+    const double pq = e / (d * d);                                     // pi (1 - pi)
+    const double h = (y + r_nb) * pq;
+    if (!(h >= h_floor)) return;
+    const double gap = -expm1(-az) / d;
+    const double hp = h * (z >= 0.0 ? -gap : gap);
+    if (has_var) acc.fq += -0.5 * (var * (pq - hp / r_nb));
+    if (has_u) acc.sq += -0.5 * (u * (h / r_nb - pi));
+  }
+};
+
+// the node loop of site_kernel; var (NULL: no corr) and u (read by a node with kReadsU only) are float64, two double2 per quad
+// on the vector path
+template <bool VEC4, typename Node>
 __global__ __launch_bounds__(kBlock) void evidence_kernel(const float* __restrict__ f, const float* __restrict__ a,
                                                           const float* __restrict__ b, const uint8_t* __restrict__ obs,
-                                                          const double* __restrict__ var, int64_t n, Family fam, double h_floor,
-                                                          float* __restrict__ root_h, float* __restrict__ corr,
-                                                          double* __restrict__ partials) {
+                                                          const double* __restrict__ var, const double* __restrict__ usol,
+                                                          int64_t n, Node node, float* __restrict__ root_h,
+                                                          float* __restrict__ corr, double* __restrict__ partials) {
   SiteAcc acc = {0.0, 0.0, 0.0, 0.0};
-  const bool has_var = var != nullptr && corr != nullptr;
+  const bool has_var = var != nullptr;
+  const bool has_u = Node::kReadsU && usol != nullptr;
   const int64_t nq = (n + 3) >> 2;
   const int64_t stride = (int64_t)gridDim.x * kBlock;
   for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nq; q += stride) {
@@ -484,28 +565,36 @@ __global__ __launch_bounds__(kBlock) void evidence_kernel(const float* __restric
       const bool any = ov.x | ov.y | ov.z | ov.w;
       const float4 av = any ? *reinterpret_cast<const float4*>(a + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 bv =
-          (Family::kReadsB && any && b) ? *reinterpret_cast<const float4*>(b + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
-      double2 v0 = make_double2(0.0, 0.0), v1 = v0;
+          (Node::kReadsB && any && b) ? *reinterpret_cast<const float4*>(b + i0) : make_float4(0.f, 0.f, 0.f, 0.f);
+      double2 v0 = make_double2(0.0, 0.0), v1 = v0, u0 = v0, u1 = v0;
       if (has_var && any) {
         v0 = *reinterpret_cast<const double2*>(var + i0);
         v1 = *reinterpret_cast<const double2*>(var + i0 + 2);
       }
+      if (has_u && any) {
+        u0 = *reinterpret_cast<const double2*>(usol + i0);
+        u1 = *reinterpret_cast<const double2*>(usol + i0 + 2);
+      }
       float4 rv, cv;
-      evidence_node(fam, fv.x, av.x, bv.x, ov.x != 0, v0.x, has_var, h_floor, rv.x, cv.x, acc);
-      evidence_node(fam, fv.y, av.y, bv.y, ov.y != 0, v0.y, has_var, h_floor, rv.y, cv.y, acc);
-      evidence_node(fam, fv.z, av.z, bv.z, ov.z != 0, v1.x, has_var, h_floor, rv.z, cv.z, acc);
-      evidence_node(fam, fv.w, av.w, bv.w, ov.w != 0, v1.y, has_var, h_floor, rv.w, cv.w, acc);
-      *reinterpret_cast<float4*>(root_h + i0) = rv;
-      if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
+      node(fv.x, av.x, bv.x, ov.x != 0, v0.x, u0.x, has_var, has_u, rv.x, cv.x, acc);
+      node(fv.y, av.y, bv.y, ov.y != 0, v0.y, u0.y, has_var, has_u, rv.y, cv.y, acc);
+      node(fv.z, av.z, bv.z, ov.z != 0, v1.x, u1.x, has_var, has_u, rv.z, cv.z, acc);
+      node(fv.w, av.w, bv.w, ov.w != 0, v1.y, u1.y, has_var, has_u, rv.w, cv.w, acc);
+      if (Node::kWrites) {
+        *reinterpret_cast<float4*>(root_h + i0) = rv;
+        if (has_var) *reinterpret_cast<float4*>(corr + i0) = cv;
+      }
     } else {
       const int64_t i1 = i0 + 4 < n ? i0 + 4 : n;
       for (int64_t i = i0; i < i1; ++i) {
         const bool o = obs ? obs[i] != 0 : true;
         float ri, ci;
-        evidence_node(fam, f[i], o ? a[i] : 0.f, (Family::kReadsB && o && b) ? b[i] : 0.f, o, (o && has_var) ? var[i] : 0.0,
-                      has_var, h_floor, ri, ci, acc);
-        root_h[i] = ri;
-        if (has_var) corr[i] = ci;
+        node(f[i], o ? a[i] : 0.f, (Node::kReadsB && o && b) ? b[i] : 0.f, o, (o && has_var) ? var[i] : 0.0,
+             (o && has_u) ? usol[i] : 0.0, has_var, has_u, ri, ci, acc);
+        if (Node::kWrites) {
+          root_h[i] = ri;
+          if (has_var) corr[i] = ci;
+        }
       }
     }
   }
@@ -768,8 +857,8 @@ size_t site_workspace_bytes(int64_t n) { return n < 1 ? 0 : (size_t)site_blocks(
 bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // the second launch of every site entry point: sums[4] from the partials of `blocks` workgroups
-int sum_partials(const double* partials, int blocks, double* sums, bool sum_first, hipStream_t st) {
-  hipLaunchKernelGGL(site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, sum_first);
+int sum_partials(const double* partials, int blocks, double* sums, bool sum_first, hipStream_t st, int nout = 4) {
+  hipLaunchKernelGGL(site_sum_kernel, dim3(1), dim3(kBlock), 0, st, partials, blocks, sums, sum_first, nout);
   MGP_LAUNCH_CHECK();
   return MGP_OK;
 }
@@ -794,27 +883,34 @@ int launch_site(const float* f, const float* qf, const float* a, const float* b,
   return sum_partials(partials, blocks, sums, false, st);
 }
 
-// The evidence stage of one family, as launch_site.  corr is written only where var is given too.
+// The evidence stage's loop over one kind of node, as launch_site: the first nout of { lp, fq, sq, mx } leave in sums.
+template <typename Node>
+int launch_evidence_nodes(const float* f, const float* a, const float* b, const uint8_t* obs, const double* var, const double* u,
+                          int64_t n, const Node& node, float* root_h, float* corr, double* sums, int nout, void* work,
+                          size_t work_bytes, void* stream) {
+  if (!work || !aligned_to(work, 8) || work_bytes < site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
+  const int blocks = site_blocks(n);
+  double* partials = static_cast<double*>(work);
+  const bool vec4 = aligned_to(f, 16) && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
+                    aligned_to(u, 16) && aligned_to(root_h, 16) && aligned_to(corr, 16);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  hipStream_t st = mgp_stream(stream);
+  if (vec4)
+    hipLaunchKernelGGL((evidence_kernel<true, Node>), grid, block, 0, st, f, a, b, obs, var, u, n, node, root_h, corr, partials);
+  else
+    hipLaunchKernelGGL((evidence_kernel<false, Node>), grid, block, 0, st, f, a, b, obs, var, u, n, node, root_h, corr, partials);
+  MGP_LAUNCH_CHECK();
+  return sum_partials(partials, blocks, sums, true, st, nout);
+}
+
+// The evidence stage of one family.  corr is written only where var is given too.
 template <typename Family>
 int launch_evidence(const float* f, const float* a, const float* b, const uint8_t* obs, const double* var, int64_t n,
                     const Family& fam, double h_floor, float* root_h, float* corr, double* sums, void* work, size_t work_bytes,
                     void* stream) {
-  if (!work || !aligned_to(work, 8) || work_bytes < site_workspace_bytes(n)) return MGP_ERR_WORKSPACE;
   if (!var || !corr) var = nullptr, corr = nullptr;
-  const int blocks = site_blocks(n);
-  double* partials = static_cast<double*>(work);
-  const bool vec4 = aligned_to(f, 16) && aligned_to(a, 16) && aligned_to(b, 16) && aligned_to(obs, 4) && aligned_to(var, 16) &&
-                    aligned_to(root_h, 16) && aligned_to(corr, 16);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  hipStream_t st = mgp_stream(stream);
-  if (vec4)
-    hipLaunchKernelGGL((evidence_kernel<true, Family>), grid, block, 0, st, f, a, b, obs, var, n, fam, h_floor, root_h, corr,
-                       partials);
-  else
-    hipLaunchKernelGGL((evidence_kernel<false, Family>), grid, block, 0, st, f, a, b, obs, var, n, fam, h_floor, root_h, corr,
-                       partials);
-  MGP_LAUNCH_CHECK();
-  return sum_partials(partials, blocks, sums, true, st);
+  return launch_evidence_nodes(f, a, b, obs, var, nullptr, n, EvidenceNode<Family>{fam, h_floor}, root_h, corr, sums, 4, work,
+                               work_bytes, stream);
 }
 
 // the dispersion of the negative-binomial entry points: one finite scalar in [2^-10, 2^20] (NaN fails the comparison)
@@ -903,6 +999,17 @@ extern "C" int mgp_nb_evidence_site(const float* f, const float* y, const float*
   if (!f || !y || !root_h || !sums || n < 1 || !(h_floor >= 0.0) || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
   return launch_evidence(f, y, aux, obs, var, n, CountEvidence<3>{mean, dispersion, std::log(dispersion)}, h_floor, root_h, corr,
                          sums, work, work_bytes, stream);
+}
+
+extern "C" size_t mgp_nb_dispersion_sums_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }
+
+extern "C" int mgp_nb_dispersion_sums(const float* f, const float* y, const float* aux, const uint8_t* obs, const double* var,
+                                      const double* u, int64_t n, double mean, double dispersion, double h_floor, double* out,
+                                      void* work, size_t work_bytes, void* stream) {
+  if (!f || !y || !out || n < 1 || !(h_floor >= 0.0) || !nb_dispersion_ok(dispersion)) return MGP_ERR_ARG;
+  const double lift = dispersion < (double)kPsiLift ? psi_lift(dispersion) : 0.0;
+  return launch_evidence_nodes(f, y, aux, obs, var, u, n, DispersionNode{mean, dispersion, std::log(dispersion), lift, h_floor},
+                               nullptr, nullptr, out, 3, work, work_bytes, stream);
 }
 
 extern "C" size_t mgp_ordinal_evidence_site_workspace_bytes(int64_t n) { return site_workspace_bytes(n); }

@@ -20,7 +20,9 @@ added to the value as sur - sur.detach() the way solvers.inv_quad_logdet does.
 The ordered-category fit (ordinal.OrdinalLaplaceFit) has the same evidence with its own site stage (mgp_ordinal_evidence_site: the
 node's interval of cutpoints in the place of the observation) and one more set of parameters, the cutpoints b: d log Z / d b_k
 is three per-cutpoint sums over the nodes (mgp_ordinal_cut_sums, docs/kernels/ordinal.md) of the same v and u, with no trace
-estimate, and enters the value as the surrogate (G . b).
+estimate, and enters the value as the surrogate (G . b).  The negative-binomial count fit has one more parameter too, its
+dispersion r: d log Z / dr is three sums over the nodes of the same v and u (mgp_nb_dispersion_sums, docs/kernels/counts.md) and
+enters the value as (G r).
 
 The C-class softmax fit (classification.MulticlassLaplaceFit) has a Hessian that is not diagonal; its evidence, with the block
 factor R in the place of S and a curvature term accumulated from latent samples, is the last part of this module
@@ -211,10 +213,13 @@ class LaplaceEvidence:
     of (Z, root_h, corr, w, s_ref, Y float32; u, X float64; with the cutpoints' gradient alone: root_h, corr, w, s_ref, u);
     site_sums: the four sums of mgp_laplace_evidence_site (sum_obs l without the families' constants, m, sum corr, max |corr|);
     cutpoint_grad: None, or for an ordinal fit asked for the cutpoints' gradient the three rows [3, K - 1] float64 of
-    mgp_ordinal_cut_sums on the device, whose column sum is d log Z / d b."""
+    mgp_ordinal_cut_sums on the device, whose column sum is d log Z / d b; dispersion_grad: None, or for a negative-binomial fit
+    asked for the dispersion's gradient the three rows [3] float64 of mgp_nb_dispersion_sums on the device, whose sum is
+    d log Z / dr."""
 
-    def __init__(self, value, se, log_likelihood, quad, logdet, logdet_se, method, m, per_probe, solves, site_sums=None,
-                 cutpoint_grad=None):
+    def __init__(self, value, se, log_likelihood, quad, logdet, logdet_se, method, m, per_probe, solves, dispersion_grad=None,
+                 site_sums=None, cutpoint_grad=None):
+        self.dispersion_grad = dispersion_grad
         self.value, self.se, self.log_likelihood, self.quad = value, se, log_likelihood, quad
         self.logdet, self.logdet_se, self.method, self.m = logdet, logdet_se, method, m
         self.per_probe, self.solves, self.site_sums, self.cutpoint_grad = per_probe, solves, site_sums, cutpoint_grad
@@ -279,8 +284,22 @@ def _check_cutpoints(fit, family, cutpoints):
     return bool(cutpoints.requires_grad)
 
 
+def _check_dispersion(fit, family, dispersion):
+    """True when the dispersion's gradient is asked for: dispersion a 0-dim float64 tensor that requires grad and equals the
+    fit's own."""
+    if dispersion is None:
+        return False
+    if family != NB_FAMILY:
+        raise ValueError("dispersion belongs to a negative_binomial fit, this is a %s fit" % family)
+    if not torch.is_tensor(dispersion) or dispersion.dtype != torch.float64 or dispersion.dim() != 0:
+        raise ValueError("dispersion must be a 0-dim float64 tensor")
+    if float(dispersion.detach()) != fit.dispersion:
+        raise ValueError("dispersion is not the fit's: %r against fit.dispersion = %r" % (float(dispersion.detach()), fit.dispersion))
+    return bool(dispersion.requires_grad)
+
+
 def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_probes=16, steps=12, seed=1337, solve_tol=1e-6,
-                     method="auto", probes=None, max_iter=5000, cutpoints=None):
+                     method="auto", probes=None, max_iter=5000, dispersion=None, cutpoints=None):
     """log Z of a LaplaceFit, a CountLaplaceFit or an OrdinalLaplaceFit: a LaplaceEvidence.
     logdet B by logdet_b(num_probes, steps, seed, solve_tol,
     method, probes).  operator: the model's precision(noise=False), the operator fit.desc describes; when one of its
@@ -291,25 +310,29 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
     cutpoints (ordinal fits only): a float64 tensor [K - 1] whose float32 rounding is fit.cutpoints, for example the output of an
     ordinal.CutpointParameter; when it requires grad, value carries d log Z / d b as the surrogate (G . cutpoints) with G the
     column sum of mgp_ordinal_cut_sums (LaplaceEvidence.cutpoint_grad holds the three rows): it needs the variance and the u solve
-    of the hyper-parameter gradient, and neither probes nor X and Y."""
+    of the hyper-parameter gradient, and neither probes nor X and Y.
+    dispersion (negative-binomial fits only): a 0-dim float64 tensor equal to fit.dispersion, for example the output of a
+    counts.DispersionParameter; when it requires grad, value carries d log Z / dr as the surrogate (G dispersion) with G the sum
+    of mgp_nb_dispersion_sums (LaplaceEvidence.dispersion_grad holds the three rows), from the same variance and u solve."""
     from .autograd import needs_grad
     from .solvers import cg_solve
     if not hasattr(fit, "_pseudo") or fit.mean.dim() != 1:
         raise NotImplementedError("laplace_evidence takes a binary, a count or an ordinal fit")
     desc = fit.desc
-    family, mean, aux, s_ref, dispersion = _site_of(fit)
+    family, mean, aux, s_ref, r_nb = _site_of(fit)
     grad = operator is not None and needs_grad(*getattr(operator, "_hyper_tensors", lambda: [])())
     cut_grad = _check_cutpoints(fit, family, cutpoints)
+    disp_grad = _check_dispersion(fit, family, dispersion)
     with torch.no_grad():
         f = fit.mean
-        if (grad or cut_grad) and variance is None:
+        if (grad or cut_grad or disp_grad) and variance is None:
             variance = fit.latent_variance(var_samples)[0]
         if family == ORDINAL_FAMILY:
             from .ordinal import ordinal_cut_sums, ordinal_evidence_site
             root_h, corr, sums = ordinal_evidence_site(f, fit._lo, fit._hi, fit.observed, variance if grad or cut_grad else None)
         else:
-            root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad else None, mean, family,
-                                              dispersion=dispersion)
+            root_h, corr, sums = evidence_site(f, fit.y, aux, fit.observed, variance if grad or disp_grad else None, mean, family,
+                                              dispersion=r_nb)
         sums = sums.tolist()                              # the one host read of the site stage
         m = int(sums[1])
         if m < 1:
@@ -324,26 +347,29 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
                                           max_iter)
     ll = float(fit.log_likelihood)
     value = torch.tensor(ll - quad - 0.5 * logdet, dtype=torch.float64, device=f.device)
-    solves = G = None
-    if grad or cut_grad:
+    solves = G = Gr = None
+    if grad or cut_grad or disp_grad:
         with torch.no_grad():
             # X and u only weight the operator's output, so they enter the bilinear forms as the float64 solutions the refined
             # solves accumulate: a float32 X cannot hold a true residual of 2 solve_tol on Q itself (its rounding alone leaves
             # 2.4e-6 on the 1546-node dumbbell, cond Q = 1e3; the unrefined factorised solve of the Lanczos products 4.8e-6).
             # Y goes through the float32 operator chain and stays float32 (refined as sampling.posterior_variance solves form 3).
             kw = dict(tol=float(solve_tol), stop_mode=1, max_iter=int(max_iter))
-            w = _weights(fit, family, mean, aux, s_ref, dispersion)
+            w = _weights(fit, family, mean, aux, s_ref, r_nb)
             d3 = desc.with_(form=3, noise=s_ref, obs_w=w)
             kw3 = dict(kw, jacobi=sampling.OBSERVED_JACOBI[0])
             if grad:
                 SZ = scale_rows(root_h, Z)
                 X = _solve64(desc, SZ, dict(kw, refine=REFINE_ROUNDS))
                 Y = cg_solve(d3, SZ * s_ref, **dict(kw3, refine=1))[0]
-            # u = A^-1 (v o h') serves both gradients: one solve
+            # u = A^-1 (v o h') serves every gradient: one solve
             u = _solve64(d3, (corr * s_ref).view(-1, 1), dict(kw3, refine=REFINE_ROUNDS)).view(-1)
             solves = dict(root_h=root_h, corr=corr, w=w, s_ref=s_ref, u=u)
             if cut_grad:
                 G = ordinal_cut_sums(f, fit._lo, fit._hi, fit.y, fit.observed, variance, u, fit.num_categories)
+            if disp_grad:
+                from .counts import nb_dispersion_sums
+                Gr = nb_dispersion_sums(f, fit.y, aux, fit.observed, variance, u, mean, r_nb)
             if grad:
                 P = Z.shape[1]
                 V = torch.cat([f.view(-1, 1), Y], 1).contiguous()
@@ -355,7 +381,11 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
     if cut_grad:
         sur = (G.sum(0).to(cutpoints.device) * cutpoints).sum()
         value = value + (sur - sur.detach()).to(value.device)
-    return LaplaceEvidence(value, 0.5 * logdet_se, ll, quad, logdet, logdet_se, method, m, per, solves, sums, G)
+    if disp_grad:
+        sur = Gr.sum().to(dispersion.device) * dispersion
+        value = value + (sur - sur.detach()).to(value.device)
+    return LaplaceEvidence(value, 0.5 * logdet_se, ll, quad, logdet, logdet_se, method, m, per, solves, dispersion_grad=Gr,
+                           site_sums=sums, cutpoint_grad=G)
 
 
 # ------------------------------------------------------------------------------------------------ the softmax family

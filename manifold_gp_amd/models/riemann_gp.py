@@ -216,13 +216,14 @@ class RiemannGP(torch.nn.Module):
         caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta.
         family "ordinal" (laplace_posterior_ordinal) takes num_categories= and cutpoints=; cutpoints may be an
         ordinal.CutpointParameter or a float64 tensor that requires grad: the fit runs at their detached values and value carries
-        d log Z / d cutpoints as well.
+        d log Z / d cutpoints as well.  family "negative_binomial" takes dispersion= in the same way: a number, or a
+        counts.DispersionParameter or a float64 tensor that requires grad, for which value carries d log Z / d dispersion too.
         family "multiclass" (laplace_posterior_multiclass) takes num_classes=; the other arguments go to
         evidence.softmax_evidence (curvature, var_samples, block, num_probes, ...)."""
         import inspect
         from ..classification import laplace_fit, laplace_fit_multiclass
-        from ..counts import laplace_fit_counts
-        from ..evidence import MULTICLASS_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
+        from ..counts import _live_dispersion, laplace_fit_counts
+        from ..evidence import MULTICLASS_FAMILY, NB_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
         from ..ordinal import _live_cutpoints, laplace_fit_ordinal
         if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
             _family(family)
@@ -239,6 +240,10 @@ class RiemannGP(torch.nn.Module):
             fit_kw, live = _live_cutpoints(fit_kw)
             if live is not None:
                 evidence_kw.setdefault("cutpoints", live)
+        if family == NB_FAMILY:
+            fit_kw, live = _live_dispersion(fit_kw)
+            if live is not None:
+                evidence_kw.setdefault("dispersion", live)
         fit = self._laplace_fit(observed, family, **fit_kw)
         if family == MULTICLASS_FAMILY:
             return softmax_evidence(fit, operator=self.precision(noise=False), **evidence_kw)

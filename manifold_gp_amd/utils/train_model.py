@@ -100,12 +100,15 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     """Train the kernel hyper-parameters of `model` (a RiemannGP) on the Laplace evidence of its node fit: the loss is
     -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
     model.train_targets), "poisson", "binomial" or "negative_binomial" (counts; fit_kw carries exposure / trials / mean, and the negative binomial's
-    fixed dispersion); "ordinal" (ordered categories; fit_kw carries num_categories and cutpoints: an ordinal.CutpointParameter is
+    dispersion: a number stays fixed, a counts.DispersionParameter or a float64 tensor that requires grad is evaluated every epoch
+    and trained along by the same optimizer); "ordinal" (ordered categories; fit_kw carries num_categories and cutpoints: an ordinal.CutpointParameter is
     evaluated every epoch and its parameters, held by the same optimizer, are trained along); "multiclass" (class indices; fit_kw
     carries num_classes, the evidence is evidence.softmax_evidence).  Every epoch refits the mode
     from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
     the last loss."""
     from ..evidence import MULTICLASS_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
+    from ..counts import _live_dispersion
+    from ..evidence import NB_FAMILY
     from ..ordinal import _live_cutpoints
     if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
         _family(family)
@@ -119,10 +122,16 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     loss = torch.zeros(())
     while epoch <= max_iter:
         optimizer.zero_grad()
-        epoch_kw, live = _live_cutpoints(fit_kw) if family == ORDINAL_FAMILY else (fit_kw, None)
+        epoch_kw, live, live_r = fit_kw, None, None
+        if family == ORDINAL_FAMILY:
+            epoch_kw, live = _live_cutpoints(fit_kw)
+        elif family == NB_FAMILY:
+            epoch_kw, live_r = _live_dispersion(fit_kw)
         fit = model._laplace_fit(observed, family, f0=f0, **epoch_kw)
         f0 = fit.mean
         epoch_ev = evidence_kw if live is None else dict(evidence_kw, cutpoints=live)
+        if live_r is not None:
+            epoch_ev = dict(epoch_ev, dispersion=live_r)
         ev = evidence_of(fit, operator=model.precision(noise=False), **epoch_ev)
         loss = -ev.value
         for _, module, prior, closure, _ in _named_priors(model):

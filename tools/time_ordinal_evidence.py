@@ -1,7 +1,8 @@
-"""Time the two kernels of the ordinal evidence (mgp_ordinal_evidence_site and mgp_ordinal_cut_sums, both launches each) through
-the C entry points with preallocated outputs: device events around a window of back-to-back calls on one stream, after 50 warm-up
+"""Time the two kernels of the ordinal evidence (mgp_ordinal_evidence_site and mgp_ordinal_cut_sums, both launches each) and the
+two of the negative-binomial evidence that run the same node loop (mgp_nb_evidence_site, mgp_nb_dispersion_sums; r = 2, counts of
+mean 20, a sixth of them above the 32 where the digamma difference changes its form) through the C entry points with preallocated outputs: device events around a window of back-to-back calls on one stream, after 50 warm-up
 calls, five windows each, at n = 60 000 and n = 1 000 000 (K = 5, every node observed, var and u given).  The method of the table
-in docs/kernels/ordinal.md.  Prints one JSON line.  Nothing here is an acceptance bar.
+in docs/kernels/ordinal.md and of "Learning the dispersion" in docs/kernels/counts.md.  Prints one JSON line.  Nothing here is an acceptance bar.
 
     python tools/time_ordinal_evidence.py [--calls 2000] [--windows 5]
 """
@@ -70,8 +71,21 @@ def main():
         def cut_sums():
             check(lib.mgp_ordinal_cut_sums(ptr(f), ptr(lo), ptr(hi), ptr(catd), None, ptr(var), ptr(u), n, K, 1e-30, ptr(out),
                                            ptr(work), work.numel(), st), "mgp_ordinal_cut_sums")
+        y = up(rng.negative_binomial(2.0, 2.0 / 22.0, n).astype(np.float32))
+        aux = up(np.log(rng.uniform(0.5, 20.0, n)).astype(np.float32))
+        out3 = torch.empty(3, dtype=torch.float64, device=dev)
+
+        def nb_site():
+            check(lib.mgp_nb_evidence_site(ptr(f), ptr(y), ptr(aux), None, ptr(var), n, 0.0, 2.0, 1e-30, ptr(root), ptr(corr), ptr(sums),
+                                           ptr(work), work.numel(), st), "mgp_nb_evidence_site")
+
+        def nb_dispersion():
+            check(lib.mgp_nb_dispersion_sums(ptr(f), ptr(y), ptr(aux), None, ptr(var), ptr(u), n, 0.0, 2.0, 1e-30, ptr(out3), ptr(work),
+                                             work.numel(), st), "mgp_nb_dispersion_sums")
         res["evidence_site_us_n%d" % n] = _windows(site, args.calls, args.windows)
         res["cut_sums_us_n%d" % n] = _windows(cut_sums, args.calls, args.windows)
+        res["nb_evidence_site_us_n%d" % n] = _windows(nb_site, args.calls, args.windows)
+        res["nb_dispersion_sums_us_n%d" % n] = _windows(nb_dispersion, args.calls, args.windows)
     print(json.dumps(res))
 
 
