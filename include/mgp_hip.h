@@ -1036,6 +1036,30 @@ int mgp_gram_f64(const float* A, int64_t n, int b, double* G, void* work, size_t
 int mgp_gram_set_mfma(int on);
 int mgp_lowrank_residual(const float* Z, int64_t n, int m, const double* T, const float* V, int C, double scale,
                          float* out, void* stream);
+/* One Newton evaluation of a Laplace fit on the spectral features (csrc/spectral_laplace.hip, docs/kernels/spectral_laplace.md;
+ * spectral_laplace.spectral_laplace_fit): the latent function is f = Z w + mean with Z [n, m] row-major float32 (any alignment:
+ * 16-byte loads where m % 4 == 0 and Z is 16-byte aligned, scalar ones otherwise; 1 <= m <= 512, finite entries) and w [m]
+ * float64.  family: 0 Bernoulli-logit (a = labels, class 1 where a > 0.5), 1 Poisson (a = counts, b = log-exposure or NULL:
+ * zeros), 2 binomial (b = trials), 3 negative binomial (b = log-exposure or NULL, dispersion in [2^-10, 2^20]), 4 ordinal (a, b =
+ * the row's interval (lo, hi] of cutpoints, infinite ends allowed).  a and b [n] float32 are read at observed rows only (NaN
+ * allowed elsewhere); obs [n] bytes, NULL: every row.  f_i = z_i . w is formed in float64 (fma's and a fixed tree) and goes
+ * straight into the family's formulas, those of mgp_bernoulli_site, mgp_count_site, mgp_nb_site and mgp_ordinal_site, at
+ * f_i + mean (l, g = dl / df, h = -dg / df; the Poisson exp at min(eta, 700); 0 at unobserved rows).  Outputs, float64 on the
+ * device:
+ *   f [n] (nullable) = z_i . w without the mean,   grad [m] = Z^T g,   hess [m, m] (nullable) = Z^T diag(h) Z,
+ *   sums [2] = { sum_obs l_i (without the families' f-independent constants),  max_i |f_i| over every row }.
+ * The prior's terms (-w / s, I / s, -w . w / (2 s)) are the caller's.  hess comes from the fp64 matrix cores in a second pass
+ * over Z that skips 32-row stages without an observed row; it is bitwise symmetric.  Sums are one partial per workgroup or row
+ * chunk and a second launch that adds them in a fixed order: no atomics, repeated calls are bitwise equal, and f, grad and sums
+ * of a call with hess == NULL equal those of a call with it bit for bit.  Finite outputs for finite inputs with |f| <= 1e4.
+ * `work`: mgp_spectral_site_workspace_bytes(n, m, with_hessian) bytes, 8-byte aligned (0 for arguments the entry point refuses).
+ * MGP_ERR_ARG for null Z, w, a, grad or sums, n < 1, m outside 1 .. 512, a missing b (families 2, 4), a dispersion out of range
+ * (family 3) or a misaligned array; MGP_ERR_UNSUPPORTED for any other family; MGP_ERR_WORKSPACE for a null, misaligned or short
+ * `work`.  The checks precede every launch. */
+size_t mgp_spectral_site_workspace_bytes(int64_t n, int m, int with_hessian);
+int mgp_spectral_site(const float* Z, int64_t n, int m, const double* w, int family, const float* a, const float* b,
+                      const uint8_t* obs, double mean, double dispersion, double* f, double* grad, double* hess, double* sums,
+                      void* work, size_t work_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU (one process per GPU, RCCL over xGMI): row-partitioned operator apply and CG.

@@ -245,6 +245,9 @@ SIGNATURES = {
     "mgp_gram_f64": (c_int, [_P, c_int64, c_int, _P, _P, c_size_t, _P]),
     "mgp_gram_set_mfma": (c_int, [c_int]),
     "mgp_lowrank_residual": (c_int, [_P, c_int64, c_int, _P, _P, c_int, c_double, _P, _P]),
+    "mgp_spectral_site_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "mgp_spectral_site": (c_int, [_P, c_int64, c_int, _P, c_int, _P, _P, _P, c_double, c_double, _P, _P, _P, _P, _P, c_size_t,
+                                  _P]),
 }
 
 

@@ -72,6 +72,7 @@
 
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "site_formulas.h"
 #include "softmax_rows.h"
 
 namespace {
@@ -162,7 +163,7 @@ __device__ __forceinline__ float sat_f32(double v) {
 }
 
 // ---- Newton stage.  A family: its scalars, kReadsB (it reads the second array) and operator(): one node, observed or not --
-// log p into acc.lp, g and h, then site_tail.
+// log p into acc.lp, g and h (site_formulas.h, shared with spectral_laplace.hip), then site_tail.
 
 // w, rhs and the three sums of a node from its g and h (0 at an unobserved node).  SATURATE: the counts, whose h is unbounded
 template <bool SATURATE>
@@ -185,22 +186,16 @@ struct BernoulliSite {
     const double f = (double)f32;
     double g = 0.0, h = 0.0;
     if (obs) {
-      const bool t = y32 > 0.5f;
-      const double a = t ? f : -f;
-      const double e = exp(-fabs(f));
-      const double d = 1.0 + e;
-      const double pi = f >= 0.0 ? 1.0 / d : e / d;
-      acc.lp += (a < 0.0 ? a : 0.0) - log1p(e);
-      g = (t ? 1.0 : 0.0) - pi;
-      h = e / (d * d);
+      double lp;
+      mgp_bernoulli_lgh(f, y32, lp, g, h);
+      acc.lp += lp;
     }
     site_tail<false>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
   }
 };
 
 // FAMILY 0: Poisson, a32 the log-exposure; FAMILY 1: binomial, a32 the trials; FAMILY 2: negative binomial with the dispersion
-// r_nb (log_r = log r), a32 the log-exposure: the binomial arithmetic with y + r "trials" and r "failures" at the predictor
-// z = f + mean + a - log r (pi = mu / (r + mu))
+// r_nb (log_r = log r), a32 the log-exposure (mgp_count_lgh)
 template <int FAMILY>
 struct CountSite {
   static constexpr bool kReadsB = true;
@@ -210,33 +205,15 @@ struct CountSite {
     const double f = (double)f32;
     double g = 0.0, h = 0.0;
     if (obs) {
-      const double y = (double)y32;
-      if (FAMILY == 0) {
-        const double eta = f + mean + (double)a32;
-        const double mu = exp(eta < 700.0 ? eta : 700.0);
-        acc.lp += y * eta - mu;
-        g = y - mu;
-        h = mu;
-      } else {
-        const double eta = FAMILY == 1 ? f + mean : f + mean + (double)a32 - log_r;
-        const double N = FAMILY == 1 ? (double)a32 : y + r_nb;
-        const double m = FAMILY == 1 ? N - y : r_nb;                     // failures (binomial: exact, both are integers <= 2^24)
-        const double e = exp(-fabs(eta));
-        const double d = 1.0 + e;
-        const double l1 = log1p(e);
-        const double pi = eta >= 0.0 ? 1.0 / d : e / d;
-        const double pib = eta >= 0.0 ? e / d : 1.0 / d;                 // 1 - pi without the subtraction
-        acc.lp += -m * ((eta > 0.0 ? eta : 0.0) + l1) - y * ((eta < 0.0 ? -eta : 0.0) + l1);
-        g = y * pib - m * pi;
-        h = N * e / (d * d);
-      }
+      double lp;
+      mgp_count_lgh<FAMILY>(f, mean, r_nb, log_r, y32, a32, lp, g, h);
+      acc.lp += lp;
     }
     site_tail<true>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
   }
 };
 
-// the category is the interval (lo32, hi32] of cutpoints, -inf / +inf at the end categories.  exp(-|x|) is 0 at an infinite end,
-// so sigma, log sigma and sigma (1 - sigma) need no special case there
+// the category is the interval (lo32, hi32] of cutpoints, -inf / +inf at the end categories (mgp_ordinal_lgh)
 struct OrdinalSite {
   static constexpr bool kReadsB = true;
   double s_ref;
@@ -245,12 +222,9 @@ struct OrdinalSite {
     const double f = (double)f32;
     double g = 0.0, h = 0.0;
     if (obs) {
-      const double u = (double)hi32 - f, l = (double)lo32 - f;
-      const double eu = exp(-fabs(u)), el = exp(-fabs(l));
-      const double du = 1.0 + eu, dl = 1.0 + el;
-      acc.lp += -((u < 0.0 ? -u : 0.0) + log1p(eu)) - ((l > 0.0 ? l : 0.0) + log1p(el));   // log sigma(u) + log sigma(-l)
-      g = (l >= 0.0 ? 1.0 / dl : el / dl) - (u >= 0.0 ? eu / du : 1.0 / du);               // sigma(l) - sigma(-u)
-      h = eu / (du * du) + el / (dl * dl);
+      double lp;
+      mgp_ordinal_lgh(f, lo32, hi32, lp, g, h);
+      acc.lp += lp;
     }
     site_tail<false>(s_ref, f, (double)qf32, g, h, w, rhs, acc);
   }

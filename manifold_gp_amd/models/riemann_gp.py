@@ -189,6 +189,30 @@ class RiemannGP(torch.nn.Module):
         desc, _, y = self._sampling_args()
         return laplace_fit_ordinal(desc, y, num_categories, cutpoints, observed, **kw)
 
+    def spectral_laplace_posterior(self, observed=None, family="bernoulli", **kw):
+        """The Laplace fit of train_targets through the spectral kernel K = s Z Z^T, which predicts at points that were not in
+        the graph: a spectral_laplace.SpectralLaplaceFit bound to the kernel, whose latent / predict_* methods take points
+        x [T, d] (or their feature rows).  Z = base_kernel.features(train_x), s = covar_module.outputscale; family "bernoulli",
+        "poisson", "binomial", "negative_binomial" or "ordinal"; train_targets are read at `observed` (bool [N]; None: every
+        node; NaN allowed elsewhere); kw as spectral_laplace.spectral_laplace_fit (exposure, trials, dispersion, num_categories,
+        cutpoints, mean, rtol, max_newton, w0).  Needs eval(): the eigenpairs are computed there.  The Gaussian likelihood's
+        noise is not used."""
+        from ..spectral_laplace import spectral_laplace_fit
+        if self.labeled is not None:
+            raise NotImplementedError("the spectral Laplace fit of semi-supervised (Schur-complement) models is not supported")
+        kernel = self.base_kernel
+        if getattr(kernel, "eigvec", None) is None:
+            raise RuntimeError("spectral_laplace_posterior needs the kernel's eigenpairs: call model.eval() first")
+        for name in ("outputscale", "kernel"):
+            if name in kw:
+                raise ValueError("%s is the model's own: spectral_laplace_posterior takes none" % name)
+        with torch.no_grad():
+            Z = kernel.features(self.train_inputs[0])
+            s = float(self.covar_module.outputscale) if hasattr(self.covar_module, "outputscale") else 1.0
+        fit = spectral_laplace_fit(Z, self.train_targets, observed, family, outputscale=s, **kw)
+        fit.kernel = kernel
+        return fit
+
     def _laplace_fit(self, observed, family, **kw):
         """The binary fit (family "bernoulli"), the count fit ("poisson", "binomial", "negative_binomial"), the ordered-category
         fit ("ordinal", with num_categories= and cutpoints= in kw) or the C-class fit ("multiclass", with num_classes= in kw) of
