@@ -6,7 +6,8 @@
  *   - extern "C", plain device pointers + sizes + a hipStream_t passed as void*; no torch types;
  *   - returns int: 0 = ok, <0 = argument error (MGP_ERR_*), >0 = hipError_t from the runtime;
  *   - never allocates or frees caller memory: scratch comes from an explicit `work` buffer whose
- *     size the matching *_workspace_bytes() query returns;
+ *     size the matching *_workspace_bytes() query returns; a `work_bytes` below that size is
+ *     MGP_ERR_WORKSPACE before any launch, also where the carve would fit in less (docs/memory_contract.md);
  *   - asynchronous on `stream` unless the comment says it synchronises (graph-build calls that
  *     must report a data-dependent size do);
  *   - all matrices of right-hand sides are row-major [N, C] fp32, indices int32, values fp32.

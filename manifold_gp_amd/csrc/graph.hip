@@ -232,7 +232,8 @@ extern "C" int mgp_graph_build(const float* D, const int32_t* I, int64_t n, int 
   hipStream_t st = mgp_stream(stream);
   const int64_t total = n * (int64_t)(k - 1);
   GraphWork w;
-  if (!carve(w, work, work_bytes, 2 * total, n)) return MGP_ERR_WORKSPACE;
+  // the boundary contract: scratch is the size the query returns (the carve alone would also fit without the query's slack)
+  if (work_bytes < mgp_graph_workspace_bytes(n, k) || !carve(w, work, work_bytes, 2 * total, n)) return MGP_ERR_WORKSPACE;
 
   hipLaunchKernelGGL(make_directed_keys, dim3(grid_for(total)), dim3(kBlock), 0, st, D, I, n, k, 1, w.keys_a, w.vals_a);
   MGP_LAUNCH_CHECK();
@@ -294,7 +295,7 @@ extern "C" int mgp_graph_edges(const float* D, const int32_t* I, int64_t n, int 
   }
   if (!work) return MGP_ERR_ARG;
   GraphWork w;
-  if (!carve(w, work, work_bytes, 2 * total, n)) return MGP_ERR_WORKSPACE;
+  if (work_bytes < mgp_graph_workspace_bytes(n, k + 1) || !carve(w, work, work_bytes, 2 * total, n)) return MGP_ERR_WORKSPACE;
   hipLaunchKernelGGL(make_directed_keys, dim3(grid_for(total)), dim3(kBlock), 0, st, D, I, n, k, first, w.keys_a, w.vals_a);
   MGP_LAUNCH_CHECK();
   hipcub::DoubleBuffer<uint64_t> kb(w.keys_a, w.keys_b);
@@ -322,7 +323,8 @@ extern "C" int mgp_graph_from_coo(const int32_t* tri_row, const int32_t* tri_col
   if (!tri_row || !tri_col || !tri_val || !rowptr || !col || !d2 || !eid || !nnz || !work) return MGP_ERR_ARG;
   if (n <= 0 || M < 0 || 2 * M > 0x7fffffff) return MGP_ERR_ARG;
   GraphWork w;
-  if (!carve(w, work, work_bytes, 2 * M > 0 ? 2 * M : 1, n)) return MGP_ERR_WORKSPACE;
+  if (work_bytes < graph_bytes(2 * M > 0 ? 2 * M : 1, n) || !carve(w, work, work_bytes, 2 * M > 0 ? 2 * M : 1, n))
+    return MGP_ERR_WORKSPACE;          // (graph_bytes: what mgp_graph_coo_workspace_bytes returns)
   return csr_from_tri(w, tri_row, tri_col, tri_val, M, n, rowptr, col, d2, eid, nnz, mgp_stream(stream));
 }
 
@@ -448,6 +450,7 @@ extern "C" int mgp_graph_tiles(int64_t n, const int32_t* rowptr, const int32_t* 
   if (n <= 0 || nnz <= 0 || nnz > 0x7fffffff || tile_rows < 1) return MGP_ERR_ARG;
   hipStream_t st = mgp_stream(stream);
   const int64_t ntiles = mgp_cdiv(n, tile_rows);
+  if (work_bytes < tile_bytes(n, nnz)) return MGP_ERR_WORKSPACE;      // what mgp_graph_tiles_workspace_bytes returns
   MgpArena ar(work, work_bytes);
   const int64_t items = nnz > n + 2 ? nnz : n + 2;
   uint64_t* keys_a = ar.take<uint64_t>(items);

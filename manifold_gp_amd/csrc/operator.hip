@@ -334,6 +334,9 @@ extern "C" int mgp_operator_apply_double(const mgp_operator_t* op, const double*
 
 extern "C" int mgp_operator_apply(const mgp_operator_t* op, const float* X, int C, float* Y, void* work,
                                   size_t work_bytes, void* stream) {
+  // the boundary contract: scratch is the size the query returns (the carve below would also fit without the query's alignment
+  // slack when `work` happens to be 256-byte aligned -- a caller must not learn to rely on that)
+  if (check_op(op) == MGP_OK && X && Y && X != Y && C > 0 && work_bytes < mgp_operator_workspace_bytes(op, C)) return MGP_ERR_WORKSPACE;
   return mgp_operator_apply_ex(op, X, C, Y, nullptr, nullptr, nullptr, nullptr, work, work_bytes, stream);
 }
 
@@ -341,6 +344,7 @@ extern "C" int mgp_operator_apply_dot(const mgp_operator_t* op, const float* X, 
                                       const float* dotw, float* dot_partials, void* work, size_t work_bytes,
                                       void* stream) {
   if (!dotw || !dot_partials) return MGP_ERR_ARG;
+  if (check_op(op) == MGP_OK && X && Y && X != Y && C > 0 && work_bytes < mgp_operator_workspace_bytes(op, C)) return MGP_ERR_WORKSPACE;
   return mgp_operator_apply_ex(op, X, C, Y, dotw, dot_partials, nullptr, nullptr, work, work_bytes, stream);
 }
 

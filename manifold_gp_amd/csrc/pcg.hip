@@ -718,9 +718,9 @@ extern "C" int mgp_pcg_plan_create(const mgp_operator_t* op, const int64_t* laun
   }
   if (launch_rows[op->nu - 1] < n_loc) return MGP_ERR_ARG;
   if ((int64_t)world * nbu_for(n_loc) > (int64_t)kMaxSlots * kBlock) return MGP_ERR_UNSUPPORTED;
-  const bool own_shared = shared == nullptr;
-  const size_t need = (pcg_private_floats(n_glob) + (own_shared ? mgp_pcg_shared_floats(n_glob, n_loc, world) : 0)) * sizeof(float) + 16 * 256;
-  if (work_bytes < need) return MGP_ERR_WORKSPACE;
+  // the boundary contract: scratch is the size the query returns, whether or not the caller brings the shared buffers (a virtual
+  // rank's plan carves less, but the query cannot know and a caller must not learn to pass less)
+  if (work_bytes < mgp_pcg_workspace_bytes(n_glob, n_loc, world)) return MGP_ERR_WORKSPACE;
   PcgPlan* pl = new (std::nothrow) PcgPlan();
   if (!pl) return MGP_ERR_ARG;
   memset(pl, 0, sizeof(*pl));
