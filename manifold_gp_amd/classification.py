@@ -33,7 +33,7 @@ import warnings
 
 import torch
 
-from . import _lib, _sites, sampling
+from . import _lib, _sites, families, sampling
 from ._lib import check, lib, ptr, stream
 
 S_REF = 4.0              # obs_w = S_REF h <= 1
@@ -105,20 +105,7 @@ def _validate(desc, y, observed, link, f0):
     n = desc.n
     if link not in LINKS:
         raise ValueError("link must be one of %s, got %r" % (sorted(LINKS), link))
-    if not torch.is_tensor(y) or y.numel() != n:
-        raise ValueError("y must be a tensor of %d labels, got %s" % (n, tuple(y.shape) if torch.is_tensor(y) else type(y)))
-    y = y.reshape(-1)
-    if observed is not None:
-        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        if observed.dim() != 1 or observed.shape[0] != n:
-            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
-        if not bool(observed.any()):
-            raise ValueError("observed selects no node")
-        observed = observed.to(y.device)
-    seen = y if observed is None else y[observed]
-    if not bool(((seen == 0) | (seen == 1)).all()):
-        raise ValueError("labels at the observed nodes must all be 0 or 1")
+    y, observed = families.check_labels(y, observed, n)
     if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != n):
         raise ValueError("f0 must be a tensor of %d latent values" % n)
     return y, observed
@@ -127,7 +114,9 @@ def _validate(desc, y, observed, link, f0):
 class LaplaceFit:
     """The Laplace approximation N(mean, (Q2 + H)^-1) of the latent posterior (laplace_fit).
     mean [n] float32: the mode; converged, iterations; history: one (psi, relative gradient, step, CG iterations) per
-    Newton step; log_likelihood: sum_obs log p(t_i | mean_i)."""
+    Newton step; log_likelihood: sum_obs log p(t_i | mean_i).  family: the fit's row of families.TABLE; prior_mean, _aux, s_ref and
+    dispersion are what the site kernels of the family read beside y (evidence._site_of)."""
+    family, prior_mean, _aux, s_ref, dispersion = "bernoulli", 0.0, None, S_REF, None
 
     def __init__(self, desc, y, observed, mean, converged, iterations, history, log_likelihood):
         self.desc, self.y, self.observed = desc, y, observed
@@ -138,18 +127,23 @@ class LaplaceFit:
         """sigma(mean): the class-1 probability at the mode, [n] float64 (ignores the latent variance)."""
         return torch.sigmoid(self.mean.double())
 
+    def _gh(self, f, obs):
+        """(g, h) of the family in float64 at the mode f; obs: the observed nodes, the others are not used"""
+        return families.TABLE[self.family].gh(f, self.y, None, None)
+
+    def _weights(self):
+        """obs_w = (float)(s_ref h) of the fit's own form-3 system at the mode, from the kernel its Newton steps used"""
+        return bernoulli_site(self.mean, None, self.y, self.observed, self.s_ref)[0]
+
     def _pseudo(self):
-        """(pseudo-targets f_hat + g / h, pseudo-noise 1 / h, obs_eff) in float64 from the mode; entries outside obs_eff are
-        0 and 1."""
+        """(pseudo-targets f_hat + g / h, pseudo-noise 1 / h, obs_eff) in float64 from the mode, with the family's g and h
+        (_gh); entries outside obs_eff are 0 and 1."""
         f = self.mean.double()
-        e = torch.exp(-f.abs())
-        h = e / (1.0 + e) ** 2
         obs = torch.ones_like(f, dtype=torch.bool) if self.observed is None else self.observed
+        g, h = self._gh(f, obs)
         eff = obs & (h >= H_FLOOR)
         if not bool(eff.any()):
             raise RuntimeError("no observed node has a curvature above %g: the latent values have run away" % H_FLOOR)
-        t = (torch.nan_to_num(self.y.double(), nan=0.0) > 0.5).double()
-        g = t - torch.where(f >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
         one, zero = torch.ones((), dtype=f.dtype, device=f.device), torch.zeros((), dtype=f.dtype, device=f.device)
         noise = torch.where(eff, 1.0 / h.clamp_min(H_FLOOR), one)
         targets = torch.where(eff, f + g * noise, zero)
@@ -234,30 +228,39 @@ def laplace_fit(desc, y, observed=None, link="logit", rtol=1e-5, max_newton=30, 
     the other nodes are not read and may be NaN), by Newton's method with step halving: LaplaceFit.
     desc: a form-0 precision descriptor as the samplers take.  Stops when max |g - Q2 f| <= rtol times its value at f = 0;
     every step is a form-3 CG solve to the relative residual cg_tol.  f0 [n]: the starting point (default 0)."""
-    from .solvers import cg_solve
     y, observed = _validate(desc, y, observed, link, f0)
     _lib.require_device(y, f0)
     dev = desc.data.graph.device
-    n = desc.n
     y = _lib.f32c(y.to(dev))
     obs = None if observed is None else observed.to(dev).contiguous()
+    f, sums, converged, its, history = _newton_form3("laplace_fit", desc, lambda f, qf: bernoulli_site(f, qf, y, obs, S_REF, link),
+                                                     S_REF, f0, rtol, max_newton, cg_tol, max_iter)
+    return LaplaceFit(desc, y, obs, f, converged, its, history, sums[0])
 
-    def site(f, qf):
-        w, rhs, sums = bernoulli_site(f, qf, y, obs, S_REF, link)
+
+def _newton_form3(name, desc, site, s_ref, f0, rtol, max_newton, cg_tol, max_iter, step_tol=None):
+    """_newton for one latent function on the nodes (the binary, count and ordinal fits): site(f, qf) is the family's kernel,
+    (w, rhs, sums on the device); a step is the form-3 CG solve with obs_w = w and noise = s_ref to the relative residual cg_tol.
+    Returns (f, sums, converged, steps, history)."""
+    from .solvers import cg_solve
+    dev = desc.data.graph.device
+
+    def evaluate(f, qf):
+        w, rhs, sums = site(f, qf)
         return w, rhs, sums.tolist()                      # the one host read of an evaluation
 
     def solve(w, rhs):
         # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
-        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=S_REF, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
+        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=s_ref, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
                                     jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
         return delta, cg_its
 
     with torch.no_grad():
-        zero = torch.zeros(n, dtype=torch.float32, device=dev)
+        zero = torch.zeros(desc.n, dtype=torch.float32, device=dev)
         start = None if f0 is None else _lib.f32c(f0.to(dev).reshape(-1))
-        f, _, sums, converged, its, history = _newton("laplace_fit", site, lambda v: _q2(desc, v), solve, zero, start, rtol,
-                                                      max_newton)
-    return LaplaceFit(desc, y, obs, f, converged, its, history, sums[0])
+        f, _, sums, converged, its, history = _newton(name, evaluate, lambda v: _q2(desc, v), solve, zero, start, rtol, max_newton,
+                                                      step_tol)
+    return f, sums, converged, its, history
 
 
 # ------------------------------------------------------------------------------------------------ C classes: softmax
@@ -328,6 +331,15 @@ def softmax_noise_factor(pi, eps):
     return root * eps - pi.to(eps.dtype) * (root * eps).sum(-1, keepdim=True)
 
 
+def _check_cg_args(tol, max_iter, check_every):
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError("max_iter must be a positive int, got %r" % (max_iter,))
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+        raise ValueError("check_every must be a positive int, got %r" % (check_every,))
+    if not tol >= 0.0:
+        raise ValueError("tol must be >= 0, got %r" % (tol,))
+
+
 def softmax_cg_solve(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8):
     """Solve (Q2 (x) I_C + H(pi)) X = rhs as one system of size n C (mgp_softmax_cg): (X [n, C] float32, iterations, relative
     residual of the recurrence).  desc: a form-0 precision descriptor; pi, rhs [n, C].  Where the graph has a locality order
@@ -341,12 +353,7 @@ def softmax_cg_solve(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8):
     n, C = pi.shape
     _classes(int(C))
     pi, rhs = _block(pi, n, C, "pi"), _block(rhs, n, C, "rhs")
-    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
-        raise ValueError("max_iter must be a positive int, got %r" % (max_iter,))
-    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
-        raise ValueError("check_every must be a positive int, got %r" % (check_every,))
-    if not tol >= 0.0:
-        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    _check_cg_args(tol, max_iter, check_every)
     _lib.require_device(pi, rhs)
     rg = None
     if RELABEL_SOLVES[0]:
@@ -410,12 +417,7 @@ def softmax_cg_solve_block(desc, pi, rhs, tol=1e-3, max_iter=5000, check_every=8
     if S * C > MAX_BLOCK_COLUMNS:
         raise ValueError("rhs holds S C = %d x %d = %d columns: the limit is %d" % (S, C, S * C, MAX_BLOCK_COLUMNS))
     pi, rhs = _block(pi, n, C, "pi"), _lib.f32c(rhs)
-    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
-        raise ValueError("max_iter must be a positive int, got %r" % (max_iter,))
-    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
-        raise ValueError("check_every must be a positive int, got %r" % (check_every,))
-    if not tol >= 0.0:
-        raise ValueError("tol must be >= 0, got %r" % (tol,))
+    _check_cg_args(tol, max_iter, check_every)
     _lib.require_device(pi, rhs)
     rg = None
     wide = S * C >= 48               # 48 columns and more: the matrix-core tile SpMM on the chain-relabelled matrix, as CgPlan
@@ -455,13 +457,7 @@ def _validate_multiclass(desc, labels, num_classes, observed, f0):
     if not torch.is_tensor(labels) or labels.dim() != 1 or labels.shape[0] != n or labels.dtype == torch.bool:
         raise ValueError("labels must be a tensor of %d class indices, got %s"
                          % (n, tuple(labels.shape) if torch.is_tensor(labels) else type(labels)))
-    if observed is not None:
-        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        if observed.dim() != 1 or observed.shape[0] != n:
-            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
-        if not bool(observed.any()):
-            raise ValueError("observed selects no node")
+    if _sites.check_mask(observed, n) is not None:
         observed = observed.to(labels.device)
     seen = labels if observed is None else labels[observed]
     if not bool(((seen >= 0) & (seen < C) & (seen == seen.round() if seen.is_floating_point() else True)).all()):
@@ -482,6 +478,7 @@ class MulticlassLaplaceFit:
     mean [n, C] float32: the mode, rows summing to 0 up to the solver's tolerance; converged, iterations; history: one
     (psi, relative gradient, step, CG iterations) per Newton step; log_likelihood: sum_obs log softmax(mean_i)[t_i];
     pi [n, C] float32: softmax(mean) on the observed rows, 0 elsewhere (the weights of H)."""
+    family = "multiclass"
 
     def __init__(self, desc, labels, observed, mean, pi, converged, iterations, history, log_likelihood):
         self.desc, self.labels, self.observed = desc, labels, observed

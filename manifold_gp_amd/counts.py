@@ -27,7 +27,7 @@ for counts max |g(0)| is the size of the largest count, and a gradient rule rela
 from the mode than the same rule does for 0/1 labels (docs/kernels/counts.md has the numbers).
 
 The Laplace posterior N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets
-f_hat + g / h: CountLaplaceFit restates _pseudo() for the family and inherits latent_variance / latent_samples.
+f_hat + g / h: CountLaplaceFit supplies the family's (g, h) (families.TABLE) and inherits _pseudo, latent_variance / latent_samples.
 
 The predictive distribution of a new count -- its pmf, the log density of held-out counts, exceedance probabilities and
 equal-tailed intervals (CountLaplaceFit.predict_pmf / predict_log_density / predict_exceedance / predict_interval) -- comes from
@@ -37,38 +37,27 @@ import math
 
 import torch
 
-from . import _lib, _sites, sampling
+from . import _lib, _sites, families, sampling
 from ._lib import check, lib, ptr, stream
-from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2, bernoulli_predict
+from .classification import H_FLOOR, LaplaceFit, _newton_form3, _points
+from ._sites import _int, _node_vector, _real
+from .families import DISPERSION_MAX, DISPERSION_MIN, ETA_MAX, MAX_COUNT, check_dispersion, nb_log_constant  # noqa: F401
 
-FAMILIES = {"poisson": 0, "binomial": 1, "negative_binomial": 2}
-NB = 2                       # the family with entry points of its own (mgp_nb_*): mgp_count_* refuse every code but 0 and 1
-DISPERSION_MIN, DISPERSION_MAX = 2.0 ** -10, 2.0 ** 20
-MAX_COUNT = 2 ** 24          # counts and trials are float32 on the device: integers are exact up to here
-ETA_MAX = 700.0              # mu = exp(min(eta, ETA_MAX)) stays finite in float64
+FAMILIES = families.codes("count")
+_NB = families.TABLE[families.with_own("nb")]        # the family with entry points of its own (mgp_nb_*)
+NB = _NB.count               # mgp_count_* refuse every code but the other two
 PMF_POINTS = 65              # the default rule of the predictive pmf (docs/kernels/count_predict.md)
 PMF_MAX_BLOCK = 65536        # counts per node in one mgp_count_predict_pmf call
 
 
-def _family(family):
-    if family not in FAMILIES:
-        raise ValueError("family must be one of %s, got %r" % (sorted(FAMILIES), family))
-    return FAMILIES[family]
-
-
-def _dispersion(fam, dispersion):
-    """float(dispersion) for the negative binomial (required: a finite scalar in [2^-10, 2^20]); None for the other families, which
-    take none"""
-    if fam != NB:
-        if dispersion is not None:
-            raise ValueError("dispersion belongs to the negative_binomial family")
-        return None
-    if dispersion is None:
-        raise ValueError("the negative_binomial family needs dispersion=")
-    r = _real(dispersion, "dispersion")
-    if not DISPERSION_MIN <= r <= DISPERSION_MAX:            # (NaN fails the comparison)
-        raise ValueError("dispersion must be a finite scalar in [2^-10, 2^20], got %r" % (dispersion,))
-    return r
+def _count_family(family, dispersion, aux):
+    """(record, dispersion as check_dispersion returns it) of a count family; aux: what a kernel wrapper got, which has to hold
+    the trials of the binomial family"""
+    rec = families._family(family, "count")
+    r = check_dispersion(rec, dispersion)
+    if rec.aux == "trials" and aux is None:
+        raise ValueError("the binomial family needs the trials in aux")
+    return rec, r
 
 
 def count_site(f, qf, y, aux, observed, s_ref, mean, family, dispersion=None):
@@ -76,19 +65,12 @@ def count_site(f, qf, y, aux, observed, s_ref, mean, family, dispersion=None):
     +-FLT_MAX), sums [4] float64 on the device (sum_obs l without the f-independent constant, sum f qf, max |g - qf|,
     sum (g - qf)^2).  f, y [n] float32; qf [n] or None (zeros); aux [n]: the log-exposure (family "poisson"; None: zeros) or the
     trials (family "binomial"); observed [n] bool or None (every node); mean: the constant added to f in the linear predictor."""
-    fam = _family(family)
-    r = _dispersion(fam, dispersion)
-    if fam == 1 and aux is None:
-        raise ValueError("the binomial family needs the trials in aux")
+    rec, r = _count_family(family, dispersion, aux)
+    site, name, workspace_bytes, code = families.stage(rec, "site", r)
     f, qf, (y, aux), observed, n, w, rhs, sums, work = _sites.newton_args(
-        f, qf, (("y", y),), (("aux", aux),), observed, "count_site",
-        lib().mgp_nb_site_workspace_bytes if fam == NB else lib().mgp_count_site_workspace_bytes)
-    if fam == NB:
-        check(lib().mgp_nb_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), r, ptr(w), ptr(rhs),
-                                ptr(sums), ptr(work), work.numel(), stream()), "mgp_nb_site")
-        return w, rhs, sums
-    check(lib().mgp_count_site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), fam, ptr(w),
-                               ptr(rhs), ptr(sums), ptr(work), work.numel(), stream()), "mgp_count_site")
+        f, qf, (("y", y),), (("aux", aux),), observed, "count_site", workspace_bytes)
+    check(site(ptr(f), ptr(qf), ptr(y), ptr(aux), ptr(observed), n, float(s_ref), float(mean), code, ptr(w), ptr(rhs), ptr(sums),
+               ptr(work), work.numel(), stream()), name)
     return w, rhs, sums
 
 
@@ -98,7 +80,7 @@ def nb_dispersion_sums(f, y, aux, observed, variance, u, mean, dispersion, h_flo
     the mode (0 when u is None); their sum is the derivative, the mean and the exposure held fixed.  f [n] float32: the mode;
     y [n] the counts and aux [n] the log-exposure (None: zeros), read at observed nodes only; observed [n] bool or None;
     variance [n]: diag(A^-1) and u [n]: A^-1 (variance o h'), taken as float64; mean: the constant of the linear predictor."""
-    r = _dispersion(NB, dispersion)
+    r = check_dispersion(_NB, dispersion)
     n = _sites.check_evidence_args(f, (("y", y),), (("aux", aux),), observed, variance, h_floor, (("u", u),))
     _lib.require_device(f, y, aux, observed, variance, u)
     f, y = _lib.f32c(f.reshape(-1)), _lib.f32c(y.reshape(-1))
@@ -119,12 +101,6 @@ def _pmf_points(points):
     return points
 
 
-def _int(v, name):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise ValueError("%s must be an int, got %r" % (name, v))
-    return v
-
-
 def _count_range(kmin, kmax):
     kmin, kmax = _int(kmin, "kmin"), _int(kmax, "kmax")
     if not 0 <= kmin <= kmax <= MAX_COUNT or kmax - kmin + 1 > PMF_MAX_BLOCK:
@@ -133,12 +109,9 @@ def _count_range(kmin, kmax):
 
 
 def _predict_inputs(eta, var, aux, family, dispersion=None):
-    """(family code, eta, var as contiguous float64 [n], aux as contiguous float32 [n] or None, the dispersion or None), on the
+    """(family record, eta, var as contiguous float64 [n], aux as contiguous float32 [n] or None, the dispersion or None), on the
     device"""
-    fam = _family(family)
-    r = _dispersion(fam, dispersion)
-    if fam == 1 and aux is None:
-        raise ValueError("the binomial family needs the trials in aux")
+    rec, r = _count_family(family, dispersion, aux)
     _lib.require_device(eta, var, aux)
     eta = eta.reshape(-1).to(torch.float64).contiguous()
     var = var.reshape(-1).to(torch.float64).contiguous()
@@ -146,7 +119,7 @@ def _predict_inputs(eta, var, aux, family, dispersion=None):
     for name, t in (("var", var), ("aux", aux)):
         if t is not None and t.shape[0] != eta.shape[0]:
             raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], eta.shape[0]))
-    return fam, eta, var, aux, r
+    return rec, eta, var, aux, r
 
 
 def count_predict_pmf(eta, var, aux, family, kmin, kmax, points=PMF_POINTS, log=False, dispersion=None):
@@ -157,15 +130,11 @@ def count_predict_pmf(eta, var, aux, family, kmin, kmax, points=PMF_POINTS, log=
     or the trials (family "binomial").  At most 65536 counts per call."""
     points = _pmf_points(points)
     kmin, kmax = _count_range(kmin, kmax)
-    fam, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
+    rec, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
     n, K = eta.shape[0], kmax - kmin + 1
     out = torch.empty((n, K), dtype=torch.float64, device=eta.device)
-    if fam == NB:
-        check(lib().mgp_nb_predict_pmf(ptr(eta), ptr(var), ptr(aux), n, r, kmin, K, points, int(bool(log)), ptr(out), stream()),
-              "mgp_nb_predict_pmf")
-        return out
-    check(lib().mgp_count_predict_pmf(ptr(eta), ptr(var), ptr(aux), n, fam, kmin, K, points, int(bool(log)), ptr(out), stream()),
-          "mgp_count_predict_pmf")
+    pmf, name, _, code = families.stage(rec, "predict_pmf", r)
+    check(pmf(ptr(eta), ptr(var), ptr(aux), n, code, kmin, K, points, int(bool(log)), ptr(out), stream()), name)
     return out
 
 
@@ -176,7 +145,7 @@ def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS, disper
     points = _pmf_points(points)
     if at is not None and (not torch.is_tensor(at) or at.dtype != torch.bool):
         raise ValueError("at must be a bool tensor [n]")
-    fam, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
+    rec, eta, var, aux, r = _predict_inputs(eta, var, aux, family, dispersion)
     _lib.require_device(y, at)
     n = eta.shape[0]
     y = _lib.f32c(y.reshape(-1))
@@ -185,29 +154,9 @@ def count_predict_logpmf(eta, var, aux, y, at, family, points=PMF_POINTS, disper
         if t is not None and t.shape[0] != n:
             raise ValueError("%s has %d entries, eta %d" % (name, t.shape[0], n))
     out = torch.empty(n, dtype=torch.float64, device=eta.device)
-    if fam == NB:
-        check(lib().mgp_nb_predict_logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, r, points, ptr(out), stream()),
-              "mgp_nb_predict_logpmf")
-        return out
-    check(lib().mgp_count_predict_logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, fam, points, ptr(out), stream()),
-          "mgp_count_predict_logpmf")
+    logpmf, name, _, code = families.stage(rec, "predict_logpmf", r)
+    check(logpmf(ptr(eta), ptr(var), ptr(aux), ptr(y), ptr(at), n, code, points, ptr(out), stream()), name)
     return out
-
-
-def _node_vector(t, n, name):
-    if not torch.is_tensor(t) or t.numel() != n or t.dtype == torch.bool:
-        raise ValueError("%s must be a tensor of %d values, got %s" % (name, n, tuple(t.shape) if torch.is_tensor(t) else type(t)))
-    return t.reshape(-1).to(torch.float64)
-
-
-def _real(v, name):
-    """float(v) of a real scalar: a Python or numpy number, or a tensor of one element"""
-    if isinstance(v, (bool, str)) or (torch.is_tensor(v) and (v.numel() != 1 or v.dtype == torch.bool)):
-        raise ValueError("%s must be a real scalar, got %r" % (name, v))
-    try:
-        return float(v)
-    except (TypeError, ValueError):
-        raise ValueError("%s must be a real scalar (a number or a tensor of one element), got %s" % (name, type(v).__name__))
 
 
 def _ceil_log2(m):
@@ -218,41 +167,13 @@ def _ceil_log2(m):
 def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, dispersion=None):
     """The host-side argument checks of laplace_fit_counts / laplace_fit_negative_binomial, before any device call.  Returns
     (y, observed, extra, mean, s_ref) with y and extra (exposure or trials; None: ones) float64 [n] on the device they came on.
-    dispersion: the negative binomial's, already checked (_dispersion); it enters s_ref."""
+    dispersion: the negative binomial's, already checked (families.check_dispersion); it enters s_ref."""
     sampling._check_desc(desc)
-    fam = _family(family)
+    rec = families._family(family, "count")
     n = desc.n
-    y = _node_vector(y, n, "y")
-    if observed is not None:
-        if not torch.is_tensor(observed) or observed.dtype != torch.bool:
-            raise ValueError("observed must be a bool tensor [n]")
-        if observed.dim() != 1 or observed.shape[0] != n:
-            raise ValueError("observed has shape %s, the graph %d nodes" % (tuple(observed.shape), n))
-        if not bool(observed.any()):
-            raise ValueError("observed selects no node")
-        observed = observed.to(y.device)
-    pick = (lambda t: t) if observed is None else (lambda t: t[observed.to(t.device)])
+    y, observed, extra = families.check_counts(rec, n, y, observed, exposure, trials)
+    pick = _sites.picker(observed)
     seen = pick(y)
-    if not bool(((seen >= 0) & (seen <= MAX_COUNT) & (seen == seen.round())).all()):
-        raise ValueError("counts at the observed nodes must all be integers in [0, 2^24]")
-    if fam != 1:
-        if trials is not None:
-            raise ValueError("trials belong to the binomial family; the Poisson %s exposure"
-                             % ("family takes" if fam == 0 else "and negative_binomial families take"))
-        extra = None if exposure is None else _node_vector(exposure, n, "exposure")
-        if extra is not None and not bool((torch.isfinite(pick(extra)) & (pick(extra) > 0)).all()):
-            raise ValueError("exposure at the observed nodes must be finite and positive")
-    else:
-        if exposure is not None:
-            raise ValueError("exposure belongs to the Poisson family; the binomial family takes trials")
-        if trials is None:
-            raise ValueError("the binomial family needs trials")
-        extra = _node_vector(trials, n, "trials")
-        N = pick(extra)
-        if not bool(((N >= 1) & (N <= MAX_COUNT) & (N == N.round())).all()):
-            raise ValueError("trials at the observed nodes must all be integers in [1, 2^24]")
-        if not bool((N >= seen.to(N.device)).all()):
-            raise ValueError("trials must be at least the counts at the observed nodes")
     if mean is not None:
         mean = _real(mean, "mean")
         if not math.isfinite(mean):
@@ -261,13 +182,13 @@ def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, d
         raise ValueError("step_tol must be positive, got %r" % (step_tol,))
     if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != n):
         raise ValueError("f0 must be a tensor of %d latent values" % n)
-    if fam != 1:
+    if rec.aux != "trials":
         total = float(seen.sum())
         if mean is None:
             if total == 0.0:
                 raise ValueError("every observed count is 0: the intercept-only estimate of the mean is -inf; pass mean=")
             mean = math.log(total / (float(seen.numel()) if extra is None else float(pick(extra).sum())))
-        if fam == 0:
+        if rec.extra is None:
             s_ref = 2.0 ** -_ceil_log2(max(1.0, float(seen.max())))
         else:                                             # h <= (y + r) / 4: w <= 1 as for the binomial
             s_ref = 4.0 * 2.0 ** -_ceil_log2(math.ceil(float(seen.max()) + dispersion))
@@ -275,23 +196,6 @@ def _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, d
         mean = 0.0 if mean is None else mean
         s_ref = 4.0 * 2.0 ** -_ceil_log2(float(pick(extra).max()))
     return y, observed, extra, float(mean), s_ref
-
-
-def _site64(family, eta, y, extra, dispersion=None):
-    """(g, h) in float64 with the formulas of mgp_count_site / mgp_nb_site; eta already holds the mean (and the log-exposure)."""
-    if family == "poisson":
-        mu = torch.exp(eta.clamp_max(ETA_MAX))
-        return y - mu, mu
-    if family == "negative_binomial":                     # y + r trials, r failures at z = eta - log r
-        eta, extra = eta - math.log(dispersion), y + dispersion
-        fail = dispersion
-    else:
-        fail = extra - y
-    e = torch.exp(-eta.abs())
-    d = 1.0 + e
-    pi = torch.where(eta >= 0, 1.0 / d, e / d)
-    pib = torch.where(eta >= 0, e / d, 1.0 / d)
-    return y * pib - fail * pi, extra * e / (d * d)
 
 
 class CountLaplaceFit(LaplaceFit):
@@ -317,24 +221,17 @@ class CountLaplaceFit(LaplaceFit):
         """f_hat + prior_mean: the linear predictor at the mode without the exposure, float64 [n]."""
         return self.mean.double() + self.prior_mean
 
-    def _pseudo(self):
-        """(pseudo-targets f_hat + g / h, pseudo-noise 1 / h, obs_eff) in float64 from the mode, with the family's g and h;
-        entries outside obs_eff are 0 and 1."""
-        f = self.mean.double()
-        obs = torch.ones_like(f, dtype=torch.bool) if self.observed is None else self.observed
+    def _gh(self, f, obs):
         y = torch.where(obs, self.y.double(), torch.zeros_like(f))
-        if self.family != "binomial":                     # (_aux is finite at every node: laplace_fit_counts)
-            g, h = _site64(self.family, self.eta() if self._aux is None else self.eta() + self._aux.double(), y, None,
-                           self.dispersion)
-        else:
-            g, h = _site64(self.family, self.eta(), y, self._aux.double())
-        eff = obs & (h >= H_FLOOR)
-        if not bool(eff.any()):
-            raise RuntimeError("no observed node has a curvature above %g: the latent values have run away" % H_FLOOR)
-        one, zero = torch.ones((), dtype=f.dtype, device=f.device), torch.zeros((), dtype=f.dtype, device=f.device)
-        noise = torch.where(eff, 1.0 / h.clamp_min(H_FLOOR), one)
-        targets = torch.where(eff, f + g * noise, zero)
-        return targets, noise, eff
+        rec = families.TABLE[self.family]
+        if rec.aux == "trials":
+            return rec.gh(self.eta(), y, self._aux.double(), None)
+        # (_aux is finite at every node: laplace_fit_counts)
+        return rec.gh(self.eta() if self._aux is None else self.eta() + self._aux.double(), y, None, self.dispersion)
+
+    def _weights(self):
+        return count_site(self.mean, None, self.y, self._aux, self.observed, self.s_ref, self.prior_mean, self.family,
+                          self.dispersion)[0]
 
     def map_proba(self):
         raise NotImplementedError("a count fit has no class probability: see map_mean and predict_mean")
@@ -351,21 +248,15 @@ class CountLaplaceFit(LaplaceFit):
 
     def predict_mean(self, S=64, seed=None, points=129):
         """(mean, var, latent_var): the mean and the variance of a new count at every node under the Laplace posterior, and the
-        latent marginal variance v they used (latent_variance(S, seed)[0]); float64 [n] each.
-        Poisson, in closed form (the rate is log-normal): m = E exp(eta_hat + v / 2), var = m + m^2 (e^v - 1).
-        Negative binomial, in closed form as well: the same m, var = m + m^2 (e^v - 1) + m^2 e^v / r (E[mu^2] / r on top).
-        Binomial: p = int sigma(eta) N(eta; eta_hat, v) d eta by the trapezoid rule of bernoulli_predict (eta_hat as float32, the
-        kernel's input format), mean = N p, var = N p (1 - p): the variance of a draw with the success probability p."""
+        latent marginal variance v they used (latent_variance(S, seed)[0]); float64 [n] each.  The formulas are
+        families.count_moments': closed forms for the Poisson and the negative binomial, a quadrature for the binomial."""
         points = _points(points)
         v = self.latent_variance(S, seed)[0]
-        if self.family == "poisson":
-            m = self.exposure * torch.exp(self.eta() + 0.5 * v)
-            return m, m + m * m * torch.expm1(v), v
-        if self.family == "negative_binomial":
-            m = self.exposure * torch.exp(self.eta() + 0.5 * v)
-            return m, m + m * m * torch.expm1(v) + m * m * torch.exp(v) / self.dispersion, v
-        p = bernoulli_predict(self.eta().float(), v, points)
-        return self.trials * p, self.trials * p * (1.0 - p), v
+        return self._moments(v, points) + (v,)
+
+    def _moments(self, v, points=129):
+        extra = self.exposure if self.trials is None else self.trials
+        return families.count_moments(families.TABLE[self.family], self.eta(), v, extra, self.dispersion, points)
 
     # -------------------------------------------------------------------------- the predictive distribution of a new count
     def _variance(self, variance, S, seed):
@@ -425,18 +316,7 @@ class CountLaplaceFit(LaplaceFit):
         (clamped at 0).  threshold: an int or an integer tensor [n], 0 .. 65535 (one block of predict_pmf)."""
         points = _pmf_points(points)
         n = self.mean.shape[0]
-        if torch.is_tensor(threshold):
-            if (threshold.dtype == torch.bool or threshold.is_floating_point() or threshold.is_complex()
-                    or threshold.numel() != n):
-                raise ValueError("threshold must be an int or an integer tensor of %d values" % n)
-            thr = threshold.reshape(-1).to(torch.int64)
-            top, low = int(thr.max()), int(thr.min())
-        else:
-            top = low = _int(threshold, "threshold")
-            thr = None
-        if low < 0 or top >= PMF_MAX_BLOCK:
-            raise ValueError("threshold must lie in 0 .. %d, got %d .. %d" % (PMF_MAX_BLOCK - 1, low, top))
-        _lib.require_device(thr)
+        thr, top = _sites.threshold(threshold, n, "threshold", PMF_MAX_BLOCK - 1)
         pmf, _ = self.predict_pmf(top, S, seed, points, variance=variance)
         if thr is not None:
             keep = torch.arange(top + 1, device=pmf.device)[None, :] <= thr.to(pmf.device)[:, None]
@@ -458,10 +338,7 @@ class CountLaplaceFit(LaplaceFit):
         v = self._variance(variance, S, seed)
         if kmax is None:
             if self.family != "binomial":
-                m = self.exposure * torch.exp(self.eta() + 0.5 * v)
-                var = m + m * m * torch.expm1(v)
-                if self.family == "negative_binomial":
-                    var = var + m * m * torch.exp(v) / self.dispersion
+                m, var = self._moments(v)
                 top = float((m + 8.0 * var.sqrt()).max())
             else:
                 top = float(self.trials.max())
@@ -488,7 +365,7 @@ def laplace_fit_counts(desc, y, observed=None, family="poisson", exposure=None, 
     Exposure / trials at unobserved nodes are used by predict_mean where they are valid and count as 1 elsewhere.
     desc: a form-0 precision descriptor as the samplers take.  Stops after an accepted full Newton step with
     max |delta| <= step_tol; every step is a form-3 CG solve to the relative residual cg_tol.  f0 [n]: the start (default 0)."""
-    if _family(family) == NB:
+    if families._family(family, "count").extra is not None:
         raise ValueError("the negative_binomial family needs dispersion=: laplace_fit_negative_binomial(desc, y, dispersion, ...) "
                          "or fit_counts(..., family=, dispersion=)")
     return _fit(desc, y, observed, family, exposure, trials, mean, step_tol, max_newton, cg_tol, max_iter, f0, None)
@@ -506,7 +383,7 @@ def laplace_fit_negative_binomial(desc, y, dispersion, observed=None, exposure=N
 def fit_counts(desc, y, observed=None, family="poisson", dispersion=None, **kw):
     """The count fit of any family: family "negative_binomial" with dispersion= (required there, refused elsewhere) goes to
     laplace_fit_negative_binomial, "poisson" and "binomial" to laplace_fit_counts; kw as those take them."""
-    if _dispersion(_family(family), dispersion) is None:
+    if check_dispersion(families._family(family, "count"), dispersion) is None:
         return laplace_fit_counts(desc, y, observed, family, **kw)
     if kw.get("trials") is not None:
         raise ValueError("trials belong to the binomial family; the Poisson and negative_binomial families take exposure")
@@ -516,8 +393,8 @@ def fit_counts(desc, y, observed=None, family="poisson", dispersion=None, **kw):
 
 def _fit(desc, y, observed, family, exposure, trials, mean, step_tol, max_newton, cg_tol, max_iter, f0, dispersion):
     """laplace_fit_counts and laplace_fit_negative_binomial: the checks, the constant of the likelihood and the Newton loop"""
-    from .solvers import cg_solve
-    r = _dispersion(_family(family), dispersion)
+    rec = families._family(family, "count")
+    r = check_dispersion(rec, dispersion)
     y, observed, extra, mean, s_ref = _validate(desc, y, observed, family, exposure, trials, mean, step_tol, f0, r)
     _lib.require_device(y, f0, extra)
     dev = desc.data.graph.device
@@ -534,63 +411,13 @@ def _fit(desc, y, observed, family, exposure, trials, mean, step_tol, max_newton
         valid = torch.isfinite(extra) & (extra > 0) if family != "binomial" else (extra >= 1) & (extra == extra.round())
         extra = torch.where(seen | valid, extra, one)
         aux = (extra.log() if family != "binomial" else extra).float().contiguous()
-    if family == "poisson":
-        const = -float(torch.lgamma(y[seen] + 1.0).sum())
-    elif family == "negative_binomial":
-        const = float(nb_log_constant(y[seen], r).sum())
-    else:
-        N = extra[seen]
-        const = float((torch.lgamma(N + 1.0) - torch.lgamma(y[seen] + 1.0) - torch.lgamma(N - y[seen] + 1.0)).sum())
+    const = float(rec.constant(y[seen], extra[seen], r).sum())
     y32 = y.float().contiguous()
 
-    def site(f, qf):
-        w, rhs, sums = count_site(f, qf, y32, aux, obs, s_ref, mean, family, r)
-        return w, rhs, sums.tolist()                      # the one host read of an evaluation
-
-    def solve(w, rhs):
-        # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
-        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=s_ref, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
-                                    jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
-        return delta, cg_its
-
-    with torch.no_grad():
-        start = None if f0 is None else _lib.f32c(f0.to(dev).reshape(-1))
-        f, _, sums, converged, its, history = _newton("laplace_fit_counts", site, lambda v: _q2(desc, v), solve,
-                                                      torch.zeros(n, dtype=torch.float32, device=dev), start, 0.0, max_newton,
-                                                      step_tol=float(step_tol))
+    f, sums, converged, its, history = _newton_form3(
+        "laplace_fit_counts", desc, lambda f, qf: count_site(f, qf, y32, aux, obs, s_ref, mean, family, r), s_ref, f0, 0.0,
+        max_newton, cg_tol, max_iter, step_tol=float(step_tol))
     return CountLaplaceFit(desc, y32, obs, f, converged, its, history, sums[0] + const, family, mean, s_ref, aux, extra, r)
-
-
-_STIRLING = (1.0 / 12, -1.0 / 360, 1.0 / 1260, -1.0 / 1680, 1.0 / 1188, -691.0 / 360360)
-
-
-def _stirling_s(x):
-    zi = 1.0 / x
-    z2 = zi * zi
-    s = _STIRLING[5]
-    for c in _STIRLING[4::-1]:
-        s = c + z2 * s
-    return zi * s
-
-
-def nb_log_constant(k, r):
-    """c(k, r) = lgamma(k + r) - lgamma(r) - lgamma(k + 1) of a float64 tensor of counts k and the scalar dispersion r, in the
-    form of the device's nb_const (csrc/count_predict.hip): sum_{j < k} log((r + j) / (j + 1)) for k < 32, Stirling differences
-    beyond it -- no term is larger than the result's scale, where lgamma(k + r) and lgamma(r) are 1.3e7 each at r = 2^20."""
-    k = k.to(torch.float64)
-    r = float(r)
-    small = torch.zeros_like(k)
-    for j in range(31):
-        small = small + torch.where(k > j, torch.full_like(k, math.log((r + j) / (j + 1.0))), torch.zeros_like(k))
-    kk = k.clamp_min(32.0)                                # (the branch not taken stays finite)
-    x = kk + r
-    if r >= 33.0:
-        big_r = (x - 0.5) * torch.log1p(kk / r) + kk * math.log(r) - kk + (_stirling_s(x) - _stirling_s(r)) - torch.lgamma(kk + 1.0)
-    else:
-        big_r = torch.zeros_like(k)
-    y, d = kk + 1.0, r - 1.0
-    big_k = (x - 0.5) * torch.log1p(d / y) + d * torch.log(y) - d + (_stirling_s(x) - _stirling_s(y)) - math.lgamma(r)
-    return torch.where(k < 32.0, small, torch.where(kk + 1.0 <= r, big_r, big_k))
 
 
 class DispersionParameter(torch.nn.Module):
@@ -600,7 +427,7 @@ class DispersionParameter(torch.nn.Module):
 
     def __init__(self, init):
         super().__init__()
-        r = _dispersion(NB, init)
+        r = check_dispersion(_NB, init)
         self.register_buffer("init", torch.tensor(r, dtype=torch.float64))
         self.register_buffer("rho0", torch.tensor(math.log(r), dtype=torch.float64))
         self.raw = torch.nn.Parameter(self.rho0.clone())
@@ -637,11 +464,7 @@ def learn_dispersion(desc, y, dispersion0, observed=None, exposure=None, mean=No
     the step's update).  Warns when r ends on a bound of [2^-10, 2^20]: 2^20 is the Poisson limit, which the data may prefer."""
     import warnings
     from .evidence import laplace_evidence
-    steps = _int(steps, "steps")
-    if steps < 1 or not float(lr) > 0.0:
-        raise ValueError("steps must be >= 1 and lr positive, got %r and %r" % (steps, lr))
-    if variance is not None and not callable(variance):
-        raise ValueError("variance must be None or a callable fit -> tensor [n]")
+    steps = _sites.learning_args(steps, lr, variance)
     fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
     param = DispersionParameter(dispersion0)
     opt = torch.optim.Adam(param.parameters(), lr=float(lr))
@@ -677,7 +500,7 @@ def dispersion_profile(desc, y, dispersions, observed=None, exposure=None, mean=
         if bad in ev_kw:
             raise ValueError("dispersion_profile takes no %s=" % bad)
     try:
-        candidates = [_dispersion(NB, r) for r in dispersions]
+        candidates = [check_dispersion(_NB, r) for r in dispersions]
     except TypeError:
         raise ValueError("dispersions must be a sequence of scalars")
     if not candidates:

@@ -33,23 +33,16 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, _sites, sampling
+from . import _lib, _sites, families, sampling
 from ._lib import check, lib, ptr, stream
-from .classification import H_FLOOR, S_REF
+from .classification import H_FLOOR
 
-FAMILIES = {"poisson": 0, "binomial": 1, "bernoulli": 2}
-NB_FAMILY, NB = "negative_binomial", 3     # the family with an entry point of its own (mgp_nb_evidence_site)
-ORDINAL_FAMILY = "ordinal"                 # the ordered-category fit: intervals of cutpoints, not (y, aux) (mgp_ordinal_evidence_site)
+FAMILIES = families.codes("evidence", own=False)           # the families of mgp_laplace_evidence_site
+NB_FAMILY = families.with_own("nb")        # the family with an entry point of its own (mgp_nb_evidence_site)
+NB = families.TABLE[NB_FAMILY].evidence
+ORDINAL_FAMILY = families.with_own("ordinal")   # the ordered-category fit: intervals of cutpoints, not (y, aux) (mgp_ordinal_evidence_site)
 DENSE_MAX = 512           # method "auto": the m x m Cholesky up to here
 MAX_COLUMNS = sampling.CHUNK
-
-
-def _family(family):
-    if family == NB_FAMILY:
-        return NB
-    if family not in FAMILIES:
-        raise ValueError("family must be one of %s, got %r" % (sorted(list(FAMILIES) + [NB_FAMILY]), family))
-    return FAMILIES[family]
 
 
 def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR, dispersion=None):
@@ -59,24 +52,17 @@ def evidence_site(f, y, aux, observed, variance, mean, family, h_floor=H_FLOOR, 
     log-exposure (family "poisson" and "negative_binomial", the latter with its dispersion, mgp_nb_evidence_site; None: zeros) or
     the trials ("binomial"); family "bernoulli" reads y as labels and takes no aux; observed [n] bool or None (every node); variance [n] (taken as float64) or None; mean: the constant of the linear
     predictor."""
-    fam = _family(family)
-    from .counts import NB as COUNT_NB, _dispersion
-    r = _dispersion(COUNT_NB if fam == NB else -1, dispersion)       # (the codes differ: 2 is Bernoulli here)
-    if fam == 1 and aux is None:
+    rec = families._family(family, "evidence")
+    r = families.check_dispersion(rec, dispersion)
+    if rec.aux == "trials" and aux is None:
         raise ValueError("the binomial family needs the trials in aux")
-    if fam == 2 and aux is not None:
+    if rec.aux is None and aux is not None:
         raise ValueError("the bernoulli family takes no aux")
+    site, name, workspace_bytes, code = families.stage(rec, "evidence_site", r)
     f, (y, aux), observed, variance, n, root_h, corr, sums, work = _sites.evidence_args(
-        f, (("y", y),), (("aux", aux),), observed, variance, h_floor,
-        lib().mgp_nb_evidence_site_workspace_bytes if fam == NB else lib().mgp_laplace_evidence_site_workspace_bytes)
-    if fam == NB:
-        check(lib().mgp_nb_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), r, float(h_floor),
-                                         ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),
-              "mgp_nb_evidence_site")
-        return root_h, corr, sums
-    check(lib().mgp_laplace_evidence_site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), fam,
-                                          float(h_floor), ptr(root_h), ptr(corr), ptr(sums), ptr(work), work.numel(), stream()),
-          "mgp_laplace_evidence_site")
+        f, (("y", y),), (("aux", aux),), observed, variance, h_floor, workspace_bytes)
+    check(site(ptr(f), ptr(y), ptr(aux), ptr(observed), ptr(variance), n, float(mean), code, float(h_floor), ptr(root_h), ptr(corr),
+               ptr(sums), ptr(work), work.numel(), stream()), name)
     return root_h, corr, sums
 
 
@@ -229,26 +215,9 @@ class LaplaceEvidence:
 
 
 def _site_of(fit):
-    """(family, mean, aux, s_ref, dispersion) of a binary, a count or an ordinal fit."""
-    from . import ordinal
-    if isinstance(fit, ordinal.OrdinalLaplaceFit):
-        return ORDINAL_FAMILY, 0.0, None, ordinal.S_REF, None
-    family = getattr(fit, "family", None)
-    if family is None:
-        return "bernoulli", 0.0, None, S_REF, None
-    return family, fit.prior_mean, fit._aux, fit.s_ref, getattr(fit, "dispersion", None)
-
-
-def _weights(fit, family, mean, aux, s_ref, dispersion=None):
-    """obs_w = (float)(s_ref h) of the fit's own form-3 system at the mode, from the kernel its Newton steps used."""
-    if family == ORDINAL_FAMILY:
-        from .ordinal import ordinal_site
-        return ordinal_site(fit.mean, None, fit._lo, fit._hi, fit.observed, s_ref)[0]
-    if family == "bernoulli":
-        from .classification import bernoulli_site
-        return bernoulli_site(fit.mean, None, fit.y, fit.observed, s_ref)[0]
-    from .counts import count_site
-    return count_site(fit.mean, None, fit.y, aux, fit.observed, s_ref, mean, family, dispersion)[0]
+    """(family, mean, aux, s_ref, dispersion) of a binary, a count or an ordinal fit: what the site kernels of its family read
+    beside the observations (a fit without a mean, an aux or a dispersion carries 0 and None, classification.LaplaceFit)."""
+    return fit.family, fit.prior_mean, fit._aux, fit.s_ref, fit.dispersion
 
 
 REFINE_ROUNDS = 4         # refinement rounds of the float64 solves of the gradient (they stop at a true residual of 2 tol)
@@ -274,7 +243,7 @@ def _check_cutpoints(fit, family, cutpoints):
     fit's own cutpoints in float32."""
     if cutpoints is None:
         return False
-    if family != ORDINAL_FAMILY:
+    if families.TABLE[family].extra != "cutpoints":
         raise ValueError("cutpoints belong to an ordinal fit, this is a %s fit" % family)
     K = fit.num_categories
     if not torch.is_tensor(cutpoints) or cutpoints.dtype != torch.float64 or cutpoints.shape != (K - 1,):
@@ -289,7 +258,7 @@ def _check_dispersion(fit, family, dispersion):
     fit's own."""
     if dispersion is None:
         return False
-    if family != NB_FAMILY:
+    if families.TABLE[family].extra != "dispersion":
         raise ValueError("dispersion belongs to a negative_binomial fit, this is a %s fit" % family)
     if not torch.is_tensor(dispersion) or dispersion.dtype != torch.float64 or dispersion.dim() != 0:
         raise ValueError("dispersion must be a 0-dim float64 tensor")
@@ -327,7 +296,7 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
         f = fit.mean
         if (grad or cut_grad or disp_grad) and variance is None:
             variance = fit.latent_variance(var_samples)[0]
-        if family == ORDINAL_FAMILY:
+        if families.TABLE[family].aux == "interval":      # the node's interval of cutpoints in the place of (y, aux)
             from .ordinal import ordinal_cut_sums, ordinal_evidence_site
             root_h, corr, sums = ordinal_evidence_site(f, fit._lo, fit._hi, fit.observed, variance if grad or cut_grad else None)
         else:
@@ -355,7 +324,7 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
             # 2.4e-6 on the 1546-node dumbbell, cond Q = 1e3; the unrefined factorised solve of the Lanczos products 4.8e-6).
             # Y goes through the float32 operator chain and stays float32 (refined as sampling.posterior_variance solves form 3).
             kw = dict(tol=float(solve_tol), stop_mode=1, max_iter=int(max_iter))
-            w = _weights(fit, family, mean, aux, s_ref, r_nb)
+            w = fit._weights()                            # obs_w of the fit's own form-3 system, from its site kernel
             d3 = desc.with_(form=3, noise=s_ref, obs_w=w)
             kw3 = dict(kw, jacobi=sampling.OBSERVED_JACOBI[0])
             if grad:
@@ -399,7 +368,7 @@ def laplace_evidence(fit, operator=None, variance=None, var_samples=64, num_prob
 # as [n, C, b], sample fastest: at once an [n, C b] right-hand-side block of cg_solve and an [n C, b] block of the generic block
 # Lanczos.  The gradient is that of the module docstring with v o h' replaced by g_ic = tr(V_i dH_i / df_ic), V_i the C x C
 # diagonal block of A^-1, which mgp_softmax_curvature accumulates from latent deviations.
-MULTICLASS_FAMILY = "multiclass"
+MULTICLASS_FAMILY = families.with_own("softmax")
 DENSE_MAX_ENTRIES = 4096  # method "auto": the m C x m C Cholesky up to here (128 MiB of float64)
 LAYOUTS = ("cs", "sc")    # [n, C, S] (a block of Lanczos vectors) and [n, S, C] (the coupled block solver's)
 
@@ -654,8 +623,7 @@ def softmax_evidence(fit, operator=None, curvature=None, var_samples=64, block=N
     refined float64 form-0 solve (_solve64), u and Y the float64 sums of _softmax_solve64, all to a true residual of 2 solve_tol;
     Y enters the operator rounded to float32.  solves: None, or dict(Z, u, X, Y, g, g_se) with X, Y [n, C, P]."""
     from .autograd import needs_grad
-    from .classification import MulticlassLaplaceFit
-    if not isinstance(fit, MulticlassLaplaceFit):
+    if getattr(fit, "family", None) != MULTICLASS_FAMILY:
         raise NotImplementedError("softmax_evidence takes a MulticlassLaplaceFit")
     desc, F, pi = fit.desc, fit.mean, _lib.f32c(fit.pi)
     n, C = _pi_block(pi)

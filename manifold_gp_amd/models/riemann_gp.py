@@ -214,64 +214,36 @@ class RiemannGP(torch.nn.Module):
         return fit
 
     def _laplace_fit(self, observed, family, **kw):
-        """The binary fit (family "bernoulli"), the count fit ("poisson", "binomial", "negative_binomial"), the ordered-category
-        fit ("ordinal", with num_categories= and cutpoints= in kw) or the C-class fit ("multiclass", with num_classes= in kw) of
-        train_targets."""
-        if family == "bernoulli":
-            return self.laplace_posterior(observed, **kw)
-        if family == "multiclass":
-            if "num_classes" not in kw:
-                raise ValueError("family 'multiclass' needs num_classes")
-            kw = dict(kw)
-            return self.laplace_posterior_multiclass(kw.pop("num_classes"), observed, **kw)
-        if family == "ordinal":
-            if "num_categories" not in kw:
-                raise ValueError("family 'ordinal' needs num_categories")
-            kw = dict(kw)
-            return self.laplace_posterior_ordinal(kw.pop("num_categories"), kw.pop("cutpoints", None), observed, **kw)
-        return self.laplace_posterior_counts(observed, family=family, **kw)
+        """The node fit of train_targets for a family of families.TABLE, by the fitter its record names; kw carries what the record
+        says the family needs (num_categories, num_classes) and the fitter's other keywords."""
+        from .. import families
+        rec = families.fit_family(family)
+        families.check_needs(rec, kw)
+        desc, _, y = self._sampling_args()
+        return families.fitter(rec)(desc, y, observed=observed, **kw)
 
     def laplace_evidence(self, observed=None, family="bernoulli", **kw):
-        """Fit the nodes (family "bernoulli": laplace_posterior; "poisson" / "binomial" / "negative_binomial": laplace_posterior_counts) and
-        return the Laplace approximation of log p(train_targets[observed]), an evidence.LaplaceEvidence.  kw: the arguments of the
-        fit (dispersion, exposure, trials, mean, f0, tolerances) go to it, the others to evidence.laplace_evidence (num_probes, steps, seed,
-        method, ...).  max_iter is an argument of both and goes to the FIT; fit_kw= and evidence_kw= (dicts, as
-        utils.laplace_train takes them) name the receiver explicitly and win over the split: evidence_kw=dict(max_iter=...)
-        caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries d log Z / d theta.
-        family "ordinal" (laplace_posterior_ordinal) takes num_categories= and cutpoints=; cutpoints may be an
-        ordinal.CutpointParameter or a float64 tensor that requires grad: the fit runs at their detached values and value carries
-        d log Z / d cutpoints as well.  family "negative_binomial" takes dispersion= in the same way: a number, or a
-        counts.DispersionParameter or a float64 tensor that requires grad, for which value carries d log Z / d dispersion too.
-        family "multiclass" (laplace_posterior_multiclass) takes num_classes=; the other arguments go to
-        evidence.softmax_evidence (curvature, var_samples, block, num_probes, ...)."""
-        import inspect
-        from ..classification import laplace_fit, laplace_fit_multiclass
-        from ..counts import _live_dispersion, laplace_fit_counts
-        from ..evidence import MULTICLASS_FAMILY, NB_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
-        from ..ordinal import _live_cutpoints, laplace_fit_ordinal
-        if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
-            _family(family)
+        """Fit the nodes (_laplace_fit: any family of families.TABLE) and return the Laplace approximation of
+        log p(train_targets[observed]), an evidence.LaplaceEvidence.  kw: the arguments of the family's fit (those of the fitter
+        its record names: exposure, trials, mean, f0, tolerances, ...) go to it, the others to the evidence function the record
+        names (num_probes, steps, seed, method, ...).  max_iter is an argument of both and goes to the FIT; fit_kw= and
+        evidence_kw= (dicts, as utils.laplace_train takes them) name the receiver explicitly and win over the split:
+        evidence_kw=dict(max_iter=...) caps the evidence's solves.  Where a kernel hyper-parameter requires grad, value carries
+        d log Z / d theta.  A family with an extra parameter (the record's `extra`: cutpoints, dispersion) takes it as a number
+        or a tensor, or live: as a module (ordinal.CutpointParameter, counts.DispersionParameter) or a float64 tensor that
+        requires grad; the fit then runs at the detached values and value carries the derivative in the parameter as well."""
+        from .. import families
+        rec = families.fit_family(family)
         kw = dict(kw)
         fit_kw, evidence_kw = dict(kw.pop("fit_kw", None) or {}), dict(kw.pop("evidence_kw", None) or {})
-        fitter = {"bernoulli": laplace_fit, ORDINAL_FAMILY: laplace_fit_ordinal,
-                  MULTICLASS_FAMILY: laplace_fit_multiclass}.get(family, laplace_fit_counts)
-        names = set(inspect.signature(fitter).parameters)
-        if fitter is laplace_fit_counts:
-            names.add("dispersion")                       # (counts.fit_counts: the negative binomial's, refused elsewhere)
+        names = families.fit_keywords(rec)
         fit_kw = dict({k: v for k, v in kw.items() if k in names}, **fit_kw)
         evidence_kw = dict({k: v for k, v in kw.items() if k not in names}, **evidence_kw)
-        if family == ORDINAL_FAMILY:
-            fit_kw, live = _live_cutpoints(fit_kw)
-            if live is not None:
-                evidence_kw.setdefault("cutpoints", live)
-        if family == NB_FAMILY:
-            fit_kw, live = _live_dispersion(fit_kw)
-            if live is not None:
-                evidence_kw.setdefault("dispersion", live)
+        fit_kw, live = families.split_live(rec, fit_kw)
+        for name, value in live.items():
+            evidence_kw.setdefault(name, value)
         fit = self._laplace_fit(observed, family, **fit_kw)
-        if family == MULTICLASS_FAMILY:
-            return softmax_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
-        return laplace_evidence(fit, operator=self.precision(noise=False), **evidence_kw)
+        return families.evidence_of(rec)(fit, operator=self.precision(noise=False), **evidence_kw)
 
     # ------------------------------------------------------------------ riemann_gp.py:41-43
     def modulation(self, x):

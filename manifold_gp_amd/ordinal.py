@@ -19,7 +19,7 @@ The cutpoints are fixed during the fit: the caller's, or the logits of the smoot
 labels (ordinal_cutpoints).  They are rounded to float32, the format the kernel reads them in, and the fit keeps those values.
 
 The Laplace posterior N(f_hat, (Q2 + H)^-1) is the form-3 GMRF posterior with pseudo-noise 1 / h and pseudo-targets
-f_hat + g / h: OrdinalLaplaceFit restates _pseudo() and inherits latent_variance / latent_samples.  The predictive probabilities
+f_hat + g / h: OrdinalLaplaceFit supplies (g, h) (families.TABLE) and inherits _pseudo, latent_variance / latent_samples.  The predictive probabilities
 of the K categories come from one quadrature per (node, category) in float64 (mgp_ordinal_predict).
 
 The Laplace evidence of the fit is evidence.laplace_evidence (OrdinalLaplaceFit.laplace_evidence) with the per-node stage
@@ -31,8 +31,10 @@ import torch
 
 from . import _lib, _sites, sampling
 from ._lib import check, lib, ptr, stream
-from .classification import H_FLOOR, LaplaceFit, _newton, _points, _q2
-from .counts import CountLaplaceFit, _int
+from .classification import H_FLOOR, LaplaceFit, _newton_form3, _points
+from .counts import CountLaplaceFit
+from ._sites import check_mask
+from .families import TABLE, _sig, _widths
 
 MAX_CATEGORIES = 64
 S_REF = 2.0              # obs_w = S_REF h <= 1
@@ -43,18 +45,6 @@ def _categories(num_categories):
     if isinstance(num_categories, bool) or not isinstance(num_categories, int) or not 2 <= num_categories <= MAX_CATEGORIES:
         raise ValueError("num_categories must be an int in 2 .. %d, got %r" % (MAX_CATEGORIES, num_categories))
     return num_categories
-
-
-def _mask(observed, n, name="observed"):
-    if observed is None:
-        return None
-    if not torch.is_tensor(observed) or observed.dtype != torch.bool:
-        raise ValueError("%s must be a bool tensor [n]" % name)
-    if observed.dim() != 1 or observed.shape[0] != n:
-        raise ValueError("%s has shape %s, the graph %d nodes" % (name, tuple(observed.shape), n))
-    if not bool(observed.any()):
-        raise ValueError("%s selects no node" % name)
-    return observed
 
 
 def _labels(y, n, K, mask, what):
@@ -91,20 +81,6 @@ def _cutpoints(cutpoints, K=None, min_gap=0.0):
     return b
 
 
-def _sig(x):
-    """(sigma(x), sigma(-x), sigma(x) sigma(-x)) in the dtype of x from one e = exp(-|x|), x = +-inf included"""
-    e = torch.exp(-x.abs())
-    d = 1.0 + e
-    up = x >= 0
-    return torch.where(up, 1.0 / d, e / d), torch.where(up, e / d, 1.0 / d), e / (d * d)
-
-
-def _widths(b):
-    """c_k = 1 - exp(-(b_{k+1} - b_k)) for the K categories of the cutpoints b [K - 1] (float64), 1 at the two ends"""
-    one = torch.ones(1, dtype=b.dtype, device=b.device)
-    return torch.cat([one, -torch.expm1(-(b[1:] - b[:-1])), one])
-
-
 def ordinal_cutpoints(y, num_categories, observed=None):
     """Cutpoints from the labels: float64 [K - 1] on the host, b_k = logit(sum_{j < k} (n_j + 1/2) / (N + K / 2)), the logits of the
     cumulative frequencies of the N observed labels with half a count added to every category -- strictly increasing with
@@ -114,7 +90,7 @@ def ordinal_cutpoints(y, num_categories, observed=None):
     if not torch.is_tensor(y) or y.dim() != 1:
         raise ValueError("y must be a tensor [n] of categories")
     n = y.shape[0]
-    observed = _mask(observed, n)
+    observed = check_mask(observed, n)
     labels = _labels(y, n, K, observed, "observed").cpu()
     if observed is not None:
         labels = labels[observed.cpu()]
@@ -224,11 +200,7 @@ def learn_cutpoints(desc, y, num_categories, observed=None, cutpoints0=None, ste
     OrdinalLaplaceFit at them; history: one (log Z, se) per step, taken before the step's update)."""
     from .evidence import laplace_evidence
     K = _categories(num_categories)
-    steps = _int(steps, "steps")
-    if steps < 1 or not float(lr) > 0.0:
-        raise ValueError("steps must be >= 1 and lr positive, got %r and %r" % (steps, lr))
-    if variance is not None and not callable(variance):
-        raise ValueError("variance must be None or a callable fit -> tensor [n]")
+    steps = _sites.learning_args(steps, lr, variance)
     fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
     if cutpoints0 is None:
         labels, mask, _ = _validate(desc, y, K, None, observed, None)
@@ -271,14 +243,21 @@ def ordinal_predict(eta, var, cutpoints, points=129, log=False):
 
 
 def _validate(desc, y, num_categories, cutpoints, observed, f0):
-    """The host-side argument checks of laplace_fit_ordinal, before any device call.  Returns (labels int64 [n] on y's device
-    with 0 at unobserved nodes, observed, cutpoints float64 [K - 1] on the host as float32 holds them)."""
+    """The host-side argument checks of laplace_fit_ordinal, before any device call: the descriptor's, check_data and the start's"""
     sampling._check_desc(desc)
+    checked = check_data(desc.n, y, num_categories, cutpoints, observed)
+    if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != desc.n):
+        raise ValueError("f0 must be a tensor of %d latent values" % desc.n)
+    return checked
+
+
+def check_data(n, y, num_categories, cutpoints, observed):
+    """The categories and the cutpoints of n nodes (or rows of features).  Returns (labels int64 [n] on y's device with 0 at
+    unobserved nodes, observed, cutpoints float64 [K - 1] on the host as float32 holds them)."""
     K = _categories(num_categories)
-    n = desc.n
     if torch.is_tensor(y) and y.numel() == n:
         y = y.reshape(-1)
-    observed = _mask(observed, n)
+    observed = check_mask(observed, n)
     labels = _labels(y, n, K, observed, "observed")
     if cutpoints is None:
         cutpoints = ordinal_cutpoints(labels, K, None if observed is None else observed.to(labels.device))
@@ -286,8 +265,6 @@ def _validate(desc, y, num_categories, cutpoints, observed, f0):
     b32 = b.float().double()
     if not bool(torch.isfinite(b32).all()) or not bool((b32[1:] > b32[:-1]).all()):
         raise ValueError("cutpoints must stay finite and strictly increasing when rounded to float32")
-    if f0 is not None and (not torch.is_tensor(f0) or f0.numel() != n):
-        raise ValueError("f0 must be a tensor of %d latent values" % n)
     return labels, observed, b32
 
 
@@ -297,27 +274,18 @@ class OrdinalLaplaceFit(LaplaceFit):
     Newton step, psi without the likelihood's f-independent factor; log_likelihood: sum_obs log P(y_i | f_hat_i) with it;
     y [n] int64: the labels, 0 at unobserved nodes; cutpoints [K - 1] float64 on the device, the values the fit used (the
     caller's rounded to float32); num_categories."""
+    family, s_ref = "ordinal", S_REF
 
     def __init__(self, desc, y, observed, mean, converged, iterations, history, log_likelihood, cutpoints, lo, hi):
         super().__init__(desc, y, observed, mean, converged, iterations, history, log_likelihood)
         self.cutpoints, self.num_categories = cutpoints, int(cutpoints.shape[0]) + 1
         self._lo, self._hi = lo, hi           # what the kernel read: float32 [n], the interval of category 0 at unobserved nodes
 
-    def _pseudo(self):
-        """(pseudo-targets f_hat + g / h, pseudo-noise 1 / h, obs_eff) in float64 from the mode, with the ordinal g and h;
-        entries outside obs_eff are 0 and 1."""
-        f = self.mean.double()
-        obs = torch.ones_like(f, dtype=torch.bool) if self.observed is None else self.observed
-        _, sig_mu, hu = _sig(self._hi.double() - f)
-        sig_l, _, hl = _sig(self._lo.double() - f)
-        g, h = sig_l - sig_mu, hu + hl
-        eff = obs & (h >= H_FLOOR)
-        if not bool(eff.any()):
-            raise RuntimeError("no observed node has a curvature above %g: the latent values have run away" % H_FLOOR)
-        one, zero = torch.ones((), dtype=f.dtype, device=f.device), torch.zeros((), dtype=f.dtype, device=f.device)
-        noise = torch.where(eff, 1.0 / h.clamp_min(H_FLOOR), one)
-        targets = torch.where(eff, f + g * noise, zero)
-        return targets, noise, eff
+    def _gh(self, f, obs):
+        return TABLE[self.family].gh(f, self._lo.double(), self._hi.double(), None)
+
+    def _weights(self):
+        return ordinal_site(self.mean, None, self._lo, self._hi, self.observed, self.s_ref)[0]
 
     def evidence(self, **kw):
         raise NotImplementedError("the evidence of the ordinal fit is OrdinalLaplaceFit.laplace_evidence(...) or "
@@ -354,7 +322,7 @@ class OrdinalLaplaceFit(LaplaceFit):
         elsewhere (NaN allowed)."""
         points = _points(points)
         n = self.mean.shape[0]
-        at = _mask(at, n, "at")
+        at = check_mask(at, n, "at")
         labels = _labels(y, n, self.num_categories, at, "asked")
         _lib.require_device(y, at)
         logp = self.predict_proba(S, seed, points, variance, log=True)[0]
@@ -368,17 +336,7 @@ class OrdinalLaplaceFit(LaplaceFit):
         positive: no 1 - cdf).  k: an int or an integer tensor [n], 0 .. K - 1."""
         points = _points(points)
         n, K = self.mean.shape[0], self.num_categories
-        if torch.is_tensor(k):
-            if k.dtype == torch.bool or k.is_floating_point() or k.is_complex() or k.numel() != n:
-                raise ValueError("k must be an int or an integer tensor of %d values" % n)
-            thr = k.reshape(-1).to(torch.int64)
-            low, top = int(thr.min()), int(thr.max())
-        else:
-            low = top = _int(k, "k")
-            thr = None
-        if low < 0 or top > K - 1:
-            raise ValueError("k must lie in 0 .. %d, got %d .. %d" % (K - 1, low, top))
-        _lib.require_device(thr)
+        thr, top = _sites.threshold(k, n, "k", K - 1)
         p = self.predict_proba(S, seed, points, variance)[0]
         ks = torch.arange(K, device=p.device)[None, :]
         above = ks > (top if thr is None else thr.to(p.device)[:, None])
@@ -406,33 +364,17 @@ def laplace_fit_ordinal(desc, y, num_categories, cutpoints=None, observed=None, 
     desc: a form-0 precision descriptor as the samplers take.  Stops when max |g - Q2 f| <= rtol times its value at f = 0
     (|g| <= 1, as for 0/1 labels); every step is a form-3 CG solve to the relative residual cg_tol.  f0 [n]: the start
     (default 0)."""
-    from .solvers import cg_solve
     labels, observed, b = _validate(desc, y, num_categories, cutpoints, observed, f0)
     _lib.require_device(labels, f0)
     dev = desc.data.graph.device
-    n = desc.n
     labels = labels.to(dev)
     obs = None if observed is None else observed.to(dev).contiguous()
     b = b.to(dev)
     inf = torch.full((1,), float("inf"), dtype=torch.float64, device=dev)
     lo = torch.cat([-inf, b])[labels].float().contiguous()
     hi = torch.cat([b, inf])[labels].float().contiguous()
-    widths = torch.log(_widths(b))[labels]
+    widths = TABLE["ordinal"].constant(labels, None, b)
     const = float((widths if obs is None else widths[obs]).sum())
-
-    def site(f, qf):
-        w, rhs, sums = ordinal_site(f, qf, lo, hi, obs, S_REF)
-        return w, rhs, sums.tolist()                      # the one host read of an evaluation
-
-    def solve(w, rhs):
-        # a fresh w every evaluation: the CG plan is rebound by the tensor's address (solvers._cached_plan)
-        delta, cg_its, _ = cg_solve(desc.with_(form=3, noise=S_REF, obs_w=w), rhs, tol=cg_tol, stop_mode=1,
-                                    jacobi=sampling.OBSERVED_JACOBI[0], max_iter=max_iter)
-        return delta, cg_its
-
-    with torch.no_grad():
-        zero = torch.zeros(n, dtype=torch.float32, device=dev)
-        start = None if f0 is None else _lib.f32c(f0.to(dev).reshape(-1))
-        f, _, sums, converged, its, history = _newton("laplace_fit_ordinal", site, lambda v: _q2(desc, v), solve, zero, start,
-                                                      rtol, max_newton)
+    f, sums, converged, its, history = _newton_form3("laplace_fit_ordinal", desc, lambda f, qf: ordinal_site(f, qf, lo, hi, obs, S_REF),
+                                                     S_REF, f0, rtol, max_newton, cg_tol, max_iter)
     return OrdinalLaplaceFit(desc, labels, obs, f, converged, its, history, sums[0] + const, b, lo, hi)

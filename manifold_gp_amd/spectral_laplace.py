@@ -23,37 +23,19 @@ import warnings
 
 import torch
 
-from . import _lib
+from . import _lib, families
 from ._lib import check, lib, ptr, stream
 from .classification import MAX_HALVINGS, _points, bernoulli_predict
-from .classification import _validate as _validate_labels
-from .counts import PMF_POINTS, _dispersion, _node_vector, _real, count_predict_logpmf, count_predict_pmf, nb_log_constant
-from .counts import FAMILIES as _COUNT_FAMILIES
-from .counts import _validate as _validate_counts
-from .ordinal import _validate as _validate_ordinal
-from .ordinal import _labels, _widths, ordinal_predict
+from .counts import PMF_POINTS, count_predict_logpmf, count_predict_pmf
+from ._sites import _node_vector, _real
+from .ordinal import _labels, check_data as _check_categories, ordinal_predict
 
-FAMILIES = {"bernoulli": 0, "poisson": 1, "binomial": 2, "negative_binomial": 3, "ordinal": 4}
-COUNT_FAMILIES = ("poisson", "binomial", "negative_binomial")
+FAMILIES = families.codes("spectral")
+COUNT_FAMILIES = tuple(sorted(families.codes("count"), key=families.codes("count").get))
 MAX_MODES = 512              # the cap of mgp_spectral_site (and of mgp_gram_f64)
 # A trial point is taken when psi does not decrease beyond the rounding of its two terms: both are float64 sums of at most
 # n + m terms, SLACK of their size covers 2^13 ulps
 SLACK = 2.0 ** -40
-
-
-class _Rows:
-    """What the node fits' argument checks read of a precision descriptor, for n rows of features: they then check labels, counts,
-    trials, exposure and cutpoints with their own rules and messages."""
-    form, noise, nu, pre, post, data = 0, 0.0, 1, None, None, None
-
-    def __init__(self, n):
-        self.n = n
-
-
-def _family(family):
-    if family not in FAMILIES:
-        raise ValueError("family must be one of %s, got %r" % (sorted(FAMILIES), family))
-    return FAMILIES[family]
 
 
 def _features(Z, name="Z"):
@@ -84,11 +66,12 @@ def spectral_site(Z, w, family, a, b=None, observed=None, mean=0.0, dispersion=N
     allowed elsewhere): labels (bernoulli), counts and log-exposure or None (poisson, negative_binomial with dispersion=),
     counts and trials (binomial), the ends (lo, hi] of the row's interval of cutpoints (ordinal); observed [n] bool or None
     (every row); mean: the constant added to f inside the likelihood."""
-    fam = _family(family)
+    rec = families._family(family, "spectral")
     n, m = _features(Z)
-    r = _dispersion(_COUNT_FAMILIES["negative_binomial"] if fam == 3 else -1, dispersion)
-    if fam in (2, 4) and b is None:
-        raise ValueError("the binomial family needs the trials in b" if fam == 2 else "the ordinal family needs the upper cutpoints in b")
+    r = families.check_dispersion(rec, dispersion)
+    if rec.aux in ("trials", "interval") and b is None:
+        raise ValueError("the binomial family needs the trials in b" if rec.aux == "trials"
+                         else "the ordinal family needs the upper cutpoints in b")
     mean = _mean(mean)
     if not torch.is_tensor(w) or w.numel() != m or not w.is_floating_point():
         raise ValueError("w must be a float tensor of %d weights" % m)
@@ -112,7 +95,7 @@ def spectral_site(Z, w, family, a, b=None, observed=None, mean=0.0, dispersion=N
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     nbytes = lib().mgp_spectral_site_workspace_bytes(n, m, int(bool(hessian)))
     work = _lib.workspace(nbytes, "spectral_site", dev)
-    check(lib().mgp_spectral_site(ptr(Z), n, m, ptr(w), fam, ptr(a), ptr(b), ptr(observed), mean, 0.0 if r is None else r, ptr(f),
+    check(lib().mgp_spectral_site(ptr(Z), n, m, ptr(w), rec.spectral, ptr(a), ptr(b), ptr(observed), mean, 0.0 if r is None else r, ptr(f),
                                   ptr(grad), ptr(hess), ptr(sums), ptr(work), work.numel(), stream()), "mgp_spectral_site")
     return f, grad, hess, sums
 
@@ -185,25 +168,11 @@ class SpectralLaplaceFit:
     # ------------------------------------------------------------------------------------------------ counts
     def _aux(self, T, exposure, trials, dev):
         """(log-exposure float64 [T] or None, trials float32 [T] or None) of T test rows; ones where none is given"""
+        extra = families.check_aux(families.TABLE[self.family], T, exposure, trials)
+        _lib.require_device(exposure, trials)
         if self.family == "binomial":
-            if exposure is not None:
-                raise ValueError("exposure belongs to the Poisson family; the binomial family takes trials")
-            if trials is None:
-                return None, torch.ones(T, dtype=torch.float32, device=dev)
-            N = _node_vector(trials, T, "trials")
-            if not bool(((N >= 1) & (N <= 2 ** 24) & (N == N.round())).all()):
-                raise ValueError("trials must all be integers in [1, 2^24]")
-            _lib.require_device(trials)
-            return None, N.to(dev).float()
-        if trials is not None:
-            raise ValueError("trials belong to the binomial family; the Poisson and negative_binomial families take exposure")
-        if exposure is None:
-            return None, None
-        E = _node_vector(exposure, T, "exposure")
-        if not bool((torch.isfinite(E) & (E > 0)).all()):
-            raise ValueError("exposure must be finite and positive")
-        _lib.require_device(exposure)
-        return E.to(dev).log(), None
+            return None, torch.ones(T, dtype=torch.float32, device=dev) if extra is None else extra.to(dev).float()
+        return None if extra is None else extra.to(dev).log(), None
 
     def _count_args(self, Zs, exposure, trials):
         eta, var = self.latent(Zs)
@@ -216,16 +185,9 @@ class SpectralLaplaceFit:
         quadrature of bernoulli_predict for the binomial.  exposure / trials [T]: the test rows' own (None: ones)."""
         self._only(COUNT_FAMILIES, "expected count: see predict_proba")
         points = _points(points)
-        eta, v, N = self._count_args(Zs, exposure, trials)
-        if self.family == "binomial":
-            p = bernoulli_predict(eta, v, points)
-            N = N.double()
-            return N * p, N * p * (1.0 - p)
-        mu = torch.exp(eta + 0.5 * v)
-        var = mu + mu * mu * torch.expm1(v)
-        if self.family == "negative_binomial":
-            var = var + mu * mu * torch.exp(v) / self.dispersion
-        return mu, var
+        eta, v, N = self._count_args(Zs, exposure, trials)             # (the exposure is in eta)
+        return families.count_moments(families.TABLE[self.family], eta, v, None if N is None else N.double(), self.dispersion,
+                                      points)
 
     def predict_pmf(self, Zs, kmax, kmin=0, exposure=None, trials=None, points=PMF_POINTS, log=False):
         """P(y_new = k) for k = kmin .. kmax at the test rows, [T, kmax - kmin + 1] float64 (its log with log=True):
@@ -293,42 +255,35 @@ def spectral_laplace_fit(Z, y, observed=None, family="bernoulli", outputscale=1.
     logits of ordinal.ordinal_cutpoints), each checked with the rules and messages of its node fit; outputscale: s of
     K = s Z Z^T; mean: the constant prior mean of the latent function.  Stops when max |grad| <= rtol times its value at w = 0;
     one host read per evaluation; a step is halved at most MAX_HALVINGS times.  w0 [m]: the start (default 0)."""
-    fam = _family(family)
+    rec = families._family(family, "spectral")
     n, m, s, mean = _check_fit_args(Z, outputscale, mean, rtol, max_newton, w0)
-    rows = _Rows(n)
     r = cuts = None
-    if family != "ordinal" and (num_categories is not None or cutpoints is not None):
+    if rec.data != "categories" and (num_categories is not None or cutpoints is not None):
         raise ValueError("num_categories and cutpoints belong to the ordinal family")
-    if family not in COUNT_FAMILIES and (exposure is not None or trials is not None or dispersion is not None):
+    if rec.data != "counts" and (exposure is not None or trials is not None or dispersion is not None):
         raise ValueError("exposure, trials and dispersion belong to the count families")
-    if family == "bernoulli":
-        y, observed = _validate_labels(rows, y, observed, "logit", None)
+    if rec.data == "labels":
+        y, observed = families.check_labels(y, observed, n)
         a64, b64, const = torch.nan_to_num(y.reshape(-1).double(), nan=0.0), None, None
-    elif family == "ordinal":
+    elif rec.data == "categories":
         if num_categories is None:
-            raise ValueError("family 'ordinal' needs num_categories")
-        labels, observed, cuts = _validate_ordinal(rows, y, num_categories, cutpoints, observed, None)
+            raise ValueError("family %r needs %s" % (family, rec.needs))
+        labels, observed, cuts = _check_categories(n, y, num_categories, cutpoints, observed)
         inf = torch.full((1,), float("inf"), dtype=torch.float64)
         a64 = torch.cat([-inf, cuts])[labels.cpu()]
         b64 = torch.cat([cuts, inf])[labels.cpu()]
-        const = torch.log(_widths(cuts))[labels.cpu()]
+        const = rec.constant(labels.cpu(), None, cuts)
     else:
-        r = _dispersion(_COUNT_FAMILIES[family], dispersion)
-        y, observed, extra, mean, _ = _validate_counts(rows, y, observed, family, exposure, trials, mean, 1.0, None, r)
+        r = families.check_dispersion(rec, dispersion)
+        y, observed, extra = families.check_counts(rec, n, y, observed, exposure, trials)
         seen = torch.ones(n, dtype=torch.bool, device=y.device) if observed is None else observed
         a64 = torch.where(seen, y, torch.zeros_like(y))
         if extra is None:
             b64 = None
         else:
             extra = torch.where(seen.to(extra.device), extra, torch.ones_like(extra))
-            b64 = extra.log() if family != "binomial" else extra
-        if family == "poisson":
-            const = -torch.lgamma(a64 + 1.0)
-        elif family == "negative_binomial":
-            const = nb_log_constant(a64, r)
-        else:
-            N = b64.to(a64.device)
-            const = torch.lgamma(N + 1.0) - torch.lgamma(a64 + 1.0) - torch.lgamma(N - a64 + 1.0)
+            b64 = extra.log() if rec.aux != "trials" else extra
+        const = rec.constant(a64, None if rec.aux != "trials" else b64.to(a64.device), r)
     _lib.require_device(Z, y, observed, exposure, trials, w0)
     dev = Z.device
     Z = _lib.f32c(Z)

@@ -98,21 +98,16 @@ def manifold_informed_train(model, optimizer, max_iter=100, tolerance=1e-2, upda
 def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=50, tolerance=1e-2, fit_kw=None, evidence_kw=None,
                   verbose=False):
     """Train the kernel hyper-parameters of `model` (a RiemannGP) on the Laplace evidence of its node fit: the loss is
-    -log Z / m minus the log-priors, its gradient the surrogate of laplace_evidence.  family "bernoulli" (0/1 labels in
-    model.train_targets), "poisson", "binomial" or "negative_binomial" (counts; fit_kw carries exposure / trials / mean, and the negative binomial's
-    dispersion: a number stays fixed, a counts.DispersionParameter or a float64 tensor that requires grad is evaluated every epoch
-    and trained along by the same optimizer); "ordinal" (ordered categories; fit_kw carries num_categories and cutpoints: an ordinal.CutpointParameter is
-    evaluated every epoch and its parameters, held by the same optimizer, are trained along); "multiclass" (class indices; fit_kw
-    carries num_classes, the evidence is evidence.softmax_evidence).  Every epoch refits the mode
-    from the previous one (f0=).  Stops when the loss moves by <= tolerance between two epochs or after max_iter epochs; returns
-    the last loss."""
-    from ..evidence import MULTICLASS_FAMILY, ORDINAL_FAMILY, _family, laplace_evidence, softmax_evidence
-    from ..counts import _live_dispersion
-    from ..evidence import NB_FAMILY
-    from ..ordinal import _live_cutpoints
-    if family not in (ORDINAL_FAMILY, MULTICLASS_FAMILY):
-        _family(family)
-    evidence_of = softmax_evidence if family == MULTICLASS_FAMILY else laplace_evidence
+    -log Z / m minus the log-priors, its gradient the surrogate of the family's evidence function.  family: a row of
+    families.TABLE, which names the fit (model.train_targets are its labels, counts, categories or class indices), what fit_kw
+    must carry (the record's `needs`) and may carry (the fitter's keywords), and the evidence function.  The family's extra
+    parameter (the record's `extra`: dispersion, cutpoints) given as a number or a plain tensor stays fixed; given live, as a
+    module (counts.DispersionParameter, ordinal.CutpointParameter) or a float64 tensor that requires grad, it is evaluated every
+    epoch and trained along by the same optimizer.  Every epoch refits the mode from the previous one (f0=).  Stops when the
+    loss moves by <= tolerance between two epochs or after max_iter epochs; returns the last loss."""
+    from .. import families
+    rec = families.fit_family(family)
+    evidence_of = families.evidence_of(rec)
     model.train()
     fit_kw, evidence_kw = dict(fit_kw or {}), dict(evidence_kw or {})
     graph = getattr(getattr(model.base_kernel, "knn", None), "knn_graph", None)
@@ -122,17 +117,10 @@ def laplace_train(model, optimizer, observed=None, family="bernoulli", max_iter=
     loss = torch.zeros(())
     while epoch <= max_iter:
         optimizer.zero_grad()
-        epoch_kw, live, live_r = fit_kw, None, None
-        if family == ORDINAL_FAMILY:
-            epoch_kw, live = _live_cutpoints(fit_kw)
-        elif family == NB_FAMILY:
-            epoch_kw, live_r = _live_dispersion(fit_kw)
+        epoch_kw, live = families.split_live(rec, fit_kw)
         fit = model._laplace_fit(observed, family, f0=f0, **epoch_kw)
         f0 = fit.mean
-        epoch_ev = evidence_kw if live is None else dict(evidence_kw, cutpoints=live)
-        if live_r is not None:
-            epoch_ev = dict(epoch_ev, dispersion=live_r)
-        ev = evidence_of(fit, operator=model.precision(noise=False), **epoch_ev)
+        ev = evidence_of(fit, operator=model.precision(noise=False), **dict(evidence_kw, **live))
         loss = -ev.value
         for _, module, prior, closure, _ in _named_priors(model):
             loss = loss - prior.log_prob(closure(module)).sum().to(loss)

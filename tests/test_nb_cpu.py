@@ -446,17 +446,17 @@ def test_python_argument_checks():
 
 
 def test_exports_and_the_site_formulas_of_the_fit():
-    """_site64 of counts.py (the pseudo-observations of latent_variance / latent_samples) is the restatement's g and h; the public
-    names exist; dispersion= goes wherever family= is public."""
-    from manifold_gp_amd import counts as ct, evidence as ev
+    """The family's float64 (g, h) of families.py (the pseudo-observations of latent_variance / latent_samples) is the restatement's
+    g and h; the public names exist; dispersion= goes wherever family= is public."""
+    from manifold_gp_amd import counts as ct, evidence as ev, families
     from manifold_gp_amd.models import RiemannGP
     rng = np.random.default_rng(0)
     f, y = rng.uniform(-8, 8, 50), rng.integers(0, 50, 50).astype(np.float64)
     for r in (0.37, 2.0, 2.0 ** 20):
         _, g, h, _, _ = nb.site(f, y, None, None, 0.25, r)
-        tg, th = ct._site64("negative_binomial", torch.from_numpy(f + 0.25), torch.from_numpy(y), None, r)
+        tg, th = families.TABLE["negative_binomial"].gh(torch.from_numpy(f + 0.25), torch.from_numpy(y), None, r)
         assert np.abs(tg.numpy() - g).max() <= 1e-13 * (y.max() + r) and np.abs(th.numpy() - h).max() <= 1e-13 * (y.max() + r)
-    assert ct.FAMILIES["negative_binomial"] == 2 and ev._family("negative_binomial") == 3
+    assert ct.FAMILIES["negative_binomial"] == 2 and families._family("negative_binomial", "evidence").code("evidence") == 3
     assert "dispersion" in inspect.signature(ct.fit_counts).parameters
     assert list(inspect.signature(ct.laplace_fit_negative_binomial).parameters)[:3] == ["desc", "y", "dispersion"]
     assert "dispersion" in inspect.signature(ct.CountLaplaceFit.__init__).parameters
