@@ -9,7 +9,11 @@
  *     size the matching *_workspace_bytes() query returns; a `work_bytes` below that size is
  *     MGP_ERR_WORKSPACE before any launch, also where the carve would fit in less (docs/memory_contract.md);
  *   - asynchronous on `stream` unless the comment says it synchronises (graph-build calls that
- *     must report a data-dependent size do);
+ *     must report a data-dependent size do).  In tested terms (docs/stream_contract.md): every launch, copy and memset of
+ *     a call is ordered on `stream` and on no other; a call issued behind pending work of `stream` reads its inputs
+ *     only once that work is done, and its results are those of the same call on an idle null stream (bit for bit wherever two such calls agree bit for bit);
+ *     work on other streams neither waits for it nor is waited for; a plan replays its captured graphs on the stream
+ *     it was created with;
  *   - all matrices of right-hand sides are row-major [N, C] fp32, indices int32, values fp32.
  *
  * Each entry point cites the reference interface it replaces (paths relative to the

@@ -322,8 +322,12 @@ _WORK = {}
 
 
 def workspace(nbytes, tag, device):
-    """Per-(tag, device) scratch tensor, grown geometrically; owned by the torch caching allocator."""
-    key = (tag, str(device))
+    """Per-(tag, device, current stream) scratch tensor, grown geometrically; owned by the torch caching allocator.  The stream
+    handle is part of the key for the reason solvers._cached_plan gives for plans: the kernels that use the scratch are ordered on
+    the stream that was current when it was handed out, so two streams that are not synchronised with each other must not share
+    one, and a scratch that is outgrown goes back to the allocator pool of the stream it was allocated -- and only ever used -- on."""
+    dev = torch.device(device)
+    key = (tag, str(device), int(torch.cuda.current_stream(dev).cuda_stream) if dev.type == "cuda" else 0)
     buf = _WORK.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes * 1.25), 1 << 16), dtype=torch.uint8, device=device)
@@ -332,14 +336,13 @@ def workspace(nbytes, tag, device):
 
 
 def workspace_bytes(tag, device):
-    """Size of the cached scratch of (tag, device); 0 when there is none."""
-    buf = _WORK.get((tag, str(device)))
-    return 0 if buf is None else int(buf.numel())
+    """Bytes the cached scratch of (tag, device) holds, over all streams; 0 when there is none."""
+    return sum(int(buf.numel()) for key, buf in _WORK.items() if key[0] == tag and key[1] == str(device))
 
 
 def release_workspace(tag, device=None):
-    """Drop the cached scratch of `tag` (all devices when device is None): the 60k x 60k key slab of a graph build is
-    ~18 GB that nothing needs once the lists exist (the allocator hands it to the next large request)."""
+    """Drop the cached scratch of `tag` on every stream (all devices when device is None): the 60k x 60k key slab of a graph build
+    is ~18 GB that nothing needs once the lists exist (the allocator hands it to the next large request)."""
     for key in [k for k in _WORK if k[0] == tag and (device is None or k[1] == str(device))]:
         del _WORK[key]
 

@@ -10,6 +10,10 @@ A case may run a sequence (plan create / solve / rebind / destroy, begin / step 
 exercised inside another one's case.  EXEMPT names those that launch no device work of their own on caller memory, each with its
 category.  PENDING names those that do and have no case yet (none today).  tests/test_guarded_cpu.py keeps the four sets a
 partition of SIGNATURES, so a new entry point cannot be added without landing in one of them.
+
+The same cases run on a side stream behind pending work (tests/test_gpu_stream_order.py, docs/stream_contract.md): every case takes
+its stream from _stream() when it is built or run, and _sync() -- the device sync between the steps of a sequence and behind every
+call -- runs SYNC_HOOK behind the sync when one is set, which is where that run re-arms the arena.
 """
 import contextlib
 import ctypes
@@ -29,9 +33,15 @@ def _stream():
     return _lib.stream() if torch.cuda.is_available() else ctypes.c_void_p(0)
 
 
+SYNC_HOOK = None          # set by _guarded.sync_hook for the length of a side-stream run (tests/test_gpu_stream_order.py), else None
+
+
 def _sync():
+    """The device sync between the steps of a sequence and behind a call; SYNC_HOOK, when set, runs right behind it."""
     if torch.cuda.is_available():
         torch.cuda.synchronize()
+    if SYNC_HOOK is not None:
+        SYNC_HOOK()
 
 
 def _rng(shape, salt=0):

@@ -11,6 +11,8 @@ workspaces and 0 where the header demands 16-byte alignment).
 
 Fills: LO is all bytes 0x00, HI all bytes 0xFF (NaN as float or double, -1 as int32).  The guards take one, the workspace and the
 pure outputs the other, so a stray write cannot match both and a stale read differs between the two runs.
+
+The second half of the file is the stream-order run of tests/test_gpu_stream_order.py on the same arena (run_stream_order).
 """
 import numpy as np
 import torch
@@ -296,3 +298,222 @@ def run_contract(case, shape, device, sync=lambda: None):
 
 def report(found):
     return "\n".join("[%s] %s" % (c, m) for c in CHECKS for m in found[c])
+
+
+# ======================================================================================================================================
+# Stream order (tests/test_gpu_stream_order.py, docs/stream_contract.md): the same case, run on a side stream behind pending work.
+#
+# The arena is put into a DECOY state -- every float input rolled by one element, indices / masks / sizes true, workspace and outputs
+# zero -- and the side stream gets, in this order: a bounded delay, one copy of the TRUE image over the whole arena, the case.  A
+# launch on the side stream sees the true inputs.  A launch issued on any other stream runs while the delay is pending: it reads the
+# decoy (valid values at true addresses, so a wrong number and never a wrong address), and whatever it writes is wiped by the image
+# copy.  At every inner sync of a sequence the arena is re-armed, so each step runs behind pending work.
+ORDER_CHECKS = ("rc", "guards", "inputs", "order", "window")
+DELAY_CAP_MS = 200.0
+DELAY_FLOOR_MS = 10.0     # twice the smallest of 5 / 10 / 20 / 50 ms at which every control was reported 10 times out of 10: measured,
+                          # docs/stream_contract.md.  The delay of a run is max(20 x its default-stream duration, this), capped
+_FLOATS = (torch.float32, torch.float64)
+
+
+def carries_decoy(spec):
+    return spec.role in ("in", "inout") and spec.dtype in _FLOATS
+
+
+def decoy_image(specs, true_bytes):
+    """The decoy state of an arena whose true bytes are `true_bytes` (uint8 numpy, arena.mem): a copy in which every float32 /
+    float64 array of role in / inout holds its values rolled by one element.  Integer and uint8 arrays, guards, workspace and outputs
+    stay as they are.  Returns (image, names of the arrays that differ from their decoy, names of the float inputs that do not: a
+    constant array has no decoy)."""
+    image = np.array(true_bytes, dtype=np.uint8, copy=True)
+    differ, constant = [], []
+    for s in specs:
+        if not carries_decoy(s) or s.numel == 0:
+            continue
+        cur = image[s.start:s.start + s.nbytes].view(_NP[s.dtype])
+        rolled = np.roll(cur, 1)
+        (constant if rolled.tobytes() == cur.tobytes() else differ).append(s.name)
+        image[s.start:s.start + s.nbytes] = rolled.view(np.uint8)
+    return image, differ, constant
+
+
+class sync_hook:
+    """`with sync_hook(owner, fn):` makes owner.SYNC_HOOK = fn (owner: tests/_entry_cases.py, whose _sync() calls it behind every
+    device sync) and puts back what was there before, also when the body raises."""
+
+    def __init__(self, owner, fn):
+        self.owner, self.fn = owner, fn
+
+    def __enter__(self):
+        self.keep = self.owner.SYNC_HOOK
+        self.owner.SYNC_HOOK = self.fn
+        return self
+
+    def __exit__(self, *exc):
+        self.owner.SYNC_HOOK = self.keep
+        return False
+
+
+class Delay:
+    """A bounded stretch of device time on the current stream: torch.cuda._sleep, calibrated once against events; a chain of
+    matmuls where this torch build cannot spin.  Never a gate the host releases: a test that died would leave the stream waiting."""
+
+    def __init__(self, device):
+        try:
+            torch.cuda._sleep(1000)
+            self.unit = lambda k: torch.cuda._sleep(int(k))
+            self.kind, probe = "torch.cuda._sleep", 1 << 24
+        except (AttributeError, RuntimeError):
+            a = torch.ones(1024, 1024, device=device)
+            b, c = a.clone(), a.clone()
+
+            def chain(k):
+                for _ in range(int(k)):
+                    torch.mm(a, b, out=c)
+            self.unit, self.kind, probe = chain, "matmul chain", 64
+        self.unit(probe // 8)
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        self.unit(probe)
+        t1.record()
+        t1.synchronize()
+        self.per_ms = probe / max(t0.elapsed_time(t1), 1e-3)
+
+    def enqueue(self, ms):
+        self.unit(max(1, int(ms * self.per_ms)))
+
+
+def window_open(delay, ms, between=lambda: None):
+    """On the current (side) stream: enqueues a delay of `ms`, an event behind it and whatever `between` enqueues; then a marker op
+    on the default stream.  True when the marker completed while the event was still unsignalled: work on the default stream
+    overtakes the side stream for the length of the delay."""
+    dev = torch.cuda.current_stream().device
+    delay.enqueue(ms)
+    ev = torch.cuda.Event()
+    ev.record()
+    between()
+    with torch.cuda.stream(torch.cuda.default_stream(dev)):
+        torch.zeros(1, device=dev).add_(1.0)
+        done = torch.cuda.Event()
+        done.record()
+    done.synchronize()
+    return not ev.query(), ev
+
+
+def side_stream(device, delay, tries=8, probe_ms=2.0):
+    """A fresh torch.cuda.Stream that does not wait for the default stream, nor the default stream for it.  The runtime maps its
+    streams onto a few hardware queues, and two streams that land on one queue run in issue order: behind such a stream nothing is
+    pending from the default stream's point of view, and work issued there by mistake is ordered all the same.  So a new stream is
+    probed with a short delay and dropped for the next one when the marker does not overtake it (one stream alive at a time)."""
+    side = None
+    for _ in range(tries):
+        side = None                                    # (drop the last one before the next is made)
+        side = torch.cuda.Stream(device)
+        with torch.cuda.stream(side):
+            ok, _ = window_open(delay, probe_ms)
+        side.synchronize()
+        if ok:
+            break
+    return side
+
+
+def _differing(name, idx, what):
+    return "%s: %s at %d element(s), first %d, last %d" % (name, what, idx.size, idx[0], idx[-1])
+
+
+def run_stream_order(case, shape, device, owner, delay, floor_ms=None):
+    """Runs `case` at `shape` once on the default stream and once on a fresh side stream behind a delay (see above; `owner` is the
+    module whose SYNC_HOOK re-arms the arena at the inner syncs, `delay` a Delay).  Returns ({check: [messages]} for ORDER_CHECKS,
+    info): `order` = the side-stream result differs from the default-stream one under the case's fill_bar; `window` = a marker on
+    the default stream did not complete while the delay was still pending, so the run proves nothing.  info: decoys (arrays that
+    differ from their decoy), constant (float inputs that do not), rearms, delay_ms, ref_ms."""
+    floor_ms = DELAY_FLOOR_MS if floor_ms is None else floor_ms
+    rec = Recorder()
+    case(rec, shape)
+    fresh = lambda: Arena([Spec(s.name, s.dtype, s.numel, s.role, s.init, s.floor) for s in rec.specs], "aligned", HI, LO, device)
+    found = {c: [] for c in ORDER_CHECKS}
+    info = dict(decoys=0, constant=[], rearms=0, delay_ms=0.0, ref_ms=0.0)
+    # 1. the reference: default stream, nothing pending
+    arena = fresh()
+    call = case(arena.carve, shape)
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    rc, host = call.run(None)
+    t1.record()
+    t1.synchronize()
+    info["ref_ms"] = t0.elapsed_time(t1)
+    if rc != 0:
+        found["rc"].append("default stream: returned %d" % rc)
+        return found, info
+    if call.probe is not None:
+        call.probe(host)
+    ref = _result(arena, call, host)
+    del arena, call
+    # 2. the second arena, its true image and its decoy state
+    arena = fresh()
+    case(arena.carve, shape)
+    torch.cuda.synchronize()
+    true = arena.mem.clone()
+    image, differ, constant = decoy_image(arena.specs, true.cpu().numpy())
+    info["decoys"], info["constant"] = len(differ), constant
+    arena.mem.copy_(torch.from_numpy(image).to(device))
+    torch.cuda.synchronize()
+    info["delay_ms"] = ms = min(DELAY_CAP_MS, max(20.0 * info["ref_ms"], floor_ms))
+    # 3. / 4. the side-stream run
+    side = side_stream(device, delay)
+    state = {}
+
+    def arm(restore):
+        """On the side stream: delay, then `restore` over the arena; the marker on the default stream checks the window."""
+        state["restore"] = restore                       # alive until the copy has run
+        ok, state["ev"] = window_open(delay, ms, lambda: arena.mem.copy_(restore))
+        if not ok:
+            found["window"].append("arm %d: the delay of %.1f ms had run out before a marker on the default stream completed"
+                                   % (info["rearms"], ms))
+
+    def rearm():
+        """Behind a device sync: keep what the arena holds, roll the float inputs, then delay + restore on the side stream."""
+        snap = arena.mem.clone()
+        for s in arena.specs:
+            if carries_decoy(s) and s.numel:
+                arena.views[s.name].copy_(torch.roll(snap[s.start:s.start + s.nbytes].view(s.dtype), 1))
+        torch.cuda.synchronize()
+        info["rearms"] += 1
+        arm(snap)
+
+    try:
+        with torch.cuda.stream(side):
+            arm(true)
+            with sync_hook(owner, rearm):
+                call = case(arena.carve, shape)
+                if state["ev"].query():              # building the case waited for the device: the delay is spent, arm again
+                    torch.cuda.synchronize()
+                    rearm()
+                rc, host = call.run(None)
+    finally:
+        torch.cuda.synchronize()
+    if rc != 0:
+        found["rc"].append("side stream: returned %d" % rc)
+        return found, info
+    guards = arena.check()
+    if guards:
+        found["guards"].append("side stream: %s" % describe(guards))
+    arena.before = true
+    for s in arena.specs:
+        if s.role == "in":
+            ch = arena.changed(s.name)
+            if ch:
+                found["inputs"].append("side stream: const input %s changed at byte offsets %d .. %d (%d bytes)" % ((s.name,) + ch))
+    got = _result(arena, call, host)
+    for name in ref:
+        a, isz, dtype, _ = ref[name]
+        idx = _compare(a, got[name][0], isz, dtype, call.fill_bar, name)
+        if idx.size:
+            found["order"].append(_differing(name, idx, "differs between the default stream and the side stream (bar: %s)"
+                                             % _bar_name(call.fill_bar)))
+    return found, info
+
+
+def report_order(found):
+    return "\n".join("[%s] %s" % (c, m) for c in ORDER_CHECKS for m in found[c])

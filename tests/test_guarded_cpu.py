@@ -4,6 +4,8 @@
    _guarded.run_contract -- the evidence that tests/test_gpu_memory_contract.py fails on a kernel with that defect.
 2. Completeness: CASES, COVERED_BY, EXEMPT and PENDING of _entry_cases are a partition of _lib.SIGNATURES.
 3. Refusals return before any launch, so the library loads here: a workspace one byte short is MGP_ERR_WORKSPACE.
+4. The host-side parts of the stream-order run (_guarded.run_stream_order, tests/test_gpu_stream_order.py): the decoy keeps integer
+   arrays and rolls float arrays, constant arrays have no decoy, the sync hook is restored after an exception.
 """
 import os
 import re
@@ -120,6 +122,103 @@ def test_short_workspace_must_be_refused_and_touch_nothing():
         return call
     found = G.run_contract(sloppy, dict(n=5), CPU)
     assert {c for c in G.CHECKS if found[c]} == {"short"}, G.report(found)
+
+
+# ------------------------------------------------------------------------------------------- stream order: the host-side parts
+def test_decoy_rolls_float_inputs_and_keeps_everything_else():
+    def case(carve, shape):
+        n = shape["n"]
+        carve("x", torch.float32, n, "in", np.arange(1, n + 1, dtype=np.float32))
+        carve("acc", torch.float64, n, "inout", np.linspace(0.5, 2.0, n))
+        carve("ones", torch.float32, n, "in", np.ones(n))                              # constant: its roll is itself
+        carve("col", torch.int32, n, "in", np.arange(n)[::-1])
+        carve("mask", torch.uint8, n, "in", np.arange(n) % 2)
+        carve("out", torch.float32, n, "out")
+        carve("work", torch.uint8, 64, "work", floor=8)
+        return G.Call(lambda work_bytes: (0, {}))
+    rec = G.Recorder()
+    case(rec, dict(n=5))
+    arena = G.Arena(rec.specs, "aligned", G.HI, G.LO, CPU)
+    true = arena.mem.numpy().copy()
+    image, differ, constant = G.decoy_image(arena.specs, true)
+    assert differ == ["x", "acc"] and constant == ["ones"]
+    assert (true == arena.mem.numpy()).all(), "the true image is left alone"
+    part = lambda img, name, dt: img[arena.spec(name).start:arena.spec(name).start + arena.spec(name).nbytes].view(dt)
+    assert part(image, "x", np.float32).tolist() == [5.0, 1.0, 2.0, 3.0, 4.0]
+    assert part(image, "acc", np.float64).tolist() == np.roll(np.linspace(0.5, 2.0, 5), 1).tolist()
+    changed = np.nonzero(image != true)[0]
+    inside = np.zeros(true.size, bool)
+    for name in ("x", "acc"):
+        inside[arena.spec(name).start:arena.spec(name).start + arena.spec(name).nbytes] = True
+    assert changed.size and inside[changed].all(), "only the float inputs differ: indices, masks, guards, outputs and workspace are true"
+    assert (part(image, "out", np.uint8) == G.LO).all() and (part(image, "work", np.uint8) == G.LO).all()
+    # a decoy is a valid input: every value of it is a value of the true array
+    assert sorted(part(image, "x", np.float32).tolist()) == sorted(part(true, "x", np.float32).tolist())
+    # one element: no decoy either
+    rec1 = G.Recorder()
+    case(rec1, dict(n=1))
+    one = G.Arena(rec1.specs, "aligned", G.HI, G.LO, CPU)
+    assert G.decoy_image(one.specs, one.mem.numpy())[1:] == ([], ["x", "acc", "ones"])
+
+
+def test_every_registered_case_builds_a_decoy_from_its_own_values():
+    """Over the whole registry, on host stand-ins: integer arrays never change, and the cases without any decoy are the ones
+    docs/stream_contract.md lists (one-element shapes and the integer-only graph_tiles / bfs_order)."""
+    doc = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "docs", "stream_contract.md")).read()
+    none = set()
+    for name, fam, sid in E.params():
+        case = E.CASES[name]
+        rec = G.Recorder()
+        case.fn(rec, case.shapes_of(fam)[sid])
+        arena = G.Arena(rec.specs, "aligned", G.HI, G.LO, CPU)
+        true = arena.mem.numpy().copy()
+        image, differ, constant = G.decoy_image(arena.specs, true)
+        for s in arena.specs:
+            if s.name not in differ:
+                assert (image[s.start:s.start + s.nbytes] == true[s.start:s.start + s.nbytes]).all(), (name, sid, s.name)
+        if not differ:
+            none.add(name)
+            assert all(s.numel <= 1 or not G.carries_decoy(s) or s.name in constant for s in arena.specs)
+    for name in none:
+        assert "`%s`" % name in doc.split("## Cases without a decoy")[1].split("##")[0], name
+
+
+def test_sync_hook_runs_behind_the_sync_and_is_restored_after_an_exception():
+    calls = []
+    assert E.SYNC_HOOK is None
+    with G.sync_hook(E, lambda: calls.append(1)):
+        E._sync()
+        E._sync()
+    assert calls == [1, 1] and E.SYNC_HOOK is None
+    with pytest.raises(RuntimeError, match="planted"):
+        with G.sync_hook(E, lambda: calls.append(2)):
+            E._sync()
+            raise RuntimeError("planted")
+    assert calls == [1, 1, 2] and E.SYNC_HOOK is None
+    E._sync()
+    assert calls == [1, 1, 2]
+
+    def failing():
+        raise RuntimeError("planted in the hook")
+    with pytest.raises(RuntimeError, match="in the hook"):
+        with G.sync_hook(E, failing):
+            E._sync()
+    assert E.SYNC_HOOK is None
+    outer = lambda: calls.append(3)
+    with G.sync_hook(E, outer):                                                    # nested: the outer hook comes back
+        with G.sync_hook(E, lambda: calls.append(4)):
+            E._sync()
+        assert E.SYNC_HOOK is outer
+    assert E.SYNC_HOOK is None and calls[-1] == 4
+
+
+def test_scratch_key_names_the_stream_on_the_host_too():
+    tag = "stream-order-cpu"
+    a = _lib.workspace(100, tag, CPU)
+    assert _lib.workspace(50, tag, CPU) is a and [k for k in _lib._WORK if k[0] == tag] == [(tag, "cpu", 0)]
+    assert _lib.workspace_bytes(tag, CPU) == a.numel()
+    _lib.release_workspace(tag)
+    assert _lib.workspace_bytes(tag, CPU) == 0
 
 
 # ------------------------------------------------------------------------------------------------------------ completeness
