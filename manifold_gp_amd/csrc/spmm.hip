@@ -237,6 +237,11 @@ struct TileArgs {
   const int32_t* rowid;
   int max_entries;   // multi-column tile kernel: entries of the largest tile (LDS carving)
   int part_window;   // multi-column tile kernel: quads of partial sums staged per window (multiple of 256)
+  // C == 1 tile kernels on the entry-balanced set (mgp_c1_tiles_t): rowptr_t = its rowptr_pad with vals_t and rowid NULL, a
+  // combination no row order has.  n is then the padded position space (64 ntiles positions) and the words behind the
+  // 64 ntiles + 1 offsets are shift [ntiles + 1], the empty positions in front of tile t: position p of tile t is row
+  // p - shift[t], and the tile is 64 - (shift[t + 1] - shift[t]) rows high.  (No argument of its own: the deciding step kernel
+  // has no scalar register left for another pointer, it spilled in its head.)
 };
 
 typedef unsigned short mgp_v4h __attribute__((ext_vector_type(4)));
@@ -329,6 +334,17 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
   int skipl = 0, tickl = 0;
   constexpr int TR = BS / 4;
   constexpr int NQ = 4;
+  static_assert(BS != 256 || 4 * NQ * BS == MGP_C1_TILE_CAP, "the balanced cut caps a tile at what a 256-lane workgroup holds in registers");
+  // The entry-balanced set (one tile per workgroup, the grid is the tile count; the loop form runs it only under the lab switch
+  // mgp_spmm_set_tile_loop_mode, with a loop of one pass): the two shift words of the tile come through the VECTOR path like
+  // skip and tick, requested with the ids and back with them, long before the row operands are addressed.  A nullable operand:
+  // loaded from a stand-in, selected afterwards.  The set is told by its offsets coming without a row order, and its shift words
+  // stand behind them (TileArgs); the stand-in is the offsets themselves (words t and t + 1 of rowptr: t + 1 <= n), so what is
+  // selected is an index, not a pointer: the step kernels have no scalar register pair left.  For the same reason the mode lives
+  // in a vector register (lane0: not provably uniform), not in a lane mask: shm is all ones on the balanced set, else zero, and
+  // the selects below are ANDs with it (a compare would hold a lane mask, two SGPRs, from here to the row operands).
+  const int shm = -(((t.rowptr_t != nullptr && t.rowid == nullptr) ? 1 : 0) + lane0);
+  int sh0 = 0, shd = 0;     // empty positions in front of the tile; rows the tile is short of TR
   const int lb = mgp_xcd_block(blockIdx.x, grid_x) + zero;
   const int tid = threadIdx.x, sub = tid & 3;
 #ifdef MGP_STAMP   // lab build (tools/lab/stamp_solve.py): block 0 leaves its start / end time behind the CG state words
@@ -416,7 +432,7 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
     if constexpr (STEP) {
       for (int64_t tl = t0; tl < t1; ++tl) {
         const int64_t pos = tl * TR + tid;
-        if (tid < TR && pos < p.n) cs.x[t.rowid ? (int64_t)t.rowid[pos] : pos] = 0.f;
+        if (tid < TR - shd && pos < p.n) cs.x[t.rowid ? (int64_t)t.rowid[pos] : pos - sh0] = 0.f;
       }
     }
   };
@@ -441,6 +457,11 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
     for (int k = 0; k < NQ; ++k) {
       const int j = tid + k * BS;
       c[k] = (unsigned)tile_cols[j < D ? dp + j : 0];   // empty tile: dp may be one past the end
+      if (k == 0) {                                     // behind the first id: the step kernel's first vector load stays an id
+        const int64_t si = ((TR * (int)grid_x + 1) & shm) + (int)tile;
+        sh0 = rowptr[si];
+        shd = rowptr[si + 1];
+      }
       // (round 4, measured and removed: a fixed-stride copy of the dictionaries, whose ids can be requested in the same round
       // trip as the tile's offsets instead of behind it -- 5.46 against 5.43 us back to back, 56.0 against 54.0 us per solve)
     }
@@ -473,10 +494,12 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
       l[k] = *reinterpret_cast<const mgp_v4h*>(lid + 4 * (int64_t)qi);
     }
     __builtin_amdgcn_sched_barrier(0);
+    shd = (shd - sh0) & shm;
+    sh0 &= shm;
     const int64_t row = r0 + (tid >> 2);
-    const bool valid = row < r1;
+    const bool valid = row < r1 - shd;                                   // (balanced set: r1 = r0 + TR, the tile is TR - shd high)
     const int64_t pr = valid ? row : r0;                                 // position in the tile order
-    const int64_t rr = t.rowid ? (int64_t)t.rowid[pr] : pr;              // row of the CSR / of the vectors
+    const int64_t rr = t.rowid ? (int64_t)t.rowid[pr] : pr - sh0;        // row of the CSR / of the vectors
     const int64_t grr = rr + p.goff;
     const int rs = rowptr[pr], re = rowptr[pr + 1];
     const float raw_x = x[grr];
@@ -513,7 +536,9 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
       const int j = tid + k * BS;
       if (j < D) xl[j] = g[k];
     }
-    for (int j = tid + NQ * BS; j < D; j += BS) {      // dictionaries longer than NQ * BS (rare)
+    // dictionaries longer than NQ * BS = 1024 columns: a dependent trip to memory.  The balanced set does not bound the dictionary
+    // (60k k-NN graph, CPU rebuild: 12 of 938 fixed tiles, 3 of 985 balanced ones run this loop)
+    for (int j = tid + NQ * BS; j < D; j += BS) {
       const int cc = tile_cols[dp + j];
       float gg = x[cc];
       if (PRE) gg *= prev[cc];
@@ -550,7 +575,11 @@ __device__ __forceinline__ void spmv_tile_body(const SpmmArgs pa, const TileArgs
         part[q] = s;
       }
     }
-    for (int q = tid + NQ * BS; q < Q; q += BS) {      // tiles with more than 4 * NQ * BS entries (rare)
+    // tiles with more than 4 * NQ * BS = MGP_C1_TILE_CAP entries: a dependent trip to memory behind the barrier, with everything
+    // else of the workgroup already back.  On the fixed 64-row tiles of a k-NN graph that is a third of the tiles (60k graph: 295
+    // of 938), and they end every launch.  On the balanced set the loop runs only for a tile that is ONE row heavier than the cap;
+    // it still runs wherever the fixed set is kept: locality orders, row slices, the loop form (more than 4096 tiles).
+    for (int q = tid + NQ * BS; q < Q; q += BS) {
       const mgp_v4f vv = *reinterpret_cast<const mgp_v4f*>(vals + 4 * (int64_t)(qb + q));
       const mgp_v4h ll = *reinterpret_cast<const mgp_v4h*>(lid + 4 * (int64_t)(qb + q));
       float s = vv.x * xl[ll.x];
@@ -1905,11 +1934,45 @@ static int spmm_rows_per_pass(int C, int lanes, int rows_in_flight) {
   return kBlock / spmm_cols_group(C) * 4;
 }
 
-static size_t tile_lds_bytes(const mgp_csr_t* L) {
+// ---- the tile set of the C == 1 tile kernels: the 64-row tiles of the CSR, or its entry-balanced set ---------------------------
+// The set rides beside the CSR as a host descriptor (mgp_c1_tiles_t, include/mgp_hip.h): mgp_csr_t keeps its layout, and a CSR
+// without a row order names the descriptor through tile_rowptr, which is otherwise NULL there.
+static const mgp_c1_tiles_t* c1_set(const mgp_csr_t* L) {
+  if (!L->tile_rowptr || L->tile_vals || L->tile_rowid) return nullptr;
+  const mgp_c1_tiles_t* s = reinterpret_cast<const mgp_c1_tiles_t*>(L->tile_rowptr);
+  return s->magic == MGP_C1_TILES_MAGIC ? s : nullptr;
+}
+// the offsets of a row ORDER (all three arrays or none): tile_rowptr alone is the descriptor above, not an order
+static const int32_t* order_rowptr(const mgp_csr_t* L) { return (L->tile_vals || L->tile_rowid) ? L->tile_rowptr : nullptr; }
+
+// THE statement of when the balanced set (mgp_c1_tiles_t) runs; what builds it states when it exists (graph.py
+// c1_balanced_policy: natural order, a 64-row tile over MGP_C1_TILE_CAP entries, the folded CG step kept).  It serves C == 1 only,
+// positions that are rows (no row order), whole graphs (no row offset, no row slice) and one tile per workgroup (at most kMaxGrid
+// tiles: the single-tile form of the kernel; the lab switch mgp_spmm_set_tile_loop_mode runs the same set through the loop form,
+// one pass per workgroup, so that the two forms stay comparable bit for bit).  Everything else, and every other kernel, reads
+// the 64-row set and computes what it computed before the set existed.
+static bool c1_balanced(const mgp_csr_t* L, int C, int64_t row_offset) {
+  if (C != 1 || row_offset != 0) return false;
+  const mgp_c1_tiles_t* s = c1_set(L);
+  if (!s || !s->tile_ptr || !s->tile_cols || !s->lid || !s->rowptr_pad || !s->tile_shift) return false;
+  if (L->tile_rows != 64 || s->n != L->n) return false;
+  if (L->ncols != 0 && L->ncols != L->n) return false;
+  if (s->tiles < 1 || s->tiles > kMaxGrid || (s->max_entries & 3) != 0) return false;
+  // one allocation: the kernel finds the shift words behind the offsets (TileArgs)
+  if (s->tile_shift != s->rowptr_pad + ((int64_t)s->tiles * 64 + 1)) return false;
+  return (int64_t)s->tiles * 64 >= L->n && L->n >= s->tiles;       // every row in a tile, no tile without a row
+}
+
+static size_t tile_lds_bytes(const mgp_csr_t* L, bool balanced = false) {
+  if (balanced) return ((size_t)c1_set(L)->max_cols + (size_t)(c1_set(L)->max_entries >> 2)) * sizeof(float);
   return ((size_t)L->tile_max_cols + (size_t)(L->tile_max_entries >> 2)) * sizeof(float);
 }
 
-static int tile_grid(const mgp_csr_t* L, int* tiles_per_block) {
+static int tile_grid(const mgp_csr_t* L, int* tiles_per_block, bool balanced = false) {
+  if (balanced) {                 // one workgroup per tile (c1_balanced: at most kMaxGrid of them)
+    if (tiles_per_block) *tiles_per_block = 1;
+    return c1_set(L)->tiles;
+  }
   const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
   const int64_t tpb = mgp_cdiv(ntiles, kMaxGrid);
   if (tiles_per_block) *tiles_per_block = (int)tpb;
@@ -1982,9 +2045,14 @@ static bool mt_image_fits(const mgp_csr_t* L, int C) {
   return L->mt_tiles == (int32_t)mgp_cdiv(L->n, 16);
 }
 
-static TileArgs tile_args(const mgp_csr_t* L, int tiles_per_block, int part_window) {
+static TileArgs tile_args(const mgp_csr_t* L, int tiles_per_block, int part_window, bool balanced = false) {
+  if (balanced) {
+    const mgp_c1_tiles_t* s = c1_set(L);
+    return TileArgs{s->tile_ptr, s->tile_cols, s->lid, s->tiles, 1, s->max_cols, s->rowptr_pad, nullptr, nullptr,
+                    s->max_entries, part_window};         // (tile_shift stands behind rowptr_pad: c1_balanced)
+  }
   return TileArgs{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), tiles_per_block, L->tile_max_cols,
-                  L->tile_rowptr, L->tile_vals, L->tile_rowid, L->tile_max_entries, part_window};
+                  order_rowptr(L), L->tile_vals, L->tile_rowid, L->tile_max_entries, part_window};
 }
 
 // ---- which kernel runs: the ONE statement of the policy -------------------------------------------------------------------
@@ -2006,6 +2074,7 @@ struct SpmmPlan {
   bool v4_ok;               // Gather: switch and shape allow the float4 member (the launch adds the alignment test)
   int tiles_per_block;      // TileC1, TileSmall, TileWide (Dict: 1)
   bool one_tile;            // TileC1: the single-tile form of the kernel (tiles_per_block == 1 and the loop form not forced)
+  bool balanced;            // TileC1: on the entry-balanced tile set (c1_balanced); grid, dot_blocks and lds are that set's
   int window;               // TileSmall: quads of partial sums staged per window
   int slots, stream_cap;    // Dict
   int wide_cap;             // TileWide
@@ -2019,7 +2088,7 @@ static SpmmPlan spmm_plan(const mgp_csr_t* L, int C, int64_t row_offset, bool wi
   const int tile = g_tile_mode, tile_small = g_tile_small_mode, tile_wide = g_tile_wide_mode, v4 = g_spmm_v4_mode,
             dict = g_dict_mode, mt = g_mt_mode;
   // row-tile dictionaries present and switched on; an ordered tile view is all three arrays or none
-  const int ord = (L->tile_rowptr != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
+  const int ord = (order_rowptr(L) != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
   const bool dicts = tile && (ord == 0 || ord == 3) && L->lid && L->tile_ptr && L->tile_cols;
   const bool dicts64 = dicts && L->tile_rows == 64 && (L->tile_max_entries & 3) == 0;      // 64-row tiles, quad-padded rows
   const bool wide = C > 16 && C <= 256 && (C & 3) == 0;
@@ -2028,9 +2097,10 @@ static SpmmPlan spmm_plan(const mgp_csr_t* L, int C, int64_t row_offset, bool wi
   // 1. C == 1 on 32 / 64 / 128-row tiles: the column dictionary of a tile staged in LDS (spmv_tile_kernel)
   if (C == 1 && dicts && (L->tile_rows == 32 || L->tile_rows == 64 || L->tile_rows == 128) && tile_lds_bytes(L) <= 65536 - 64) {
     pl.family = SpmmFamily::TileC1;
-    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
+    pl.balanced = c1_balanced(L, C, row_offset) && tile_lds_bytes(L, true) <= 65536 - 64;
+    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block, pl.balanced);
     pl.one_tile = pl.tiles_per_block == 1 && !g_tile_loop_mode;
-    pl.lds = tile_lds_bytes(L);
+    pl.lds = tile_lds_bytes(L, pl.balanced);
     return pl;
   }
   // 2. C in {4, 8, 12, 16} on 64-row tiles whose staged data (dictionary rows + matrix stream) fits the LDS budget
@@ -2235,7 +2305,8 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
   p.rows_per_block = pl.rows_per_block;
   switch (pl.family) {
   case SpmmFamily::TileC1: {
-    TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+    TileArgs ta = tile_args(L, pl.tiles_per_block, 0, pl.balanced);
+    if (pl.balanced) p.n = (int64_t)c1_set(L)->tiles * 64;      // the padded position space
     if (record_to) {
       TileLaunchRecord rec{p, ta};
       memcpy(record_to, &rec, sizeof(rec));
@@ -2394,7 +2465,8 @@ int mgp_spmm_cgstep(const mgp_csr_t* L, const float* T, float a, float b, const 
   // even load them (TileView<true> in spmv_tile_body holds them as constants): a caller that sets one here must change that view
   SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, T, nullptr, 1, a, b, nullptr, post, nullptr, 1.f, co,
              nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
-  const TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+  const TileArgs ta = tile_args(L, pl.tiles_per_block, 0, pl.balanced);
+  if (pl.balanced) p.n = (int64_t)c1_set(L)->tiles * 64;        // the padded position space
   const dim3 grid(pl.grid), block(256);
   hipStream_t st = mgp_stream(stream);
   auto step = [&](auto ds, auto one) {

@@ -69,6 +69,103 @@ def build_tiles(n, rowptr, col, nnz, tile_rows=None, order=None):
     return None
 
 
+# ---- entry-balanced row tiles for the single-column tile kernels (docs/kernels/spmm.md, round 8) ----------------------------
+# A workgroup of spmv_tile_kernel / spmv_tile_cgstep_kernel holds 4 quads of entries per lane in registers; a tile with more
+# takes a dependent trip to memory behind its first barrier.  On a k-NN graph a third of the fixed 64-row tiles do.  The balanced
+# set cuts the rows, in their natural order, into tiles of at most 64 rows AND at most C1_TILE_CAP padded entries.
+C1_TILE_CAP = 4096         # = MGP_C1_TILE_CAP (include/mgp_hip.h) = 4 * NQ * BS of the kernel (tests/test_c1_balanced_tiles_cpu.py)
+C1_MAX_TILES = 4096        # the single-tile form of the kernel: one workgroup per tile (csrc/spmm.hip kMaxGrid)
+C1_FOLD_PARTIALS = 1024    # partials the folded CG step sums with four slots per lane (csrc/cg_policy.h)
+C1_BALANCED = _lib.C1_BALANCED      # [True]: CSRs carry the balanced set where the policy builds it; [False]: the 64-row set alone
+
+
+def c1_balanced_cut(rowptr, rows=TILE_ROWS, cap=C1_TILE_CAP):
+    """Greedy cut of the rows 0 .. n - 1 into consecutive tiles: a tile ends when it has `rows` rows or when the next row would
+    take it past `cap` entries; a single row heavier than `cap` is a tile of its own.  rowptr: [n + 1] host integers, ascending.
+    Returns int64 [T + 1]: the first row of every tile, then n.  One searchsorted step per tile."""
+    rp = torch.as_tensor(rowptr, dtype=torch.int64, device="cpu").contiguous()
+    n = int(rp.numel()) - 1
+    first, r = [0], 0
+    while r < n:
+        # the last row boundary e with rowptr[e] <= rowptr[r] + cap
+        e = int(torch.searchsorted(rp, rp[r] + cap, right=True)) - 1
+        e = max(min(e, r + rows, n), r + 1)
+        first.append(e)
+        r = e
+    return torch.tensor(first, dtype=torch.int64)
+
+
+def c1_padded_positions(rowptr, first, rows=TILE_ROWS):
+    """The padded position space of a cut: tile t owns positions rows * t .. rows * t + rows - 1, its real rows first, then empty
+    positions.  Returns (rowptr_pad int64 [rows * T + 1], tile_shift int64 [T + 1]: the empty positions in front of tile t)."""
+    rp = torch.as_tensor(rowptr, dtype=torch.int64, device="cpu")
+    T = int(first.numel()) - 1
+    pos = torch.arange(rows * T + 1, dtype=torch.int64)
+    t = torch.clamp(pos // rows, max=max(T - 1, 0))
+    row = torch.minimum(first[t] + (pos - rows * t), first[t + 1]) if T else torch.zeros(1, dtype=torch.int64)
+    return rp[row], rows * torch.arange(T + 1, dtype=torch.int64) - first
+
+
+def c1_balanced_policy(rowptr, rows=TILE_ROWS, ordered=False):
+    """THE statement of when the balanced set is built (and therefore used): returns the cut (c1_balanced_cut) or None.
+    Built only when the 64-row set is in natural row order, has at most C1_MAX_TILES tiles of which at least one is over
+    C1_TILE_CAP entries, and the balanced set keeps to C1_MAX_TILES tiles and does not push the count of dot partials (one per
+    tile) from at most C1_FOLD_PARTIALS to more: a CG plan would lose its four-slot folded step.  Everything else runs on the
+    64-row set as before."""
+    if ordered or rows != 64:
+        return None
+    rp = torch.as_tensor(rowptr, dtype=torch.int64, device="cpu")
+    n = int(rp.numel()) - 1
+    fixed = -(-n // rows)
+    if n < 1 or fixed > C1_MAX_TILES:
+        return None
+    edges = rp[torch.clamp(torch.arange(fixed + 1, dtype=torch.int64) * rows, max=n)]
+    if int((edges[1:] - edges[:-1]).max()) <= C1_TILE_CAP:
+        return None
+    first = c1_balanced_cut(rp, rows)
+    T = int(first.numel()) - 1
+    if T > C1_MAX_TILES or (fixed <= C1_FOLD_PARTIALS < T):
+        return None
+    return first
+
+
+def c1_balanced_tiles(n, rowptr, col, nnz, tiles):
+    """The balanced set of a graph whose 64-row `tiles` exist, or None (c1_balanced_policy).  The dictionaries come from the
+    same mgp_graph_tiles, run over the padded position space: col and vals are untouched, consecutive rows keep their entry
+    order, so there is no entry map and no second copy of the values."""
+    if tiles is None or nnz <= 0 or not col.is_cuda:
+        return None
+    first = c1_balanced_policy(rowptr.cpu(), tiles["rows"], ordered=tiles.get("rowid") is not None)
+    if first is None:
+        return None
+    dev = col.device
+    T = int(first.numel()) - 1
+    rp_pad, shift = c1_padded_positions(rowptr.cpu(), first)
+    # one allocation: the kernels find the shift words behind the offsets (include/mgp_hip.h, c1_tile_shift)
+    both = torch.cat([rp_pad, shift]).to(torch.int32).to(dev)
+    rowptr_pad, shift = both[:64 * T + 1], both[64 * T + 1:]
+    tile_ptr = torch.empty(T + 1, dtype=torch.int32, device=dev)
+    tile_cols = torch.empty(nnz, dtype=torch.int32, device=dev)
+    lid = torch.empty(nnz, dtype=torch.int16, device=dev)
+    work = _lib.workspace(lib().mgp_graph_tiles_workspace_bytes(64 * T, nnz), "graph", dev)
+    total, mc, me = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib().mgp_graph_tiles(64 * T, ptr(rowptr_pad), ptr(col), nnz, 64, None, None, None, ptr(tile_ptr), ptr(tile_cols),
+                               ptr(lid), ctypes.byref(total), ctypes.byref(mc), ctypes.byref(me), ptr(work), work.numel(),
+                               stream())
+    if rc == -3:
+        return None
+    check(rc, "mgp_graph_tiles")
+    if (mc.value + me.value // 4) * 4 > 65536 - 64 or (me.value & 3):
+        return None
+    tile_cols = tile_cols[:total.value].clone()
+    # the host descriptor the library reads (mgp_c1_tiles_t); it lives in this dict beside the tensors it points into
+    desc = _lib.C1TilesT(_lib.C1_TILES_MAGIC, int(n), tile_ptr.data_ptr(), tile_cols.data_ptr(), lid.data_ptr(), rowptr_pad.data_ptr(),
+                         shift.data_ptr(), T, mc.value, me.value, 0)
+    return dict(tile_ptr=tile_ptr, tile_cols=tile_cols, lid=lid, rowptr_pad=rowptr_pad, struct=desc,
+                tile_shift=shift, T=T, max_cols=mc.value, max_entries=me.value,
+                total_cols=total.value, first=first)
+
+
 def require_no_self_edges(graph, stage):
     """ValueError for a stage that reads the matrix entry by entry and takes col == row for padding: on a graph with self edges
     it would compute from another matrix than the one the products and solves apply (diag - S - S^T, whose diagonal is
@@ -148,13 +245,23 @@ def build_tiles_auto(n, rowptr, col, nnz, points=None):
     d <= 3 coordinates, else a breadth-first order of the graph."""
     t = build_tiles(n, rowptr, col, nnz)
     if t is None or t["reuse"] >= REORDER_BELOW_REUSE or n < 4 * TILE_ROWS:
-        return t
+        return with_c1_balanced(t, n, rowptr, col, nnz)
     if points is not None and points.dim() == 2 and points.shape[1] <= 3 and points.shape[0] == n:
         order = morton_order(points)
     else:
         order = bfs_order(n, rowptr, col)
     t2 = build_tiles(n, rowptr, col, nnz, order=order)
-    return t2 if (t2 is not None and t2["reuse"] > 1.3 * t["reuse"]) else t
+    return t2 if (t2 is not None and t2["reuse"] > 1.3 * t["reuse"]) else with_c1_balanced(t, n, rowptr, col, nnz)
+
+
+def with_c1_balanced(t, n, rowptr, col, nnz):
+    """`t` (64-row tiles in natural order, or None) with the balanced set of the single-column kernels under "c1" where the
+    policy builds one (c1_balanced_policy)."""
+    if t is not None and t.get("rowid") is None:
+        c1 = c1_balanced_tiles(n, rowptr, col, nnz, t)
+        if c1 is not None:
+            t["c1"] = c1
+    return t
 
 
 class KnnGraph:

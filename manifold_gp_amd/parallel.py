@@ -246,6 +246,8 @@ class PartitionedOperator:
             self.tiles, self.vals_t = g.tiles, d.vals_t
             if self.tiles is None:
                 raise RuntimeError("the partitioned solver needs the tile view of the graph")
+            # row-partitioned plans run on the 64-row tiles at every world size (the balanced set is the single-GPU plans')
+            self.tiles = {k: v for k, v in self.tiles.items() if k != "c1"}
             self.launch_rows = [g.n] * nu
             self.ghosts = [torch.empty(0, dtype=torch.int64, device=g.device) for _ in range(nu - 1)]
         else:
