@@ -209,6 +209,27 @@ int mgp_edge_values(const int32_t* tri_row, const int32_t* tri_col, const float*
                     int64_t M, const float* degree_unnorm, const float* degree, float eps,
                     int which, float* out, void* stream);
 
+/* Entry-balanced row tiles for the single-column tile kernels (graph.py c1_balanced_tiles; docs/kernels/spmm.md, round 8): a
+ * second tile set over the SAME col / vals of a CSR (mgp_csr_t, below) in natural row order, whose tiles are at most 64
+ * consecutive rows and at most MGP_C1_TILE_CAP padded entries (a single heavier row is a tile of its own).  Tile t owns positions 64 t .. 64 t + 63 of a padded
+ * position space: its rows first, then empty positions.  A HOST struct of device pointers and host numbers, named by
+ * mgp_csr_t.c1_tiles.  Taken at C == 1 only, on a CSR without a row order, without a row offset, one tile per workgroup
+ * (csrc/spmm_policy.h c1_balanced); the 64-row set of the CSR stays what every other kernel reads. */
+typedef struct {
+  int64_t n;                 /* rows of the CSR the set was cut for (== mgp_csr_t.n) */
+  const int32_t* tile_ptr;   /* [tiles + 1] offsets into tile_cols */
+  const int32_t* tile_cols;  /* distinct column ids of each balanced tile, ascending */
+  const uint16_t* lid;       /* [nnz] position of every entry's column in its balanced tile's list */
+  const int32_t* rowptr_pad; /* [64 tiles + 1] entry offsets of the positions (an empty position repeats its offset) */
+  const int32_t* tile_shift; /* [tiles + 1] empty positions in front of tile t: its first row is 64 t - tile_shift[t];
+                                tile_shift[tiles] = 64 tiles - n.  ONE allocation with the offsets: tile_shift == rowptr_pad +
+                                64 tiles + 1, else the set is not taken (the kernels have no scalar register for another pointer) */
+  int32_t tiles;             /* T */
+  int32_t max_cols;          /* max over balanced tiles of the list length */
+  int32_t max_entries;       /* max over balanced tiles of the padded entry count */
+  int32_t reserved;
+} mgp_c1_tiles_t;
+
 /* ---------------------------------------------------------------------------------------------
  * The hot kernel: fused CSR SpMV / SpMM with the symmetric Laplacian.
  *   xs_j = pre ? pre[j] * X[j,:] : X[j,:]
@@ -236,8 +257,7 @@ typedef struct {
   int32_t spmv_lanes;        /* C == 1 row-group kernel: lanes per row for THIS matrix, one of 4, 8, 16, 32, 64; 0 = the process
                                 default (mgp_spmm_set_group_hint, initially 16).  Any other value: MGP_ERR_ARG */
   /* tiles over a row ORDER (mgp_graph_tiles with row_order): all NULL = tile t is rows 64 t .. 64 t + 63.
-   * All three or none; tile_rowptr ALONE (tile_vals and tile_rowid NULL) is no row order: it then names, as a HOST pointer, the
-   * mgp_c1_tiles_t of this CSR (below), which must live as long as the struct and every plan made from it are used */
+   * Three DEVICE arrays, all three or none: a partial order selects no dictionary kernel */
   const int32_t* tile_rowptr;  /* [n+1] entry offsets in tile order */
   const float* tile_vals;      /* [nnz] vals gathered through emap */
   const int32_t* tile_rowid;   /* [n] original row of every tile-order position (= row_order) */
@@ -247,30 +267,10 @@ typedef struct {
   const float* mt_img;         /* [64 (mt_steps + 32)] tile values in MFMA operand order */
   int32_t mt_tiles;            /* ceil(n / 16) */
   int32_t mt_steps;            /* mt_sptr[mt_tiles] */
+  /* entry-balanced tile set for the single-column tile kernels (mgp_c1_tiles_t, above); NULL = none.  A HOST pointer: the
+   * descriptor must live as long as the struct and every plan made from it are used */
+  const mgp_c1_tiles_t* c1_tiles;
 } mgp_csr_t;
-
-/* Entry-balanced row tiles for the single-column tile kernels (graph.py c1_balanced_tiles; docs/kernels/spmm.md, round 8): a
- * second tile set over the SAME col / vals of a CSR in natural row order, whose tiles are at most 64 consecutive rows and at most
- * MGP_C1_TILE_CAP padded entries (a single heavier row is a tile of its own).  Tile t owns positions 64 t .. 64 t + 63 of a padded
- * position space: its rows first, then empty positions.  A HOST struct of device pointers and host numbers, named by
- * mgp_csr_t.tile_rowptr when that CSR has no row order (mgp_csr_t keeps its size and layout).  Taken at C == 1 only, without a row
- * offset, one tile per workgroup (csrc/spmm.hip c1_balanced); the 64-row set of the CSR stays what every other kernel reads. */
-typedef struct {
-  int64_t magic;             /* MGP_C1_TILES_MAGIC: anything else and the set is not taken */
-  int64_t n;                 /* rows of the CSR the set was cut for (== mgp_csr_t.n) */
-  const int32_t* tile_ptr;   /* [tiles + 1] offsets into tile_cols */
-  const int32_t* tile_cols;  /* distinct column ids of each balanced tile, ascending */
-  const uint16_t* lid;       /* [nnz] position of every entry's column in its balanced tile's list */
-  const int32_t* rowptr_pad; /* [64 tiles + 1] entry offsets of the positions (an empty position repeats its offset) */
-  const int32_t* tile_shift; /* [tiles + 1] empty positions in front of tile t: its first row is 64 t - tile_shift[t];
-                                tile_shift[tiles] = 64 tiles - n.  ONE allocation with the offsets: tile_shift == rowptr_pad +
-                                64 tiles + 1, else the set is not taken (the kernels have no scalar register for another pointer) */
-  int32_t tiles;             /* T */
-  int32_t max_cols;          /* max over balanced tiles of the list length */
-  int32_t max_entries;       /* max over balanced tiles of the padded entry count */
-  int32_t reserved;
-} mgp_c1_tiles_t;
-#define MGP_C1_TILES_MAGIC 0x31435f5053474d4dLL   /* "MMGSP_C1" */
 
 /* Padded entries a workgroup of the single-column tile kernels holds in registers (4 entries x NQ = 4 quads x 256 lanes): what
  * the balanced cut caps a tile at.  csrc/spmm.hip asserts it against the kernel's constants. */

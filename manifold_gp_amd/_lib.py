@@ -33,6 +33,14 @@ class MgpError(RuntimeError):
         super().__init__("%s failed: %s" % (fn, what))
 
 
+class C1TilesT(Structure):
+    """mgp_c1_tiles_t: the entry-balanced tile set of a CSR in natural row order, a HOST struct that CsrT.c1_tiles points to
+    (include/mgp_hip.h).  graph.c1_balanced_tiles keeps it, with its tensors, in tiles["c1"]."""
+    _fields_ = [("n", c_int64), ("tile_ptr", c_void_p), ("tile_cols", c_void_p), ("lid", c_void_p),
+                ("rowptr_pad", c_void_p), ("tile_shift", c_void_p), ("tiles", c_int32), ("max_cols", c_int32),
+                ("max_entries", c_int32), ("reserved", c_int32)]
+
+
 class CsrT(Structure):
     _fields_ = [("n", c_int64), ("rowptr", c_void_p), ("col", c_void_p), ("vals", c_void_p),
                 ("diag", c_void_p),
@@ -40,18 +48,8 @@ class CsrT(Structure):
                 ("tile_rows", c_int32), ("tile_max_cols", c_int32), ("tile_max_entries", c_int32),
                 ("spmv_lanes", c_int32), ("tile_rowptr", c_void_p), ("tile_vals", c_void_p),
                 ("tile_rowid", c_void_p),
-                ("mt_sptr", c_void_p), ("mt_dcol", c_void_p), ("mt_img", c_void_p), ("mt_tiles", c_int32), ("mt_steps", c_int32)]
-
-
-class C1TilesT(Structure):
-    """mgp_c1_tiles_t: the entry-balanced tile set of a CSR in natural row order, a HOST struct that CsrT.tile_rowptr names when
-    tile_vals and tile_rowid are NULL (include/mgp_hip.h).  graph.c1_balanced_tiles keeps it, with its tensors, in tiles["c1"]."""
-    _fields_ = [("magic", c_int64), ("n", c_int64), ("tile_ptr", c_void_p), ("tile_cols", c_void_p), ("lid", c_void_p),
-                ("rowptr_pad", c_void_p), ("tile_shift", c_void_p), ("tiles", c_int32), ("max_cols", c_int32),
-                ("max_entries", c_int32), ("reserved", c_int32)]
-
-
-C1_TILES_MAGIC = 0x31435f5053474d4d
+                ("mt_sptr", c_void_p), ("mt_dcol", c_void_p), ("mt_img", c_void_p), ("mt_tiles", c_int32), ("mt_steps", c_int32),
+                ("c1_tiles", c_void_p)]
 
 
 # Entry-balanced tiles of the single-column tile kernels (graph.c1_balanced_tiles): [True] = a CSR whose tiles carry the set
@@ -388,7 +386,7 @@ def csr_struct(n, rowptr, col, vals, diag, ncols=0, tiles=None, tile_vals=None, 
             s.tile_vals = tile_vals.data_ptr()
         c1 = tiles.get("c1") if C1_BALANCED[0] else None
         if c1 is not None and tiles.get("rowid") is None and not ncols and c1["struct"].n == int(n):
-            s.tile_rowptr = ctypes.addressof(c1["struct"])      # no row order: the field names the host descriptor of the set
+            s.c1_tiles = ctypes.addressof(c1["struct"])         # the host descriptor of the set (it lives in the tiles dict)
     if mt is not None:        # graph.MtPlan: dense 16-row tiles for the matrix-core SpMM (48 <= C <= 256)
         s.mt_sptr, s.mt_dcol, s.mt_img = mt.sptr.data_ptr(), mt.dcol.data_ptr(), mt.img.data_ptr()
         s.mt_tiles, s.mt_steps = mt.tiles, mt.steps

@@ -1575,10 +1575,9 @@ extern "C" int mgp_cg_plan_rebind(void* plan, const mgp_operator_t* op, const fl
                     (op->L.tile_rowid != nullptr) == (o.L.tile_rowid != nullptr) &&
                     (op->L.mt_img != nullptr) == (o.L.mt_img != nullptr) && op->L.mt_tiles == o.L.mt_tiles &&
                     op->L.mt_steps == o.L.mt_steps && op->L.spmv_lanes == o.L.spmv_lanes &&
-                    // no row order: tile_rowptr names the host descriptor of the entry-balanced tile set (mgp_c1_tiles_t),
-                    // whose tile count and maxima sized grids and LDS -- the SAME descriptor or none (the plan's one is not
-                    // read again: its owner may be gone)
-                    (op->L.tile_vals || op->L.tile_rowid || op->L.tile_rowptr == o.L.tile_rowptr) &&
+                    // the entry-balanced tile set's count and maxima sized grids and LDS: the SAME descriptor or none (the plan's
+                    // one is not read again: its owner may be gone)
+                    op->L.c1_tiles == o.L.c1_tiles &&
                     mgp_spmm_dot_blocks_for(&op->L, pl->C) == pl->nb_loc &&
                     (!pl->ch.fold || op->pre == op->post);        // the folded step's identity needs ONE vector P
   if (!same) return MGP_ERR_UNSUPPORTED;

@@ -16,7 +16,7 @@ inline mgp_operator_t mgp_operator_copy(const mgp_operator_t* op) {
 
 // spmv_lanes of an mgp_csr_t: lanes per row of the C == 1 row-group kernel, 0 = the process default (include/mgp_hip.h).
 // Every entry that takes the struct refuses another value with MGP_ERR_ARG.
-inline bool mgp_spmv_lanes_ok(int lanes) {
+constexpr bool mgp_spmv_lanes_ok(int lanes) {
   return lanes == 0 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64;
 }
 

@@ -27,15 +27,13 @@
 #include <type_traits>
 #include "mgp_common.h"
 #include "mgp_internal.h"
+#include "spmm_policy.h"
 #include "cg_rule.h"
 #include "cg_handoff.h"
 #include <hip/hip_ext.h>
 #include <vector>
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kMaxGrid = 4096;
 
 struct SpmmArgs {
   int64_t n;
@@ -1250,7 +1248,6 @@ __global__ __launch_bounds__(256, 4) void spmm_tile_q_kernel(SpmmArgs p, TileArg
 //   * LDS: 64 bytes x min(dictionary, 1024 columns): 64 KB on the C3 graph (two workgroups per CU), 40 KB on the 1M swiss
 //     roll.  The 0.7 % of tiles with more than 1024 columns take a second slice pass per chunk (entries whose id lies
 //     outside the staged slice contribute value 0 through a clamped id).
-constexpr int kWideCap = 1024;     // dictionary columns staged per slice (64 bytes each)
 constexpr int kWideRQ = 16;        // quads of a row held in registers for all chunks of a tile
 
 template <bool PRE, bool CBV>
@@ -1426,11 +1423,7 @@ __global__ __launch_bounds__(256, 2) void spmm_tile_wide_kernel(SpmmArgs p, Tile
 //     visited in both slices with the out-of-slice entries masked (value 0, clamped slot); the padding entries at a
 //     row's end (value 0, id = the row's own slot) are masked the same way and never stall anything but their own row.
 // Summation order per row: entries in storage order within a slice, slices ascending -- fixed, independent of the grid.
-constexpr int kDictThreads = 1024;
-constexpr int kDictLdsBudget = 160 * 1024 - 2048;   // bytes of LDS a workgroup may carve (160 KiB per CU)
-// staged float4 per thread and slice (their registers are live across the walk: what the 128-VGPR budget of a
-// 16-wave workgroup leaves)
-constexpr int dict_max_u(int nv) { return nv == 1 ? 7 : (nv == 2 ? 5 : 4); }
+// (kDictThreads, kDictLdsBudget and dict_max_u, the staged float4 per thread and slice: spmm_policy.h)
 
 // acc += v_e * a_e for the four entries of a quad, two floats at a time (v_pk_fma_f32 with the op_sel broadcast of one
 // half of the (x, y) / (z, w) value pair; entry order 0, 1, 2, 3)
@@ -1806,96 +1799,38 @@ struct SpmvTimer {
 };
 SpmvTimer g_spmv_timer;
 
-struct Plan {
-  int grid;
-  int64_t rows_per_block;
-};
-
-Plan make_plan(int64_t n, int rows_per_pass) {
-  // contiguous row range per workgroup (a multiple of one pass of its lane groups), grid <= kMaxGrid
-  int64_t rpb = rows_per_pass;
-  int64_t grid = mgp_cdiv(n, rpb);
-  if (grid > kMaxGrid) {
-    rpb = mgp_cdiv(mgp_cdiv(n, kMaxGrid), rows_per_pass) * rows_per_pass;
-    grid = mgp_cdiv(n, rpb);
-  }
-  if (grid < 1) grid = 1;
-  return Plan{(int)grid, rpb};
-}
-
-// C == 1 row-group shape: lanes per row (4 entries per lane per pass) and rows in flight per lane group.  The lanes are a
-// property of the matrix and travel with it (mgp_csr_t.spmv_lanes: the host wrapper derives them from the mean padded row
-// length of the graph it built); g_row_group_hint is only the default for structs that leave the field 0
-// (mgp_spmm_set_group_hint).  Measured best on the 60k and 500k graphs: 8 lanes x 1 row (tools/tune_spmv.py).
-std::atomic<int> g_row_group_hint{16};
-std::atomic<int> g_rows_in_flight{1};
-// Lab switches (include/mgp_hip.h): process-wide, read ONCE per call by spmm_plan, whose answer is passed down by value --
-// the helpers of one call cannot see two settings.  (Two CALLS -- sizing the dot partials, then launching -- can still see
-// different settings: the header says the switches are not to be flipped while another thread is inside this family of calls.)
-std::atomic<int> g_tile_mode{1};
-std::atomic<int> g_tile_loop_mode{0};
-std::atomic<int> g_tile_small_mode{1};
-std::atomic<int> g_tile_wide_mode{1};
-std::atomic<int> g_spmm_v4_mode{1};
-std::atomic<int> g_dict_mode{1};
-std::atomic<int> g_mt_mode{1};
+// The lab switches (include/mgp_hip.h, mgp_spmm_set_*): process-wide; every call reads them ONCE and passes them to spmm_plan
+// and its kin by value (SpmmKnobs, spmm_policy.h)
+SpmmKnobs g_knobs;
+static_assert([] { for (int l = -1; l <= 65; ++l) if (spmm_lanes_ok(l) != mgp_spmv_lanes_ok(l)) return false; return true; }(),
+              "spmm_policy.h and mgp_internal.h disagree on mgp_csr_t.spmv_lanes");
 #ifdef MGP_STAMP
 std::atomic<int> g_stamp_enable{0};
 #endif
 
 }  // namespace
 
+// The lab switches (include/mgp_hip.h) write g_knobs; the last one returns the previous setting.
 extern "C" int mgp_spmm_set_group_hint(int lanes) {
   if (!mgp_spmv_lanes_ok(lanes) || lanes == 0) return MGP_ERR_ARG;
-  g_row_group_hint = lanes;
+  g_knobs.group_hint = lanes;
   return MGP_OK;
 }
-
 extern "C" int mgp_spmm_set_rows_in_flight(int rows) {
   if (rows != 1 && rows != 2 && rows != 4 && rows != 8) return MGP_ERR_ARG;
-  g_rows_in_flight = rows;
+  g_knobs.rows_in_flight = rows;
   return MGP_OK;
 }
-
 #ifdef MGP_STAMP
 extern "C" int mgp_stamp_enable(int on) { g_stamp_enable = on ? 1 : 0; return 0; }
 #endif
-
-extern "C" int mgp_spmm_set_tile_mode(int on) {
-  g_tile_mode = on ? 1 : 0;
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_tile_loop_mode(int on) {
-  g_tile_loop_mode = on ? 1 : 0;
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_v4_mode(int on) {
-  g_spmm_v4_mode = on == 2 ? 2 : (on ? 1 : 0);
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_tile_wide_mode(int on) {
-  g_tile_wide_mode = on == 2 ? 2 : (on ? 1 : 0);
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_tile_small_mode(int on) {
-  g_tile_small_mode = on ? 1 : 0;
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_dict_mode(int on) {
-  g_dict_mode = on == 2 ? 2 : (on ? 1 : 0);
-  return MGP_OK;
-}
-
-extern "C" int mgp_spmm_set_mt_mode(int on) {
-  const int prev = g_mt_mode;
-  g_mt_mode = on ? 1 : 0;
-  return prev;
-}
+extern "C" int mgp_spmm_set_tile_mode(int on) { g_knobs.tile = on ? 1 : 0; return MGP_OK; }
+extern "C" int mgp_spmm_set_tile_loop_mode(int on) { g_knobs.tile_loop = on ? 1 : 0; return MGP_OK; }
+extern "C" int mgp_spmm_set_v4_mode(int on) { g_knobs.v4 = on == 2 ? 2 : (on ? 1 : 0); return MGP_OK; }
+extern "C" int mgp_spmm_set_tile_wide_mode(int on) { g_knobs.tile_wide = on == 2 ? 2 : (on ? 1 : 0); return MGP_OK; }
+extern "C" int mgp_spmm_set_tile_small_mode(int on) { g_knobs.tile_small = on ? 1 : 0; return MGP_OK; }
+extern "C" int mgp_spmm_set_dict_mode(int on) { g_knobs.dict = on == 2 ? 2 : (on ? 1 : 0); return MGP_OK; }
+extern "C" int mgp_spmm_set_mt_mode(int on) { const int prev = g_knobs.mt; g_knobs.mt = on ? 1 : 0; return prev; }
 
 #ifdef MGP_MT_STAMP
 extern "C" int mgp_mt_set_stamp_buffer(void* buf) {
@@ -1918,320 +1853,21 @@ extern "C" int mgp_spmm_mt_fill(int64_t n, const int32_t* rowptr, const float* v
   return MGP_OK;
 }
 
-// ---- launch geometry of the kernel families: pure functions of the CSR and the width --------------------------------------
+// ---- which kernel runs, on which grid, LDS and tile set: spmm_plan (spmm_policy.h).  The entry points below answer from it. ----
 
-static int spmm_cols_group(int C) {
-  int g = 4;
-  while (g < C && g < 64) g <<= 1;
-  return g;
-}
-
-// rows a workgroup covers per pass (the grid / dot-partial count follows from it).  C in {4,8,12,16}
-// uses 64 whichever kernel runs (the row16 kernel needs 16-byte aligned X, the generic one does not)
-static int spmm_rows_per_pass(int C, int lanes, int rows_in_flight) {
-  if (C == 1) return (kBlock / lanes) * rows_in_flight;
-  if (C <= 16 && (C & 3) == 0) return (kBlock / 16) * 4;
-  return kBlock / spmm_cols_group(C) * 4;
-}
-
-// ---- the tile set of the C == 1 tile kernels: the 64-row tiles of the CSR, or its entry-balanced set ---------------------------
-// The set rides beside the CSR as a host descriptor (mgp_c1_tiles_t, include/mgp_hip.h): mgp_csr_t keeps its layout, and a CSR
-// without a row order names the descriptor through tile_rowptr, which is otherwise NULL there.
-static const mgp_c1_tiles_t* c1_set(const mgp_csr_t* L) {
-  if (!L->tile_rowptr || L->tile_vals || L->tile_rowid) return nullptr;
-  const mgp_c1_tiles_t* s = reinterpret_cast<const mgp_c1_tiles_t*>(L->tile_rowptr);
-  return s->magic == MGP_C1_TILES_MAGIC ? s : nullptr;
-}
-// the offsets of a row ORDER (all three arrays or none): tile_rowptr alone is the descriptor above, not an order
-static const int32_t* order_rowptr(const mgp_csr_t* L) { return (L->tile_vals || L->tile_rowid) ? L->tile_rowptr : nullptr; }
-
-// THE statement of when the balanced set (mgp_c1_tiles_t) runs; what builds it states when it exists (graph.py
-// c1_balanced_policy: natural order, a 64-row tile over MGP_C1_TILE_CAP entries, the folded CG step kept).  It serves C == 1 only,
-// positions that are rows (no row order), whole graphs (no row offset, no row slice) and one tile per workgroup (at most kMaxGrid
-// tiles: the single-tile form of the kernel; the lab switch mgp_spmm_set_tile_loop_mode runs the same set through the loop form,
-// one pass per workgroup, so that the two forms stay comparable bit for bit).  Everything else, and every other kernel, reads
-// the 64-row set and computes what it computed before the set existed.
-static bool c1_balanced(const mgp_csr_t* L, int C, int64_t row_offset) {
-  if (C != 1 || row_offset != 0) return false;
-  const mgp_c1_tiles_t* s = c1_set(L);
-  if (!s || !s->tile_ptr || !s->tile_cols || !s->lid || !s->rowptr_pad || !s->tile_shift) return false;
-  if (L->tile_rows != 64 || s->n != L->n) return false;
-  if (L->ncols != 0 && L->ncols != L->n) return false;
-  if (s->tiles < 1 || s->tiles > kMaxGrid || (s->max_entries & 3) != 0) return false;
-  // one allocation: the kernel finds the shift words behind the offsets (TileArgs)
-  if (s->tile_shift != s->rowptr_pad + ((int64_t)s->tiles * 64 + 1)) return false;
-  return (int64_t)s->tiles * 64 >= L->n && L->n >= s->tiles;       // every row in a tile, no tile without a row
-}
-
-static size_t tile_lds_bytes(const mgp_csr_t* L, bool balanced = false) {
-  if (balanced) return ((size_t)c1_set(L)->max_cols + (size_t)(c1_set(L)->max_entries >> 2)) * sizeof(float);
-  return ((size_t)L->tile_max_cols + (size_t)(L->tile_max_entries >> 2)) * sizeof(float);
-}
-
-static int tile_grid(const mgp_csr_t* L, int* tiles_per_block, bool balanced = false) {
-  if (balanced) {                 // one workgroup per tile (c1_balanced: at most kMaxGrid of them)
-    if (tiles_per_block) *tiles_per_block = 1;
-    return c1_set(L)->tiles;
-  }
-  const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
-  const int64_t tpb = mgp_cdiv(ntiles, kMaxGrid);
-  if (tiles_per_block) *tiles_per_block = (int)tpb;
-  return (int)mgp_cdiv(ntiles, tpb);
-}
-
-// small-C tile kernel: quads of partial sums staged at once: what is left of a quarter of the CU's LDS (160 KB, four
-// workgroups) behind the dictionary, in steps of 256, at least 1024 (the quads a workgroup holds in registers), at most the
-// largest tile
-static int tile_small_window(const mgp_csr_t* L) {
-  const int max_q = L->tile_max_entries >> 2;
-  const long budget = 40448 - (long)L->tile_max_cols * 16;
-  long w = budget > 0 ? budget / 16 / 256 * 256 : 0;
-  if (w < 1024) w = 1024;
-  if (w > max_q) w = (max_q + 255) / 256 * 256;
-  return (int)(w > 0 ? w : 256);
-}
-static size_t tile_small_lds_bytes(const mgp_csr_t* L, int C) {
-  const size_t max_q = (size_t)(L->tile_max_entries >> 2), w = (size_t)tile_small_window(L);
-  size_t b = ((size_t)L->tile_max_cols + (max_q < w ? max_q : w)) * 16;
-  const size_t red = (size_t)64 * C * sizeof(float);        // dot-partial staging reuses the same LDS
-  return b > red ? b : red;
-}
-
-static int tile_wide_cap(const mgp_csr_t* L) {
-  int cap = (L->tile_max_cols + 63) / 64 * 64;
-  if (cap > kWideCap) cap = kWideCap;
-  if (cap < 64) cap = 64;
-  return cap;
-}
-static size_t tile_wide_lds_bytes(const mgp_csr_t* L) {
-  const size_t b = (size_t)tile_wide_cap(L) * 64;
-  return b > 4096 ? b : 4096;                                // (dot-partial staging: 64 x 16 floats)
-}
-
-// lanes-over-columns dictionary kernel: slots per slice from what the stream leaves of the CU's LDS
-static int dict_nv(int C) { return (C + 63) / 64; }
-static int dict_stream_cap(const mgp_csr_t* L) { return (L->tile_max_entries + 7) / 8 * 8; }
-static int dict_slots(const mgp_csr_t* L, int C) {
-  const int nv = dict_nv(C);
-  const long left = (long)kDictLdsBudget - (long)dict_stream_cap(L) * 6 - (long)nv * 256;      // (the zero slot)
-  long s = left / (nv * 256L);
-  const long cap = (long)dict_max_u(nv) * kDictThreads / (16 * nv);      // staged float4 per thread <= dict_max_u
-  if (s > cap) s = cap;
-  s = s / 16 * 16;
-  // no point in slices larger than the largest dictionary
-  const long need = ((long)L->tile_max_cols + 15) / 16 * 16;
-  if (s > need) s = need;
-  return (int)s;
-}
-static size_t dict_lds_bytes(const mgp_csr_t* L, int C) {
-  const size_t d = (size_t)(dict_slots(L, C) + 1) * dict_nv(C) * 256 + (size_t)dict_stream_cap(L) * 6;
-  const size_t red = (size_t)64 * dict_nv(C) * 256;
-  return d > red ? d : red;
-}
-static int dict_grid(const mgp_csr_t* L) {
-  const int64_t ntiles = mgp_cdiv(L->n, L->tile_rows);
-  return (int)(ntiles < kMaxGrid ? ntiles : kMaxGrid);
-}
-
-// the CSR carries a usable dense 16-row tile image (mgp_spmm_mt_fill) for this width
-constexpr int kMtMinCols = 48;
-static bool mt_image_fits(const mgp_csr_t* L, int C) {
-  if (!L->mt_img || !L->mt_sptr || !L->mt_dcol || L->mt_tiles <= 0 || L->mt_steps <= 0) return false;
-  // below 48 columns most lanes of a wave's 64-column block idle: the gather kernel is faster there (C = 32: 34 us against 41)
-  if (C < kMtMinCols || C > 256 || (C & 3) != 0 || L->tile_rowid) return false;
-  if (L->ncols != 0 && L->ncols != L->n) return false;        // a row slice of a partitioned operator never carries an image
-  if ((int64_t)L->n * C * 4 >= (int64_t(1) << 31) || ((int64_t)L->mt_steps + 32) * 256 >= (int64_t(1) << 31)) return false;
-  if ((L->mt_steps & 15) != 0) return false;           // every tile a whole number of bodies of four blocks
-  return L->mt_tiles == (int32_t)mgp_cdiv(L->n, 16);
-}
-
-static TileArgs tile_args(const mgp_csr_t* L, int tiles_per_block, int part_window, bool balanced = false) {
-  if (balanced) {
-    const mgp_c1_tiles_t* s = c1_set(L);
-    return TileArgs{s->tile_ptr, s->tile_cols, s->lid, s->tiles, 1, s->max_cols, s->rowptr_pad, nullptr, nullptr,
-                    s->max_entries, part_window};         // (tile_shift stands behind rowptr_pad: c1_balanced)
-  }
-  return TileArgs{L->tile_ptr, L->tile_cols, L->lid, mgp_cdiv(L->n, L->tile_rows), tiles_per_block, L->tile_max_cols,
-                  order_rowptr(L), L->tile_vals, L->tile_rowid, L->tile_max_entries, part_window};
-}
-
-// ---- which kernel runs: the ONE statement of the policy -------------------------------------------------------------------
-// spmm_plan reads the switches once, applies the precedence order once and returns everything that follows from the choice.
-// The sizing call (mgp_spmm_dot_blocks_csr), the reporting call (mgp_spmm_kernel_choice) and the launch (spmm_launch) all
-// read this value: the planned kernel and the launched one cannot disagree.
-namespace {
-enum class SpmmFamily { RowGroups, Gather, TileC1, TileSmall, MatrixCore, Dict, TileWide };
-
-struct SpmmPlan {
-  int err;                  // MGP_OK; MGP_ERR_ARG (spmv_lanes); MGP_ERR_UNSUPPORTED (tile image + row offset + dot partials)
-  SpmmFamily family;
-  int grid;
-  size_t lds;               // dynamic LDS bytes
-  int dot_blocks;           // workgroups that write dot partials
-  bool align16;             // X, Y, base and dotw must be 16-byte aligned: MGP_ERR_ARG at launch otherwise
-  int64_t rows_per_block;   // RowGroups, Gather: contiguous row range of a workgroup
-  int lanes, rows_in_flight;    // RowGroups
-  bool v4_ok;               // Gather: switch and shape allow the float4 member (the launch adds the alignment test)
-  int tiles_per_block;      // TileC1, TileSmall, TileWide (Dict: 1)
-  bool one_tile;            // TileC1: the single-tile form of the kernel (tiles_per_block == 1 and the loop form not forced)
-  bool balanced;            // TileC1: on the entry-balanced tile set (c1_balanced); grid, dot_blocks and lds are that set's
-  int window;               // TileSmall: quads of partial sums staged per window
-  int slots, stream_cap;    // Dict
-  int wide_cap;             // TileWide
-};
-}  // namespace
-
-static SpmmPlan spmm_plan(const mgp_csr_t* L, int C, int64_t row_offset, bool with_dot) {
-  SpmmPlan pl{};
-  pl.tiles_per_block = 1;
-  if (!mgp_spmv_lanes_ok(L->spmv_lanes)) { pl.err = MGP_ERR_ARG; return pl; }
-  const int tile = g_tile_mode, tile_small = g_tile_small_mode, tile_wide = g_tile_wide_mode, v4 = g_spmm_v4_mode,
-            dict = g_dict_mode, mt = g_mt_mode;
-  // row-tile dictionaries present and switched on; an ordered tile view is all three arrays or none
-  const int ord = (order_rowptr(L) != nullptr) + (L->tile_vals != nullptr) + (L->tile_rowid != nullptr);
-  const bool dicts = tile && (ord == 0 || ord == 3) && L->lid && L->tile_ptr && L->tile_cols;
-  const bool dicts64 = dicts && L->tile_rows == 64 && (L->tile_max_entries & 3) == 0;      // 64-row tiles, quad-padded rows
-  const bool wide = C > 16 && C <= 256 && (C & 3) == 0;
-  const bool big_x = (size_t)L->n * (size_t)C * sizeof(float) >= ((size_t)96 << 20);   // the X block does not sit in the caches
-
-  // 1. C == 1 on 32 / 64 / 128-row tiles: the column dictionary of a tile staged in LDS (spmv_tile_kernel)
-  if (C == 1 && dicts && (L->tile_rows == 32 || L->tile_rows == 64 || L->tile_rows == 128) && tile_lds_bytes(L) <= 65536 - 64) {
-    pl.family = SpmmFamily::TileC1;
-    pl.balanced = c1_balanced(L, C, row_offset) && tile_lds_bytes(L, true) <= 65536 - 64;
-    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block, pl.balanced);
-    pl.one_tile = pl.tiles_per_block == 1 && !g_tile_loop_mode;
-    pl.lds = tile_lds_bytes(L, pl.balanced);
-    return pl;
-  }
-  // 2. C in {4, 8, 12, 16} on 64-row tiles whose staged data (dictionary rows + matrix stream) fits the LDS budget
-  //    (spmm_tile_q_kernel); [n, C] blocks with C a multiple of 4 are 16-byte aligned row by row
-  if ((C == 4 || C == 8 || C == 12 || C == 16) && tile_small && dicts64 && tile_small_lds_bytes(L, C) <= 65536 - 64) {
-    pl.family = SpmmFamily::TileSmall;
-    pl.align16 = true;
-    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
-    pl.lds = tile_small_lds_bytes(L, C);
-    pl.window = tile_small_window(L);
-    return pl;
-  }
-  // 3. 48 <= C <= 256 on the matrix cores (spmm_mt_kernel): taken when the CSR carries the dense 16-row tile image
-  //    (mgp_spmm_mt_fill; the host wrapper builds it for graphs in natural row order whose tiles are at least 1/8 full) and the
-  //    call has no row offset (weighted dot-product partials included: one row of partials per workgroup).
-  //    mgp_spmm_set_mt_mode(0) = never (A/B runs, tests).
-  if (mt && mt_image_fits(L, C)) {
-    if (row_offset == 0) {
-      pl.family = SpmmFamily::MatrixCore;
-      pl.align16 = true;
-      pl.grid = pl.dot_blocks = (int)mgp_cdiv((int64_t)L->mt_tiles * ((C + 63) / 64), kBlock / 64);
-      return pl;
-    }
-    // a CSR that carries the tile image, a row offset AND dot partials: mgp_spmm_dot_blocks_csr sized them for the matrix-core
-    // kernel, which takes no row offset -- the one combination that is refused.  Without dot partials the rules below apply.
-    if (with_dot) { pl.err = MGP_ERR_UNSUPPORTED; return pl; }
-  }
-  // 4. 16 < C <= 256 on 64-row tiles with lanes over columns (spmm_dict_kernel), at least 32 slots per slice.
-  //    mgp_spmm_set_dict_mode: 0 never, 1 (default) where it was measured to win, 2 wherever the shape allows.
-  //    Measured (tools/lab/time_spmm_wide.py, round 3; us: this kernel | chunked dictionary kernel | float4 gather | per-column
-  //    gather):  60k graph  C = 64: 52 | 84 | 54 | 63   C = 128: 90 | 160 | 101 | 91   C = 256: 176 | 319 | 204 | 186
-  //              1M graph   C = 64: 704 | 777 | 1020 | 1188   C = 128: 1201 | 1458 | 2084 | 3037   C = 256: 2380 | 2871 | 6515 | 6828
-  //    -> taken from 64 columns up when the X block (n x C floats) is 96 MB or more, i.e. does not sit in the caches.
-  if (wide && dict && dicts64 && dict_slots(L, C) >= 32 && (dict == 2 || (C >= 64 && big_x))) {
-    pl.family = SpmmFamily::Dict;
-    pl.align16 = true;       // the kernel moves 16 bytes per lane (C % 4 == 0 makes every row aligned once the block is)
-    pl.grid = pl.dot_blocks = dict_grid(L);
-    pl.lds = dict_lds_bytes(L, C);
-    pl.slots = dict_slots(L, C);
-    pl.stream_cap = dict_stream_cap(L);
-    return pl;
-  }
-  // 5. 16 < C <= 256 on 64-row tiles in 16-column chunks (spmm_tile_wide_kernel).
-  //    Measured (tools/lab/time_spmm_wide.py): on the 60k graph the per-entry gather kernel reads its X rows out of L2 and
-  //    wins from 64 columns up (63 vs 84 us at C = 64, 91 vs 158 us at C = 128; 47 vs 59 us at C = 32 the other way, but see below); on
-  //    the 1M graph, whose X block does not fit the caches, the dictionary kernel is 1.5-2.4x faster at every width
-  //    (1.48 vs 3.04 ms at C = 128).  mode 2 forces it at any size (tests, A/B).
-  //    (and up to 64 columns the float4-lane gather kernel beats both on a cache-resident X block: 33 us at C = 32)
-  if (wide && tile_wide && dicts64 && (tile_wide == 2 || big_x)) {
-    pl.family = SpmmFamily::TileWide;
-    pl.align16 = true;
-    pl.grid = pl.dot_blocks = tile_grid(L, &pl.tiles_per_block);
-    pl.lds = tile_wide_lds_bytes(L);
-    pl.wide_cap = tile_wide_cap(L);
-    return pl;
-  }
-  // 6. C == 1 without dictionaries: a row per lane group (spmv_kernel); the lanes are the matrix's own, 0 = process default
-  if (C == 1) {
-    pl.family = SpmmFamily::RowGroups;
-    pl.lanes = L->spmv_lanes ? L->spmv_lanes : g_row_group_hint.load();
-    pl.rows_in_flight = g_rows_in_flight;
-    if (pl.rows_in_flight > pl.lanes) pl.rows_in_flight = pl.lanes;   // lane t finishes row t: needs R <= G
-    const Plan rows = make_plan(L->n, spmm_rows_per_pass(1, pl.lanes, pl.rows_in_flight));
-    pl.grid = pl.dot_blocks = rows.grid;
-    pl.rows_per_block = rows.rows_per_block;
-    return pl;
-  }
-  // 7. C > 1 gather from memory.  The plan fixes the FAMILY and its grid; the launch picks the member (row16, float4 lanes,
-  //    per-column) by pointer alignment, which a sizing call cannot know.  That is sound because all three cover the same
-  //    make_plan(n, spmm_rows_per_pass(C)) row ranges and therefore write the same dot-partial blocks.
-  //    float4 member, measured (tools/lab/time_spmm_wide.py): 33 vs 59 us at C = 32 and 54 vs 63 us at C = 64 on the 60k graph, but
-  //    101 vs 91 us at C = 128 (the X block no longer sits in L2 and the per-column kernel's whole-line pieces use
-  //    the Infinity Cache path better); on the 1M graph, when the dictionaries are not there, it wins at every width.
-  //    (quad-padded rows are what the tile builder guarantees: the CSR of a graph without dictionaries keeps the per-column kernel)
-  pl.family = SpmmFamily::Gather;
-  pl.v4_ok = v4 && wide && (v4 == 2 || C <= 64 || big_x) && (L->tile_max_entries & 3) == 0 && L->lid != nullptr;
-  const Plan rows = make_plan(L->n, spmm_rows_per_pass(C, 0, 0));
-  pl.grid = pl.dot_blocks = rows.grid;
-  pl.rows_per_block = rows.rows_per_block;
-  return pl;
-}
-
-int mgp_tile_plan(const mgp_csr_t* L) {
-  if (!L) return 0;
-  const SpmmPlan pl = spmm_plan(L, 1, 0, false);
-  return pl.err == MGP_OK && pl.family == SpmmFamily::TileC1;
-}
-
-// Static LDS of spmv_tile_cgstep_kernel on top of the tile SpMV's dynamic LDS (wave sums, state, hand-off words: 76 bytes, rounded up);
-// the plain tile kernel has 32 bytes and spmm_plan leaves 64 under the 64 KB of a workgroup
-constexpr size_t kCgStepStaticLds = 128;
-
-// 1 when spmv_tile_cgstep_kernel can run on L: the 64-row C == 1 tile plan, with room for the step's static LDS
-int mgp_spmm_cgstep_fits(const mgp_csr_t* L) {
-  if (!L) return 0;
-  const SpmmPlan pl = spmm_plan(L, 1, 0, true);
-  return pl.err == MGP_OK && pl.family == SpmmFamily::TileC1 && L->tile_rows == 64 && pl.lds + kCgStepStaticLds <= 65536;
-}
-
-int mgp_spmm_dot_blocks_for(const mgp_csr_t* L, int C) {
-  if (!L) return MGP_ERR_ARG;
-  const SpmmPlan pl = spmm_plan(L, C, 0, false);
-  return pl.err != MGP_OK ? pl.err : pl.dot_blocks;
-}
-
-// the public numbers of the families (include/mgp_hip.h; 4 was round 4's persistent 8-lanes-per-row dictionary kernel:
-// measured slower, removed in round 5)
+int mgp_tile_plan(const mgp_csr_t* L) { return spmm_tile_plan(L, g_knobs); }
+int mgp_spmm_cgstep_fits(const mgp_csr_t* L) { return spmm_cgstep_fits(L, g_knobs); }
+int mgp_spmm_dot_blocks_for(const mgp_csr_t* L, int C) { return spmm_dot_blocks_for(L, C, g_knobs); }
 extern "C" int mgp_spmm_kernel_choice(const mgp_csr_t* L, int C, int with_dot, int64_t row_offset) {
-  if (!L || L->n <= 0 || C <= 0 || C > 256) return MGP_ERR_ARG;
-  const SpmmPlan pl = spmm_plan(L, C, row_offset, with_dot != 0);
-  if (pl.err != MGP_OK) return pl.err;
-  switch (pl.family) {
-    case SpmmFamily::TileC1: return 1;
-    case SpmmFamily::TileSmall: return 2;
-    case SpmmFamily::MatrixCore: return 3;
-    case SpmmFamily::Dict: return 5;
-    case SpmmFamily::TileWide: return 6;
-    default: return 0;      // gather (C == 1: row groups)
-  }
+  return spmm_kernel_choice(L, C, with_dot, row_offset, g_knobs);
 }
+extern "C" int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C) { return spmm_dot_blocks_csr(L, C, g_knobs); }
+extern "C" int mgp_spmm_dot_blocks(int64_t n, int C) { return spmm_dot_blocks(n, C, g_knobs); }
 
-extern "C" int mgp_spmm_dot_blocks_csr(const mgp_csr_t* L, int C) {
-  if (!L || L->n <= 0 || C <= 0) return MGP_ERR_ARG;
-  return mgp_spmm_dot_blocks_for(L, C);
-}
-
-// no CSR: the gather kernels' count, C == 1 with the process-default lanes
-extern "C" int mgp_spmm_dot_blocks(int64_t n, int C) {
-  if (n <= 0 || C <= 0) return MGP_ERR_ARG;
-  const int lanes = g_row_group_hint, rif = g_rows_in_flight;
-  return make_plan(n, spmm_rows_per_pass(C, lanes, rif < lanes ? rif : lanes)).grid;
+// the kernel argument of the plan's tile set
+static TileArgs tile_args(const SpmmTileSet& s, int tiles_per_block, int part_window) {
+  return TileArgs{s.tile_ptr, s.tile_cols, s.lid, s.tiles, tiles_per_block, s.max_cols, s.rowptr_t, s.vals_t, s.rowid, s.max_entries,
+                  part_window};
 }
 
 template <int G, bool PRE, bool CBV>
@@ -2305,8 +1941,8 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
   p.rows_per_block = pl.rows_per_block;
   switch (pl.family) {
   case SpmmFamily::TileC1: {
-    TileArgs ta = tile_args(L, pl.tiles_per_block, 0, pl.balanced);
-    if (pl.balanced) p.n = (int64_t)c1_set(L)->tiles * 64;      // the padded position space
+    TileArgs ta = tile_args(pl.set, pl.tiles_per_block, 0);
+    p.n = pl.set.n;       // the positions of the set: the rows, or the padded space of the balanced set
     if (record_to) {
       TileLaunchRecord rec{p, ta};
       memcpy(record_to, &rec, sizeof(rec));
@@ -2327,7 +1963,7 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
     else forms(IntC<512>{});
   } break;
   case SpmmFamily::TileSmall: {
-    TileArgs ta = tile_args(L, pl.tiles_per_block, pl.window);
+    TileArgs ta = tile_args(pl.set, pl.tiles_per_block, pl.window);
     with_quads(C, [&](auto c4) { with_pre(pre, [&](auto P) {
       hipLaunchKernelGGL((spmm_tile_q_kernel<decltype(c4)::value, decltype(P)::value, CB>), dim3(grid), dim3(256), lds, st, p, ta);
     }); });
@@ -2347,7 +1983,7 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
     });
   } break;
   case SpmmFamily::Dict: {
-    TileArgs ta = tile_args(L, 1, 0);
+    TileArgs ta = tile_args(pl.set, 1, 0);
     const int S = pl.slots, cap = pl.stream_cap;
     hipError_t attr = hipSuccess;
     auto slices = [&](auto nv) { with_pre(pre, [&](auto P) {
@@ -2366,7 +2002,7 @@ int spmm_launch(const SpmmPlan& pl, const mgp_csr_t* L, void* record_to, SpmmArg
     MGP_HIP_TRY(attr);
   } break;
   case SpmmFamily::TileWide: {
-    TileArgs ta = tile_args(L, pl.tiles_per_block, 0);
+    TileArgs ta = tile_args(pl.set, pl.tiles_per_block, 0);
     const int cap = pl.wide_cap;
     with_pre(pre, [&](auto P) {
       hipLaunchKernelGGL((spmm_tile_wide_kernel<decltype(P)::value, CB>), dim3(grid), dim3(256), lds, st, p, ta, cap);
@@ -2430,7 +2066,7 @@ int mgp_spmm_fused_opts(const mgp_csr_t* L, const float* X, int C, float* Y, flo
   if (L->n <= 0 || C <= 0 || C > 256) return C > 256 ? MGP_ERR_UNSUPPORTED : MGP_ERR_ARG;
   if (X == Y) return MGP_ERR_ARG;  // rows gather other rows of X: never in place
   const bool self_dot = o.self_dot && dot_partials;
-  const SpmmPlan pl = spmm_plan(L, C, o.row_offset, (dotw || self_dot) && dot_partials);
+  const SpmmPlan pl = spmm_plan(L, C, o.row_offset, (dotw || self_dot) && dot_partials, g_knobs);
   if (pl.err != MGP_OK) return pl.err;
   if (o.self_dot && (pl.family != SpmmFamily::TileC1 || dotw || o.cbv || !dot_partials)) return MGP_ERR_UNSUPPORTED;
   SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, X, Y, C, a, b, pre, post, base, cb, co,
@@ -2456,17 +2092,17 @@ int mgp_spmm_cgstep(const mgp_csr_t* L, const float* T, float a, float b, const 
   if (!L || !L->rowptr || !L->col || !L->vals || !L->diag || !T || L->n <= 0) return MGP_ERR_ARG;
   if (!cs.r || !cs.x || !cs.p || !cs.s || !cs.pd_rr || !cs.pd_delta || !cs.blk || !cs.state || !cs.host_state || !cs.host_resid ||
       !cs.arrive || (cs.us && !cs.pre) || T == cs.r || T == cs.us) return MGP_ERR_ARG;
-  const SpmmPlan pl = spmm_plan(L, 1, 0, true);
+  const SpmmPlan pl = spmm_plan(L, 1, 0, true, g_knobs);
   if (pl.err != MGP_OK) return pl.err;
-  if (pl.family != SpmmFamily::TileC1 || L->tile_rows != 64 || pl.lds + kCgStepStaticLds > 65536) return MGP_ERR_UNSUPPORTED;
+  if (!spmm_cgstep_ok(pl, L)) return MGP_ERR_UNSUPPORTED;
   if (cs.nbs != pl.dot_blocks || cs.nbs < 1 || cs.nbs > 16 * 256) return MGP_ERR_ARG;
   // X = t; base = r enters through cs (form 2: dgamma), cb = 1; Y, the dot hooks, skip and tick are not used by this kernel:
   // the done flag and the iteration come with the scalar block, and the first SpMV of the step has ticked.  The kernel does not
   // even load them (TileView<true> in spmv_tile_body holds them as constants): a caller that sets one here must change that view
-  SpmmArgs p{L->n, L->rowptr, L->col, L->vals, L->diag, T, nullptr, 1, a, b, nullptr, post, nullptr, 1.f, co,
+  // (n: the positions of the plan's tile set -- the rows, or the padded space of the balanced set)
+  SpmmArgs p{pl.set.n, L->rowptr, L->col, L->vals, L->diag, T, nullptr, 1, a, b, nullptr, post, nullptr, 1.f, co,
              nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
-  const TileArgs ta = tile_args(L, pl.tiles_per_block, 0, pl.balanced);
-  if (pl.balanced) p.n = (int64_t)c1_set(L)->tiles * 64;        // the padded position space
+  const TileArgs ta = tile_args(pl.set, pl.tiles_per_block, 0);
   const dim3 grid(pl.grid), block(256);
   hipStream_t st = mgp_stream(stream);
   auto step = [&](auto ds, auto one) {

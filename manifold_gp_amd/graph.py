@@ -74,7 +74,7 @@ def build_tiles(n, rowptr, col, nnz, tile_rows=None, order=None):
 # takes a dependent trip to memory behind its first barrier.  On a k-NN graph a third of the fixed 64-row tiles do.  The balanced
 # set cuts the rows, in their natural order, into tiles of at most 64 rows AND at most C1_TILE_CAP padded entries.
 C1_TILE_CAP = 4096         # = MGP_C1_TILE_CAP (include/mgp_hip.h) = 4 * NQ * BS of the kernel (tests/test_c1_balanced_tiles_cpu.py)
-C1_MAX_TILES = 4096        # the single-tile form of the kernel: one workgroup per tile (csrc/spmm.hip kMaxGrid)
+C1_MAX_TILES = 4096        # the single-tile form of the kernel: one workgroup per tile (csrc/spmm_policy.h kMaxGrid)
 C1_FOLD_PARTIALS = 1024    # partials the folded CG step sums with four slots per lane (csrc/cg_policy.h)
 C1_BALANCED = _lib.C1_BALANCED      # [True]: CSRs carry the balanced set where the policy builds it; [False]: the 64-row set alone
 
@@ -159,7 +159,7 @@ def c1_balanced_tiles(n, rowptr, col, nnz, tiles):
         return None
     tile_cols = tile_cols[:total.value].clone()
     # the host descriptor the library reads (mgp_c1_tiles_t); it lives in this dict beside the tensors it points into
-    desc = _lib.C1TilesT(_lib.C1_TILES_MAGIC, int(n), tile_ptr.data_ptr(), tile_cols.data_ptr(), lid.data_ptr(), rowptr_pad.data_ptr(),
+    desc = _lib.C1TilesT(int(n), tile_ptr.data_ptr(), tile_cols.data_ptr(), lid.data_ptr(), rowptr_pad.data_ptr(),
                          shift.data_ptr(), T, mc.value, me.value, 0)
     return dict(tile_ptr=tile_ptr, tile_cols=tile_cols, lid=lid, rowptr_pad=rowptr_pad, struct=desc,
                 tile_shift=shift, T=T, max_cols=mc.value, max_entries=me.value,

@@ -1,6 +1,6 @@
 """The 300,071-node swiss roll that the past-the-caps tests share (tests/test_gpu_past_caps.py, tests/test_gpu_solver_contract.py).
 
-n = 300,071 is just beyond every size cap of the forward SpMM and the CG kernels (csrc/spmm.hip kMaxGrid = 4096 workgroups,
+n = 300,071 is just beyond every size cap of the forward SpMM and the CG kernels (csrc/spmm_policy.h kMaxGrid = 4096 workgroups,
 csrc/cg.hip 2 x 32 x TS delta partials per round trip): ceil(n / 64) = 4689 row tiles (two tiles per workgroup, the last
 workgroup holds one), n % 64 = 39 and n % 16 = 7 (ragged last tiles).  Built as `swiss150k` of tests/test_gpu_gradients.py
 is: k = 10, the bandwidth from synth.bandwidth_rule on the nearest-neighbour distances.  Each module that uses it builds the graphs
@@ -12,7 +12,7 @@ import torch
 
 N = 300_071
 K = 10
-MAX_GRID = 4096            # csrc/spmm.hip kMaxGrid
+MAX_GRID = 4096            # csrc/spmm_policy.h kMaxGrid
 BLOCK = 256                # csrc/spmm.hip, csrc/cg.hip kBlock
 
 

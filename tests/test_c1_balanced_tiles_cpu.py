@@ -98,7 +98,9 @@ def test_cap_is_the_kernels():
     assert re.search(r"static_assert\(BS != 256 \|\| 4 \* NQ \* BS == MGP_C1_TILE_CAP", body)
     nq = int(re.search(r"constexpr int NQ = (\d+);", body).group(1))
     assert 4 * nq * 256 == CAP                                       # BS = 256: the 64-row tiles' workgroup
-    assert G.C1_MAX_TILES == int(re.search(r"constexpr int kMaxGrid = (\d+);", src).group(1))
+    policy = open(os.path.join(ROOT, "manifold_gp_amd", "csrc", "spmm_policy.h")).read()      # the constants the kernels share with the plan
+    assert '#include "spmm_policy.h"' in src and "kMaxGrid =" not in src
+    assert G.C1_MAX_TILES == int(re.search(r"constexpr int kMaxGrid = (\d+);", policy).group(1))
 
 
 def test_policy_no_heavy_tile():

@@ -46,6 +46,10 @@ int main(void) {
   printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(mgp_csr_t), sizeof(mgp_operator_t), sizeof(mgp_cg_params_t),
          sizeof(mgp_lanczos_params_t), offsetof(mgp_operator_t, pre), offsetof(mgp_operator_t, nu), offsetof(mgp_csr_t, mt_sptr),
          offsetof(mgp_csr_t, mt_tiles), offsetof(mgp_csr_t, mt_steps), offsetof(mgp_csr_t, spmv_lanes));
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", offsetof(mgp_csr_t, c1_tiles), sizeof(mgp_c1_tiles_t), offsetof(mgp_c1_tiles_t, n),
+         offsetof(mgp_c1_tiles_t, tile_ptr), offsetof(mgp_c1_tiles_t, tile_cols), offsetof(mgp_c1_tiles_t, lid),
+         offsetof(mgp_c1_tiles_t, rowptr_pad), offsetof(mgp_c1_tiles_t, tile_shift), offsetof(mgp_c1_tiles_t, tiles),
+         offsetof(mgp_c1_tiles_t, max_cols), offsetof(mgp_c1_tiles_t, max_entries), offsetof(mgp_c1_tiles_t, reserved));
   return 0;
 }
 """)
@@ -54,8 +58,13 @@ int main(void) {
     c = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
     assert c == [ctypes.sizeof(_lib.CsrT), ctypes.sizeof(_lib.OperatorT), ctypes.sizeof(_lib.CgParamsT),
                  ctypes.sizeof(_lib.LanczosParamsT), _lib.OperatorT.pre.offset, _lib.OperatorT.nu.offset, _lib.CsrT.mt_sptr.offset,
-                 _lib.CsrT.mt_tiles.offset, _lib.CsrT.mt_steps.offset, _lib.CsrT.spmv_lanes.offset], c
-    assert ctypes.sizeof(_lib.CsrT) == 144 and ctypes.sizeof(_lib.CgParamsT) == 28 and ctypes.sizeof(_lib.LanczosParamsT) == 24
+                 _lib.CsrT.mt_tiles.offset, _lib.CsrT.mt_steps.offset, _lib.CsrT.spmv_lanes.offset,
+                 # the balanced tile set: the field that names it (appended: every earlier field keeps its offset) and the descriptor
+                 _lib.CsrT.c1_tiles.offset, ctypes.sizeof(_lib.C1TilesT)] + [getattr(_lib.C1TilesT, f).offset for f, _ in
+                                                                            _lib.C1TilesT._fields_], c
+    assert _lib.CsrT.c1_tiles.offset == 144 and [f for f, _ in _lib.C1TilesT._fields_] == [
+        "n", "tile_ptr", "tile_cols", "lid", "rowptr_pad", "tile_shift", "tiles", "max_cols", "max_entries", "reserved"]
+    assert ctypes.sizeof(_lib.CsrT) == 152 and ctypes.sizeof(_lib.CgParamsT) == 28 and ctypes.sizeof(_lib.LanczosParamsT) == 24
 
 
 def test_argument_errors_without_gpu():
@@ -86,6 +95,37 @@ def test_argument_errors_without_gpu():
     assert lib.mgp_spmm_set_group_hint(64) == 0
     assert lib.mgp_spmm_dot_blocks_csr(ctypes.byref(L), 1) == nb8 != lib.mgp_spmm_dot_blocks(n, 1)
     assert lib.mgp_spmm_set_group_hint(8) == 0
+
+
+def test_tile_rowptr_alone_is_a_partial_order_and_is_never_read():
+    """tile_rowptr means one thing, a device array of a row order, set only with tile_vals and tile_rowid.  A struct whose
+    tile_rowptr alone is set -- to an address nothing is mapped at: the plan reads through no device pointer -- is a partial order:
+    no dictionary kernel, the same choice and the same dot blocks as the struct without any order and without dictionaries."""
+    import mmap
+    from manifold_gp_amd import _lib
+    lib = _lib.lib()
+    libc = ctypes.CDLL(None, use_errno=True)
+    libc.mmap.restype, libc.mmap.argtypes = ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 3 + [ctypes.c_long]
+    # a page no access is allowed to: a read through addr would end the process
+    addr = libc.mmap(None, mmap.PAGESIZE, 0, mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS, -1, 0)
+    assert addr not in (None, ctypes.c_void_p(-1).value), ctypes.get_errno()
+    n = 5000
+    bare = _lib.CsrT()
+    bare.n, bare.rowptr, bare.col, bare.vals, bare.diag = n, addr, addr, addr, addr
+    tiled = _lib.CsrT()
+    ctypes.memmove(ctypes.byref(tiled), ctypes.byref(bare), ctypes.sizeof(bare))
+    tiled.tile_ptr, tiled.tile_cols, tiled.lid = addr, addr, addr
+    tiled.tile_rows, tiled.tile_max_cols, tiled.tile_max_entries = 64, 300, 1024
+    alone = _lib.CsrT()
+    ctypes.memmove(ctypes.byref(alone), ctypes.byref(tiled), ctypes.sizeof(tiled))
+    alone.tile_rowptr = addr
+    for C in (1, 4, 20, 64, 128):
+        want = (lib.mgp_spmm_kernel_choice(ctypes.byref(bare), C, 0, 0), lib.mgp_spmm_dot_blocks_csr(ctypes.byref(bare), C))
+        assert want[0] == 0 and want[1] > 0, (C, want)
+        got = (lib.mgp_spmm_kernel_choice(ctypes.byref(alone), C, 0, 0), lib.mgp_spmm_dot_blocks_csr(ctypes.byref(alone), C))
+        assert got == want, (C, got, want)
+    # (the same struct without the lone pointer does take the dictionary kernels)
+    assert lib.mgp_spmm_kernel_choice(ctypes.byref(tiled), 1, 0, 0) == 1 and lib.mgp_spmm_kernel_choice(ctypes.byref(tiled), 4, 0, 0) == 2
 
 
 def test_knn_workspace_sizing_follows_the_filter_switch():
